@@ -9,7 +9,13 @@ iterative_inference.py:226-294: pred_fcn_fn -> val_fn (FCN metrics, :242) -> pre
 (one-shot DAE metrics, :250-251; the same DAE forward as the loop's first step, shared) ->
 refine x10 (:258-284) -> val_fn (:287).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line: the headline leg and
+nothing else.  `--full` adds every other measurement below (roofline passes, the work-elimination
+ablations, the bf16 / bf16x3 / float64 legs, the other configs, the early-stop leg, the CPU
+baseline, the parity report and the detail record).  `--dump-outputs DIR` writes what the last
+timed step computed to DIR/<name>.npy (see `dump_outputs`).
 
 N > 1 without a torch.distributed environment: this process only LAUNCHES
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` as a child (before anything
@@ -97,21 +103,25 @@ def make_pool(n, build, X, T, num_iter, step_size, prepare=True):
     return pool
 
 
-def one_step(ii, X, T, num_iter, step_size, graph=None):
+def one_step(ii, X, T, num_iter, step_size, graph=None, keep=None):
     """One batch of the per-batch path (iterative_inference.py:237-287); returns the device-side
     metric accumulators (refined, FCN, one-shot DAE).  graph=False: every step launched from
-    Python (the roofline pass needs its per-launch events)."""
+    Python (the roofline pass needs its per-launch events).  `keep` (a dict): also hold on to the
+    maps the step handed out (no copy, no wait), for `dump_outputs`."""
     if isinstance(ii, EnginePool):
         # whole batches in flight: this batch on the pool's next engine / stream (api.EnginePool)
         with ii.lane(X, T) as engine:
-            return one_step(engine, X, T, num_iter, step_size, graph)
+            return one_step(engine, X, T, num_iter, step_size, graph, keep)
     out = ii.pred_fcn_fn(X)                                            # :237-239
     H, Y = out[:-1], out[-1]
     m_fcn = ii.val_device(Y, T)                                        # :242
-    Yii, _, _, R0 = ii.refine(H, Y, step_size, num_iter, early_stop=False,
-                              first_reconstruction=True, graph=graph)  # :258-284
+    Yii, iters, _, R0 = ii.refine(H, Y, step_size, num_iter, early_stop=False,
+                                  first_reconstruction=True, graph=graph)  # :258-284
     m_dae = ii.val_device(R0, T)                                       # :250-251 (shared forward)
-    return ii.val_device(Yii, T), m_fcn, m_dae                         # :287
+    m_ii = ii.val_device(Yii, T)                                       # :287
+    if keep is not None:
+        keep.update(fcn_probs=Y, dae_one_shot=R0, refined=Yii, iterations=iters)
+    return m_ii, m_fcn, m_dae
 
 
 def effective_cores():
@@ -407,6 +417,39 @@ def other_configs(device, step_size, no_roofline, n_fly=1):
     return res
 
 
+DUMP_SAMPLE = 1 << 21       # elements kept of a larger map: a fixed, seeded sample (8 MB in float32)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, keep, metrics):
+    """What the last timed step handed out, as DIR/<name>.npy (float32 maps, float64 counts):
+    `fcn_probs` (pred_fcn_fn's score map), `dae_one_shot` (pred_dae_fn's reconstruction), `refined`
+    (the refined map), `iterations` (steps used per image) and, per metric set (refined, fcn,
+    dae_one_shot), `confusion_*` (C x (C + 1) counts, void last) and `metrics_*` ([acc, mse]; mse
+    comes from float64 sums the metrics kernel adds atomically, so its last bits vary from run to run).
+    A map larger than DUMP_SAMPLE elements is stored as the same seeded sample of flat indices
+    for every map of its size (`sample_index_<numel>`, float64); well under 64 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    index = {}
+    for name, t in keep.items():
+        flat = t.detach().reshape(-1)
+        dt = np.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else np.float64
+        n = flat.numel()
+        if n > DUMP_SAMPLE:
+            if n not in index:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+                index[n] = idx
+                np.save(os.path.join(path, 'sample_index_%d.npy' % n), idx.astype(np.float64))
+            flat = flat.index_select(0, torch.from_numpy(index[n]).to(flat.device))
+        np.save(os.path.join(path, name + '.npy'), flat.cpu().numpy().astype(dt))
+    for name, m in zip(('refined', 'fcn', 'dae_one_shot'), metrics):
+        acc, _, mse = m.result()
+        np.save(os.path.join(path, 'confusion_%s.npy' % name),
+                m.cm.cpu().numpy().astype(np.float64).reshape(m.C, m.C + 1))
+        np.save(os.path.join(path, 'metrics_%s.npy' % name), np.array([acc, mse], np.float64))
+
+
 def _write_detail(line):
     """Everything measured (per-kernel tables, every config's roofline, notes) goes to a side file -- and to
     stderr -- so that the ONE line on stdout stays short enough for the legs a reader needs to survive in a
@@ -524,9 +567,10 @@ def compact_line(line, detail_file):
     return out
 
 
-def timed_steps(ii, Xs, Ts, steps, warmup, num_iter, step_size, world, device, start=0):
+def timed_steps(ii, Xs, Ts, steps, warmup, num_iter, step_size, world, device, start=0, keep=None):
     """W untimed + exactly K timed steps, barrier + synchronize on both sides, max over ranks.
-    Returns (seconds, per-step metric accumulators)."""
+    Returns (seconds, per-step metric accumulators).  `keep`: the last timed step's maps
+    (one_step)."""
     it, n = start, len(Xs)
     for _ in range(warmup):
         one_step(ii, Xs[it % n], Ts[it % n], num_iter, step_size)
@@ -536,8 +580,9 @@ def timed_steps(ii, Xs, Ts, steps, warmup, num_iter, step_size, world, device, s
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     results = []
-    for _ in range(steps):
-        results.append(one_step(ii, Xs[it % n], Ts[it % n], num_iter, step_size))
+    for k in range(steps):
+        results.append(one_step(ii, Xs[it % n], Ts[it % n], num_iter, step_size,
+                                keep=keep if k == steps - 1 else None))
         it += 1
     return t0, results
 
@@ -646,6 +691,12 @@ def main():
                     help='skip the other BASELINE configs (configs[2], [3], [4]: 3 timed batches each)')
     ap.add_argument('--dry-run', action='store_true',
                     help='CPU rehearsal of the launch / reduction protocol, no GPU work')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything besides the headline leg (roofline passes, ablations, the '
+                         'other precisions and configs, early stop, CPU baseline, parity report, detail '
+                         'record); the --no-* / --split-streams / --all-legs options act within it')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/<name>.npy')
     args = ap.parse_args()
 
     # N > 1 outside a torch.distributed environment: fan out FIRST, before any GPU call
@@ -661,6 +712,11 @@ def worker(args):
     if world != args.gpus:
         raise SystemExit('WORLD_SIZE=%d but --gpus %d' % (world, args.gpus))
     concat_h = ['pool4']
+    if not args.full:
+        # a plain run: the headline leg alone (set-up, warm-up, the K timed steps, the result line)
+        args.no_roofline = args.no_cpu_baseline = args.no_full_recompute = args.no_bf16 = True
+        args.no_bf16x3 = args.no_strict_f64 = args.no_early_stop = args.no_configs = True
+        args.split_streams = False
     if world > 1 and not args.all_legs:
         # a scaling run measures the headline leg; the ablation legs are single-GPU diagnostics
         args.no_full_recompute = args.no_bf16 = args.no_strict_f64 = True
@@ -685,8 +741,9 @@ def worker(args):
     pool = make_pool(n_fly, build_main, Xs[0], Ts[0], args.num_iter, args.step_size)
     ii, fp, dp = built[0]
 
+    keep = {} if args.dump_outputs and rank == 0 else None
     t0, results = timed_steps(pool, Xs, Ts, args.steps, args.warmup, args.num_iter, args.step_size,
-                              world, device)
+                              world, device, keep=keep)
     # the path's only collective: one all-reduce of the metric accumulator (RCCL over xGMI)
     accs = [iidist.EvalAccumulator(N_CLASSES) for _ in range(3)]
     for ms in results:
@@ -712,6 +769,10 @@ def worker(args):
         allr = [torch.zeros_like(mine) for _ in range(world)]
         torch.distributed.all_gather(allr, mine)
         per_rank = [float(t.item()) for t in allr]
+    if keep:
+        # after the timed steps, before anything else runs on the engines
+        dump_outputs(args.dump_outputs, keep, results[-1])
+        keep.clear()
 
     def leg(model, xs, ts, steps, warmup):
         t1, _ = timed_steps(model, xs, ts, steps, warmup, args.num_iter, args.step_size, world, device)
@@ -745,17 +806,26 @@ def worker(args):
             'note': 'images/s x 872.3 nominal GFLOP/image (SURVEY 6.2).  NOT a hardware rate: the '
                     'exact work eliminations and Winograd issue far fewer FLOPs; the hardware rate '
                     'is roofline.whole_path'},
-        'parity': {'fp32_value': 'damped synthetic set, all 10 steps free-running: <= 1e-4 with the float64 '
-                                 'mask decisions, >= 0.999 of pixels within 1e-4 with its own masks (the '
-                                 'rest: verified DePool2D near-tie flips; measured fraction / max / mean in '
-                                 '`damped_set_64_images`) (tests/test_gpu_damped.py); chaotic default set '
-                                 '(the weights this line is timed on): teacher-forced 1e-4, free-running '
-                                 'only statistically (DESIGN.md section 4)',
-                   'strict_1e-4_end_to_end': 'strict_f64 leg (float64 = the reference CPU numerics)'},
     }
-    prows, pfile = _parity_report()
-    line['parity']['damped_set_64_images'] = dict(prows.get('fp32 MFMA', {}), source=pfile,
-                                                  reference='float64 HIP path, pinned to the CPU oracle')
+    from iterative_inference_segm_amd import ops as _ops
+    # (IISEG_MMA=bf16 forces the 16-bit operand path onto the headline leg -- the profiling runs of
+    # scripts/profile_r02.sh do: the line then says so and the roofline is priced against the bf16 peak)
+    main_bf16 = _ops.DEFAULT_MMA == 'bf16'
+    if main_bf16:
+        line['dtype'] = 'bf16 operands, f32 accumulate (IISEG_MMA=bf16)'
+    prows, pfile = {}, None
+    if args.full:
+        line['parity'] = {
+            'fp32_value': 'damped synthetic set, all 10 steps free-running: <= 1e-4 with the float64 '
+                          'mask decisions, >= 0.999 of pixels within 1e-4 with its own masks (the '
+                          'rest: verified DePool2D near-tie flips; measured fraction / max / mean in '
+                          '`damped_set_64_images`) (tests/test_gpu_damped.py); chaotic default set '
+                          '(the weights this line is timed on): teacher-forced 1e-4, free-running '
+                          'only statistically (DESIGN.md section 4)',
+            'strict_1e-4_end_to_end': 'strict_f64 leg (float64 = the reference CPU numerics)'}
+        prows, pfile = _parity_report()
+        line['parity']['damped_set_64_images'] = dict(prows.get('fp32 MFMA', {}), source=pfile,
+                                                      reference='float64 HIP path, pinned to the CPU oracle')
     line['in_flight'] = {
         'engines': n_fly,
         'note': 'whole batches in flight (api.EnginePool): batch i runs on engine i %% %d, each engine on its '
@@ -763,7 +833,7 @@ def worker(args):
                 'the launches of the single-engine path (same kernels, same batch size, bit-identical '
                 'results: tests/test_gpu_e2e.py); ms_per_step = timed seconds / K, i.e. the rate, not the '
                 'latency of one batch' % n_fly}
-    if n_fly > 1:
+    if n_fly > 1 and args.full:
         line['in_flight']['one_in_flight'] = leg(ii, Xs, Ts, args.steps, 1)
     line['per_rank_images_per_s'] = [round(v, 1) for v in per_rank]
     line['metric_all_reduce_ms'] = round(t_ar * 1e3, 3)
@@ -778,12 +848,6 @@ def worker(args):
                     'note': 'consistency metric (random weights), reduced over ranks'}
     X, T = Xs[0], Ts[0]
     if not args.no_roofline:
-        from iterative_inference_segm_amd import ops as _ops
-        # (IISEG_MMA=bf16 forces the 16-bit operand path onto this leg too -- the profiling runs of
-        # scripts/profile_r02.sh do: the leg then says so and is priced against the bf16 peak)
-        main_bf16 = _ops.DEFAULT_MMA == 'bf16'
-        if main_bf16:
-            line['dtype'] = 'bf16 operands, f32 accumulate (IISEG_MMA=bf16)'
         rl = conv_roofline(ii, X, T, args.num_iter, args.step_size, ms_per_step,
                            PEAK_TFLOPS_BF16_MFMA if main_bf16 else PEAK_TFLOPS_F32_MFMA)
         line['roofline'] = rl
@@ -1017,8 +1081,12 @@ def worker(args):
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(fp, dp, args.num_iter, args.step_size, args.cpu_budget)
-        detail = _write_detail(line)
-        print(json.dumps(compact_line(line, detail)), flush=True)
+        if args.full:
+            print(json.dumps(compact_line(line, _write_detail(line))), flush=True)
+        else:
+            out = compact_line(line, None)
+            del out['detail']
+            print(json.dumps(out), flush=True)
     iidist.barrier()
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

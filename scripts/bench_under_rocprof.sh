@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r05/benchprof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/run --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-full-recompute --no-two-streams --no-strict-f64 --no-configs --no-early-stop > $O/bench_under_rocprof.json 2> $O/err.log || { tail -20 $O/err.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/run --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-full-recompute --no-two-streams --no-strict-f64 --no-configs --no-early-stop > $O/bench_under_rocprof.json 2> $O/err.log || { tail -20 $O/err.log; exit 1; }
 cd $R
 python3 - <<'PY'
 import json, glob, csv

@@ -320,3 +320,42 @@ def test_bench_line_is_short_and_ends_with_the_16_bit_leg():
     assert out['roofline']['bound'] == 'mfma' and out['cpu_baseline']['kind'] == 'port'
     tail = text[-1200:]
     assert '"all_3x3_frac"' in tail and '"one_in_flight"' in tail
+
+
+def test_bench_dump_outputs_fixed_sample_float_only(tmp_path, monkeypatch):
+    """bench.dump_outputs (`bench.py --dump-outputs DIR`): every file float32 or float64; a map larger than
+    DUMP_SAMPLE is stored as one seeded sample of flat indices, the same for every map of that size and from call
+    to call (two builds compare output for output); at full size the files stay well under 64 MB."""
+    import bench
+    full = bench.DUMP_SAMPLE
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a: None)
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
+    rng = np.random.default_rng(0)
+    keep = {n: torch.from_numpy(rng.random((2, 11, 24, 32), dtype=np.float32))
+            for n in ('fcn_probs', 'dae_one_shot', 'refined')}
+    keep['iterations'] = torch.full((2,), 10, dtype=torch.int32)
+    ms = []
+    for k in range(3):
+        m = Metrics(11, 'cpu')
+        m.cm += torch.arange(132) + k
+        m.sums += torch.tensor([1.5, 4.0])
+        ms.append(m)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), keep, ms)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b'))
+    assert names == sorted(['fcn_probs.npy', 'dae_one_shot.npy', 'refined.npy', 'iterations.npy',
+                            'sample_index_16896.npy'] +
+                           ['%s_%s.npy' % (a, b) for a in ('confusion', 'metrics')
+                            for b in ('refined', 'fcn', 'dae_one_shot')])
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+    idx = np.load(tmp_path / 'a' / 'sample_index_16896.npy').astype(np.int64)
+    assert len(np.unique(idx)) == 1000
+    for n in ('fcn_probs', 'dae_one_shot', 'refined'):
+        assert np.array_equal(np.load(tmp_path / 'a' / (n + '.npy')), keep[n].reshape(-1).numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / 'a' / 'iterations.npy'), [10.0, 10.0])
+    assert np.array_equal(np.load(tmp_path / 'a' / 'confusion_fcn.npy'), (np.arange(132) + 1).reshape(11, 12))
+    # full size: three sampled maps in float32 + their shared index in float64 (+ arrays of a few KB)
+    assert (3 * 4 + 8) * full < 48 << 20
