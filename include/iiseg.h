@@ -721,6 +721,43 @@ int iiseg_refine_update_f64(void* stream, const double* score, double* y, const 
 int iiseg_confusion_f64(void* stream, const double* y, const double* t, int64_t* cm, double* sums,
                         int32_t B, int32_t C, int32_t HW);
 
+/* ---------------------------------------------------------------------------------------
+ * Dense-CRF mean field (the "FCN-8 + CRF" baseline of the reference's crf_inference.py:143-192, which
+ * calls pydensecrf's DenseCRF2D).  Model (DESIGN.md "Dense-CRF baseline"): unary
+ * U = -log(clamp(P, clip, 1)); Q0 = softmax(-U); colour features I = clamp(floor(255 x), 0, 255) per
+ * channel (x taken as already on 0..255 with IISEG_CRF_INPUT_0_255); kernels
+ *   k_g(i,j) = exp(-d^2 / (2 sxy_g^2)),  k_b(i,j) = exp(-d^2 / (2 sxy_b^2) - |I_i - I_j|^2 / (2 srgb^2))
+ * summed EXACTLY over the in-image pixels j with |dx|, |dy| <= R (j = i included; pydensecrf
+ * approximates the sums on a permutohedral lattice); symmetric normalisation
+ * n^k_i = 1 / sqrt(sum_j k(i,j)); one iteration
+ *   Q' = softmax_l(-U + w_g n^g_i sum_j k_g n^g_j Q_j + w_b n^b_i sum_j k_b n^b_j Q_j)
+ * (the w_b term only with IISEG_CRF_BILATERAL).  Tensors (device, NCHW, caller-owned):
+ *   P (B,C,H,W) probabilities, X (B,3,H,W) image, U / Q0 / Qin / Qout (B,C,H,W), I (B,3,H,W),
+ *   ng / nb (B,H,W).  iiseg_crf_prepare writes U, Q0, I, ng, nb; iiseg_crf_step reads U, Qin, I, ng,
+ *   nb and writes Qout (Qin != Qout: ping-pong).  Supported: 1 <= B <= 65535, 2 <= C <= 16,
+ *   1 <= R <= 16, H, W >= 1 (any size, also smaller than R), positive sxy_g, sxy_b, srgb,
+ *   0 < clip <= 1; anything else is IISEG_ERR_SHAPE before any launch.
+ * ------------------------------------------------------------------------------------- */
+#define IISEG_CRF_BILATERAL 1u     /* add the appearance (bilateral) kernel            */
+#define IISEG_CRF_INPUT_0_255 2u   /* X holds 0..255 values (-test_from_0_255)         */
+
+typedef struct iiseg_crf_desc {
+    int32_t B, C, H, W, R;
+    uint32_t flags;
+    double sxy_g, w_g, sxy_b, srgb, w_b, clip;
+} iiseg_crf_desc;
+
+/* host only: 1 when the descriptor is in the supported range, else 0 */
+int iiseg_crf_supported(const iiseg_crf_desc* d);
+int iiseg_crf_prepare_f32(void* stream, const iiseg_crf_desc* d, const float* P, const float* X, float* U,
+                          float* Q0, float* I, float* ng, float* nb);
+int iiseg_crf_prepare_f64(void* stream, const iiseg_crf_desc* d, const double* P, const double* X,
+                          double* U, double* Q0, double* I, double* ng, double* nb);
+int iiseg_crf_step_f32(void* stream, const iiseg_crf_desc* d, const float* U, const float* Qin,
+                       const float* I, const float* ng, const float* nb, float* Qout);
+int iiseg_crf_step_f64(void* stream, const iiseg_crf_desc* d, const double* U, const double* Qin,
+                       const double* I, const double* ng, const double* nb, double* Qout);
+
 #ifdef __cplusplus
 }
 #endif

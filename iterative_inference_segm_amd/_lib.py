@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libiiseg_hip.so')
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 CONV_RELU = 1
 CONV_UNPOOL = 2
@@ -34,6 +34,16 @@ class DeconvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ('B', 'Cin', 'H', 'W', 'Cout', 'K', 'stride', 'oy0', 'ox0', 'OH', 'OW',
                  'AH', 'AW', 'ay0', 'ax0')]
+
+
+CRF_BILATERAL = 1
+CRF_INPUT_0_255 = 2
+
+
+class CrfDesc(C.Structure):
+    """struct iiseg_crf_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'C', 'H', 'W', 'R')] + [('flags', C.c_uint32)] + \
+               [(n, C.c_double) for n in ('sxy_g', 'w_g', 'sxy_b', 'srgb', 'w_b', 'clip')]
 
 
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -174,6 +184,12 @@ SIGNATURES = {
     'iiseg_confusion_f64': (C.c_int, [_vp] * 5 + [_i32] * 3),
     'iiseg_count_nonfinite_f32': (C.c_int, [_vp, _vp, _i64, _vp]),
     'iiseg_count_nonfinite_f64': (C.c_int, [_vp, _vp, _i64, _vp]),
+    # dense-CRF mean field
+    'iiseg_crf_supported': (C.c_int, [C.POINTER(CrfDesc)]),
+    'iiseg_crf_prepare_f32': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 7),
+    'iiseg_crf_prepare_f64': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 7),
+    'iiseg_crf_step_f32': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 6),
+    'iiseg_crf_step_f64': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 6),
 }
 
 _lib = None
