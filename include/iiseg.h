@@ -146,7 +146,8 @@ int iiseg_conv_pool_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
                         const float* pre, const float* pooled, const float* wp, const int32_t* ktab,
                         const float* bias, const float* add, float* out, float* pool_out);
 
-/* DePool2D equality masks as BYTES (halo-tile kernels only): the reference's DePool2D needs
+/* DePool2D equality masks as BYTES (halo-tile kernels here; the Winograd form has its own entry,
+ * iiseg_conv_wino_mask_f32): the reference's DePool2D needs
  * pre == pooled per element (layers/mylayers.py:111-114); instead of keeping the pre-pool map for
  * that comparison, the conv whose epilogue does the pooling can write
  *     mask[b][c][y/2][x/2] bit (y & 1) * 2 + (x & 1) = (pre[b][c][y][x] == pooled[b][c][y/2][x/2])
@@ -208,6 +209,23 @@ int iiseg_conv_wino_pack_f32(void* stream, const iiseg_conv_desc* d, const float
 int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
                         const float* pre, const float* pooled, const float* U, const float* bias,
                         const float* add, float* workspace, float* out, uint32_t stages);
+/* The Winograd call with the 2x2 max-pool and the DePool2D mask bytes (as iiseg_conv_mask_f32):
+ *   pool_out   (may be NULL) the FULL pooled tensor (B, Cout, fullH/2, fullW/2); the pooled
+ *              positions of the window are written in place by the output transform (or the fused
+ *              kernel's epilogue).  Needs a tile to be one pooling window:
+ *              iiseg_conv_wino_pool_supported = even tile anchor (tile_y0 = tile_x0 = 0), even
+ *              window origin, even extent unless the window ends at the map's last row / column.
+ *   mask_out   (may be NULL, needs pool_out) the mask bytes of those windows, pool_out's shape
+ *   out        may be NULL when pool_out is given: the pre-pool map is not stored
+ *   mask_in    (may be NULL; IISEG_CONV_UNPOOL) bytes of x1's shape replacing pre / pooled: the
+ *              input transform reads up + one byte per 2x2 instead of pre, pooled and up.
+ * Same arithmetic as iiseg_conv_wino_f32: the pooled values and the masks equal, bit for bit,
+ * iiseg_maxpool2x2_window_f32 / iiseg_maxpool2x2_mask_window_f32 of the stored map. */
+int iiseg_conv_wino_pool_supported(const iiseg_conv_desc* d);
+int iiseg_conv_wino_mask_f32(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
+                             const float* pre, const float* pooled, const uint8_t* mask_in,
+                             const float* U, const float* bias, const float* add, float* workspace,
+                             float* out, float* pool_out, uint8_t* mask_out, uint32_t stages);
 
 /* ---------------------------------------------------------------------------------------
  * 16-bit MFMA path (BASELINE north_star "fp16 MFMA peak", configs[2] "bf16 with fp32 accumulate"):
@@ -447,6 +465,13 @@ int iiseg_maxpool2x2_window_f32(void* stream, const float* x, float* out, int32_
                                 int32_t W, int32_t y0, int32_t x0, int32_t wh, int32_t ww);
 int iiseg_maxpool2x2_window_f64(void* stream, const double* x, double* out, int32_t BC, int32_t H,
                                 int32_t W, int32_t y0, int32_t x0, int32_t wh, int32_t ww);
+/* iiseg_maxpool2x2_window_f32 that also writes the DePool2D mask bytes of those windows into `mask`
+ * (uint8, the shape of `out`; bit (y & 1) * 2 + (x & 1) = x == out, see iiseg_conv_mask_f32): for
+ * layers whose own epilogue cannot pool (Winograd layers at an odd tile anchor), so that the decoder
+ * still reads up + mask bytes instead of the pre-pool map. */
+int iiseg_maxpool2x2_mask_window_f32(void* stream, const float* x, float* out, uint8_t* mask,
+                                     int32_t BC, int32_t H, int32_t W, int32_t y0, int32_t x0,
+                                     int32_t wh, int32_t ww);
 
 /* Equality-mask unpool, materialised (the fused form is IISEG_CONV_UNPOOL).  Replaces
  * DePool2D.get_output_for, layers/mylayers.py:88-115:

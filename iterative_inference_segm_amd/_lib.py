@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libiiseg_hip.so')
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 CONV_RELU = 1
 CONV_UNPOOL = 2
@@ -73,6 +73,8 @@ SIGNATURES = {
     'iiseg_conv_wino_workspace_elems': (_i64, [C.POINTER(ConvDesc)]),
     'iiseg_conv_wino_pack_f32': (C.c_int, [_vp, C.POINTER(ConvDesc), _vp, _i64, _i64, _vp]),
     'iiseg_conv_wino_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 9 + [C.c_uint32]),
+    'iiseg_conv_wino_pool_supported': (C.c_int, [C.POINTER(ConvDesc)]),
+    'iiseg_conv_wino_mask_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 12 + [C.c_uint32]),
     'iiseg_conv_wino_bf16_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_wino_bf16_weight_bytes': (_i64, [C.POINTER(ConvDesc)]),
     'iiseg_conv_wino_bf16_workspace_bytes': (_i64, [C.POINTER(ConvDesc)]),
@@ -125,6 +127,7 @@ SIGNATURES = {
     'iiseg_unpool_eqmask_f32': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32]),
     'iiseg_maxpool2x2_window_f32': (C.c_int, [_vp] * 3 + [_i32] * 7),
     'iiseg_maxpool2x2_window_f64': (C.c_int, [_vp] * 3 + [_i32] * 7),
+    'iiseg_maxpool2x2_mask_window_f32': (C.c_int, [_vp] * 4 + [_i32] * 7),
     'iiseg_unpool_eqmask_window_f32': (C.c_int, [_vp] * 5 + [_i32] * 7),
     'iiseg_unpool_eqmask_window_f64': (C.c_int, [_vp] * 5 + [_i32] * 7),
     'iiseg_deconv_f32': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 5),

@@ -20,7 +20,9 @@
 //
 // Replaces the same Lasagne Conv2DLayer(3x3, stride 1) call sites as conv_taps.hip for layers
 // with Cin % 16 == 0 (models/fcn8.py:41-71, models/fcn_down.py:102-104, models/fcn_up.py:83-86);
-// fusions kept: two-source channel concat (h first), bias / skip-add / ReLU / window / placement.
+// fusions kept: two-source channel concat (h first), bias / skip-add / ReLU / window / placement;
+// DePool2D input from pre / pooled or from mask bytes; at an even tile anchor the 2x2 max-pool and its
+// mask bytes in the output transform (a tile is then one pooling window, its four values in one lane).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -35,8 +37,9 @@ namespace {
 struct WinoParams {
     const float* x1;
     const float* x2;
-    const float* pre;     // unpool mode: x1 = up, pre, pooled (DePool2D operands)
+    const float* pre;     // unpool mode: x1 = up, pre, pooled (DePool2D operands) ...
     const float* pooled;
+    const uint8_t* mask_in;   // ... or x1 = up and the mask bytes (then pre / pooled are unused)
     int h2, w2;
     const float* U;
     const float* bias;
@@ -54,7 +57,30 @@ struct WinoParams {
     int relu;
     int out_ctot, out_c0, out_H, out_W, out_y0, out_x0;
     int n_ttiles, n_mtiles;
+    // fused 2x2 max-pool (even tile anchor: a tile IS a pooling window): FULL pooled tensor
+    // (B, Cout, pool_H, pool_W) and its DePool2D mask bytes (may be NULL); out may then be NULL
+    float* pool;
+    uint8_t* mask_out;
+    int pool_H, pool_W;
 };
+
+// max of a 2x2 window in the order of maxpool2x2 (pool_unpool.hip): same value, same sign of zero
+__device__ __forceinline__ float pool4(float v00, float v01, float v10, float v11) {
+    const float a = v00 > v01 ? v00 : v01;
+    const float b = v10 > v11 ? v10 : v11;
+    return a > b ? a : b;
+}
+
+// pooled value + mask byte (bit (y & 1) * 2 + (x & 1): pre == pooled) of one whole tile
+__device__ __forceinline__ void pool_store(const WinoParams& p, int b, int co, int ay, int ax,
+                                           float v00, float v01, float v10, float v11) {
+    const float m = pool4(v00, v01, v10, v11);
+    const size_t po = ((size_t)b * p.Cout + co) * p.pool_H * p.pool_W + (size_t)(ay >> 1) * p.pool_W + (ax >> 1);
+    p.pool[po] = m;
+    if (p.mask_out)
+        p.mask_out[po] = (uint8_t)((v00 == m ? 1u : 0u) | (v01 == m ? 2u : 0u) |
+                                   (v10 == m ? 4u : 0u) | (v11 == m ? 8u : 0u));
+}
 
 constexpr int RSRC_W3 = 0x00027000;
 
@@ -100,8 +126,10 @@ __global__ void wino_weight_kernel(const float* __restrict__ w, int64_t so, int6
 // while loading the patch: element (iy, ix) = pre == pooled[iy/2, ix/2] ? up[iy/2, ix/2] : 0 inside
 // the 2h x 2w region, 0 outside.  PY / PX = parity of the patch origin (uniform over a launch), so
 // the 3x3 block of pooled/up values a 4x4 patch touches is indexed at compile time.
+// MB (with UNPOOL): the mask comes as bytes (p.mask_in, bit (iy & 1) * 2 + (ix & 1) = pre == pooled,
+// written by the pooling conv or pool kernel): up + one byte per 2x2 instead of pre / pooled / up.
 constexpr int ICH = 4;
-template <bool UNPOOL, int PY, int PX>
+template <bool UNPOOL, int PY, int PX, bool MB = false>
 __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
@@ -140,12 +168,24 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
     // moved up: V and the inputs may alias as far as the compiler knows.)
     constexpr int NC_ = UNPOOL ? ICH / 2 : ICH;
     const int c0 = blockIdx.y * NC_;
-    float pv[NC_][4][4];
-    float pq[UNPOOL ? NC_ : 1][NQY][NQX], uq[UNPOOL ? NC_ : 1][NQY][NQX];
+    float pv[MB ? 1 : NC_][4][4];
+    float pq[UNPOOL && !MB ? NC_ : 1][NQY][NQX], uq[UNPOOL ? NC_ : 1][NQY][NQX];
+    uint32_t mq[MB ? NC_ : 1][NQY][NQX];
 #pragma unroll
     for (int cc = 0; cc < NC_; ++cc) {
         const int c = min(c0 + cc, p.Kc - 1);
-        if constexpr (UNPOOL) {
+        if constexpr (MB) {
+            const uint8_t* mp = p.mask_in + ((size_t)b * p.C1 + c) * hw2;
+            const float* upp = p.x1 + ((size_t)b * p.C1 + c) * hw2;
+#pragma unroll
+            for (int i = 0; i < NQY; ++i)
+#pragma unroll
+                for (int j = 0; j < NQX; ++j) {
+                    const int o = (qrok[i] && qcok[j]) ? qoff[i] + j : 0;
+                    mq[cc][i][j] = mp[o];
+                    uq[cc][i][j] = upp[o];
+                }
+        } else if constexpr (UNPOOL) {
             const float* prep = p.pre + ((size_t)b * p.C1 + c) * HW;
             const float* poolp = p.pooled + ((size_t)b * p.C1 + c) * hw2;
             const float* upp = p.x1 + ((size_t)b * p.C1 + c) * hw2;
@@ -179,7 +219,12 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if constexpr (UNPOOL) {
+                if constexpr (MB) {
+                    const int qi = (PY + i) >> 1, qj = (PX + j) >> 1;
+                    const int bit = ((PY + i) & 1) * 2 + ((PX + j) & 1);
+                    const bool ok = rok[i] && cok[j] && qrok[qi] && qcok[qj];
+                    d[i][j] = (ok && ((mq[cc][qi][qj] >> bit) & 1u)) ? uq[cc][qi][qj] : 0.f;
+                } else if constexpr (UNPOOL) {
                     const int qi = (PY + i) >> 1, qj = (PX + j) >> 1;
                     const bool ok = rok[i] && cok[j] && qrok[qi] && qcok[qj];
                     d[i][j] = (ok && pv[cc][i][j] == pq[cc][qi][qj]) ? uq[cc][qi][qj] : 0.f;
@@ -212,7 +257,8 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
 // coalesced loads, ~1.3 loads per tile and channel instead of 16; the DePool2D mask is applied per
 // staged element, 3 loads instead of 34 per tile) and every thread reads its 4x4 patch from LDS.
 constexpr int ILDS_E = 12, ILDS_CH = 8;   // staged elements per thread, channels per workgroup
-template <bool UNPOOL, int NT>
+// MB: mask bytes instead of pre / pooled, as in wino_input_kernel (2 loads per staged element).
+template <bool UNPOOL, int NT, bool MB = false>
 __global__ __launch_bounds__(NT) void wino_input_lds_kernel(const WinoParams p, const int chunks) {
     constexpr int ILDS_CAP = ILDS_E * NT;
     __shared__ __attribute__((aligned(16))) float Ls[2][ILDS_CAP];
@@ -236,6 +282,7 @@ __global__ __launch_bounds__(NT) void wino_input_lds_kernel(const WinoParams p, 
         if constexpr (UNPOOL) {
             ok = ok && iy < 2 * p.h2 && ix < 2 * p.w2;
             qoff[i] = ok ? (iy >> 1) * p.w2 + (ix >> 1) : -1;
+            if constexpr (MB) goff[i] = (iy & 1) * 2 + (ix & 1);   // (pre is not read: the mask bit)
         }
     }
     const int tyl = tl / p.ntx, txl = tl - tyl * p.ntx;
@@ -247,7 +294,21 @@ __global__ __launch_bounds__(NT) void wino_input_lds_kernel(const WinoParams p, 
     float v[ILDS_E];
 
     auto fetch = [&](int c) __attribute__((always_inline)) {
-        if constexpr (UNPOOL) {
+        if constexpr (MB) {
+            const uint8_t* mp = p.mask_in + ((size_t)b * p.C1 + c) * hw2;
+            const float* upp = p.x1 + ((size_t)b * p.C1 + c) * hw2;
+            uint32_t mq[ILDS_E];
+            float uq[ILDS_E];
+#pragma unroll
+            for (int i = 0; i < ILDS_E; ++i) {
+                const int qo = qoff[i] >= 0 ? qoff[i] : 0;
+                mq[i] = mp[qo];
+                uq[i] = upp[qo];
+            }
+#pragma unroll
+            for (int i = 0; i < ILDS_E; ++i)
+                v[i] = (qoff[i] >= 0 && ((mq[i] >> goff[i]) & 1u)) ? uq[i] : 0.f;
+        } else if constexpr (UNPOOL) {
             const float* prep = p.pre + ((size_t)b * p.C1 + c) * HW;
             const float* poolp = p.pooled + ((size_t)b * p.C1 + c) * hw2;
             const float* upp = p.x1 + ((size_t)b * p.C1 + c) * hw2;
@@ -633,8 +694,10 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wino_fused_kernel(const Wi
         const bool rok[2] = {(unsigned)wy < (unsigned)p.OH, (unsigned)(wy + 1) < (unsigned)p.OH};
         const bool cok[2] = {(unsigned)wx < (unsigned)p.OW, (unsigned)(wx + 1) < (unsigned)p.OW};
         const bool pair = cok[0] && cok[1];
-        float* ob = p.out + ((size_t)b * p.out_ctot + p.out_c0) * OPL +
-                    (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx;
+        const bool whole = p.pool && rok[1] && cok[1];   // even anchor: the tile is a pooling window
+        float* ob = p.out ? p.out + ((size_t)b * p.out_ctot + p.out_c0) * OPL +
+                                (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx
+                          : nullptr;
         const float* ab = p.add ? p.add + (size_t)b * p.Cout * APL +
                                       (ptrdiff_t)(p.ay0 + wy) * p.AW + p.ax0 + wx
                                 : nullptr;
@@ -645,8 +708,29 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wino_fused_kernel(const Wi
                 const int co = m0 + wm * WTM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (co >= p.Cout) continue;
                 const float bias = bias_r[i][r];
-                float* oc = ob + (size_t)co * OPL;
+                float* oc = ob ? ob + (size_t)co * OPL : nullptr;
                 const float* ac = ab ? ab + (size_t)co * APL : nullptr;
+                if (whole) {   // all four inside the window: values for the pool (+ the plain stores)
+                    float v[2][2];
+#pragma unroll
+                    for (int a = 0; a < 2; ++a) {
+                        v[a][0] = Y[2 * a][i][j][r] + bias;
+                        v[a][1] = Y[2 * a + 1][i][j][r] + bias;
+                        if (ac) {
+                            const f32x2u a2 = *reinterpret_cast<const f32x2u*>(ac + a * p.AW);
+                            v[a][0] += a2[0];
+                            v[a][1] += a2[1];
+                        }
+                        if (p.relu) {
+                            v[a][0] = fmaxf(v[a][0], 0.f);
+                            v[a][1] = fmaxf(v[a][1], 0.f);
+                        }
+                        if (oc) *reinterpret_cast<f32x2u*>(oc + (size_t)a * p.out_W) = f32x2u{v[a][0], v[a][1]};
+                    }
+                    pool_store(p, b, co, p.oy0 + wy, p.ox0 + wx, v[0][0], v[0][1], v[1][0], v[1][1]);
+                    continue;
+                }
+                if (!oc) continue;
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     if (!rok[a]) continue;
@@ -729,21 +813,26 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
             s2[1][j] = m1 - m2 - m3;
         }
         const float bias = p.bias ? p.bias[co] : 0.f;
-        float* o = p.out + ((size_t)b * p.out_ctot + p.out_c0 + co) * OPL +
-                   (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx;
+        float* o = p.out ? p.out + ((size_t)b * p.out_ctot + p.out_c0 + co) * OPL +
+                               (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx
+                         : nullptr;
+        float vt[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // (A^T m) A
             float y[2] = {s2[i][0] + s2[i][1] + s2[i][2], s2[i][1] - s2[i][2] - s2[i][3]};
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                if (okr[i] && okc[j]) {
-                    float v = y[j] + bias;
-                    if (p.add) v += av[cc][i * 2 + j];
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    o[(ptrdiff_t)i * p.out_W + j] = v;
-                }
+                float v = y[j] + bias;
+                if (p.add) v += av[cc][i * 2 + j];
+                if (p.relu) v = fmaxf(v, 0.f);
+                vt[i][j] = v;
+                if (o && okr[i] && okc[j]) o[(ptrdiff_t)i * p.out_W + j] = v;
             }
         }
+        // even anchor: the tile is one pooling window; a tile cut by the window's end is the map's
+        // unpaired last row / column (the caller launches whole windows) and has no pooled value
+        if (p.pool && okr[1] && okc[1])
+            pool_store(p, b, co, p.oy0 + wy, p.ox0 + wx, vt[0][0], vt[0][1], vt[1][0], vt[1][1]);
     }
 }
 
@@ -786,6 +875,7 @@ int wino_geom(const iiseg_conv_desc* d, WinoGeom& g) {
 }
 
 void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
+    const bool mb = unpool && p.mask_in;
     static const int lds = getenv("IISEG_WINO_INPUT_LDS") ? atoi(getenv("IISEG_WINO_INPUT_LDS")) : 1;
     const int ntt = p.nty * p.ntx;
     // tiles per workgroup (one image per workgroup): the size that leaves the fewest idle lanes
@@ -802,8 +892,9 @@ void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
     if (lds && nt && best >= 0.8 && p.Kc % ILDS_CH == 0) {
         const int chunks = (ntt + nt - 1) / nt;
         const dim3 g2(p.B * chunks, p.Kc / ILDS_CH);
-#define WINO_ILDS(U, N) IISEG_LAUNCH((wino_input_lds_kernel<U, N>), g2, dim3(N), 0, s, p, chunks)
-        if (unpool) { if (nt == 256) WINO_ILDS(true, 256); else if (nt == 128) WINO_ILDS(true, 128); else WINO_ILDS(true, 64); }
+#define WINO_ILDS(U, N, ...) IISEG_LAUNCH((wino_input_lds_kernel<U, N, ##__VA_ARGS__>), g2, dim3(N), 0, s, p, chunks)
+        if (mb) { if (nt == 256) WINO_ILDS(true, 256, true); else if (nt == 128) WINO_ILDS(true, 128, true); else WINO_ILDS(true, 64, true); }
+        else if (unpool) { if (nt == 256) WINO_ILDS(true, 256); else if (nt == 128) WINO_ILDS(true, 128); else WINO_ILDS(true, 64); }
         else { if (nt == 256) WINO_ILDS(false, 256); else if (nt == 128) WINO_ILDS(false, 128); else WINO_ILDS(false, 64); }
 #undef WINO_ILDS
         return;
@@ -815,6 +906,13 @@ void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
         return;
     }
     const int py = (p.ty0 - p.pad) & 1, px = (p.tx0 - p.pad) & 1;  // patch-origin parity
+    if (mb) {
+        if (py && px) IISEG_LAUNCH((wino_input_kernel<true, 1, 1, true>), grid, block, 0, s, p);
+        else if (py) IISEG_LAUNCH((wino_input_kernel<true, 1, 0, true>), grid, block, 0, s, p);
+        else if (px) IISEG_LAUNCH((wino_input_kernel<true, 0, 1, true>), grid, block, 0, s, p);
+        else IISEG_LAUNCH((wino_input_kernel<true, 0, 0, true>), grid, block, 0, s, p);
+        return;
+    }
     if (py && px) IISEG_LAUNCH((wino_input_kernel<true, 1, 1>), grid, block, 0, s, p);
     else if (py) IISEG_LAUNCH((wino_input_kernel<true, 1, 0>), grid, block, 0, s, p);
     else if (px) IISEG_LAUNCH((wino_input_kernel<true, 0, 1>), grid, block, 0, s, p);
@@ -881,24 +979,47 @@ extern "C" int iiseg_conv_wino_pack_f32(void* stream, const iiseg_conv_desc* d, 
     return iiseg_check_launch();
 }
 
-extern "C" int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
-                                   const float* x2, const float* pre, const float* pooled,
-                                   const float* U, const float* bias,
-                                   const float* add, float* workspace, float* out,
-                                   uint32_t stages) {
+// the fused pool needs a tile to BE a pooling window: even tile anchor, even window origin, and an
+// even extent unless the window ends at the map's last (unpaired) row / column
+static bool wino_pool_ok(const iiseg_conv_desc* d) {
+    WinoGeom g;
+    if (wino_geom(d, g) != IISEG_OK) return false;
+    const int fullH = d->H + 2 * d->pad - 2, fullW = d->W + 2 * d->pad - 2;
+    if ((d->tile_y0 | d->tile_x0 | d->oy0 | d->ox0) & 1) return false;
+    if ((d->OH & 1) && d->oy0 + d->OH != fullH) return false;
+    if ((d->OW & 1) && d->ox0 + d->OW != fullW) return false;
+    return true;
+}
+
+extern "C" int iiseg_conv_wino_pool_supported(const iiseg_conv_desc* d) {
+    return wino_pool_ok(d) ? 1 : 0;
+}
+
+static int wino_run(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
+                    const float* pre, const float* pooled, const uint8_t* mask_in, const float* U,
+                    const float* bias, const float* add, float* workspace, float* out,
+                    float* pool_out, uint8_t* mask_out, uint32_t stages) {
     WinoGeom g;
     const int st = wino_geom(d, g);
     if (st) return st;
-    if (!x1 || !U || !workspace || !out) return IISEG_ERR_NULL;
+    if (!x1 || !U || !workspace || !(out || pool_out)) return IISEG_ERR_NULL;
     if (d->C2 > 0 && !x2) return IISEG_ERR_NULL;
     const bool unpool = (d->flags & IISEG_CONV_UNPOOL) != 0;
-    if (unpool && (!pre || !pooled)) return IISEG_ERR_NULL;
+    if (mask_in && !unpool) return IISEG_ERR_UNSUPPORTED;
+    if (unpool && !mask_in && (!pre || !pooled)) return IISEG_ERR_NULL;
+    if (mask_out && !pool_out) return IISEG_ERR_UNSUPPORTED;
+    if (pool_out && !wino_pool_ok(d)) return IISEG_ERR_UNSUPPORTED;
     if (((uintptr_t)U & 15) || ((uintptr_t)workspace & 15)) return IISEG_ERR_ALIGN;
-    WinoParams p;
+    WinoParams p = {};
     p.x1 = x1;
     p.x2 = x2;
-    p.pre = pre;
-    p.pooled = pooled;
+    p.pre = mask_in ? nullptr : pre;
+    p.pooled = mask_in ? nullptr : pooled;
+    p.mask_in = mask_in;
+    p.pool = pool_out;
+    p.mask_out = mask_out;
+    p.pool_H = (d->H + 2 * d->pad - 2) / 2;
+    p.pool_W = (d->W + 2 * d->pad - 2) / 2;
     p.h2 = d->H / 2;
     p.w2 = d->W / 2;
     p.U = U;
@@ -1011,6 +1132,24 @@ extern "C" int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const
         IISEG_LAUNCH(wino_output_kernel, dim3(tb, (d->Cout + OCH - 1) / OCH), dim3(256), 0, s,
                            p);
     return iiseg_check_launch();
+}
+
+extern "C" int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
+                                   const float* x2, const float* pre, const float* pooled,
+                                   const float* U, const float* bias,
+                                   const float* add, float* workspace, float* out,
+                                   uint32_t stages) {
+    return wino_run(stream, d, x1, x2, pre, pooled, nullptr, U, bias, add, workspace, out, nullptr,
+                    nullptr, stages);
+}
+
+extern "C" int iiseg_conv_wino_mask_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
+                                        const float* x2, const float* pre, const float* pooled,
+                                        const uint8_t* mask_in, const float* U, const float* bias,
+                                        const float* add, float* workspace, float* out,
+                                        float* pool_out, uint8_t* mask_out, uint32_t stages) {
+    return wino_run(stream, d, x1, x2, pre, pooled, mask_in, U, bias, add, workspace, out, pool_out,
+                    mask_out, stages);
 }
 
 // ================================================================================================

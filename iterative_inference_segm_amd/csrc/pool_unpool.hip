@@ -47,12 +47,14 @@ __global__ __launch_bounds__(256) void unpool_eqmask_kernel(const T* __restrict_
     }
 }
 
-// window form: only pooled outputs [y0,y0+wh) x [x0,x0+ww) of every (h,w) plane, in place
+// window form: only pooled outputs [y0,y0+wh) x [x0,x0+ww) of every (h,w) plane, in place.
+// mask (may be NULL): the DePool2D mask bytes of those windows, bit (y & 1) * 2 + (x & 1) = x == out
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool2x2_window_kernel(const T* __restrict__ x,
-                                                                T* __restrict__ out, int BC, int H,
-                                                                int W, int h, int w, int y0, int x0,
-                                                                int wh, int ww) {
+                                                                T* __restrict__ out,
+                                                                uint8_t* __restrict__ mask, int BC,
+                                                                int H, int W, int h, int w, int y0,
+                                                                int x0, int wh, int ww) {
     const size_t n = (size_t)BC * wh * ww;
     if (n < ((size_t)1 << 31)) {
         // (32-bit index arithmetic: the 64-bit divisions below are a few dozen instructions each, and the windows
@@ -67,7 +69,12 @@ __global__ __launch_bounds__(256) void maxpool2x2_window_kernel(const T* __restr
             const T* r1 = r0 + W;
             const T a = r0[0] > r0[1] ? r0[0] : r0[1];
             const T b = r1[0] > r1[1] ? r1[0] : r1[1];
-            out[((size_t)bc * h + oy) * (size_t)w + ox] = a > b ? a : b;
+            const T m = a > b ? a : b;
+            const size_t o = ((size_t)bc * h + oy) * (size_t)w + ox;
+            out[o] = m;
+            if (mask)
+                mask[o] = (uint8_t)((r0[0] == m ? 1u : 0u) | (r0[1] == m ? 2u : 0u) |
+                                    (r1[0] == m ? 4u : 0u) | (r1[1] == m ? 8u : 0u));
         }
         return;
     }
@@ -81,7 +88,12 @@ __global__ __launch_bounds__(256) void maxpool2x2_window_kernel(const T* __restr
         const T* r1 = r0 + W;
         const T a = r0[0] > r0[1] ? r0[0] : r0[1];
         const T b = r1[0] > r1[1] ? r1[0] : r1[1];
-        out[(bc * h + oy) * (size_t)w + ox] = a > b ? a : b;
+        const T m = a > b ? a : b;
+        const size_t o = (bc * h + oy) * (size_t)w + ox;
+        out[o] = m;
+        if (mask)
+            mask[o] = (uint8_t)((r0[0] == m ? 1u : 0u) | (r0[1] == m ? 2u : 0u) |
+                                (r1[0] == m ? 4u : 0u) | (r1[1] == m ? 8u : 0u));
     }
 }
 
@@ -188,13 +200,13 @@ int unpool(void* stream, const T* up, const T* pre, const T* pooled, T* out, int
 
 template <typename T>
 int maxpool_window(void* stream, const T* x, T* out, int32_t BC, int32_t H, int32_t W, int32_t y0,
-                   int32_t x0, int32_t wh, int32_t ww) {
+                   int32_t x0, int32_t wh, int32_t ww, uint8_t* mask = nullptr) {
     if (!x || !out) return IISEG_ERR_NULL;
     if (BC <= 0 || H < 2 || W < 2 || y0 < 0 || x0 < 0 || wh <= 0 || ww <= 0 || y0 + wh > H / 2 ||
         x0 + ww > W / 2)
         return IISEG_ERR_SHAPE;
     IISEG_LAUNCH(maxpool2x2_window_kernel<T>, dim3(grid_for((size_t)BC * wh * ww)), dim3(256),
-                       0, (hipStream_t)stream, x, out, BC, H, W, H / 2, W / 2, y0, x0, wh, ww);
+                       0, (hipStream_t)stream, x, out, mask, BC, H, W, H / 2, W / 2, y0, x0, wh, ww);
     return iiseg_check_launch();
 }
 
@@ -257,6 +269,12 @@ extern "C" int iiseg_maxpool2x2_window_f32(void* stream, const float* x, float* 
                                            int32_t H, int32_t W, int32_t y0, int32_t x0,
                                            int32_t wh, int32_t ww) {
     return maxpool_window<float>(stream, x, out, BC, H, W, y0, x0, wh, ww);
+}
+extern "C" int iiseg_maxpool2x2_mask_window_f32(void* stream, const float* x, float* out,
+                                                uint8_t* mask, int32_t BC, int32_t H, int32_t W,
+                                                int32_t y0, int32_t x0, int32_t wh, int32_t ww) {
+    if (!mask) return IISEG_ERR_NULL;
+    return maxpool_window<float>(stream, x, out, BC, H, W, y0, x0, wh, ww, mask);
 }
 extern "C" int iiseg_maxpool2x2_window_f64(void* stream, const double* x, double* out, int32_t BC,
                                            int32_t H, int32_t W, int32_t y0, int32_t x0,

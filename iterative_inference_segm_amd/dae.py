@@ -182,15 +182,65 @@ class StandardDAE:
             return frozenset()
         levels = set()
         for L in range(1, self.total + 1):
-            enc = self.enc['conv%d_%d' % (L, self.conv_before_pool)]
+            name = 'conv%d_%d' % (L, self.conv_before_pool)
+            enc = self.enc[name]
             fed_by_h = self.conv_before_pool == 1 and \
                 ('input' if L == 1 else 'pool%d' % (L - 1)) in self.concat_h
+            if fed_by_h and name in self.hsplit and self._wino_f32(self.hsplit[name][1]):
+                # h split off the concat: the y-half conv adds the cached h-half in its epilogue and
+                # pools after that add -- the same values the pool kernel would see (the Winograd
+                # output transform only: the halo kernels' pooling epilogue takes no add)
+                enc, fed_by_h = self.hsplit[name][1], False
             # (the levels of the fp32-NCHW form of `scores`: a Conv built for C8 input answers for the
             # form that runs on NCHW input)
-            if not fed_by_h and enc.pool_fusable(False) and enc.mask_ok(False) and \
-                    self.dec['up_conv%d' % L].mask_ok(False):
+            if fed_by_h or not enc.mask_ok(False) or not self.dec['up_conv%d' % L].mask_ok(False):
+                continue
+            # halo kernels pool (and write the bytes) in their epilogue; fp32 Winograd layers do at an
+            # even tile anchor, else the pool kernel writes the bytes (`scores`)
+            if enc.pool_fusable(False) or self._wino_f32(enc):
                 levels.add(L)
         return frozenset(levels)
+
+    @staticmethod
+    def _wino_f32(conv):
+        """The layer runs the fp32 Winograd form (pool + mask bytes in its output transform)."""
+        return conv.wino and conv.mma == 'f32' and conv.dtype == torch.float32
+
+    def _conv_pool(self, conv, p, i, t, kw, dep, primed, session, masked, masks, hb=None):
+        """Encoder conv i of level p + 1 (hb: the cached h-half of a split concat, added in the
+        epilogue).  The last conv of a level on a kernel with a pooling epilogue (halo kernels, fp32
+        Winograd at an even tile anchor) also writes pool_p: the window is widened to whole pooling
+        windows, the extra row / column recomputed to the values it already has.  Byte-mask levels
+        (`_mask_levels`) then write the mask bytes instead of the pre-pool map; where the pool is
+        not fused the pool kernel writes them.  Returns (t, fused pooled map or None, mask bytes
+        for the pool kernel or None); t is a shape-only stand-in when the map was not stored."""
+        pw_ = None
+        fh, fw = conv.out_hw(t.shape[2], t.shape[3])
+        if i == self.conv_before_pool and not self.bn and (hb is None or self._wino_f32(conv)):
+            pw_ = conv.pool_window(t.shape[2], t.shape[3], dep if primed else None, c8=False,
+                                   anchor=kw['anchor'])
+        fused_pool = pool_mask = None
+        if pw_ is not None:
+            if primed:
+                fused_pool = session['pool%d' % (p + 1)]
+                kw.update(window=pw_, place=(pw_[0], pw_[1]))
+            else:
+                fused_pool = torch.empty((t.shape[0], conv.Cout, fh // 2, fw // 2),
+                                         dtype=t.dtype, device=t.device)
+            kw['pool_out'] = fused_pool
+        if hb is not None:
+            kw.update(add=hb, add_off=kw['place'] if 'place' in kw else (0, 0))
+        if (p + 1) not in masked or i != self.conv_before_pool:
+            return conv(t, **kw), fused_pool, None
+        m = session['mask%d' % (p + 1)] if primed else \
+            torch.empty((t.shape[0], conv.Cout, fh // 2, fw // 2), dtype=torch.uint8, device=t.device)
+        masks[p + 1] = m
+        if pw_ is None:                  # (fp32 Winograd at an odd anchor) the pool kernel writes them
+            return conv(t, **kw), None, m
+        kw.update(mask_out=m, store_out=False)
+        conv(t, **kw)
+        # the pre-pool map is not stored: a shape-only stand-in from here on
+        return torch.empty((t.shape[0], conv.Cout, fh, fw), dtype=t.dtype, device='meta'), fused_pool, None
 
     def new_session(self, h_list=None, y=None, tags=None):
         """State of one refinement loop (h fixed, y evolving): see `scores`.
@@ -290,7 +340,7 @@ class StandardDAE:
             return lo, max(hi - lo, 0)
 
         for p in range(self.total):                      # fcn_down.py:77-136
-            fused_pool = None
+            fused_pool = pool_mask = None
             for i in range(1, self.conv_before_pool + 1):
                 name = 'conv%d_%d' % (p + 1, i)
                 conv = self.enc[name]
@@ -328,42 +378,15 @@ class StandardDAE:
                         hx0, hw = clip(hd[1] + conv_h.pad - (conv_h.KW - 1), hd[1] + hd[3] + conv_h.pad,
                                        hb.shape[3])
                         conv_h(pending_h, window=(hy0, hx0, hh, hw), out=hb, place=(hy0, hx0))
-                    off = kw['place'] if 'place' in kw else (0, 0)
-                    t = conv_y(t, add=hb, add_off=off, **kw)
                     pending_h = None
+                    t, fused_pool, pool_mask = self._conv_pool(conv_y, p, i, t, kw, dep, primed, session,
+                                                               masked, masks, hb=hb)
                 elif pending_h is not None:              # h first, then features (P13)
                     t = conv(pending_h, x2=t, **kw)
                     pending_h = None
                 else:
-                    # last conv of the level on the halo kernel: its epilogue also writes pool_p
-                    # (the window is widened to whole pooling windows; the extra row / column is
-                    # recomputed to the values it already has)
-                    pw_ = None
-                    if i == self.conv_before_pool and not self.bn:
-                        pw_ = conv.pool_window(t.shape[2], t.shape[3], dep if primed else None, c8=False)
-                    if pw_ is not None:
-                        fh, fw = conv.out_hw(t.shape[2], t.shape[3])
-                        if primed:
-                            pooled_t = session['pool%d' % (p + 1)]
-                            kw.update(window=pw_, place=(pw_[0], pw_[1]))
-                        else:
-                            pooled_t = torch.empty((t.shape[0], conv.Cout, fh // 2, fw // 2),
-                                                   dtype=t.dtype, device=t.device)
-                        fused_pool = pooled_t
-                        kw['pool_out'] = pooled_t
-                    if (p + 1) in masked:
-                        if pw_ is None:
-                            raise RuntimeError('internal: level %d was planned for byte masks but '
-                                               'its pool is not fused' % (p + 1))
-                        m = session['mask%d' % (p + 1)] if primed else \
-                            torch.empty(pooled_t.shape, dtype=torch.uint8, device=t.device)
-                        masks[p + 1] = m
-                        kw.update(mask_out=m, store_out=False)
-                        conv(t, **kw)
-                        # the pre-pool map is not stored: a shape-only stand-in from here on
-                        t = torch.empty((t.shape[0], conv.Cout, fh, fw), dtype=t.dtype, device='meta')
-                    else:
-                        t = conv(t, **kw)
+                    t, fused_pool, pool_mask = self._conv_pool(conv, p, i, t, kw, dep, primed, session,
+                                                               masked, masks)
                 if self.bn:
                     ops.bn_affine(t, self.enc_bn[name], window=dep if primed else None)
                 if session is not None and not primed:
@@ -380,9 +403,10 @@ class StandardDAE:
                 qy0, qh = clip(dep[0] // 2, (dep[0] + dep[2] + 1) // 2, buf.shape[2])
                 qx0, qw = clip(dep[1] // 2, (dep[1] + dep[3] + 1) // 2, buf.shape[3])
                 dep = (qy0, qx0, qh, qw)
-                t = buf if fused_pool is not None else ops.maxpool2x2(t, out=buf, window=dep)
+                t = buf if fused_pool is not None else \
+                    ops.maxpool2x2(t, out=buf, window=dep, mask=pool_mask)
             else:
-                t = fused_pool if fused_pool is not None else ops.maxpool2x2(t)   # :122
+                t = fused_pool if fused_pool is not None else ops.maxpool2x2(t, mask=pool_mask)   # :122
                 if session is not None:
                     session['pool%d' % (p + 1)] = t
             pool[p + 1] = t

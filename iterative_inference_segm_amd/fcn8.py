@@ -138,8 +138,10 @@ class FCN8:
                 if primed:
                     kw.update(window=dep, out=session[name], place=(dep[0], dep[1]))
                 if name == names[-1] and pending is None:
-                    # last conv of the block on the halo kernel: the pool rides in its epilogue
-                    pw_ = conv.pool_window(t.shape[2], t.shape[3], dep if primed else None, c8=c8)
+                    # last conv of the block on the halo kernel (or an fp32 Winograd layer at an even
+                    # tile anchor): the pool rides in its epilogue
+                    pw_ = conv.pool_window(t.shape[2], t.shape[3], dep if primed else None, c8=c8,
+                                           anchor=kw['anchor'])
                     if pw_ is not None:
                         if primed:
                             fused_pool = session['pool%d' % (bi + 1)]

@@ -42,6 +42,9 @@ WINO_MIN_COUT = int(os.environ.get('IISEG_WINO_MIN_COUT', '128'))
 WINO_FUSED_MAX_CIN = int(os.environ.get('IISEG_WINO_FUSED_MAX_CIN', '256'))
 # fuse the 2x2 max-pool behind a halo-kernel conv into that conv's epilogue
 POOL_FUSE = os.environ.get('IISEG_POOL_FUSE', '1') != '0'
+# ... and behind an fp32 Winograd layer (even tile anchor) into its output transform, with the DePool2D
+# mask bytes on both sides of such layers (IISEG_WINO_POOL_FUSE=0: pre / pooled maps, the pool kernel)
+WINO_POOL_FUSE = os.environ.get('IISEG_WINO_POOL_FUSE', '1') != '0'
 # float64 path: the same in the halo-tile float64 kernel's epilogue (conv_halo_f64.hip)
 F64_POOL_FUSE = os.environ.get('IISEG_F64_POOL_FUSE', '1') != '0'
 # ... and DePool2D masks as bytes between its encoder / decoder layers (the float64 pre-pool map is never stored)
@@ -438,7 +441,8 @@ class Conv:
         B, C1 = x1.shape[0], x1.shape[1]
         if masked:
             if not self.mask_ok(False):
-                raise RuntimeError('DePool2D byte masks need a halo-kernel layer (Conv.mask_ok)')
+                raise RuntimeError('DePool2D byte masks need a halo-kernel or fp32 Winograd layer '
+                                   '(Conv.mask_ok)')
             if mask_in is not None and (pre is not None or mask_in.dtype != torch.uint8 or
                                         mask_in.shape != x1.shape or unpool_hw is None or
                                         (unpool_hw[0] // 2, unpool_hw[1] // 2) != tuple(x1.shape[2:])):
@@ -535,10 +539,17 @@ class Conv:
                 self.lib.iiseg_conv_halo_bf16_supported(C.byref(d)):
             return self._call_halo_bf16(d, x1, x2, pre, pooled, add, out, pool_out, mask_in,
                                         mask_out, prof, B, H, W)
-        if not masked and pool_out is None and self.wino and \
+        # (fp32 operands: the pool and the mask bytes ride in the Winograd kernels too, iiseg_conv_wino_mask_f32)
+        if self.wino and (self.mma == 'f32' or (not masked and pool_out is None)) and \
                 self.lib.iiseg_conv_wino_supported(C.byref(d)) and \
                 self._form_by_full_map(self.lib.iiseg_conv_wino_supported, d):
-            return self._call_wino(d, x1, x2, pre, pooled, add, out, prof)
+            if pool_out is not None:
+                fh, fw = self.out_hw(H, W)
+                if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2) or pool_out.dtype != dt or \
+                        not self.lib.iiseg_conv_wino_pool_supported(C.byref(d)):
+                    raise RuntimeError('conv + pool fusion is not available for this launch '
+                                       '(Winograd: even tile anchor and whole pooling windows)')
+            return self._call_wino(d, x1, x2, pre, pooled, add, out, prof, mask_in, pool_out, mask_out)
         if masked and dt == torch.float64:
             if pool_out is not None:
                 fh, fw = self.out_hw(H, W)
@@ -732,11 +743,13 @@ class Conv:
             self._form_cache['f64_halo'] = ok
         return ok
 
-    def pool_fusable(self, c8=None):
-        """True if this layer runs on a halo kernel whose epilogue can do the 2x2 max-pool.  `c8`:
+    def pool_fusable(self, c8=None, anchor=None):
+        """True if this layer runs on a kernel whose epilogue can do the 2x2 max-pool.  `c8`:
         whether the call will hand it a C8 tensor (None: the form the layer was built for) -- a
         layer built with mma='bf16c8' and called on fp32 NCHW input runs the 'bf16' forms, and
-        those decide."""
+        those decide.  `anchor`: the Winograd tile anchor of the call -- an fp32 Winograd layer
+        pools in its output transform only at an even anchor (a 2x2 tile is then one pooling
+        window); without an anchor such a layer answers False."""
         if not POOL_FUSE:
             return False
         if self.dtype == torch.float64:
@@ -749,12 +762,15 @@ class Conv:
             return True
         if self.mma == 'bf16':
             return self.halo_bf16
-        return not (self.wino or self.kernel != 'conv_halo_f32_kernel' or not 16 < self.Cout < 256)
+        if self.wino:
+            return anchor is not None and WINO_POOL_FUSE and not (int(anchor[0]) & 1 or int(anchor[1]) & 1)
+        return not (self.kernel != 'conv_halo_f32_kernel' or not 16 < self.Cout < 256)
 
     def mask_ok(self, c8=None):
-        """True if this layer can take / produce DePool2D masks as bytes (halo kernels only, and
-        only where the byte form runs the very kernel the pre / pooled form runs).  `c8` as in
-        `pool_fusable`."""
+        """True if this layer can take / produce DePool2D masks as bytes (halo kernels and the fp32
+        Winograd form, only where the byte form runs the very kernel the pre / pooled form runs).
+        `c8` as in `pool_fusable`.  (A Winograd layer produces them with its fused pool at an even
+        tile anchor; at an odd one its caller pools with `maxpool2x2(..., mask=)`.)"""
         if self.c8 and c8 is not False:
             return True
         if self.dtype == torch.float64:
@@ -762,16 +778,21 @@ class Conv:
             return F64_MASKS and (self.KH, self.KW) == (3, 3) and self.dil == 1 and not self.transposed and \
                 not self.wino_f64 and self._f64_halo_runs()
         if self.dtype != torch.float32 or (self.KH, self.KW) != (3, 3) or self.dil != 1 or \
-                self.transposed or self.kernel != 'conv_halo_f32_kernel' or self.wino_bf16:
+                self.transposed or self.wino_bf16:
+            return False
+        if self.mma == 'f32' and self.wino:
+            return WINO_POOL_FUSE
+        if self.kernel != 'conv_halo_f32_kernel':
             return False
         return self.halo_bf16 if self.mma == 'bf16' else not self.wino
 
-    def pool_window(self, H, W, region=None, c8=None):
+    def pool_window(self, H, W, region=None, c8=None, anchor=None):
         """If the 2x2 max-pool that follows this layer can be fused into its epilogue: the conv
         window (y0, x0, h, w) to launch so that every pooling window touching `region` (of the
         conv output; None = the whole map) is whole -- even origin, even extent unless it ends at
-        the map's last row / column.  None if the layer does not run on the halo kernel."""
-        if not self.pool_fusable(c8):
+        the map's last row / column.  None if the layer has no such epilogue (`pool_fusable`,
+        `anchor` as there)."""
+        if not self.pool_fusable(c8, anchor):
             return None
         fh, fw = self.out_hw(H, W)
         if region is None:
@@ -1121,8 +1142,10 @@ class Conv:
             prof.append(('wino64_gemm_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
         return out
 
-    def _call_wino(self, d, x1, x2, pre, pooled, add, out, prof):
-        """Winograd F(2x2,3x3) form of the layer (include/iiseg.h, iiseg_conv_wino_f32)."""
+    def _call_wino(self, d, x1, x2, pre, pooled, add, out, prof, mask_in=None, pool_out=None,
+                   mask_out=None):
+        """Winograd F(2x2,3x3) form of the layer (include/iiseg.h, iiseg_conv_wino_f32; with a
+        fused pool or mask bytes iiseg_conv_wino_mask_f32)."""
         lib = self.lib
         if self._U is None:
             self._U = torch.empty(lib.iiseg_conv_wino_weight_elems(C.byref(d)), dtype=torch.float32,
@@ -1130,13 +1153,20 @@ class Conv:
             check(lib.iiseg_conv_wino_pack_f32(_stream(), C.byref(d), _ptr(self.W), self.so, self.sc,
                                                _ptr(self._U)), 'iiseg_conv_wino_pack_f32')
         ws = _wino_workspace(lib.iiseg_conv_wino_workspace_elems(C.byref(d)), x1.device)
-        args = (C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre), _ptr(pooled), _ptr(self._U),
-                _ptr(self.b), _ptr(add), _ptr(ws), _ptr(out))
+        if mask_in is None and pool_out is None:
+            fn, what = lib.iiseg_conv_wino_f32, 'iiseg_conv_wino_f32'
+            args = (C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre), _ptr(pooled), _ptr(self._U),
+                    _ptr(self.b), _ptr(add), _ptr(ws), _ptr(out))
+        else:
+            fn, what = lib.iiseg_conv_wino_mask_f32, 'iiseg_conv_wino_mask_f32'
+            args = (C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre), _ptr(pooled), _ptr(mask_in, torch.uint8),
+                    _ptr(self._U), _ptr(self.b), _ptr(add), _ptr(ws), _ptr(out), _ptr(pool_out),
+                    _ptr(mask_out, torch.uint8))
         # (a skip-add would be read by the fused kernel's epilogue, uncoalesced and with nothing to
         # hide its latency: such layers keep the separate, coalesced output transform)
         fused = 8 if (self.Cin <= WINO_FUSED_MAX_CIN and self.Cin % 32 == 0 and add is None) else 0
         if prof is None:
-            check(lib.iiseg_conv_wino_f32(_stream(), *args, 7 | fused), 'iiseg_conv_wino_f32')
+            check(fn(_stream(), *args, 7 | fused), what)
             return out
         # profiling: the kernels separately, events around each
         stages = (1 | fused, 2 | fused) if fused else (1, 2, 4)
@@ -1147,7 +1177,7 @@ class Conv:
         gemm_flops = 16 * 2.0 * self.Cin * self.Cout * T      # multiplies actually issued
         ev0 = _ev()
         for i, stage in enumerate(stages):
-            check(lib.iiseg_conv_wino_f32(_stream(), *args, stage), 'iiseg_conv_wino_f32')
+            check(fn(_stream(), *args, stage), what)
             ev1 = _ev()
             prof.append((names[i], gemm_flops if i == 1 else 0.0, ev0, ev1))
             ev0 = ev1
@@ -1346,11 +1376,22 @@ def pool_mask_c8(pre, pooled, mask, origin, full_hw, window, x3=False):
     return pooled
 
 
-def maxpool2x2(x, out=None, window=None):
-    """`window` = (y0, x0, h, w) in pooled coordinates: only that region of `out` is written."""
+def maxpool2x2(x, out=None, window=None, mask=None):
+    """`window` = (y0, x0, h, w) in pooled coordinates: only that region of `out` is written.
+    `mask` (uint8, out's shape; float32): also the DePool2D mask bytes of those windows (bit
+    (y&1)*2+(x&1) = x == out, as a conv's `mask_out`)."""
     B, Cc, H, W = x.shape
     if out is None:
         out = torch.empty((B, Cc, H // 2, W // 2), dtype=x.dtype, device=x.device)
+    if mask is not None:
+        if x.dtype != torch.float32 or mask.dtype != torch.uint8 or mask.shape != out.shape:
+            raise RuntimeError('maxpool2x2 mask: float32 input, uint8 of the pooled shape')
+        y0, x0, wh, ww = window if window is not None else (0, 0, H // 2, W // 2)
+        check(_lib.load().iiseg_maxpool2x2_mask_window_f32(_stream(), _ptr(x), _ptr(out),
+                                                            _ptr(mask, torch.uint8), B * Cc, H, W,
+                                                            y0, x0, wh, ww),
+              'iiseg_maxpool2x2_mask_window_f32')
+        return out
     if window is not None:
         y0, x0, wh, ww = window
         check(_fn('maxpool2x2_window', x.dtype)(_stream(), _ptr(x, x.dtype), _ptr(out, x.dtype),
