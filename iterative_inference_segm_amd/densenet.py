@@ -357,7 +357,7 @@ class FCDenseNet:
         copy of x into the graph's input + one replay.  Same kernels in the same order: same bits.  The results
         are handed out as copies -- a later forward does not overwrite what an earlier one returned."""
         dev = x.device
-        key = (tuple(x.shape), ops._WS_TAG[0])
+        key = (tuple(x.shape), ops.current_workspace_tag())
         ctx = self._c8_graphs.get(key)
         if ctx is None:
             while len(self._c8_graphs) >= 2:

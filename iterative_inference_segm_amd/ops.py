@@ -5,6 +5,7 @@ call through the C ABI (include/iiseg.h).  All ops enqueue on torch's current st
 never synchronise.  Two arithmetic modes: float32 (throughput path) and float64 (strict-parity
 path: the reference's CPU numerics), selected by the tensors' dtype.
 """
+import collections
 import ctypes as C
 import os
 
@@ -106,15 +107,13 @@ def _bf16_static_pick(Cin, OW):
 C8_M16 = os.environ.get('IISEG_C8_M16', '1') != '0'
 BF16_UPCONV1 = os.environ.get('IISEG_BF16_UPCONV1', '0') != '0'
 BF16_WINO_MIN_COUT = int(os.environ.get('IISEG_BF16_WINO_MIN_COUT', '256'))
-_wino_ws = {}   # device -> workspace tensor shared by all layers (launches are stream-ordered)
-_wino_ws64 = {}
-_bn_ws = {}     # device -> BN partial-sum workspace (stream-ordered reuse)
-
-
 # Scratch is reused by consecutive launches of ONE stream (stream-ordered).  Engines that run
 # concurrently on different streams (bench.py --streams 2) must not share it: every
-# IterativeInference tags its launches (`workspace_tag`), and the caches are keyed (device, tag).
-_WS_TAG = [0]
+# IterativeInference tags its launches (`workspace_tag`), and the cache is keyed (kind, device, tag).
+# Kinds, in `workspace_refs` order: fp32 / float64 Winograd + GEMM scratch, BN partial sums, split-K slabs (C8 m16)
+_SCRATCH_KINDS = {'f32': torch.float32, 'f64': torch.float64, 'bn': torch.float64, 'm16': torch.uint8}
+_scratch = {}
+_ws_tag = [0]
 
 
 class workspace_tag:
@@ -124,55 +123,39 @@ class workspace_tag:
         self.tag, self.prev = tag, None
 
     def __enter__(self):
-        self.prev, _WS_TAG[0] = _WS_TAG[0], self.tag
+        self.prev, _ws_tag[0] = _ws_tag[0], self.tag
         return self
 
     def __exit__(self, *exc):
-        _WS_TAG[0] = self.prev
+        _ws_tag[0] = self.prev
         return False
 
 
-def _ws_key(device):
-    return (device, _WS_TAG[0])
+def current_workspace_tag():
+    return _ws_tag[0]
 
 
-def _wino_workspace(n, device):
-    key = _ws_key(device)
-    ws = _wino_ws.get(key)
+def _workspace(kind, n, device):
+    """At least `n` elements of scratch of `kind` under the current workspace tag.  One grow rule: the
+    old tensor is dropped before the larger one is allocated."""
+    key = (kind, device, _ws_tag[0])
+    ws = _scratch.get(key)
     if ws is None or ws.numel() < n:
-        _wino_ws[key] = None
-        ws = _wino_ws[key] = torch.empty(int(n), dtype=torch.float32, device=device)
+        _scratch[key] = None
+        ws = _scratch[key] = torch.empty(int(n), dtype=_SCRATCH_KINDS[kind], device=device)
     return ws
 
 
-def _wino_workspace64(n, device):
-    """float64 scratch of the current workspace tag (Winograd V / M, the GEMM form's V / partial sums)."""
-    key = _ws_key(device)
-    ws = _wino_ws64.get(key)
-    if ws is None or ws.numel() < n:
-        _wino_ws64[key] = None
-        ws = _wino_ws64[key] = torch.empty(int(n), dtype=torch.float64, device=device)
-    return ws
-
-
-_m16_ws = {}
-
-
-def _m16_workspace(nbytes, device):
-    """Scratch of the split-K launches of the 16-row C8 kernel (fp32 slabs of partial sums)."""
-    key = _ws_key(device)
-    ws = _m16_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _m16_ws[key] = None
-        ws = _m16_ws[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-    return ws
+def drop_workspaces(tag):
+    """Forget the scratch buffers of `tag` (an engine that goes away)."""
+    for key in [k for k in _scratch if k[2] == tag]:
+        _scratch.pop(key, None)
 
 
 def workspace_refs(device):
     """The scratch tensors launches under the current workspace tag point into (fp32 / float64
-    Winograd workspaces, BN partial sums): a captured HIP graph keeps them alive."""
-    key = _ws_key(device)
-    return tuple(c.get(key) for c in (_wino_ws, _wino_ws64, _bn_ws, _m16_ws))
+    Winograd workspaces, BN partial sums, split-K slabs): a captured HIP graph keeps them alive."""
+    return tuple(_scratch.get((kind, device, _ws_tag[0])) for kind in _SCRATCH_KINDS)
 
 
 def workspace_ptrs(device):
@@ -259,10 +242,52 @@ def _fn(name, dtype):
     return getattr(_lib.load(), 'iiseg_%s_%s' % (name, _SUFFIX[dtype]))
 
 
+def _launch(kernel, flops, fn, *args):
+    """One call `fn(stream, *args)` of the library.  With CONV_PROFILE (read here, at call time) the call --
+    and nothing else: operands, packing and scratch are the caller's business before it -- sits between two
+    marks on the launch stream and is recorded as (kernel, flops, start, end).  `kernel` may be a function
+    that names the kernel: it is evaluated only when profiling."""
+    prof = CONV_PROFILE
+    if prof is None:
+        check(fn(_stream(), *args), fn.__name__)
+        return
+    ev0 = _ev()
+    check(fn(_stream(), *args), fn.__name__)
+    ev1 = _ev()
+    prof.append((kernel() if callable(kernel) else kernel, flops, ev0, ev1))
+
+
+def _launch_staged(fn, args, whole, stages):
+    """The entry points whose last argument is a bit set of the kernels to run: one call with `whole`, or,
+    under CONV_PROFILE, one call per (kernel, bits, flops) of `stages`, each recorded between its own marks."""
+    prof = CONV_PROFILE
+    if prof is None:
+        check(fn(_stream(), *args, whole), fn.__name__)
+        return
+    ev0 = _ev()
+    for kernel, bits, flops in stages:
+        check(fn(_stream(), *args, bits), fn.__name__)
+        ev1 = _ev()
+        prof.append((kernel, flops, ev0, ev1))
+        ev0 = ev1
+
+
+# the descriptor and operands of one NCHW launch of a Conv, as its `_run_<form>` methods take them
+_Launch = collections.namedtuple('_Launch', 'd x1 x2 pre pooled add out pool_out mask_in mask_out')
+
+
 class Conv:
     """One convolution layer bound to its weights: packed-weight (+ gather-table) cache per
     input geometry.  Weight layouts: 'oihw' (Lasagne Conv2DLayer W[out,in,kh,kw], P1) or
-    'iohw' (DilatedConv2DLayer W[in,out,kh,kw], P11)."""
+    'iohw' (DilatedConv2DLayer W[in,out,kh,kw], P11).  A call on NCHW tensors is three steps:
+    `_describe_call` (host only), `_choose` (the kernel FORM, by name; host only), `_run_<form>`."""
+
+    # every form `_choose` can name; each has a `_run_<form>`
+    FORMS = ('wino_bf16', 'halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32', 'pool_f64', 'pool_f32',
+             'gemm_bf16', 'gemm_f32', 'gemm_f64', 'wino_f64', 'direct')
+    # ... those with the 2x2 max-pool in their epilogue, and those that read / write DePool2D mask bytes
+    POOL_FORMS = ('halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32', 'pool_f64', 'pool_f32')
+    MASK_FORMS = ('halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32')
 
     def __init__(self, W, b, pad, relu, dil=1, layout='oihw', device='cuda', dtype=torch.float32,
                  transposed=False, mma=None):
@@ -300,6 +325,8 @@ class Conv:
         else:
             raise ValueError(layout)
         self.pad, self.dil, self.relu = int(pad), int(dil), bool(relu)
+        # a plain 3x3 layer: what every Winograd / halo / C8 form requires
+        self.plain3x3 = (self.KH, self.KW) == (3, 3) and self.dil == 1 and not self.transposed
         taps = (self.KH, self.KW) in ((1, 1), (3, 3)) or \
             ((self.KH, self.KW) == (4, 4) and dtype == torch.float32)
         # which kernel family the C ABI dispatches this filter shape to
@@ -321,25 +348,21 @@ class Conv:
                      (self.dil in (2, 4, 8, 16) and self.Cout <= 16)):
                 self.kernel = 'conv_halo_f32_kernel'
             self.via_im2col = False
-        self.wino = (dtype == torch.float32 and (self.KH, self.KW) == (3, 3) and self.dil == 1 and
-                     not self.transposed and self.Cin % 16 == 0 and
+        self.wino = (dtype == torch.float32 and self.plain3x3 and self.Cin % 16 == 0 and
                      0 < WINO_MIN_CIN <= self.Cin and self.Cout >= WINO_MIN_COUT)
-        self.wino_f64 = (dtype == torch.float64 and WINO_F64 and (self.KH, self.KW) == (3, 3) and
-                         self.dil == 1 and not self.transposed and self.Cin % 16 == 0 and
+        self.wino_f64 = (dtype == torch.float64 and WINO_F64 and self.plain3x3 and self.Cin % 16 == 0 and
                          self.Cin >= WINO_F64_MIN_CIN and self.Cout >= WINO_F64_MIN_COUT)
-        self.wino_bf16 = (self.mma == 'bf16' and (self.KH, self.KW) == (3, 3) and self.dil == 1 and
-                          not self.transposed and self.Cin >= BF16_WINO_MIN_CIN and
+        self.wino_bf16 = (self.mma == 'bf16' and self.plain3x3 and self.Cin >= BF16_WINO_MIN_CIN and
                           self.Cout >= BF16_WINO_MIN_COUT)
         # bf16 mode: every other plain 3x3 layer on the bf16 halo kernel (conv_halo_bf16.hip)
-        self.halo_bf16 = (self.mma == 'bf16' and (self.KH, self.KW) == (3, 3) and self.dil == 1 and
-                          not self.transposed and not self.wino_bf16)
-        self.c8 = self.c8 and (self.KH, self.KW) == (3, 3) and self.dil == 1 and not self.transposed
+        self.halo_bf16 = self.mma == 'bf16' and self.plain3x3 and not self.wino_bf16
+        self.c8 = self.c8 and self.plain3x3
         self._U = None
         self._U16 = None
         self._W16 = None
         self._W16c8 = None
         self._form_cache = {}
-        self._plans = {}
+        self._descs = {}
         self._packs = {}
 
     def out_hw(self, H, W):
@@ -352,12 +375,15 @@ class Conv:
         """Nominal 2*Cin*Cout*k*k*OH*OW*B (SURVEY 6.2 convention)."""
         return 2.0 * self.Cin * self.Cout * self.KH * self.KW * OH * OW * B
 
-    def _plan(self, B, C1, C2, H, W, window, add_geom, unpool, out_slice=None, place=None,
-              anchor=(0, 0)):
+
+    def _describe(self, B, C1, C2, H, W, window, add_geom, unpool, out_slice=None, place=None,
+                  anchor=(0, 0)):
+        """The planned ConvDesc of a launch (iiseg_conv_plan / _f64 fill Kpad, Mpad and refuse bad
+        geometry): no device, no stream.  Cached per argument tuple."""
         key = (B, C1, C2, H, W, window, add_geom, unpool, out_slice, place, anchor)
-        plan = self._plans.get(key)
-        if plan is not None:
-            return plan
+        d = self._descs.get(key)
+        if d is not None:
+            return d
         if C1 + C2 != self.Cin:
             raise RuntimeError('conv expects %d input channels, got %d+%d' % (self.Cin, C1, C2))
         fullH, fullW = self.out_hw(H, W)
@@ -375,37 +401,231 @@ class Conv:
         if place is not None:
             d.out_H, d.out_W, d.out_y0, d.out_x0 = place
         d.tile_y0, d.tile_x0 = int(anchor[0]) & 1, int(anchor[1]) & 1
-        so, sc = self.so, self.sc
         if self.via_im2col:
             # logical layer: 1x1 over C*KH*KW channels of the im2col'd tensor (OH x OW)
             d.C1, d.C2, d.H, d.W = C1 * self.KH * self.KW, 0, fullH, fullW
             d.KH = d.KW = 1
-            so, sc = self.Cin * self.KH * self.KW, 1
-        # the packed weights (and the gather table of the table-driven kernel) depend on the input
-        # geometry only: one copy per (C1, C2, H, W), shared by every window / placement variant
-        pkey = (d.C1, d.C2, d.H, d.W)
-        packed = self._packs.get(pkey)
         if self.dtype == torch.float64:
             check(self.lib.iiseg_conv_plan_f64(C.byref(d)), 'iiseg_conv_plan_f64')
-            if packed is None:
-                wp = torch.empty(d.Kpad * d.Mpad, dtype=self.dtype, device=self.W.device)
-                check(self.lib.iiseg_conv_pack_f64(_stream(), C.byref(d), _ptr(self.W, self.dtype),
-                                                   so, sc, _ptr(wp, self.dtype)),
-                      'iiseg_conv_pack_f64')
-                packed = self._packs[pkey] = (wp, None)
         else:
             check(self.lib.iiseg_conv_plan(C.byref(d)), 'iiseg_conv_plan')
-            if packed is None:
-                wp = torch.empty(d.Kpad * d.Mpad, dtype=self.dtype, device=self.W.device)
+        self._descs[key] = d
+        return d
+
+    def _packed(self, d):
+        """(wp, ktab): the direct kernels' packed weights (+ gather table), made on first use.  They depend
+        on the input geometry only: one copy per (C1, C2, H, W), shared by every window / placement."""
+        pkey = (d.C1, d.C2, d.H, d.W)
+        packed = self._packs.get(pkey)
+        if packed is None:
+            so, sc = (self.Cin * self.KH * self.KW, 1) if self.via_im2col else (self.so, self.sc)
+            wp = torch.empty(d.Kpad * d.Mpad, dtype=self.dtype, device=self.W.device)
+            if self.dtype == torch.float64:
+                check(self.lib.iiseg_conv_pack_f64(_stream(), C.byref(d), _ptr(self.W, self.dtype),
+                                                   so, sc, _ptr(wp, self.dtype)), 'iiseg_conv_pack_f64')
+                packed = (wp, None)
+            else:
                 ktab = torch.empty(d.Kpad * 4, dtype=torch.int32, device=self.W.device)
                 check(self.lib.iiseg_conv_pack_f32(_stream(), C.byref(d), _ptr(self.W), so, sc,
-                                                   _ptr(wp), _ptr(ktab, torch.int32)),
-                      'iiseg_conv_pack_f32')
-                packed = self._packs[pkey] = (wp, ktab)
-        wp, ktab = packed
-        plan = (d, wp, ktab)
-        self._plans[key] = plan
-        return plan
+                                                   _ptr(wp), _ptr(ktab, torch.int32)), 'iiseg_conv_pack_f32')
+                packed = (wp, ktab)
+            self._packs[pkey] = packed
+        return packed
+
+    def _plan(self, B, C1, C2, H, W, window, add_geom, unpool, out_slice=None, place=None,
+              anchor=(0, 0)):
+        """(d, wp, ktab): descriptor + the direct kernels' packed weights (`_describe`, `_packed`)."""
+        d = self._describe(B, C1, C2, H, W, window, add_geom, unpool, out_slice, place, anchor)
+        return (d,) + self._packed(d)
+
+
+    def _choose(self, d, unpool=False, masked=False, pool=False, add=False, x2=False, mask_in=False,
+                tune=None):
+        """The FORM (one of Conv.FORMS) that runs the launch `d` describes, given the few facts of the call
+        that matter: DePool2D input, mask bytes on either side (`masked`), a fused pool, a skip-add, a second
+        source, mask bytes as input.  The order below IS the precedence.  Only the library's host-side
+        `*_supported` queries are asked: no stream, no allocation, no launch.  `tune(key)`: BF16_TUNE's
+        timing of both 16-bit forms, handed in by the caller."""
+        lib, dp, f64 = self.lib, C.byref(d), self.dtype == torch.float64
+        if masked and not self.mask_ok(False):
+            raise RuntimeError('DePool2D byte masks need a halo-kernel or fp32 Winograd layer '
+                               '(Conv.mask_ok)')
+        plain = not masked and not pool
+        if plain and self.wino_bf16 and lib.iiseg_conv_wino_bf16_supported(dp):
+            if lib.iiseg_conv_halo_bf16_supported(dp):
+                # both 16-bit forms can run this layer: table of measured winners, else the static rule
+                # (see BF16_PICKS above).  The key carries no batch size: an image gets the same form
+                # alone and in a batch.
+                key = _bf16_key(self.Cin, self.Cout, d.C1, d.C2, unpool, d.OH, d.OW)
+                pick = BF16_FORCE or BF16_PICKS.get(key)
+                if not pick and tune is not None:
+                    pick = tune(key)
+                if (pick or _bf16_static_pick(self.Cin, d.OW)) == 'halo':
+                    return 'halo_bf16'
+            return 'wino_bf16'
+        # (the DAE's last layer -- DePool2D input, <= 16 output channels: reading pre / pooled it is
+        # read-bound and faster on the 16-row fp32 kernel, 0.60 vs 0.74 ms at configs[1]; from mask
+        # bytes the bf16 kernel wins, 0.45 vs 0.58 ms)
+        if self.halo_bf16 and not (unpool and self.Cout <= 16 and not mask_in and not BF16_UPCONV1) and \
+                lib.iiseg_conv_halo_bf16_supported(dp):
+            return 'halo_bf16'
+        # (fp32 operands: the pool and the mask bytes ride in the Winograd kernels too, iiseg_conv_wino_mask_f32)
+        if self.wino and (self.mma == 'f32' or plain) and lib.iiseg_conv_wino_supported(dp) and \
+                self._form_by_full_map(lib.iiseg_conv_wino_supported, d):
+            return 'wino_f32'
+        if masked:
+            return 'mask_f64' if f64 else 'mask_f32'
+        if pool:
+            return 'pool_f64' if f64 else 'pool_f32'
+        if CONV_GEMM and not x2 and not unpool and not add:
+            # 'valid' KxK layers without a static-tap variant (7x7 fc6), and deep 1x1 layers on few pixels
+            # (fc7, score_fr), where the same split-K GEMM beats the 1x1 tap kernel
+            if not f64 and (self.kernel == 'conv_igemm_f32_kernel' or
+                            ((self.KH, self.KW) == (1, 1) and self.Cin >= 1024)):
+                if self.mma == 'bf16' and lib.iiseg_conv_gemm_bf16_supported(dp):
+                    return 'gemm_bf16'
+                if lib.iiseg_conv_gemm_supported(dp):
+                    return 'gemm_f32'
+            # float64 (fc6 after im2col, fc7, score_fr): split-K GEMM on the Winograd path's kernel
+            if f64 and (d.KH, d.KW) == (1, 1) and d.C1 >= 1024 and lib.iiseg_conv_gemm_f64_supported(dp):
+                return 'gemm_f64'
+        if self.wino_f64 and not self.via_im2col and lib.iiseg_conv_wino_f64_supported(dp) and \
+                self._form_by_full_map(lib.iiseg_conv_wino_f64_supported, d):
+            return 'wino_f64'
+        return 'direct'
+
+    def _form_by_full_map(self, supported, d):
+        """A layer's kernel FORM (Winograd or direct) is decided on its FULL-MAP geometry, not on the
+        window a launch covers: a form with a size limit (workspace within 32-bit offsets) that takes a
+        small window but not the full map would otherwise compute the loop-invariant border with one
+        kernel and the recomputed window with another -- and the two differ in their last bits, which the
+        exact work eliminations rule out (ADVICE round 3).  Cached per input geometry."""
+        key = (id(supported), d.B, d.C1, d.C2, d.H, d.W, d.flags)
+        ok = self._form_cache.get(key)
+        if ok is None:
+            full = ConvDesc()
+            C.memmove(C.byref(full), C.byref(d), C.sizeof(ConvDesc))
+            fh, fw = self.out_hw(d.H, d.W)
+            full.oy0, full.ox0, full.OH, full.OW = 0, 0, fh, fw
+            full.out_H = full.out_W = full.out_y0 = full.out_x0 = 0
+            if full.AH:
+                full.AH, full.AW, full.ay0, full.ax0 = max(full.AH, fh), max(full.AW, fw), 0, 0
+            ok = self._form_cache[key] = bool(supported(C.byref(full)))
+        return ok
+
+    def _direct_kernel(self, d, add):
+        """The 'direct' form's profile label: which kernel the C side's own dispatch (iiseg_conv_f32 /
+        _f64) takes for `d`.  Evaluated only under profiling."""
+        kern = self.kernel
+        if self.dtype == torch.float64:
+            if self.lib.iiseg_conv_halo_f64_supported(C.byref(d)):
+                kern = 'conv_halo_f64_kernel'
+        elif (add is None or self.b is None) and self.lib.iiseg_conv_small_supported(C.byref(d)):
+            kern = 'conv_small_f32_kernel'         # vector ALU, HBM-bound: algorithmic bytes for the roofline
+            KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
+                4.0 * d.B * (self.Cin * d.H * d.W + (2 if add is not None else 1) * self.Cout * d.OH * d.OW)
+        if kern == 'conv_halo_f32_kernel' and d.C2 > 0 and d.C1 % 4:
+            kern = 'conv_taps_f32_kernel'      # a k-tile would straddle the two sources
+        return kern
+
+    def _check_pool(self, form, d, add=False):
+        """The form-specific refusals of a fused pool (host only)."""
+        lib, dp = self.lib, C.byref(d)
+        if form == 'wino_f32' and not lib.iiseg_conv_wino_pool_supported(dp):
+            raise RuntimeError('conv + pool fusion is not available for this launch '
+                               '(Winograd: even tile anchor and whole pooling windows)')
+        if (form == 'pool_f64' and (add or not lib.iiseg_conv_pool_f64_supported(dp))) or \
+                (form == 'pool_f32' and not lib.iiseg_conv_pool_supported(dp)):
+            raise RuntimeError('conv + pool fusion is not available for this launch')
+
+
+    def _extras_form(self):
+        """Where `_choose` sends a pooled / masked launch of this layer as far as the layer's own flags
+        decide it (its order of precedence without the per-launch queries): 'halo_bf16', 'wino_f32', or the
+        direct kernels' pool / mask entry points ('f64' / 'f32')."""
+        if self.halo_bf16:
+            return 'halo_bf16'
+        if self.wino and self.mma == 'f32':
+            return 'wino_f32'
+        return 'f64' if self.dtype == torch.float64 else 'f32'
+
+    def _f64_halo_runs(self):
+        """float64: does the LIBRARY run this layer on the halo-tile kernel (the only float64 kernel with the
+        fused pool and the mask bytes)?  Asked once per layer on a representative request -- the switch
+        IISEG_F64_HALO, the packed-weight shape (Kpad % 36, Mpad % 64) -- so that `pool_fusable` / `mask_ok`
+        never promise what iiseg_conv_pool_f64 / iiseg_conv_mask_f64 would refuse (ADVICE round 4)."""
+        ok = self._form_cache.get('f64_halo')
+        if ok is None:
+            d = ConvDesc()
+            d.B, d.C1, d.C2, d.H, d.W = 1, self.Cin, 0, 16, 16
+            d.Cout, d.KH, d.KW, d.pad, d.dil = self.Cout, self.KH, self.KW, self.pad, self.dil
+            d.OH, d.OW = self.out_hw(16, 16)
+            d.flags = CONV_RELU if self.relu else 0
+            ok = self.lib.iiseg_conv_plan_f64(C.byref(d)) == 0 and \
+                bool(self.lib.iiseg_conv_halo_f64_supported(C.byref(d)))
+            self._form_cache['f64_halo'] = ok
+        return ok
+
+    def pool_fusable(self, c8=None, anchor=None):
+        """True if this layer runs on a kernel whose epilogue can do the 2x2 max-pool.  `c8`:
+        whether the call will hand it a C8 tensor (None: the form the layer was built for) -- a
+        layer built with mma='bf16c8' and called on fp32 NCHW input runs the 'bf16' forms, and
+        those decide.  `anchor`: the Winograd tile anchor of the call -- an fp32 Winograd layer
+        pools in its output transform only at an even anchor (a 2x2 tile is then one pooling
+        window); without an anchor such a layer answers False."""
+        if not POOL_FUSE or self.dtype not in _SUFFIX:
+            return False
+        if self.c8 and c8 is not False:
+            return True
+        form = self._extras_form()
+        if form == 'halo_bf16':
+            return True
+        if form == 'wino_f32':
+            return anchor is not None and WINO_POOL_FUSE and not (int(anchor[0]) & 1 or int(anchor[1]) & 1)
+        if form == 'f64':
+            # float64: the halo-tile kernel's epilogue (conv_halo_f64.hip), layers it runs with > 16 output channels
+            return F64_POOL_FUSE and self.plain3x3 and not self.wino_f64 and self.Cout > 16 and \
+                self._f64_halo_runs()
+        # iiseg_conv_pool_f32: the fp32 halo kernel's epilogue (a bf16 layer that gets here is a Winograd one)
+        return self.mma == 'f32' and self.kernel == 'conv_halo_f32_kernel' and 16 < self.Cout < 256
+
+    def mask_ok(self, c8=None):
+        """True if this layer can take / produce DePool2D masks as bytes (halo kernels and the fp32
+        Winograd form, only where the byte form runs the very kernel the pre / pooled form runs).
+        `c8` as in `pool_fusable`.  (A Winograd layer produces them with its fused pool at an even
+        tile anchor; at an odd one its caller pools with `maxpool2x2(..., mask=)`.)"""
+        if self.c8 and c8 is not False:
+            return True
+        if not self.plain3x3 or self.dtype not in _SUFFIX:
+            return False
+        form = self._extras_form()
+        if form == 'wino_f32':
+            return WINO_POOL_FUSE
+        if form == 'f64':
+            # float64: layers of the halo-tile kernel (the mask bytes hold float64 comparisons)
+            return F64_MASKS and not self.wino_f64 and self._f64_halo_runs()
+        # iiseg_conv_halo_bf16 / iiseg_conv_mask_f32 (a bf16 layer on the latter is a Winograd one: no bytes)
+        return self.kernel == 'conv_halo_f32_kernel' and (form == 'halo_bf16' or self.mma == 'f32')
+
+    def pool_window(self, H, W, region=None, c8=None, anchor=None):
+        """If the 2x2 max-pool that follows this layer can be fused into its epilogue: the conv
+        window (y0, x0, h, w) to launch so that every pooling window touching `region` (of the
+        conv output; None = the whole map) is whole -- even origin, even extent unless it ends at
+        the map's last row / column.  None if the layer has no such epilogue (`pool_fusable`,
+        `anchor` as there)."""
+        if not self.pool_fusable(c8, anchor):
+            return None
+        fh, fw = self.out_hw(H, W)
+        if region is None:
+            return (0, 0, fh, fw)
+        y0, x0 = region[0] & ~1, region[1] & ~1
+        y1, x1 = min((region[0] + region[2] + 1) & ~1, fh), min((region[1] + region[3] + 1) & ~1, fw)
+        if region[0] + region[2] == fh:
+            y1 = fh
+        if region[1] + region[3] == fw:
+            x1 = fw
+        return (y0, x0, y1 - y0, x1 - x0)
+
 
     def __call__(self, x1, x2=None, pre=None, pooled=None, add=None, add_off=(0, 0),
                  window=None, out=None, out_c0=None, place=None, anchor=(0, 0), pool_out=None,
@@ -435,14 +655,23 @@ class Conv:
                                  zins)
         if zins or in_c is not None or bn is not None or stats is not None or fold is not None:
             raise RuntimeError('in_c / bn / stats: C8 input only (layers with at most 16 output channels)')
+        launch = self._describe_call(x1, x2, pre, pooled, add, add_off, window, out, out_c0, place, anchor,
+                                     pool_out, mask_in, unpool_hw, mask_out, store_out)
+        tune = None
+        if BF16_TUNE and self.wino_bf16 and not torch.cuda.is_current_stream_capturing():
+            tune = lambda key: self._tune_bf16(key, launch)
+        getattr(self, '_run_' + self._form(launch, tune))(launch)
+        return launch.out
+
+    def _describe_call(self, x1, x2=None, pre=None, pooled=None, add=None, add_off=(0, 0), window=None,
+                       out=None, out_c0=None, place=None, anchor=(0, 0), pool_out=None, mask_in=None,
+                       unpool_hw=None, mask_out=None, store_out=True):
+        """Step 1: `__call__`'s arguments checked, the launch described, `out` settled (shapes / dtypes only)."""
         dt = self.dtype
         unpool = pre is not None or mask_in is not None
         masked = mask_in is not None or mask_out is not None
         B, C1 = x1.shape[0], x1.shape[1]
         if masked:
-            if not self.mask_ok(False):
-                raise RuntimeError('DePool2D byte masks need a halo-kernel or fp32 Winograd layer '
-                                   '(Conv.mask_ok)')
             if mask_in is not None and (pre is not None or mask_in.dtype != torch.uint8 or
                                         mask_in.shape != x1.shape or unpool_hw is None or
                                         (unpool_hw[0] // 2, unpool_hw[1] // 2) != tuple(x1.shape[2:])):
@@ -476,17 +705,12 @@ class Conv:
         if self.via_im2col:
             if x2 is not None or unpool or window is not None:
                 raise NotImplementedError('float64 im2col path: plain single-source conv only')
-            fullH, fullW = self.out_hw(H, W)
-            cols = torch.empty((B, C1 * self.KH * self.KW, fullH, fullW), dtype=dt, device=x1.device)
-            check(self.lib.iiseg_im2col_f64(_stream(), _ptr(x1, dt), _ptr(cols, dt), B, C1, H, W,
-                                            self.KH, self.KW), 'iiseg_im2col_f64')
-            d, wp, ktab = self._plan(B, C1, 0, H, W, None, add_geom, False)
-            x1 = cols
+            d = self._describe(B, C1, 0, H, W, None, add_geom, False)
         else:
             out_slice = None if out_c0 is None else (out.shape[1], int(out_c0))
             pl = None if place is None else (out.shape[2], out.shape[3], int(place[0]), int(place[1]))
-            d, wp, ktab = self._plan(B, C1, C2, H, W, window, add_geom, unpool, out_slice, pl,
-                                     (int(anchor[0]) & 1, int(anchor[1]) & 1))
+            d = self._describe(B, C1, C2, H, W, window, add_geom, unpool, out_slice, pl,
+                               (int(anchor[0]) & 1, int(anchor[1]) & 1))
         if not store_out:
             out = None                     # geometry taken above; nothing is written
         elif place is not None:
@@ -501,184 +725,192 @@ class Conv:
             out = torch.empty((B, self.Cout, d.OH, d.OW), dtype=dt, device=x1.device)
         elif tuple(out.shape) != (B, self.Cout, d.OH, d.OW) or out.dtype != dt:
             raise RuntimeError('out shape %s != %s' % (tuple(out.shape), (B, self.Cout, d.OH, d.OW)))
-        # profiling: every launch is bracketed by events recorded IMMEDIATELY around the ctypes
-        # call (after all planning / workspace work), so a bracket holds the kernel and nothing else
-        prof = CONV_PROFILE
-        wino16 = not masked and pool_out is None and self.wino_bf16 and \
-            bool(self.lib.iiseg_conv_wino_bf16_supported(C.byref(d)))
-        if wino16 and self.lib.iiseg_conv_halo_bf16_supported(C.byref(d)):
-            # both 16-bit forms can run this layer: table of measured winners, else the static rule
-            # (see BF16_PICKS above).  The key carries no batch size: an image gets the same form
-            # alone and in a batch.
-            key = _bf16_key(self.Cin, self.Cout, C1, C2, unpool, d.OH, d.OW)
-            pick = BF16_FORCE or BF16_PICKS.get(key)
-            if not pick and BF16_TUNE and not torch.cuda.is_current_stream_capturing():
-                forms = (lambda: self._call_wino_bf16(d, x1, x2, pre, pooled, add, out, None),
-                         lambda: self._call_halo_bf16(d, x1, x2, pre, pooled, add, out, None, None,
-                                                      None, None, B, H, W))
-                ms = []
-                for f in forms:
-                    f()                                       # packs the weights, warms up
-                    e0 = _ev(); f(); f(); f(); e1 = _ev()
-                    e1.synchronize()
-                    ms.append(e0.elapsed_time(e1))
-                pick = BF16_PICKS[key] = 'wino' if ms[0] <= ms[1] else 'halo'
-                BF16_TIMES[key] = ms
-            if not pick:
-                pick = _bf16_static_pick(self.Cin, d.OW)
-            if pick == 'halo':
-                return self._call_halo_bf16(d, x1, x2, pre, pooled, add, out, None, None, None, prof,
-                                            B, H, W)
-        if wino16:
-            return self._call_wino_bf16(d, x1, x2, pre, pooled, add, out, prof)
-        # (the DAE's last layer -- DePool2D input, <= 16 output channels: reading pre / pooled it is
-        # read-bound and faster on the 16-row fp32 kernel, 0.60 vs 0.74 ms at configs[1]; from mask
-        # bytes the bf16 kernel wins, 0.45 vs 0.58 ms)
-        if self.halo_bf16 and \
-                not (unpool and self.Cout <= 16 and mask_in is None and not BF16_UPCONV1) and \
-                self.lib.iiseg_conv_halo_bf16_supported(C.byref(d)):
-            return self._call_halo_bf16(d, x1, x2, pre, pooled, add, out, pool_out, mask_in,
-                                        mask_out, prof, B, H, W)
-        # (fp32 operands: the pool and the mask bytes ride in the Winograd kernels too, iiseg_conv_wino_mask_f32)
-        if self.wino and (self.mma == 'f32' or (not masked and pool_out is None)) and \
-                self.lib.iiseg_conv_wino_supported(C.byref(d)) and \
-                self._form_by_full_map(self.lib.iiseg_conv_wino_supported, d):
-            if pool_out is not None:
-                fh, fw = self.out_hw(H, W)
-                if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2) or pool_out.dtype != dt or \
-                        not self.lib.iiseg_conv_wino_pool_supported(C.byref(d)):
-                    raise RuntimeError('conv + pool fusion is not available for this launch '
-                                       '(Winograd: even tile anchor and whole pooling windows)')
-            return self._call_wino(d, x1, x2, pre, pooled, add, out, prof, mask_in, pool_out, mask_out)
-        if masked and dt == torch.float64:
-            if pool_out is not None:
-                fh, fw = self.out_hw(H, W)
-                if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2) or pool_out.dtype != dt:
-                    raise RuntimeError('pool_out shape %s' % (tuple(pool_out.shape),))
-            ev0 = _ev() if prof is not None else None
-            check(self.lib.iiseg_conv_mask_f64(_stream(), C.byref(d), _ptr(x1, dt), _ptr(x2, dt), _ptr(pre, dt),
-                                               _ptr(pooled, dt), _ptr(mask_in, torch.uint8), _ptr(wp, dt),
-                                               _ptr(self.b, dt), _ptr(add, dt), _ptr(out, dt), _ptr(pool_out, dt),
-                                               _ptr(mask_out, torch.uint8)), 'iiseg_conv_mask_f64')
-            if prof is not None:
-                prof.append(('conv_halo_f64_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
-            return out
-        if masked:
-            if pool_out is not None:
-                fh, fw = self.out_hw(H, W)
-                if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2):
-                    raise RuntimeError('pool_out shape %s' % (tuple(pool_out.shape),))
-            ev0 = _ev() if prof is not None else None
-            check(self.lib.iiseg_conv_mask_f32(_stream(), C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre),
-                                               _ptr(pooled), _ptr(mask_in, torch.uint8), _ptr(wp),
-                                               _ptr(ktab, torch.int32), _ptr(self.b), _ptr(add),
-                                               _ptr(out), _ptr(pool_out),
-                                               _ptr(mask_out, torch.uint8)), 'iiseg_conv_mask_f32')
-            if prof is not None:
-                prof.append((self.kernel, self.flops(B, d.OH, d.OW), ev0, _ev()))
-            return out
-        if pool_out is not None and dt == torch.float64:
-            fh, fw = self.out_hw(H, W)
-            if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2) or pool_out.dtype != dt or \
-                    not self.lib.iiseg_conv_pool_f64_supported(C.byref(d)) or add is not None:
-                raise RuntimeError('conv + pool fusion is not available for this launch')
-            ev0 = _ev() if prof is not None else None
-            check(self.lib.iiseg_conv_pool_f64(_stream(), C.byref(d), _ptr(x1, dt), _ptr(x2, dt), _ptr(pre, dt),
-                                               _ptr(pooled, dt), _ptr(wp, dt), _ptr(self.b, dt), None,
-                                               _ptr(out, dt), _ptr(pool_out, dt)), 'iiseg_conv_pool_f64')
-            if prof is not None:
-                prof.append(('conv_halo_f64_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
-            return out
         if pool_out is not None:
             fh, fw = self.out_hw(H, W)
-            if dt != torch.float32 or tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2) or \
-                    not self.lib.iiseg_conv_pool_supported(C.byref(d)):
-                raise RuntimeError('conv + pool fusion is not available for this launch')
-            ev0 = _ev() if prof is not None else None
-            check(self.lib.iiseg_conv_pool_f32(_stream(), C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre),
-                                               _ptr(pooled), _ptr(wp), _ptr(ktab, torch.int32),
-                                               _ptr(self.b), _ptr(add), _ptr(out), _ptr(pool_out)),
-                  'iiseg_conv_pool_f32')
-            if prof is not None:
-                prof.append((self.kernel, self.flops(B, d.OH, d.OW), ev0, _ev()))
-            return out
-        gemm_shape = self.kernel == 'conv_igemm_f32_kernel' or (
-            # deep 1x1 layers on few pixels (fc7, score_fr): the same split-K GEMM beats the 1x1 tap
-            # kernel
-            dt == torch.float32 and (self.KH, self.KW) == (1, 1) and self.Cin >= 1024)
-        if gemm_shape and CONV_GEMM and self.mma == 'bf16' and x2 is None and not unpool and \
-                add is None and self.lib.iiseg_conv_gemm_bf16_supported(C.byref(d)):
-            lib = self.lib
-            if self._W16 is None:
-                self._W16 = torch.empty(lib.iiseg_conv_gemm_bf16_weight_bytes(C.byref(d)) // 2,
-                                        dtype=torch.bfloat16, device=self.W.device)
-                check(lib.iiseg_conv_gemm_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
-                                                    self.sc, _ptr(self._W16, torch.bfloat16)),
-                      'iiseg_conv_gemm_bf16_pack')
-            ws = _wino_workspace((lib.iiseg_conv_gemm_bf16_workspace_bytes(C.byref(d)) + 3) // 4,
-                                 x1.device)
-            ev0 = _ev() if prof is not None else None
-            check(lib.iiseg_conv_gemm_bf16(_stream(), C.byref(d), _ptr(x1),
-                                           _ptr(self._W16, torch.bfloat16), _ptr(self.b), _ptr(ws),
-                                           _ptr(out)), 'iiseg_conv_gemm_bf16')
-            if prof is not None:
-                prof.append(('wino_gemm_bf16_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
-            return out
-        if gemm_shape and CONV_GEMM and x2 is None and not unpool and \
-                add is None and self.lib.iiseg_conv_gemm_supported(C.byref(d)):
-            ws = _wino_workspace(self.lib.iiseg_conv_gemm_workspace_elems(C.byref(d)), x1.device)
-            args = (C.byref(d), _ptr(x1), _ptr(wp), _ptr(self.b), _ptr(ws), _ptr(out))
-            if prof is None:
-                check(self.lib.iiseg_conv_gemm_f32(_stream(), *args, 7), 'iiseg_conv_gemm_f32')
-                return out
-            names = ('gemm_im2col_kernel', 'wino_gemm_kernel', 'gemm_output_kernel')
-            ev0 = _ev()
-            for i, stage in enumerate((1, 2, 4)):        # the three kernels separately
-                check(self.lib.iiseg_conv_gemm_f32(_stream(), *args, stage), 'iiseg_conv_gemm_f32')
-                ev1 = _ev()
-                prof.append((names[i], self.flops(B, d.OH, d.OW) if i == 1 else 0.0, ev0, ev1))
-                ev0 = ev1
-            return out
-        if dt == torch.float64 and CONV_GEMM and (d.KH, d.KW) == (1, 1) and d.C1 >= 1024 and x2 is None and \
-                not unpool and add is None and self.lib.iiseg_conv_gemm_f64_supported(C.byref(d)):
-            # deep 1x1 layers (fc6 after im2col, fc7, score_fr): split-K GEMM on the Winograd path's kernel
-            ws = _wino_workspace64(self.lib.iiseg_conv_gemm_f64_workspace_elems(C.byref(d)), x1.device)
-            ev0 = _ev() if prof is not None else None
-            check(self.lib.iiseg_conv_gemm_f64(_stream(), C.byref(d), _ptr(x1, dt), _ptr(wp, dt),
-                                               _ptr(self.b, dt), _ptr(ws, dt), _ptr(out, dt)),
-                  'iiseg_conv_gemm_f64')
-            if prof is not None:
-                prof.append(('wino64_gemm_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
-            return out
-        if dt == torch.float64 and self.wino_f64 and not self.via_im2col and \
-                self.lib.iiseg_conv_wino_f64_supported(C.byref(d)) and \
-                self._form_by_full_map(self.lib.iiseg_conv_wino_f64_supported, d):
-            return self._call_wino_f64(d, x1, x2, pre, pooled, add, out, prof, B)
-        ev0 = _ev() if prof is not None else None
-        if dt == torch.float64:
-            check(self.lib.iiseg_conv_f64(_stream(), C.byref(d), _ptr(x1, dt), _ptr(x2, dt),
-                                          _ptr(pre, dt), _ptr(pooled, dt), _ptr(wp, dt),
-                                          _ptr(self.b, dt), _ptr(add, dt), _ptr(out, dt)),
-                  'iiseg_conv_f64')
-        else:
-            check(self.lib.iiseg_conv_f32(_stream(), C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre),
-                                          _ptr(pooled), _ptr(wp), _ptr(ktab, torch.int32),
-                                          _ptr(self.b), _ptr(add), _ptr(out)), 'iiseg_conv_f32')
-        if prof is not None:
-            ev1 = _ev()
-            kern = self.kernel
-            if dt == torch.float64 and self.lib.iiseg_conv_halo_f64_supported(C.byref(d)):
-                kern = 'conv_halo_f64_kernel'
-            if dt == torch.float32 and (add is None or self.b is None) and \
-                    self.lib.iiseg_conv_small_supported(C.byref(d)):
-                kern = 'conv_small_f32_kernel'         # vector ALU, HBM-bound: algorithmic bytes for the roofline
-                KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
-                    4.0 * B * (self.Cin * d.H * d.W + (2 if add is not None else 1) * self.Cout * d.OH * d.OW)
-            if kern == 'conv_halo_f32_kernel' and C2 > 0 and C1 % 4:
-                kern = 'conv_taps_f32_kernel'      # a k-tile would straddle the two sources
-            prof.append((kern, self.flops(B, d.OH, d.OW), ev0, ev1))
-        return out
+            if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2) or pool_out.dtype != dt:
+                raise RuntimeError('pool_out shape %s %s' % (tuple(pool_out.shape), pool_out.dtype))
+        return _Launch(d, x1, x2, pre, pooled, add, out, pool_out, mask_in, mask_out)
 
+    def _form(self, c, tune=None):
+        """Step 2: the form of the described launch `c`; refuses a fused pool that form cannot do."""
+        form = self._choose(c.d, unpool=c.pre is not None or c.mask_in is not None,
+                            masked=c.mask_in is not None or c.mask_out is not None,
+                            pool=c.pool_out is not None, add=c.add is not None, x2=c.x2 is not None,
+                            mask_in=c.mask_in is not None, tune=tune)
+        if c.pool_out is not None:
+            self._check_pool(form, c.d, c.add is not None)
+        return form
+
+    def _tune_bf16(self, key, c):
+        """BF16_TUNE: times both 16-bit forms of a launch (unprofiled), fills BF16_TIMES / BF16_PICKS."""
+        global CONV_PROFILE
+        prof, CONV_PROFILE = CONV_PROFILE, None
+        try:
+            ms = []
+            for f in (self._run_wino_bf16, self._run_halo_bf16):
+                f(c)                                          # packs the weights, warms up
+                e0 = _ev(); f(c); f(c); f(c); e1 = _ev()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+        finally:
+            CONV_PROFILE = prof
+        BF16_TIMES[key] = ms
+        pick = BF16_PICKS[key] = 'wino' if ms[0] <= ms[1] else 'halo'
+        return pick
+
+
+    def _source(self, c):
+        """x1 as the kernels read it: float64 layers without a static-tap variant run on its im2col."""
+        if not self.via_im2col:
+            return c.x1
+        B, C1, H, W = c.x1.shape
+        cols = torch.empty((B, c.d.C1, c.d.H, c.d.W), dtype=self.dtype, device=c.x1.device)
+        check(self.lib.iiseg_im2col_f64(_stream(), _ptr(c.x1, self.dtype), _ptr(cols, self.dtype), B, C1, H, W,
+                                        self.KH, self.KW), 'iiseg_im2col_f64')
+        return cols
+
+    def _direct_args(self, c, x1, *between):
+        """Operands the direct kernels' entry points share: sources, [`between`,] packed weights (+ the fp32
+        gather table), bias, skip-add, output."""
+        d, dt = c.d, self.dtype
+        wp, ktab = self._packed(d)
+        tab = () if ktab is None else (_ptr(ktab, torch.int32),)
+        return (C.byref(d), _ptr(x1, dt), _ptr(c.x2, dt), _ptr(c.pre, dt), _ptr(c.pooled, dt), *between,
+                _ptr(wp, dt), *tab, _ptr(self.b, dt), _ptr(c.add, dt), _ptr(c.out, dt))
+
+    def _run_direct(self, c):
+        """The C side's own dispatch among the direct kernels (iiseg_conv_f32 / iiseg_conv_f64)."""
+        d = c.d
+        _launch(lambda: self._direct_kernel(d, c.add), self.flops(d.B, d.OH, d.OW), _fn('conv', self.dtype),
+                *self._direct_args(c, self._source(c)))
+
+    def _halo_kernel(self):
+        return 'conv_halo_f64_kernel' if self.dtype == torch.float64 else self.kernel
+
+    def _run_mask_f32(self, c):
+        """The direct kernel with DePool2D mask bytes in and / or pool + bytes out (iiseg_conv_mask_f32 / _f64)."""
+        _launch(self._halo_kernel(), self.flops(c.d.B, c.d.OH, c.d.OW), _fn('conv_mask', self.dtype),
+                *self._direct_args(c, c.x1, _ptr(c.mask_in, torch.uint8)), _ptr(c.pool_out, self.dtype),
+                _ptr(c.mask_out, torch.uint8))
+
+    def _run_pool_f32(self, c):
+        """The direct kernel with the 2x2 max-pool in its epilogue (iiseg_conv_pool_f32 / _f64)."""
+        _launch(self._halo_kernel(), self.flops(c.d.B, c.d.OH, c.d.OW), _fn('conv_pool', self.dtype),
+                *self._direct_args(c, c.x1), _ptr(c.pool_out, self.dtype))
+
+    _run_mask_f64, _run_pool_f64 = _run_mask_f32, _run_pool_f32
+
+    def _run_gemm_bf16(self, c):
+        """im2col + split-K GEMM on bf16 operands (iiseg_conv_gemm_bf16)."""
+        lib, d = self.lib, c.d
+        if self._W16 is None:
+            self._W16 = torch.empty(lib.iiseg_conv_gemm_bf16_weight_bytes(C.byref(d)) // 2,
+                                    dtype=torch.bfloat16, device=self.W.device)
+            check(lib.iiseg_conv_gemm_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
+                                                self.sc, _ptr(self._W16, torch.bfloat16)),
+                  'iiseg_conv_gemm_bf16_pack')
+        ws = _workspace('f32', (lib.iiseg_conv_gemm_bf16_workspace_bytes(C.byref(d)) + 3) // 4, c.x1.device)
+        _launch('wino_gemm_bf16_kernel', self.flops(d.B, d.OH, d.OW), lib.iiseg_conv_gemm_bf16,
+                C.byref(d), _ptr(c.x1), _ptr(self._W16, torch.bfloat16), _ptr(self.b), _ptr(ws), _ptr(c.out))
+
+    def _run_gemm_f32(self, c):
+        """im2col + split-K GEMM + output pass (iiseg_conv_gemm_f32): three kernels."""
+        d = c.d
+        wp, _ = self._packed(d)
+        ws = _workspace('f32', self.lib.iiseg_conv_gemm_workspace_elems(C.byref(d)), c.x1.device)
+        _launch_staged(self.lib.iiseg_conv_gemm_f32,
+                       (C.byref(d), _ptr(c.x1), _ptr(wp), _ptr(self.b), _ptr(ws), _ptr(c.out)), 7,
+                       (('gemm_im2col_kernel', 1, 0.0),
+                        ('wino_gemm_kernel', 2, self.flops(d.B, d.OH, d.OW)),
+                        ('gemm_output_kernel', 4, 0.0)))
+
+    def _run_gemm_f64(self, c):
+        """Deep 1x1 layers in float64: split-K GEMM on the Winograd path's kernel (iiseg_conv_gemm_f64)."""
+        d, dt = c.d, self.dtype
+        wp, _ = self._packed(d)
+        x1 = self._source(c)
+        ws = _workspace('f64', self.lib.iiseg_conv_gemm_f64_workspace_elems(C.byref(d)), x1.device)
+        _launch('wino64_gemm_kernel', self.flops(d.B, d.OH, d.OW), self.lib.iiseg_conv_gemm_f64,
+                C.byref(d), _ptr(x1, dt), _ptr(wp, dt), _ptr(self.b, dt), _ptr(ws, dt), _ptr(c.out, dt))
+
+    def _run_halo_bf16(self, c):
+        """Direct 3x3 form on the bf16 matrix pipe (include/iiseg.h, iiseg_conv_halo_bf16)."""
+        lib, d = self.lib, c.d
+        if self._W16 is None:
+            self._W16 = torch.empty(lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(d)) // 2,
+                                    dtype=torch.bfloat16, device=self.W.device)
+            check(lib.iiseg_conv_halo_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
+                                                self.sc, _ptr(self._W16, torch.bfloat16)),
+                  'iiseg_conv_halo_bf16_pack')
+        _launch('conv_halo_bf16_kernel', self.flops(d.B, d.OH, d.OW), lib.iiseg_conv_halo_bf16,
+                C.byref(d), _ptr(c.x1), _ptr(c.x2), _ptr(c.pre), _ptr(c.pooled),
+                _ptr(self._W16, torch.bfloat16), _ptr(self.b), _ptr(c.add), _ptr(c.out), _ptr(c.pool_out),
+                _ptr(c.mask_in, torch.uint8), _ptr(c.mask_out, torch.uint8))
+
+    def _wino_gemm_flops(self, d, K):
+        """Multiplies the 16 Winograd GEMMs of a launch actually issue: 16 * 2 * K * Cout * tiles."""
+        r0, c0 = d.oy0 - ((d.oy0 - d.tile_y0) & 1), d.ox0 - ((d.ox0 - d.tile_x0) & 1)
+        T = d.B * ((d.oy0 + d.OH - r0 + 1) // 2) * ((d.ox0 + d.OW - c0 + 1) // 2)
+        return 16 * 2.0 * K * self.Cout * T
+
+    def _run_wino_bf16(self, c):
+        """bf16-operand Winograd form (include/iiseg.h, iiseg_conv_wino_bf16): input transform ->
+        V16, then one kernel for the 16 GEMMs + output transform + epilogue."""
+        lib, d = self.lib, c.d
+        if self._U16 is None:
+            self._U16 = torch.empty(lib.iiseg_conv_wino_bf16_weight_bytes(C.byref(d)) // 2,
+                                    dtype=torch.bfloat16, device=self.W.device)
+            check(lib.iiseg_conv_wino_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
+                                                self.sc, _ptr(self._U16, torch.bfloat16)),
+                  'iiseg_conv_wino_bf16_pack')
+        ws = _workspace('f32', (lib.iiseg_conv_wino_bf16_workspace_bytes(C.byref(d)) + 3) // 4, c.x1.device)
+        _launch_staged(lib.iiseg_conv_wino_bf16,
+                       (C.byref(d), _ptr(c.x1), _ptr(c.x2), _ptr(c.pre), _ptr(c.pooled),
+                        _ptr(self._U16, torch.bfloat16), _ptr(self.b), _ptr(c.add), _ptr(ws), _ptr(c.out)), 3,
+                       (('wino_input_bf16_kernel', 1, 0.0),      # (the GEMM's K is padded to 64)
+                        ('wino_fused_bf16_kernel', 2, self._wino_gemm_flops(d, (self.Cin + 63) // 64 * 64))))
+
+    def _run_wino_f64(self, c):
+        """float64 Winograd form (include/iiseg.h, iiseg_conv_wino_f64)."""
+        lib, d, dt = self.lib, c.d, torch.float64
+        if self._U is None:
+            self._U = torch.empty(lib.iiseg_conv_wino_f64_weight_elems(C.byref(d)), dtype=dt,
+                                  device=self.W.device)
+            check(lib.iiseg_conv_wino_pack_f64(_stream(), C.byref(d), _ptr(self.W, dt), self.so, self.sc,
+                                               _ptr(self._U, dt)), 'iiseg_conv_wino_pack_f64')
+        ws = _workspace('f64', lib.iiseg_conv_wino_f64_workspace_elems(C.byref(d)), c.x1.device)
+        _launch('wino64_gemm_kernel', self.flops(d.B, d.OH, d.OW), lib.iiseg_conv_wino_f64,
+                C.byref(d), _ptr(c.x1, dt), _ptr(c.x2, dt), _ptr(c.pre, dt), _ptr(c.pooled, dt),
+                _ptr(self._U, dt), _ptr(self.b, dt), _ptr(c.add, dt), _ptr(ws, dt), _ptr(c.out, dt))
+
+    def _run_wino_f32(self, c):
+        """Winograd F(2x2,3x3) form of the layer (include/iiseg.h, iiseg_conv_wino_f32; with a
+        fused pool or mask bytes iiseg_conv_wino_mask_f32)."""
+        lib, d = self.lib, c.d
+        if self._U is None:
+            self._U = torch.empty(lib.iiseg_conv_wino_weight_elems(C.byref(d)), dtype=torch.float32,
+                                  device=self.W.device)
+            check(lib.iiseg_conv_wino_pack_f32(_stream(), C.byref(d), _ptr(self.W), self.so, self.sc,
+                                               _ptr(self._U)), 'iiseg_conv_wino_pack_f32')
+        ws = _workspace('f32', lib.iiseg_conv_wino_workspace_elems(C.byref(d)), c.x1.device)
+        if c.mask_in is None and c.pool_out is None:
+            fn = lib.iiseg_conv_wino_f32
+            args = (C.byref(d), _ptr(c.x1), _ptr(c.x2), _ptr(c.pre), _ptr(c.pooled), _ptr(self._U),
+                    _ptr(self.b), _ptr(c.add), _ptr(ws), _ptr(c.out))
+        else:
+            fn = lib.iiseg_conv_wino_mask_f32
+            args = (C.byref(d), _ptr(c.x1), _ptr(c.x2), _ptr(c.pre), _ptr(c.pooled),
+                    _ptr(c.mask_in, torch.uint8), _ptr(self._U), _ptr(self.b), _ptr(c.add), _ptr(ws),
+                    _ptr(c.out), _ptr(c.pool_out), _ptr(c.mask_out, torch.uint8))
+        gemm_flops = self._wino_gemm_flops(d, self.Cin)
+        # (a skip-add would be read by the fused kernel's epilogue, uncoalesced and with nothing to
+        # hide its latency: such layers keep the separate, coalesced output transform)
+        if self.Cin <= WINO_FUSED_MAX_CIN and self.Cin % 32 == 0 and c.add is None:
+            _launch_staged(fn, args, 7 | 8, (('wino_input_kernel', 1 | 8, 0.0),
+                                             ('wino_fused_kernel', 2 | 8, gemm_flops)))
+        else:
+            _launch_staged(fn, args, 7, (('wino_input_kernel', 1, 0.0), ('wino_gemm_kernel', 2, gemm_flops),
+                                         ('wino_output_kernel', 4, 0.0)))
 
     def bnrelu_conv(self, stack, n, bn, out, out_c0):
         """BN_ReLU_Conv as one kernel (iiseg_conv_bnrelu_f32): the conv reads the first `n`
@@ -686,130 +918,63 @@ class Conv:
         (bn = (beta, gamma, mean, inv_std), batch statistics); the result goes to channels
         [out_c0, out_c0 + Cout) of `out`.  Returns None when the layer has no such kernel (the
         caller then runs bn_relu + the plain conv)."""
-        if self.dtype != torch.float32 or not BNRELU_FUSE or (self.KH, self.KW) != (3, 3) or \
-                self.Cout > 16 or self.dil != 1 or self.transposed:
+        if self.dtype != torch.float32 or not BNRELU_FUSE or not self.plain3x3 or self.Cout > 16:
             return None
         B, cap, H, W = stack.shape
-        pl = None
-        out_slice = (out.shape[1], int(out_c0))
-        d, wp, ktab = self._plan(B, n, 0, H, W, None, None, False, out_slice, pl)
+        d, wp, ktab = self._plan(B, n, 0, H, W, None, None, False, (out.shape[1], int(out_c0)), None)
         if not self.lib.iiseg_conv_bnrelu_supported(C.byref(d)) or \
                 tuple(out.shape[2:]) != (d.OH, d.OW) or out_c0 + self.Cout > out.shape[1]:
             return None
-        prof = CONV_PROFILE
         beta, gamma, mean, inv_std = bn
-        ev0 = _ev() if prof is not None else None
-        check(self.lib.iiseg_conv_bnrelu_f32(_stream(), C.byref(d), _ptr(stack), cap * H * W,
-                                             _ptr(beta), _ptr(gamma), _ptr(mean), _ptr(inv_std),
-                                             _ptr(wp), _ptr(ktab, torch.int32), _ptr(self.b),
-                                             _ptr(out)), 'iiseg_conv_bnrelu_f32')
-        if prof is not None:
-            prof.append((self.kernel, self.flops(B, d.OH, d.OW), ev0, _ev()))
+        _launch(self.kernel, self.flops(B, d.OH, d.OW), self.lib.iiseg_conv_bnrelu_f32,
+                C.byref(d), _ptr(stack), cap * H * W, _ptr(beta), _ptr(gamma), _ptr(mean), _ptr(inv_std),
+                _ptr(wp), _ptr(ktab, torch.int32), _ptr(self.b), _ptr(out))
         return out
 
-    def _form_by_full_map(self, supported, d):
-        """A layer's kernel FORM (Winograd or direct) is decided on its FULL-MAP geometry, not on the
-        window a launch covers: a form with a size limit (workspace within 32-bit offsets) that takes a
-        small window but not the full map would otherwise compute the loop-invariant border with one
-        kernel and the recomputed window with another -- and the two differ in their last bits, which the
-        exact work eliminations rule out (ADVICE round 3).  Cached per input geometry."""
-        key = (id(supported), d.B, d.C1, d.C2, d.H, d.W, d.flags)
-        ok = self._form_cache.get(key)
-        if ok is None:
-            full = ConvDesc()
-            C.memmove(C.byref(full), C.byref(d), C.sizeof(ConvDesc))
-            fh, fw = self.out_hw(d.H, d.W)
-            full.oy0, full.ox0, full.OH, full.OW = 0, 0, fh, fw
-            full.out_H = full.out_W = full.out_y0 = full.out_x0 = 0
-            if full.AH:
-                full.AH, full.AW, full.ay0, full.ax0 = max(full.AH, fh), max(full.AW, fw), 0, 0
-            ok = self._form_cache[key] = bool(supported(C.byref(full)))
-        return ok
-
-    def _f64_halo_runs(self):
-        """float64: does the LIBRARY run this layer on the halo-tile kernel (the only float64 kernel with the
-        fused pool and the mask bytes)?  Asked once per layer on a representative request -- the switch
-        IISEG_F64_HALO, the packed-weight shape (Kpad % 36, Mpad % 64) -- so that `pool_fusable` / `mask_ok`
-        never promise what iiseg_conv_pool_f64 / iiseg_conv_mask_f64 would refuse (ADVICE round 4)."""
-        ok = self._form_cache.get('f64_halo')
-        if ok is None:
-            d = ConvDesc()
-            d.B, d.C1, d.C2, d.H, d.W = 1, self.Cin, 0, 16, 16
-            d.Cout, d.KH, d.KW, d.pad, d.dil = self.Cout, self.KH, self.KW, self.pad, self.dil
-            d.OH, d.OW = self.out_hw(16, 16)
-            d.flags = CONV_RELU if self.relu else 0
-            ok = self.lib.iiseg_conv_plan_f64(C.byref(d)) == 0 and \
-                bool(self.lib.iiseg_conv_halo_f64_supported(C.byref(d)))
-            self._form_cache['f64_halo'] = ok
-        return ok
-
-    def pool_fusable(self, c8=None, anchor=None):
-        """True if this layer runs on a kernel whose epilogue can do the 2x2 max-pool.  `c8`:
-        whether the call will hand it a C8 tensor (None: the form the layer was built for) -- a
-        layer built with mma='bf16c8' and called on fp32 NCHW input runs the 'bf16' forms, and
-        those decide.  `anchor`: the Winograd tile anchor of the call -- an fp32 Winograd layer
-        pools in its output transform only at an even anchor (a 2x2 tile is then one pooling
-        window); without an anchor such a layer answers False."""
-        if not POOL_FUSE:
-            return False
-        if self.dtype == torch.float64:
-            # float64: the halo-tile kernel's epilogue (conv_halo_f64.hip), layers it runs with > 16 output channels
-            return F64_POOL_FUSE and (self.KH, self.KW) == (3, 3) and self.dil == 1 and not self.transposed and \
-                not self.wino_f64 and self.Cout > 16 and self._f64_halo_runs()
-        if self.dtype != torch.float32:
-            return False
-        if self.c8 and c8 is not False:
-            return True
-        if self.mma == 'bf16':
-            return self.halo_bf16
-        if self.wino:
-            return anchor is not None and WINO_POOL_FUSE and not (int(anchor[0]) & 1 or int(anchor[1]) & 1)
-        return not (self.kernel != 'conv_halo_f32_kernel' or not 16 < self.Cout < 256)
-
-    def mask_ok(self, c8=None):
-        """True if this layer can take / produce DePool2D masks as bytes (halo kernels and the fp32
-        Winograd form, only where the byte form runs the very kernel the pre / pooled form runs).
-        `c8` as in `pool_fusable`.  (A Winograd layer produces them with its fused pool at an even
-        tile anchor; at an odd one its caller pools with `maxpool2x2(..., mask=)`.)"""
-        if self.c8 and c8 is not False:
-            return True
-        if self.dtype == torch.float64:
-            # float64: layers of the halo-tile kernel (the mask bytes hold float64 comparisons)
-            return F64_MASKS and (self.KH, self.KW) == (3, 3) and self.dil == 1 and not self.transposed and \
-                not self.wino_f64 and self._f64_halo_runs()
-        if self.dtype != torch.float32 or (self.KH, self.KW) != (3, 3) or self.dil != 1 or \
-                self.transposed or self.wino_bf16:
-            return False
-        if self.mma == 'f32' and self.wino:
-            return WINO_POOL_FUSE
-        if self.kernel != 'conv_halo_f32_kernel':
-            return False
-        return self.halo_bf16 if self.mma == 'bf16' else not self.wino
-
-    def pool_window(self, H, W, region=None, c8=None, anchor=None):
-        """If the 2x2 max-pool that follows this layer can be fused into its epilogue: the conv
-        window (y0, x0, h, w) to launch so that every pooling window touching `region` (of the
-        conv output; None = the whole map) is whole -- even origin, even extent unless it ends at
-        the map's last row / column.  None if the layer has no such epilogue (`pool_fusable`,
-        `anchor` as there)."""
-        if not self.pool_fusable(c8, anchor):
-            return None
-        fh, fw = self.out_hw(H, W)
-        if region is None:
-            return (0, 0, fh, fw)
-        y0, x0 = region[0] & ~1, region[1] & ~1
-        y1, x1 = min((region[0] + region[2] + 1) & ~1, fh), min((region[1] + region[3] + 1) & ~1, fw)
-        if region[0] + region[2] == fh:
-            y1 = fh
-        if region[1] + region[3] == fw:
-            x1 = fw
-        return (y0, x0, y1 - y0, x1 - x0)
 
     def c8_tiling(self, d, pool):
         """(kind, th, tw, quad) of a C8 launch: include/iiseg.h iiseg_conv_c8_tiling."""
         t = (C.c_int32 * 4)()
         check(self.lib.iiseg_conv_c8_tiling(C.byref(d), 1 if pool else 0, t), 'iiseg_conv_c8_tiling')
         return tuple(t)
+
+    def _c8_weights(self):
+        """The layer's weights packed for the C8 kernels, once per layer, for the REAL channel count (the
+        rows of padding channels are zero); shared by `_call_c8` and `_call_c8_m16`.  A captured graph may
+        point at them: never replaced after first use."""
+        if self._W16c8 is None:
+            lib = self.lib
+            dp = ConvDesc()
+            dp.B, dp.C1, dp.C2, dp.H, dp.W = 1, self.Cin, 0, 8, 8
+            dp.Cout, dp.KH, dp.KW, dp.pad, dp.dil = self.Cout, 3, 3, 1, 1
+            dp.OH, dp.OW = 8, 8
+            Wsrc, so, sc = self.W, self.so, self.sc
+            if self.x3:
+                # two k-groups of whole 16-channel k-tiles [W_hi | W_lo]; the split values are bf16
+                # numbers, the pack's rounding leaves them as they are
+                Cp = (self.Cin + 15) // 16 * 16
+                Wsrc = torch.empty((self.Cout, 2 * Cp, 3, 3), dtype=torch.float32, device=self.W.device)
+                check(lib.iiseg_conv_c8_split_weights(_stream(), _ptr(self.W), self.so, self.sc,
+                                                      self.Cout, self.Cin, _ptr(Wsrc)),
+                      'iiseg_conv_c8_split_weights')
+                dp.C1, so, sc = 2 * Cp, 2 * Cp * 9, 9
+            self._W16c8 = torch.empty(lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(dp)) // 2,
+                                      dtype=torch.bfloat16, device=self.W.device)
+            check(lib.iiseg_conv_halo_bf16_pack(_stream(), C.byref(dp), _ptr(Wsrc), so, sc,
+                                                _ptr(self._W16c8, torch.bfloat16)),
+                  'iiseg_conv_halo_bf16_pack')
+        return _ptr(self._W16c8, torch.bfloat16)
+
+    @staticmethod
+    def _c8_unpool_hw(x1, mask_in, unpool_hw, chunks, ok):
+        """(H, W) of a DePool2D input on C8: `mask_in` uint8 (B, chunks, h, w, 8) over x1's (h, w) planes,
+        `unpool_hw` the unpooled size; `ok`: what else the kernel at hand demands of such a launch."""
+        if not ok or unpool_hw is None or not is_c8_mask(mask_in) or \
+                tuple(mask_in.shape) != (x1.shape[0], chunks) + tuple(x1.shape[2:]) or \
+                (unpool_hw[0] // 2, unpool_hw[1] // 2) != tuple(x1.shape[2:4]):
+            raise RuntimeError('C8 DePool2D input: up %s, mask %s, unpool_hw %s'
+                               % (tuple(x1.shape), tuple(mask_in.shape), unpool_hw))
+        return int(unpool_hw[0]), int(unpool_hw[1])
 
     def _call_c8_m16(self, x1, window, out, place, mask_in, unpool_hw, out_format, out_c0, in_c, bn,
                      stats=None, fold=None):
@@ -830,12 +995,8 @@ class Conv:
             raise RuntimeError('conv of %d input channels on the first %d of %d C8 channels'
                                % (self.Cin, C1, in_ctot))
         if unpool:
-            if unpool_hw is None or not is_c8_mask(mask_in) or tuple(mask_in.shape) != tuple(x1.shape) or \
-                    (unpool_hw[0] // 2, unpool_hw[1] // 2) != tuple(x1.shape[2:4]) or C1 != in_ctot or \
-                    not x1.is_contiguous():
-                raise RuntimeError('C8 DePool2D input: up %s, mask %s, unpool_hw %s'
-                                   % (tuple(x1.shape), tuple(mask_in.shape), unpool_hw))
-            H, W = int(unpool_hw[0]), int(unpool_hw[1])
+            H, W = self._c8_unpool_hw(x1, mask_in, unpool_hw, x1.shape[1],
+                                      C1 == in_ctot and x1.is_contiguous())
         else:
             H, W = x1.shape[2], x1.shape[3]
         fullH, fullW = self.out_hw(H, W)
@@ -870,23 +1031,6 @@ class Conv:
         if bn is not None:
             if len(bn) != 2 or any(t.dtype != torch.float32 or t.numel() < C1 for t in bn):
                 raise RuntimeError('bn = (a, b): float32, at least %d entries' % C1)
-        if self._W16c8 is None:     # (packed once per layer, for the REAL channel count, shared with _call_c8:
-            #                          a captured graph may point at it -- never replaced after first use)
-            dp = ConvDesc()
-            dp.B, dp.C1, dp.C2, dp.H, dp.W = 1, self.Cin, 0, 8, 8
-            dp.Cout, dp.KH, dp.KW, dp.pad, dp.dil = self.Cout, 3, 3, 1, 1
-            dp.OH, dp.OW = 8, 8
-            self._W16c8 = torch.empty(lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(dp)) // 2,
-                                      dtype=torch.bfloat16, device=self.W.device)
-            check(lib.iiseg_conv_halo_bf16_pack(_stream(), C.byref(dp), _ptr(self.W), self.so, self.sc,
-                                                _ptr(self._W16c8, torch.bfloat16)),
-                  'iiseg_conv_halo_bf16_pack')
-        dtp = lambda t: None if t is None else (_c8ptr(t) if is_c8(t) else _ptr(t, t.dtype))
-        prof = CONV_PROFILE
-        ev0 = _ev() if prof is not None else None
-        # split-K launches (small maps, long channel loops) sum their slices through a scratch buffer
-        nws = lib.iiseg_conv_c8_m16_workspace_bytes(C.byref(d))
-        ws = _m16_workspace(nws, x1.device) if nws else None
         if stats is not None and (fmt != 'c8' or stats[0].dtype != torch.float32 or
                                   stats[1].dtype != torch.float32 or
                                   min(stats[0].numel(), stats[1].numel()) < (out_c0 or 0) + 16):
@@ -894,22 +1038,23 @@ class Conv:
         if fold is not None and (stats is None or any(t.dtype != torch.float32 or t.numel() < fold[4]
                                                       for t in fold[:4])):
             raise RuntimeError('fold = (beta, gamma, a, b, n) needs stats and float32 vectors of n entries')
-        check(lib.iiseg_conv_c8_m16_ws(_stream(), C.byref(d), dtp(x1), in_ctot, dtp(mask_in),
-                                       None if bn is None else _ptr(bn[0]), None if bn is None else _ptr(bn[1]),
-                                       dtp(self._W16c8), _ptr(self.b), dtp(out), 3 if fmt == 'nchw' else 1,
-                                       None if ws is None else C.c_void_p(ws.data_ptr()), int(nws),
-                                       None if stats is None else _ptr(stats[0]),
-                                       None if stats is None else _ptr(stats[1]),
-                                       float(stats[2]) if stats is not None else 0.0,
-                                       *((_ptr(fold[0]), _ptr(fold[1]), _ptr(fold[2]), _ptr(fold[3]), int(fold[4]))
-                                         if fold is not None else (None, None, None, None, 0))),
-              'iiseg_conv_c8_m16_ws')
-        if prof is not None:
-            prof.append(('conv_c8_m16_kernel', self.flops(B, OH, OW), ev0, _ev()))
-            if CONV_PROFILE_INFO is not None:
-                CONV_PROFILE_INFO.append(dict(
-                    Cin=self.Cin, Cout=self.Cout, C1=C1, C2=0, H=H, W=W, OH=OH, OW=OW, B=B,
-                    unpool=unpool, pool=False, add=0, kind=3 if fmt == 'nchw' else 1, flat='m16'))
+        w16 = self._c8_weights()
+        # split-K launches (small maps, long channel loops) sum their slices through a scratch buffer
+        nws = lib.iiseg_conv_c8_m16_workspace_bytes(C.byref(d))
+        ws = _workspace('m16', nws, x1.device) if nws else None
+        _launch('conv_c8_m16_kernel', self.flops(B, OH, OW), lib.iiseg_conv_c8_m16_ws,
+                C.byref(d), _operand(x1), in_ctot, _operand(mask_in),
+                None if bn is None else _ptr(bn[0]), None if bn is None else _ptr(bn[1]),
+                w16, _ptr(self.b), _operand(out), 3 if fmt == 'nchw' else 1,
+                None if ws is None else C.c_void_p(ws.data_ptr()), int(nws),
+                None if stats is None else _ptr(stats[0]), None if stats is None else _ptr(stats[1]),
+                float(stats[2]) if stats is not None else 0.0,
+                *((_ptr(fold[0]), _ptr(fold[1]), _ptr(fold[2]), _ptr(fold[3]), int(fold[4]))
+                  if fold is not None else (None, None, None, None, 0)))
+        if CONV_PROFILE is not None and CONV_PROFILE_INFO is not None:
+            CONV_PROFILE_INFO.append(dict(
+                Cin=self.Cin, Cout=self.Cout, C1=C1, C2=0, H=H, W=W, OH=OH, OW=OW, B=B,
+                unpool=unpool, pool=False, add=0, kind=3 if fmt == 'nchw' else 1, flat='m16'))
         return out
 
     def _call_c8(self, x1, x2, add, add_off, window, out, place, pool_out, mask_in, unpool_hw,
@@ -918,8 +1063,9 @@ class Conv:
         """The layer on bf16 C8 activations (include/iiseg.h, iiseg_conv_c8).  x1 / x2 / pool_out:
         C8 tensors (`is_c8`); add: C8 bf16 or C8 fp32 (float32, same 5-D shape); mask_in / mask_out:
         uint8 (B, C/8, h, w, 8).  out_format: 'c8' (default), 'c8f32', or 'nchw' (fp32 NCHW, the
-        class-score layer: default when Cout is not a multiple of 8).  Returns the output tensor
-        (None with store_out=False)."""
+        class-score layer: default when Cout is not a multiple of 8).  x1 and `out` may be channel slices
+        of wider C8 tensors; every other operand is contiguous.  Returns the output tensor (None with
+        store_out=False)."""
         lib = self.lib
         if not self.c8:
             raise RuntimeError("C8 input needs a 3x3 layer built with mma='bf16c8'")
@@ -931,6 +1077,9 @@ class Conv:
             raise RuntimeError('stats: layers with at most 16 output channels')
         if in_c is not None or bn is not None:
             raise RuntimeError('in_c / bn on C8 input: layers with at most 16 output channels')
+        for name, t in (('x2', x2), ('add', add), ('pool_out', pool_out), ('mask_out', mask_out)):
+            if t is not None and not t.is_contiguous():
+                raise RuntimeError('C8 launch: %s must be contiguous' % name)
         unpool = mask_in is not None
         x3 = self.x3
         pair = 2 if x3 else 1                     # chunk planes of a kind-1 tensor per channel chunk
@@ -938,12 +1087,7 @@ class Conv:
             raise RuntimeError('bf16x3 layer: hi / lo pair input, no channel concat')
         B, CC1 = x1.shape[0], x1.shape[1] // pair
         if unpool:
-            if unpool_hw is None or not is_c8_mask(mask_in) or \
-                    tuple(mask_in.shape) != (B, CC1) + tuple(x1.shape[2:]) or \
-                    (unpool_hw[0] // 2, unpool_hw[1] // 2) != tuple(x1.shape[2:4]) or x2 is not None:
-                raise RuntimeError('C8 DePool2D input: up %s, mask %s, unpool_hw %s'
-                                   % (tuple(x1.shape), tuple(mask_in.shape), unpool_hw))
-            H, W = int(unpool_hw[0]), int(unpool_hw[1])
+            H, W = self._c8_unpool_hw(x1, mask_in, unpool_hw, CC1, x2 is None)
         elif zins:
             # the logical input is x1 zero-inserted (include/iiseg.h IISEG_CONV_ZINS): TransitionUp
             if x3 or x2 is not None or self.pad != 0:
@@ -1025,162 +1169,19 @@ class Conv:
                 raise RuntimeError('mask_out: uint8 (B, Cout/8, H/2, W/2, 8)')
         elif mask_out is not None:
             raise RuntimeError('mask_out needs pool_out')
-        if self._W16c8 is None:
-            # packed for the REAL channel count: the rows of padding channels are zero
-            dp = ConvDesc()
-            dp.B, dp.C1, dp.C2, dp.H, dp.W = 1, self.Cin, 0, 8, 8
-            dp.Cout, dp.KH, dp.KW, dp.pad, dp.dil = self.Cout, 3, 3, 1, 1
-            dp.OH, dp.OW = 8, 8
-            Wsrc, so, sc = self.W, self.so, self.sc
-            if x3:
-                # two k-groups of whole 16-channel k-tiles [W_hi | W_lo]; the split values are bf16
-                # numbers, the pack's rounding leaves them as they are
-                Cp = (self.Cin + 15) // 16 * 16
-                Wsrc = torch.empty((self.Cout, 2 * Cp, 3, 3), dtype=torch.float32, device=self.W.device)
-                check(lib.iiseg_conv_c8_split_weights(_stream(), _ptr(self.W), self.so, self.sc,
-                                                      self.Cout, self.Cin, _ptr(Wsrc)),
-                      'iiseg_conv_c8_split_weights')
-                dp.C1, so, sc = 2 * Cp, 2 * Cp * 9, 9
-            self._W16c8 = torch.empty(lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(dp)) // 2,
-                                      dtype=torch.bfloat16, device=self.W.device)
-            check(lib.iiseg_conv_halo_bf16_pack(_stream(), C.byref(dp), _ptr(Wsrc), so, sc,
-                                                _ptr(self._W16c8, torch.bfloat16)),
-                  'iiseg_conv_halo_bf16_pack')
-            del Wsrc
-        dtp = lambda t: None if t is None else (_c8ptr(t) if (is_c8(t) and t is not self._W16c8) else
-                                                _ptr(t, t.dtype))
         if out is not None and is_c8(out) and not out.is_contiguous():
             c8_ctot(out)                   # (validates the slice layout)
+        w16 = self._c8_weights()
         # (the pool rides in the conv's epilogue on every pixel tiling: with pool_out the pixels of a
         # tile are ordered by 2x2 pooling windows)
-        conv_out, conv_kind, conv_pool, conv_mask = out, kind, pool_out, mask_out
-        prof = CONV_PROFILE
-        ev0 = _ev() if prof is not None else None
-        check(lib.iiseg_conv_c8_slice(_stream(), C.byref(d), dtp(x1), int(x1_ctot), dtp(x2), dtp(mask_in),
-                                      dtp(self._W16c8), _ptr(self.b), dtp(add), add_kind, dtp(conv_out),
-                                      conv_kind, dtp(conv_pool), dtp(conv_mask)), 'iiseg_conv_c8_slice')
-        if prof is not None:
-            prof.append(('conv_c8_kernel<x3>' if x3 else 'conv_c8_kernel', self.flops(B, OH, OW), ev0,
-                         _ev()))
-            if CONV_PROFILE_INFO is not None:
-                CONV_PROFILE_INFO.append(dict(
-                    Cin=self.Cin, Cout=self.Cout, C1=d.C1, C2=d.C2, H=H, W=W, OH=OH, OW=OW, B=B,
-                    unpool=unpool, pool=pool_out is not None, add=add_kind, kind=conv_kind,
-                    flat=self.c8_tiling(d, pool_out is not None)))
-        return out
-
-    def _call_halo_bf16(self, d, x1, x2, pre, pooled, add, out, pool_out, mask_in, mask_out, prof,
-                        B, H, W):
-        """Direct 3x3 form on the bf16 matrix pipe (include/iiseg.h, iiseg_conv_halo_bf16)."""
-        if pool_out is not None:
-            fh, fw = self.out_hw(H, W)
-            if tuple(pool_out.shape) != (B, self.Cout, fh // 2, fw // 2):
-                raise RuntimeError('pool_out shape %s' % (tuple(pool_out.shape),))
-        if self._W16 is None:
-            self._W16 = torch.empty(self.lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(d)) // 2,
-                                    dtype=torch.bfloat16, device=self.W.device)
-            check(self.lib.iiseg_conv_halo_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
-                                                     self.sc, _ptr(self._W16, torch.bfloat16)),
-                  'iiseg_conv_halo_bf16_pack')
-        ev0 = _ev() if prof is not None else None
-        check(self.lib.iiseg_conv_halo_bf16(_stream(), C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre),
-                                            _ptr(pooled), _ptr(self._W16, torch.bfloat16),
-                                            _ptr(self.b), _ptr(add), _ptr(out), _ptr(pool_out),
-                                            _ptr(mask_in, torch.uint8),
-                                            _ptr(mask_out, torch.uint8)),
-              'iiseg_conv_halo_bf16')
-        if prof is not None:
-            prof.append(('conv_halo_bf16_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
-        return out
-
-    def _call_wino_bf16(self, d, x1, x2, pre, pooled, add, out, prof):
-        """bf16-operand Winograd form (include/iiseg.h, iiseg_conv_wino_bf16): input transform ->
-        V16, then one kernel for the 16 GEMMs + output transform + epilogue."""
-        lib = self.lib
-        if self._U16 is None:
-            self._U16 = torch.empty(lib.iiseg_conv_wino_bf16_weight_bytes(C.byref(d)) // 2,
-                                    dtype=torch.bfloat16, device=self.W.device)
-            check(lib.iiseg_conv_wino_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
-                                                self.sc, _ptr(self._U16, torch.bfloat16)),
-                  'iiseg_conv_wino_bf16_pack')
-        ws = _wino_workspace((lib.iiseg_conv_wino_bf16_workspace_bytes(C.byref(d)) + 3) // 4,
-                             x1.device)
-        args = (C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre), _ptr(pooled),
-                _ptr(self._U16, torch.bfloat16), _ptr(self.b), _ptr(add), _ptr(ws), _ptr(out))
-        if prof is None:
-            check(lib.iiseg_conv_wino_bf16(_stream(), *args, 3), 'iiseg_conv_wino_bf16')
-            return out
-        r0, c0 = d.oy0 - ((d.oy0 - d.tile_y0) & 1), d.ox0 - ((d.ox0 - d.tile_x0) & 1)
-        T = d.B * ((d.oy0 + d.OH - r0 + 1) // 2) * ((d.ox0 + d.OW - c0 + 1) // 2)
-        kc = (self.Cin + 63) // 64 * 64
-        gemm_flops = 16 * 2.0 * kc * self.Cout * T            # multiplies actually issued
-        ev0 = _ev()
-        for name, stage, fl in (('wino_input_bf16_kernel', 1, 0.0),
-                                ('wino_fused_bf16_kernel', 2, gemm_flops)):
-            check(lib.iiseg_conv_wino_bf16(_stream(), *args, stage), 'iiseg_conv_wino_bf16')
-            ev1 = _ev()
-            prof.append((name, fl, ev0, ev1))
-            ev0 = ev1
-        return out
-
-    def _call_wino_f64(self, d, x1, x2, pre, pooled, add, out, prof, B):
-        """float64 Winograd form (include/iiseg.h, iiseg_conv_wino_f64)."""
-        lib = self.lib
-        dt = torch.float64
-        if self._U is None:
-            self._U = torch.empty(lib.iiseg_conv_wino_f64_weight_elems(C.byref(d)), dtype=dt,
-                                  device=self.W.device)
-            check(lib.iiseg_conv_wino_pack_f64(_stream(), C.byref(d), _ptr(self.W, dt), self.so, self.sc,
-                                               _ptr(self._U, dt)), 'iiseg_conv_wino_pack_f64')
-        ws = _wino_workspace64(lib.iiseg_conv_wino_f64_workspace_elems(C.byref(d)), x1.device)
-        ev0 = _ev() if prof is not None else None
-        check(lib.iiseg_conv_wino_f64(_stream(), C.byref(d), _ptr(x1, dt), _ptr(x2, dt), _ptr(pre, dt),
-                                      _ptr(pooled, dt), _ptr(self._U, dt),
-                                      _ptr(self.b, dt), _ptr(add, dt), _ptr(ws, dt), _ptr(out, dt)),
-              'iiseg_conv_wino_f64')
-        if prof is not None:
-            prof.append(('wino64_gemm_kernel', self.flops(B, d.OH, d.OW), ev0, _ev()))
-        return out
-
-    def _call_wino(self, d, x1, x2, pre, pooled, add, out, prof, mask_in=None, pool_out=None,
-                   mask_out=None):
-        """Winograd F(2x2,3x3) form of the layer (include/iiseg.h, iiseg_conv_wino_f32; with a
-        fused pool or mask bytes iiseg_conv_wino_mask_f32)."""
-        lib = self.lib
-        if self._U is None:
-            self._U = torch.empty(lib.iiseg_conv_wino_weight_elems(C.byref(d)), dtype=torch.float32,
-                                  device=self.W.device)
-            check(lib.iiseg_conv_wino_pack_f32(_stream(), C.byref(d), _ptr(self.W), self.so, self.sc,
-                                               _ptr(self._U)), 'iiseg_conv_wino_pack_f32')
-        ws = _wino_workspace(lib.iiseg_conv_wino_workspace_elems(C.byref(d)), x1.device)
-        if mask_in is None and pool_out is None:
-            fn, what = lib.iiseg_conv_wino_f32, 'iiseg_conv_wino_f32'
-            args = (C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre), _ptr(pooled), _ptr(self._U),
-                    _ptr(self.b), _ptr(add), _ptr(ws), _ptr(out))
-        else:
-            fn, what = lib.iiseg_conv_wino_mask_f32, 'iiseg_conv_wino_mask_f32'
-            args = (C.byref(d), _ptr(x1), _ptr(x2), _ptr(pre), _ptr(pooled), _ptr(mask_in, torch.uint8),
-                    _ptr(self._U), _ptr(self.b), _ptr(add), _ptr(ws), _ptr(out), _ptr(pool_out),
-                    _ptr(mask_out, torch.uint8))
-        # (a skip-add would be read by the fused kernel's epilogue, uncoalesced and with nothing to
-        # hide its latency: such layers keep the separate, coalesced output transform)
-        fused = 8 if (self.Cin <= WINO_FUSED_MAX_CIN and self.Cin % 32 == 0 and add is None) else 0
-        if prof is None:
-            check(fn(_stream(), *args, 7 | fused), what)
-            return out
-        # profiling: the kernels separately, events around each
-        stages = (1 | fused, 2 | fused) if fused else (1, 2, 4)
-        names = ('wino_input_kernel', 'wino_fused_kernel' if fused else 'wino_gemm_kernel',
-                 'wino_output_kernel')
-        r0, c0 = d.oy0 - ((d.oy0 - d.tile_y0) & 1), d.ox0 - ((d.ox0 - d.tile_x0) & 1)
-        T = d.B * ((d.oy0 + d.OH - r0 + 1) // 2) * ((d.ox0 + d.OW - c0 + 1) // 2)
-        gemm_flops = 16 * 2.0 * self.Cin * self.Cout * T      # multiplies actually issued
-        ev0 = _ev()
-        for i, stage in enumerate(stages):
-            check(fn(_stream(), *args, stage), what)
-            ev1 = _ev()
-            prof.append((names[i], gemm_flops if i == 1 else 0.0, ev0, ev1))
-            ev0 = ev1
+        _launch('conv_c8_kernel<x3>' if x3 else 'conv_c8_kernel', self.flops(B, OH, OW), lib.iiseg_conv_c8_slice,
+                C.byref(d), _operand(x1), int(x1_ctot), _operand(x2), _operand(mask_in), w16, _ptr(self.b),
+                _operand(add), add_kind, _operand(out), kind, _operand(pool_out), _operand(mask_out))
+        if CONV_PROFILE is not None and CONV_PROFILE_INFO is not None:
+            CONV_PROFILE_INFO.append(dict(
+                Cin=self.Cin, Cout=self.Cout, C1=d.C1, C2=d.C2, H=H, W=W, OH=OH, OW=OW, B=B,
+                unpool=unpool, pool=pool_out is not None, add=add_kind, kind=kind,
+                flat=self.c8_tiling(d, pool_out is not None)))
         return out
 
 
@@ -1258,8 +1259,20 @@ def c8_ctot(t):
     return C8n * 8 if B == 1 else st[0] // (H * W * 8) * 8
 
 
-def _c8ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+def _c8ptr(t, dtype=torch.bfloat16):
+    """A C8 operand that may be a channel slice of a wider tensor (`c8_ctot` validates such layouts)."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError('iiseg ops need device tensors (got %s)' % t.device)
+    if t.dtype != dtype:
+        raise RuntimeError('expected %s, got %s' % (dtype, t.dtype))
+    return C.c_void_p(t.data_ptr())
+
+
+def _operand(t):
+    """An operand of a C8 launch: a bf16 C8 tensor (or channel slice), else a contiguous one of its dtype."""
+    return None if t is None else (_c8ptr(t) if is_c8(t) else _ptr(t, t.dtype))
 
 
 def is_c8_mask(t):
@@ -1569,15 +1582,12 @@ def ctx_tail(conv6, conv7, x, y, state, step, ycat=None, cat_c0=0, cat_off=(0, 0
         if ycat.dim() != 4 or ycat.shape[0] != B or ycat.dtype != torch.float32:
             raise RuntimeError('ctx_tail: ycat %s' % (tuple(ycat.shape),))
         cat = (ycat.shape[1], int(cat_c0), ycat.shape[2], ycat.shape[3], int(cat_off[0]), int(cat_off[1]))
-    prof = CONV_PROFILE
-    ev0 = _ev() if prof is not None else None
-    check(lib.iiseg_ctx_tail_f32(_stream(), _ptr(x), _ptr(wp6), d6.Mpad, _ptr(conv6.b), _ptr(wp7), d7.Mpad,
-                                 _ptr(conv7.b), _ptr(y), _ptr(state.active, torch.int32),
-                                 _ptr(state.partial, torch.float64), _ptr(ycat), *cat, B, Cc, H, W, float(step)),
-          'iiseg_ctx_tail_f32')
-    if prof is not None:
-        kern = 'ctx_tail_kernel'
-        prof.append((kern, conv6.flops(B, H, W) + conv7.flops(B, H, W), ev0, _ev()))
+    kern = 'ctx_tail_kernel'
+    _launch(kern, conv6.flops(B, H, W) + conv7.flops(B, H, W), lib.iiseg_ctx_tail_f32,
+            _ptr(x), _ptr(wp6), d6.Mpad, _ptr(conv6.b), _ptr(wp7), d7.Mpad, _ptr(conv7.b), _ptr(y),
+            _ptr(state.active, torch.int32), _ptr(state.partial, torch.float64), _ptr(ycat), *cat, B, Cc, H, W,
+            float(step))
+    if CONV_PROFILE is not None:
         # algorithmic bytes: x planes read, y read and written, the mirror written
         KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
             4.0 * B * Cc * ((H + 2) * (W + 2) + (3 if ycat is not None else 2) * H * W)
@@ -1657,14 +1667,9 @@ class Conv1x1C8:
         a, b_ = bn if bn is not None else (None, None)
         if a is not None and (a.numel() < cin or b_.numel() < cin):
             raise RuntimeError('Conv1x1C8: folded BN vectors shorter than the input')
-        prof = CONV_PROFILE
-        ev0 = _ev() if prof is not None else None
-        check(self.lib.iiseg_conv1x1_c8(_stream(), C.c_void_p(x8.data_ptr()), B, cin, in_ctot, H, W, _ptr(a),
-                                        _ptr(b_), _ptr(wp, torch.bfloat16), _ptr(self.b), self.Cout,
-                                        1 if pool else 0, C.c_void_p(out.data_ptr()), octot, int(out_c0)),
-              'iiseg_conv1x1_c8')
-        if prof is not None:
-            prof.append(('conv1x1_c8_kernel', self.flops(B, H, W), ev0, _ev()))
+        _launch('conv1x1_c8_kernel', self.flops(B, H, W), self.lib.iiseg_conv1x1_c8,
+                C.c_void_p(x8.data_ptr()), B, cin, in_ctot, H, W, _ptr(a), _ptr(b_), _ptr(wp, torch.bfloat16),
+                _ptr(self.b), self.Cout, 1 if pool else 0, C.c_void_p(out.data_ptr()), octot, int(out_c0))
         return out
 
 
@@ -1686,11 +1691,7 @@ def bn_stats_c8(buf8, c0, n, mean, inv_std, eps=1e-4):
     lib = _lib.load()
     B, C8n, H, W, _ = buf8.shape
     ctot = c8_ctot(buf8)
-    key = _ws_key(buf8.device)
-    need = lib.iiseg_bn_stats_c8_workspace_elems(int(n))
-    ws = _bn_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _bn_ws[key] = torch.empty(int(need), dtype=torch.float64, device=buf8.device)
+    ws = _workspace('bn', lib.iiseg_bn_stats_c8_workspace_elems(int(n)), buf8.device)
     check(lib.iiseg_bn_stats_c8(_stream(), _c8ptr(buf8), B, ctot, int(c0), int(n), H, W,
                                 float(eps), _ptr(mean), _ptr(inv_std), _ptr(ws, torch.float64)),
           'iiseg_bn_stats_c8')
@@ -1704,10 +1705,7 @@ def bn_stats(buf, c0, n, mean, inv_std, eps=1e-4):
     item = buf.element_size()
     _ptr(buf, dt), _ptr(mean, dt), _ptr(inv_std, dt)
     xp = C.c_void_p(buf.data_ptr() + c0 * H * W * item)
-    ws = _bn_ws.get(_ws_key(buf.device))
-    need = _lib.load().iiseg_bn_stats_workspace_elems(n)
-    if ws is None or ws.numel() < need:
-        ws = _bn_ws[_ws_key(buf.device)] = torch.empty(int(need), dtype=torch.float64, device=buf.device)
+    ws = _workspace('bn', _lib.load().iiseg_bn_stats_workspace_elems(n), buf.device)
     check(_fn('bn_stats', dt)(_stream(), xp, Ctot * H * W, B, n, H * W, float(eps),
                               C.c_void_p(mean.data_ptr() + c0 * item),
                               C.c_void_p(inv_std.data_ptr() + c0 * item),
