@@ -783,6 +783,73 @@ int iiseg_crf_step_f32(void* stream, const iiseg_crf_desc* d, const float* U, co
 int iiseg_crf_step_f64(void* stream, const iiseg_crf_desc* d, const double* U, const double* Qin,
                        const double* I, const double* ng, const double* nb, double* Qout);
 
+/* ---------------------------------------------------------------------------------------
+ * Training the context-module DAE (reference train_dae.py, dae kind 'contextmod').
+ * Every entry checks its arguments and returns a status before any launch; every sum has a fixed order
+ * (the same inputs give the same bits on every run).  Tensors: device, NCHW, C-contiguous.
+ *
+ * Loss (metrics.py:68-91 crossentropy, :144-156 squared_error with an int `void`): score (B,C,H,W) is the
+ * 1x1 layer's output, target (B,C+1,H,W) one-hot with the void channel last, 2 <= C <= 16.
+ *   iiseg_ctx_loss_count : cnt[4] = {N_ce, N_se, 1/N_ce, 1/N_se} of the BATCH, N_ce = pixels whose arg-max
+ *       channel is not the void channel, N_se = sum of target[:, :C]; an empty mask gives the reciprocal 0,
+ *       so the loss and its gradient are then 0 (never NaN).
+ *   iiseg_ctx_loss : r = softmax(score); res[3] = {loss, crossentropy, squared_error} with
+ *       loss = [CROSSENTROPY] ce + [SQUARED_ERROR] lmb se; g (may be NULL) = dloss/dscore, NORMALISED (it
+ *       reads cnt from iiseg_ctx_loss_count); where r[label] is outside [1e-7, 1 - 1e-7] the clip is active
+ *       and the cross-entropy term's gradient is 0.
+ *   partial: 2 * iiseg_ctx_loss_partials(B, H, W) doubles of scratch.
+ *
+ * Weight gradient of a 'valid' K x K layer (K = 1 or 3, dilation dil, at most 16 channels on either side):
+ *   g_z = out ? gout * [out > 0] : gout                      (B,Cout,OH,OW), OH = H - dil (K - 1)
+ *   dW[ci][co][ky][kx] = sum_{b,y,x} x[b,ci,y + ky dil,x + kx dil] g_z[b,co,y,x],  db[co] = sum g_z
+ * dW is written in the layer's parameter layout: element (co, ci, tap) at co * so + ci * sc + tap with
+ * (so, sc) = (Cin K K, K K) for W[out,in,k,k] or (K K, Cout K K) for W[in,out,k,k].  gz (may be NULL)
+ * receives g_z inside (gz_H, gz_W) planes at (gz_y0, gz_x0) -- a zero-bordered buffer on which the data
+ * gradient runs as a 'valid' layer; the rest of gz is not touched.  slab: scratch of
+ * iiseg_conv_small_wgrad_partials(d, sizeof element) * (Cin Cout K K + Cout) elements.
+ *
+ * Optimizer step on n scalars (Lasagne's rmsprop / adam with their defaults), lr read from device memory:
+ *   RMSPROP: s1 <- 0.9 s1 + (1 - 0.9) g^2;  p <- p - lr g / sqrt(s1 + 1e-6)                 (s2, state unused)
+ *   ADAM:    state = {t, 0.9^t, 0.999^t} (start {0, 1, 1}; the powers are running products), advanced first;
+ *            alpha = lr sqrt(1 - 0.999^t) / (1 - 0.9^t);  s1 <- 0.9 s1 + (1 - 0.9) g;
+ *            s2 <- 0.999 s2 + (1 - 0.999) g^2;  p <- p - alpha s1 / (sqrt(s2) + 1e-8)
+ * Each operation is rounded on its own in the tensors' type (no FMA contraction).
+ * ------------------------------------------------------------------------------------- */
+#define IISEG_LOSS_CROSSENTROPY 1u
+#define IISEG_LOSS_SQUARED_ERROR 2u
+#define IISEG_OPT_RMSPROP 0
+#define IISEG_OPT_ADAM 1
+
+typedef struct iiseg_wgrad_desc {
+    int32_t B, Cin, Cout, H, W, K, dil;
+    int32_t gz_H, gz_W, gz_y0, gz_x0;
+    int32_t reserved;
+    int64_t so, sc;
+} iiseg_wgrad_desc;
+
+/* host only: number of partials, or a negative status */
+int iiseg_ctx_loss_partials(int32_t B, int32_t H, int32_t W);
+int iiseg_ctx_loss_count_f32(void* stream, const float* target, double* partial, double* cnt, int32_t B,
+                             int32_t C, int32_t H, int32_t W);
+int iiseg_ctx_loss_count_f64(void* stream, const double* target, double* partial, double* cnt, int32_t B,
+                             int32_t C, int32_t H, int32_t W);
+int iiseg_ctx_loss_f32(void* stream, const float* score, const float* target, const double* cnt, float* g,
+                       double* partial, double* res, int32_t B, int32_t C, int32_t H, int32_t W,
+                       uint32_t flags, double lmb);
+int iiseg_ctx_loss_f64(void* stream, const double* score, const double* target, const double* cnt, double* g,
+                       double* partial, double* res, int32_t B, int32_t C, int32_t H, int32_t W,
+                       uint32_t flags, double lmb);
+/* host only: number of slabs for elements of elem_bytes (4 or 8), or a negative status */
+int iiseg_conv_small_wgrad_partials(const iiseg_wgrad_desc* d, int32_t elem_bytes);
+int iiseg_conv_small_wgrad_f32(void* stream, const iiseg_wgrad_desc* d, const float* x, const float* gout,
+                               const float* out, float* gz, float* slab, float* dW, float* db);
+int iiseg_conv_small_wgrad_f64(void* stream, const iiseg_wgrad_desc* d, const double* x, const double* gout,
+                               const double* out, double* gz, double* slab, double* dW, double* db);
+int iiseg_opt_step_f32(void* stream, int32_t kind, float* p, const float* g, float* s1, float* s2,
+                       const float* lr, float* state, int64_t n);
+int iiseg_opt_step_f64(void* stream, int32_t kind, double* p, const double* g, double* s1, double* s2,
+                       const double* lr, double* state, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

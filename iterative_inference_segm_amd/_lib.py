@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libiiseg_hip.so')
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 CONV_RELU = 1
 CONV_UNPOOL = 2
@@ -44,6 +44,18 @@ class CrfDesc(C.Structure):
     """struct iiseg_crf_desc"""
     _fields_ = [(n, C.c_int32) for n in ('B', 'C', 'H', 'W', 'R')] + [('flags', C.c_uint32)] + \
                [(n, C.c_double) for n in ('sxy_g', 'w_g', 'sxy_b', 'srgb', 'w_b', 'clip')]
+
+
+LOSS_CROSSENTROPY = 1
+LOSS_SQUARED_ERROR = 2
+OPT_RMSPROP = 0
+OPT_ADAM = 1
+
+
+class WgradDesc(C.Structure):
+    """struct iiseg_wgrad_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'dil', 'gz_H', 'gz_W', 'gz_y0',
+                                         'gz_x0', 'reserved')] + [('so', C.c_int64), ('sc', C.c_int64)]
 
 
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
@@ -193,6 +205,17 @@ SIGNATURES = {
     'iiseg_crf_prepare_f64': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 7),
     'iiseg_crf_step_f32': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 6),
     'iiseg_crf_step_f64': (C.c_int, [_vp, C.POINTER(CrfDesc)] + [_vp] * 6),
+    # training the context-module DAE
+    'iiseg_ctx_loss_partials': (C.c_int, [_i32] * 3),
+    'iiseg_ctx_loss_count_f32': (C.c_int, [_vp] * 4 + [_i32] * 4),
+    'iiseg_ctx_loss_count_f64': (C.c_int, [_vp] * 4 + [_i32] * 4),
+    'iiseg_ctx_loss_f32': (C.c_int, [_vp] * 7 + [_i32] * 4 + [C.c_uint32, _f64]),
+    'iiseg_ctx_loss_f64': (C.c_int, [_vp] * 7 + [_i32] * 4 + [C.c_uint32, _f64]),
+    'iiseg_conv_small_wgrad_partials': (C.c_int, [C.POINTER(WgradDesc), _i32]),
+    'iiseg_conv_small_wgrad_f32': (C.c_int, [_vp, C.POINTER(WgradDesc)] + [_vp] * 7),
+    'iiseg_conv_small_wgrad_f64': (C.c_int, [_vp, C.POINTER(WgradDesc)] + [_vp] * 7),
+    'iiseg_opt_step_f32': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
+    'iiseg_opt_step_f64': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
 }
 
 _lib = None

@@ -27,6 +27,20 @@ class ContextModDAE:
         if len(concat_h) != 1:
             raise NotImplementedError('one h (the image) is concatenated at the input')
         self.concat_h = list(concat_h)
+        # ONE flat parameter buffer in PARAM_ORDER (W then b per layer): every ops.Conv below holds VIEWS of it,
+        # so an optimizer step on `flat` followed by `refresh()` reaches every path (training, section 9)
+        self.device, self.dtype = device, dtype
+        host = [(n, torch.as_tensor(params[n][0]), torch.as_tensor(params[n][1])) for n in PARAM_ORDER]
+        self.flat = torch.empty(sum(W.numel() + b.numel() for _, W, b in host), dtype=dtype, device=device)
+        self._views, off = {}, 0
+        for n, W, b in host:
+            Wv = self.flat[off:off + W.numel()].view(W.shape)
+            bv = self.flat[off + W.numel():off + W.numel() + b.numel()]
+            Wv.copy_(W.to(dtype))
+            bv.copy_(b.to(dtype))
+            self._views[n] = (Wv, bv)
+            off += W.numel() + b.numel()
+        params = self._views
         self.conv1 = ops.Conv(params['conv1'][0], params['conv1'][1], pad=1, relu=True,
                               device=device, dtype=dtype)                         # :74-76
         self.dil = []
@@ -47,9 +61,19 @@ class ContextModDAE:
         W, b = params['dilconv1']
         self.dil1_valid = ops.Conv(W, b, pad=0, relu=True, dil=DILATIONS[0], layout='iohw', device=device,
                                    dtype=dtype)
+        lo, hi = self.flat.data_ptr(), self.flat.data_ptr() + self.flat.numel() * self.flat.element_size()
+        for conv in self._shared_convs():
+            assert lo <= conv.W.data_ptr() < hi and lo <= conv.b.data_ptr() < hi      # views, not copies
         self._sessions = {}
         self._conv1_params = (params['conv1'][0], params['conv1'][1], device, dtype)
         self._hsplit = {}           # h channels -> (image-half conv, y-half conv) of the first layer
+        self._adj = None            # training: the data-gradient layers (`_adjoints`)
+        self._train = {}            # training: buffers per geometry
+        self._saved = None          # training: what `forward_train` kept for `backward`
+        self._gflat = None
+
+    def _shared_convs(self):
+        return [self.conv1, self.conv1_valid, self.dil1_valid, self.last] + self.dil
 
     def conv_layers(self):
         d = {'conv1': self.conv1, 'dilconv7': self.last}
@@ -154,6 +178,123 @@ class ContextModDAE:
                             cat_c0=session['ch'], cat_off=(1, 1))
         session['y_in_cat'] = True
         return nblk
+
+    # ---- training (reference train_dae.py with dae kind 'contextmod') ----
+    def parameters(self):
+        """{name: (W, b)} in PARAM_ORDER: views of `self.flat`, the checkpoint's arrays in the checkpoint's
+        layouts.  After changing them in place call `refresh()`."""
+        return dict(self._views)
+
+    def state_arrays(self):
+        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
+        return {n: (W.detach().cpu().float().numpy(), b.detach().cpu().float().numpy())
+                for n, (W, b) in self._views.items()}
+
+    def _adjoints(self):
+        """The data-gradient layers: the adjoint of a 'valid' dilated 3x3 layer is the same layer with the
+        channel-transposed, spatially flipped filter on g_z inside a zero border of 2 d -- W[in,out,k,k]
+        flipped and READ as W[out,in,k,k] is exactly that filter."""
+        if self._adj is None:
+            mk = lambda W, d: ops.Conv(W.flip(2, 3).contiguous(), None, pad=0, relu=False, dil=d, layout='oihw',
+                                       device=self.device, dtype=self.dtype)
+            self._adj = [mk(self._views['dilconv%d' % (i + 1)][0], d) for i, d in enumerate(DILATIONS)]
+            self._adj.append(mk(self._views['dilconv7'][0], 1))
+        return self._adj
+
+    def refresh(self):
+        """The parameters (`self.flat`) have been changed in place: every layer object that holds them -- the
+        padded and 'valid' forms of conv1 / dilconv1, the image / y halves of conv1 a session uses, the
+        data-gradient layers -- packs its weights again into the buffers it already has, and every session's cached
+        image half (`hb`) is computed again from the image it holds.  No host wait."""
+        for conv in self._shared_convs():
+            conv.refresh()
+        W1 = self._views['conv1'][0]
+        for ch, (ch_conv, y_conv) in self._hsplit.items():
+            ch_conv.W.copy_(W1[:, :ch])
+            y_conv.W.copy_(W1[:, ch:])
+            ch_conv.refresh()
+            y_conv.refresh()
+        for sess in self._sessions.values():          # the cached image half of a session that is still in use
+            if sess['split'] is not None:
+                sess['split'][0](sess['hpad'], out=sess['hb'])
+        if self._adj is not None:
+            for i, adj in enumerate(self._adj):
+                adj.W.copy_(self._views['dilconv%d' % (i + 1)][0].flip(2, 3))
+                adj.refresh()
+
+    def _train_buffers(self, B, ch, Cy, H, W, device):
+        key = (B, ch, Cy, H, W)
+        buf = self._train.get(key)
+        if buf is None:
+            zeros = lambda c, hh, ww: torch.zeros((B, c, hh, ww), dtype=self.dtype, device=device)
+            Cc = self.conv1.Cout
+            buf = {'cat': zeros(ch + Cy, H + 2, W + 2), 'pad32': zeros(Cc, H + 64, W + 64), 'gz': []}
+            hh, ww = H + 64, W + 64
+            for d in DILATIONS:                  # g_z of dilconv1..6 inside a zero border of 2 d
+                hh, ww = hh - 2 * d, ww - 2 * d
+                buf['gz'].append(zeros(Cc, hh + 4 * d, ww + 4 * d))
+            while len(self._train) >= 2:
+                self._train.pop(next(iter(self._train)))
+            self._train[key] = buf
+        return buf
+
+    def forward_train(self, h, y, noise=0.0, generator=None, eps=None):
+        """The training-mode forward pass: GaussianNoiseLayer on y (contextmod_dae.py:50-57: y + noise * N(0, 1),
+        `eps` = the caller's standard-normal sample, else drawn from `generator`), then the eight layers, whose
+        outputs are kept for `backward`.  Returns the score map (B,C,H,W) before the softmax."""
+        B, ch, H, W = h.shape
+        if tuple(y.shape[2:]) != (H, W) or y.shape[0] != B or ch + y.shape[1] != self.conv1.Cin:
+            raise RuntimeError('forward_train: h %s, y %s' % (tuple(h.shape), tuple(y.shape)))
+        buf = self._train_buffers(B, ch, y.shape[1], H, W, y.device)
+        if noise > 0:
+            if eps is None:
+                eps = torch.randn(y.shape, generator=generator, device=y.device, dtype=y.dtype)
+            y = ops.add_noise(y, eps, float(noise))
+        buf['cat'][:, :ch, 1:-1, 1:-1].copy_(h)                      # h first (P13)
+        buf['cat'][:, ch:, 1:-1, 1:-1].copy_(y)
+        self.conv1_valid(buf['cat'], out=buf['pad32'], place=(32, 32))
+        acts = [buf['pad32'], self.dil1_valid(buf['pad32'])]
+        for conv in self.dil[1:]:
+            acts.append(conv(acts[-1]))
+        score = self.last(acts[-1])
+        self._saved = {'buf': buf, 'acts': acts, 'score': score, 'hw': (H, W)}
+        return score
+
+    def saved_outputs(self):
+        """The eight layer outputs of the last `forward_train` (conv1 as its (H, W) map), for tests."""
+        s = self._saved
+        H, W = s['hw']
+        return [s['acts'][0][:, :, 32:32 + H, 32:32 + W]] + s['acts'][1:] + [s['score']]
+
+    def backward(self, g_score):
+        """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
+        g_score, after `forward_train`.  Per layer, last to first: the weight-gradient kernel (which applies
+        the ReLU mask and stores g_z inside its zero border), then the data gradient as a 'valid' layer."""
+        s = self._saved
+        if s is None:
+            raise RuntimeError('backward() needs forward_train() first')
+        if self._gflat is None:
+            self._gflat = torch.zeros_like(self.flat)
+            self._gviews, off = {}, 0
+            for n in PARAM_ORDER:
+                W, b = self._views[n]
+                self._gviews[n] = (self._gflat[off:off + W.numel()].view(W.shape),
+                                   self._gflat[off + W.numel():off + W.numel() + b.numel()])
+                off += W.numel() + b.numel()
+        gv, adj, acts, buf = self._gviews, self._adjoints(), s['acts'], s['buf']
+        H, W = s['hw']
+        ops.conv_small_wgrad(acts[6], g_score, None, *gv['dilconv7'], dil=1, layout='iohw')
+        g = adj[6](g_score)
+        for L in range(6, 0, -1):
+            d = DILATIONS[L - 1]
+            gz = buf['gz'][L - 1]
+            ops.conv_small_wgrad(acts[L - 1], g, acts[L], *gv['dilconv%d' % L], dil=d, layout='iohw', gz=gz,
+                                 gz_off=(2 * d, 2 * d))
+            # PadLayer(32)'s adjoint is the crop at (32, 32): only that window of dilconv1's data gradient
+            g = adj[L - 1](gz, window=(32, 32, H, W)) if L == 1 else adj[L - 1](gz)
+        c1 = acts[0][:, :, 32:32 + H, 32:32 + W].contiguous()
+        ops.conv_small_wgrad(buf['cat'], g, c1, *gv['conv1'], dil=1, layout='oihw')
+        return dict(gv)
 
     def __call__(self, *args):
         score = self.scores(args[:-1], args[-1])

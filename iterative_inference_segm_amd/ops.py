@@ -364,6 +364,7 @@ class Conv:
         self._form_cache = {}
         self._descs = {}
         self._packs = {}
+        self._pack_descs = {}       # the descriptor each entry of `_packs` was packed for (`refresh`)
 
     def out_hw(self, H, W):
         if self.transposed:
@@ -430,7 +431,26 @@ class Conv:
                                                    _ptr(wp), _ptr(ktab, torch.int32)), 'iiseg_conv_pack_f32')
                 packed = (wp, ktab)
             self._packs[pkey] = packed
+            self._pack_descs[pkey] = d
         return packed
+
+    def refresh(self):
+        """After `self.W` / `self.b` have been changed IN PLACE (an optimizer step): packs every entry of
+        `_packs` again into the buffers it already has -- launches that hold their addresses (a captured graph)
+        see the new weights.  Layers that already hold a Winograd / 16-bit transform of their weights are
+        refused: those live in tensors a captured graph would keep pointing at.  No host wait."""
+        if any(t is not None for t in (self._U, self._U16, self._W16, self._W16c8)):
+            raise NotImplementedError('Conv.refresh: this layer holds transformed weights (Winograd / bf16 forms); '
+                                      'only the direct kernels\' packs are refreshed in place')
+        so, sc = (self.Cin * self.KH * self.KW, 1) if self.via_im2col else (self.so, self.sc)
+        for pkey, (wp, ktab) in self._packs.items():
+            d = self._pack_descs[pkey]
+            if self.dtype == torch.float64:
+                check(self.lib.iiseg_conv_pack_f64(_stream(), C.byref(d), _ptr(self.W, self.dtype),
+                                                   so, sc, _ptr(wp, self.dtype)), 'iiseg_conv_pack_f64')
+            else:
+                check(self.lib.iiseg_conv_pack_f32(_stream(), C.byref(d), _ptr(self.W), so, sc,
+                                                   _ptr(wp), _ptr(ktab, torch.int32)), 'iiseg_conv_pack_f32')
 
     def _plan(self, B, C1, C2, H, W, window, add_geom, unpool, out_slice=None, place=None,
               anchor=(0, 0)):
@@ -1755,3 +1775,99 @@ def dropout_apply(x, keep, p):
     check(_fn('dropout_apply', dt)(_stream(), _ptr(x, dt), _ptr(keep, dt), float(p), x.numel()),
           'iiseg_dropout_apply')
     return x
+
+
+# ---- training the context-module DAE (csrc/ctx_train.hip) ----
+LOSS_FLAGS = {'crossentropy': _lib.LOSS_CROSSENTROPY, 'squared_error': _lib.LOSS_SQUARED_ERROR}
+OPTIMIZERS = {'rmsprop': _lib.OPT_RMSPROP, 'adam': _lib.OPT_ADAM}
+
+
+def ctx_loss(score, target, losses=('crossentropy',), lmb=1.0, grad=True, res=None, cnt=None, g=None):
+    """The reference's training loss on the score map (B,C,H,W) of the context module and the one-hot target
+    (B,C+1,H,W; void channel last): returns (res, g, cnt) -- res (3 doubles on the device) = [loss,
+    crossentropy, squared_error], g = dloss/dscore (normalised by the batch's mask sums; None with
+    grad=False), cnt = [N_ce, N_se, 1/N_ce, 1/N_se].  Two launches on the target (mask counts), two on the
+    score map; no host wait."""
+    dt = score.dtype
+    B, Cc, H, W = score.shape
+    if tuple(target.shape) != (B, Cc + 1, H, W) or target.dtype != dt:
+        raise RuntimeError('ctx_loss: target %s %s for score %s %s' % (tuple(target.shape), target.dtype,
+                                                                      tuple(score.shape), dt))
+    flags = 0
+    for name in losses:
+        if name not in LOSS_FLAGS:
+            raise ValueError('ctx_loss: loss %r is not built (crossentropy, squared_error)' % (name,))
+        flags |= LOSS_FLAGS[name]
+    lib = _lib.load()
+    nblk = lib.iiseg_ctx_loss_partials(B, H, W)
+    if nblk < 0:
+        check(nblk, 'iiseg_ctx_loss_partials')
+    partial = _workspace('bn', 2 * nblk, score.device)
+    f64 = torch.float64
+    if cnt is None:
+        cnt = torch.empty(4, dtype=f64, device=score.device)
+    if res is None:
+        res = torch.empty(3, dtype=f64, device=score.device)
+    if grad and g is None:
+        g = torch.empty_like(score)
+    _launch('ctx_loss_count_kernel', 0.0, _fn('ctx_loss_count', dt), _ptr(target, dt), _ptr(partial, f64),
+            _ptr(cnt, f64), B, Cc, H, W)
+    _launch('ctx_loss_kernel', 0.0, _fn('ctx_loss', dt), _ptr(score, dt), _ptr(target, dt), _ptr(cnt, f64),
+            _ptr(g, dt) if grad else None, _ptr(partial, f64), _ptr(res, f64), B, Cc, H, W, flags, float(lmb))
+    return res, (g if grad else None), cnt
+
+
+def wgrad_desc(x_shape, Cout, K, dil, layout, gz_place=None):
+    """The iiseg_wgrad_desc of a 'valid' layer on x (B,Cin,H,W); gz_place = (gz_H, gz_W, y0, x0)."""
+    B, Cin, H, W = x_shape
+    d = _lib.WgradDesc()
+    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.dil = int(B), int(Cin), int(Cout), int(H), int(W), int(K), int(dil)
+    OH, OW = H - dil * (K - 1), W - dil * (K - 1)
+    d.gz_H, d.gz_W, d.gz_y0, d.gz_x0 = (OH, OW, 0, 0) if gz_place is None else tuple(int(v) for v in gz_place)
+    kk = K * K
+    if layout == 'oihw':
+        d.so, d.sc = Cin * kk, kk
+    elif layout == 'iohw':
+        d.so, d.sc = kk, Cout * kk
+    else:
+        raise ValueError(layout)
+    return d
+
+
+def conv_small_wgrad(x, gout, out, dW, db, dil=1, layout='oihw', gz=None, gz_off=(0, 0)):
+    """dW, db (written in place, the layer's own parameter layout) of the 'valid' layer that maps x
+    (B,Cin,H,W) to `out` (B,Cout,OH,OW) = relu(...) -- or, with out=None, a linear layer -- given gout =
+    dL/dout.  gz (optional): receives g_z = gout * [out > 0] at `gz_off` of its (larger) planes."""
+    dt = x.dtype
+    K = dW.shape[2]
+    Cout = dW.shape[0] if layout == 'oihw' else dW.shape[1]
+    place = None if gz is None else (gz.shape[2], gz.shape[3], gz_off[0], gz_off[1])
+    d = wgrad_desc(tuple(x.shape), Cout, K, dil, layout, place)
+    OH, OW = x.shape[2] - dil * (K - 1), x.shape[3] - dil * (K - 1)
+    if tuple(gout.shape) != (x.shape[0], Cout, OH, OW) or (out is not None and out.shape != gout.shape) or \
+            (gz is not None and tuple(gz.shape[:2]) != (x.shape[0], Cout)) or dW.numel() != x.shape[1] * Cout * K * K \
+            or db.numel() != Cout:
+        raise RuntimeError('conv_small_wgrad: shapes x %s gout %s dW %s' % (tuple(x.shape), tuple(gout.shape),
+                                                                            tuple(dW.shape)))
+    lib = _lib.load()
+    nslab = lib.iiseg_conv_small_wgrad_partials(C.byref(d), dW.element_size())
+    if nslab < 0:
+        check(nslab, 'iiseg_conv_small_wgrad_partials')
+    slab = _workspace(_SUFFIX[dt], nslab * (dW.numel() + Cout), x.device)
+    kern = 'conv_small_wgrad_kernel'
+    _launch(kern, 2.0 * dW.numel() * x.shape[0] * OH * OW, _fn('conv_small_wgrad', dt), C.byref(d), _ptr(x, dt),
+            _ptr(gout, dt), _ptr(out, dt), _ptr(gz, dt), _ptr(slab, dt), _ptr(dW, dt), _ptr(db, dt))
+    if CONV_PROFILE is not None:
+        # byte model: x and g_out read, g_z written, once each
+        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
+            float(dW.element_size()) * (x.shape[1] + 2 * Cout) * x.shape[0] * x.shape[2] * x.shape[3]
+
+
+def opt_step(kind, p, g, s1, s2, lr, state):
+    """One optimizer step on the flat buffers p, g, s1 (, s2) in place; lr: one element on the device;
+    state (adam): [t, 0.9^t, 0.999^t], start [0, 1, 1]."""
+    dt = p.dtype
+    if not (p.numel() == g.numel() == s1.numel()) or (s2 is not None and s2.numel() != p.numel()):
+        raise RuntimeError('opt_step: buffers of different sizes')
+    _launch('opt_step_kernel', 0.0, _fn('opt_step', dt), OPTIMIZERS[kind], _ptr(p, dt), _ptr(g, dt), _ptr(s1, dt),
+            _ptr(s2, dt), _ptr(lr, dt), _ptr(state, dt), p.numel())
