@@ -13,7 +13,8 @@ import numpy as np
 
 import torch
 
-from . import ops
+from . import ops, regions
+from .regions import center
 from .weights import load_param_list
 
 # float64 decoder layers on the halo-tile kernel apply DePool2D while staging their patches
@@ -47,10 +48,6 @@ def param_order(concat_h=('pool4',), conv_before_pool=1, additional_pool=2,
 # mma='bf16c8': decoder levels with at least this many input channels materialise DePool2D (ops.unpool_c8) and run
 # their conv as a plain layer (0: every level unpools in its conv's patch staging)
 C8_UNPOOL_MIN_CIN = int(os.environ.get('IISEG_C8_UNPOOL_MIN_CIN', '1024'))
-
-
-def _center(big, small):
-    return (big - small) // 2
 
 
 class StandardDAE:
@@ -219,7 +216,7 @@ class StandardDAE:
         if i == self.conv_before_pool and not self.bn and (hb is None or self._wino_f32(conv)):
             pw_ = conv.pool_window(t.shape[2], t.shape[3], dep if primed else None, c8=False,
                                    anchor=kw['anchor'])
-        fused_pool = pool_mask = None
+        fused_pool = None
         if pw_ is not None:
             if primed:
                 fused_pool = session['pool%d' % (p + 1)]
@@ -293,6 +290,40 @@ class StandardDAE:
         d.update(self.dec)
         return d
 
+    def _plan(self, y_shape, primed=False, h_dep=None):
+        """regions.dae_plan for this net's layers: the windows of one `scores` call on a y of that
+        shape, for both activation layouts.  What depends on a Conv's chosen form (pool_window,
+        `_mask_levels`) is decided by the layout's walk, fed from the plan."""
+        convs = [(c.pad, c.KH, c.KW, c.dil) for c in
+                 (self.enc['conv%d_%d' % (p + 1, i)] for p in range(self.total)
+                  for i in range(1, self.conv_before_pool + 1))]
+        plan = regions.dae_plan(convs, self.conv_before_pool, self.total, self.n_pool, self.concat_h,
+                                (y_shape[2], y_shape[3]), primed, h_dep, self.dce)
+        if self.total in plan.feeds:
+            raise NotImplementedError('h concatenated at the last pool feeds DePool2D directly '
+                                      '(additional_pool=0); not shape-consistent in the reference')
+        return plan
+
+    def _h_half(self, name, h, step, session, convert=lambda h: h, **fmt):
+        """The h-half of the split conv behind a concat point (a per-pixel bias map the y-half adds in
+        its epilogue), kept in the session: computed once per refine(); again in full for the new
+        batch of a buffer-stable session (`h_stale`); on the window a fresh h changes when a
+        border-folded session is reused (`h_fresh`).  convert / fmt: the layout's form of h and of
+        the map.  Returns (map, whether it was allocated by this call)."""
+        conv_h = self.hsplit[name][0]
+        keep = session is not None and self.licm
+        hb = session.get('hb_' + name) if keep else None
+        if hb is None:
+            hb = conv_h(convert(h), **fmt)
+            if keep:
+                session['hb_' + name] = hb
+            return hb, True
+        assert tuple(hb.shape[2:4]) == step.out_hw
+        window = (0, 0) + step.out_hw if session.get('stable') and session.get('h_stale') else step.h_window
+        if window is not None:
+            conv_h(convert(h), window=window, out=hb, place=window[:2], **fmt)
+        return hb, False
+
     def scores(self, h_list, y, mask_override=None, session=None):
         """Runs the DAE up to the pre-softmax score map already cropped to y's size
         (fused_up1 of fcn_up.py:104-113).  Returns score (B, n_classes, H, W).
@@ -307,17 +338,12 @@ class StandardDAE:
             if mask_override is not None:
                 raise NotImplementedError("mask injection needs fp32 activations (mma='bf16' / 'f32')")
             return self._scores_c8(h_list, y, session)
-        pos = 0
-        pending_h = None
-        h_fresh = session is not None and session.get('h_fresh', False)
-        if self.concat_h[pos] == 'input':                # model_helpers.py:86-94 at the input
-            pending_h, pos = h_list[pos], pos + 1
         t = y
         pre, pool = {}, {0: y}
         # Loop-invariant code motion for the refinement loop: between two steps only y changes, so
         # only the part of every encoder map that y can reach has to be recomputed (the pad-100
         # border and everything fed by h alone keep the values of the first step).  `session`
-        # carries the full-size buffers; `dep` is the y-dependent region (y0, x0, h, w) of `t`.
+        # carries the full-size buffers; the plan's `dep` is the y-dependent region of each map.
         primed = session is not None and session.get('primed', False) and self.licm
         will_override = mask_override is not None or (
             self.emulate_noise and (self.noise > 0 or self.dropout > 0) and
@@ -331,94 +357,51 @@ class StandardDAE:
                 # the session's buffers are (re)allocated by this call: anything that captured
                 # pointers into the previous ones (api._refine_graph) must notice
                 session['gen'] = session.get('gen', 0) + 1
+        plan = self._plan(y.shape, primed, session['h_dep'] if session is not None and
+                          session.get('h_fresh', False) else None)
         masks = {}
-        dep = (0, 0, y.shape[2], y.shape[3])
-        ydep = dep    # the region y alone reaches: its origin parity anchors the Winograd tiles
-
-        def clip(lo, hi, size):
-            lo, hi = max(lo, 0), min(hi, size)
-            return lo, max(hi - lo, 0)
-
-        for p in range(self.total):                      # fcn_down.py:77-136
-            fused_pool = pool_mask = None
-            for i in range(1, self.conv_before_pool + 1):
-                name = 'conv%d_%d' % (p + 1, i)
-                conv = self.enc[name]
-                fh, fw = conv.out_hw(t.shape[2], t.shape[3])
-                ydep = (clip(ydep[0] + conv.pad - (conv.KH - 1), ydep[0] + ydep[2] + conv.pad, fh) +
-                        clip(ydep[1] + conv.pad - (conv.KW - 1), ydep[1] + ydep[3] + conv.pad, fw))
-                ydep = (ydep[0], ydep[2], ydep[1], ydep[3])
-                kw = dict(anchor=(ydep[0], ydep[1]))
-                if primed and pending_h is not None and h_fresh:
-                    # a new batch in a reused session: h changed inside its tagged region
-                    hd = session['h_dep'][pos - 1]
-                    y1 = max(dep[0] + dep[2], hd[0] + hd[2])
-                    x1 = max(dep[1] + dep[3], hd[1] + hd[3])
-                    dep = (min(dep[0], hd[0]), min(dep[1], hd[1]), 0, 0)
-                    dep = (dep[0], dep[1], y1 - dep[0], x1 - dep[1])
-                if primed:
-                    buf = session[name]
-                    fh, fw = buf.shape[2], buf.shape[3]
-                    wy0, wh = clip(dep[0] + conv.pad - (conv.KH - 1), dep[0] + dep[2] + conv.pad, fh)
-                    wx0, ww = clip(dep[1] + conv.pad - (conv.KW - 1), dep[1] + dep[3] + conv.pad, fw)
-                    dep = (wy0, wx0, wh, ww)
-                    kw.update(window=dep, out=buf, place=(wy0, wx0))
-                if pending_h is not None and name in self.hsplit:
-                    conv_h, conv_y = self.hsplit[name]
-                    keep = session is not None and self.licm
-                    hb = session.get('hb_' + name) if keep else None
-                    if hb is None:                       # loop-invariant: once per refine()
-                        hb = conv_h(pending_h)
-                        if keep:
-                            session['hb_' + name] = hb
-                    elif h_fresh:                        # reused session: only where h changed
-                        hd = session['h_dep'][pos - 1]
-                        hy0, hh = clip(hd[0] + conv_h.pad - (conv_h.KH - 1), hd[0] + hd[2] + conv_h.pad,
-                                       hb.shape[2])
-                        hx0, hw = clip(hd[1] + conv_h.pad - (conv_h.KW - 1), hd[1] + hd[3] + conv_h.pad,
-                                       hb.shape[3])
-                        conv_h(pending_h, window=(hy0, hx0, hh, hw), out=hb, place=(hy0, hx0))
-                    pending_h = None
-                    t, fused_pool, pool_mask = self._conv_pool(conv_y, p, i, t, kw, dep, primed, session,
-                                                               masked, masks, hb=hb)
-                elif pending_h is not None:              # h first, then features (P13)
-                    t = conv(pending_h, x2=t, **kw)
-                    pending_h = None
-                else:
-                    t, fused_pool, pool_mask = self._conv_pool(conv, p, i, t, kw, dep, primed, session,
-                                                               masked, masks)
-                if self.bn:
-                    ops.bn_affine(t, self.enc_bn[name], window=dep if primed else None)
-                if session is not None and not primed:
-                    session[name] = t
-                    if (p + 1) in masks and i == self.conv_before_pool:
-                        session['mask%d' % (p + 1)] = masks[p + 1]
-                self._count(name, conv, t, computed=(dep[2], dep[3]) if primed else None)
+        for step in plan.enc:                            # fcn_down.py:77-136
+            p, i, dep = step.level, step.i, step.dep
+            name = 'conv%d_%d' % (p + 1, i)
+            conv = self.enc[name]
+            if i == 1:
+                fused_pool = pool_mask = None
+            kw = dict(anchor=step.ydep[:2])
+            if primed:
+                assert tuple(session[name].shape[2:]) == step.out_hw
+                kw.update(window=dep, out=session[name], place=dep[:2])
+            if step.h is not None and name in self.hsplit:
+                hb, _ = self._h_half(name, h_list[step.h], step, session)
+                t, fused_pool, pool_mask = self._conv_pool(self.hsplit[name][1], p, i, t, kw, dep, primed,
+                                                           session, masked, masks, hb=hb)
+            elif step.h is not None:                     # h first, then features (P13)
+                t = conv(h_list[step.h], x2=t, **kw)
+            else:
+                t, fused_pool, pool_mask = self._conv_pool(conv, p, i, t, kw, dep, primed, session,
+                                                           masked, masks)
+            if self.bn:
+                ops.bn_affine(t, self.enc_bn[name], window=dep)
+            if session is not None and not primed:
+                session[name] = t
+                if (p + 1) in masks and i == self.conv_before_pool:
+                    session['mask%d' % (p + 1)] = masks[p + 1]
+            self._count(name, conv, t, computed=dep[2:] if primed else None)
+            if i < self.conv_before_pool:
+                continue
             pre[p + 1] = t
-            ydep = (ydep[0] // 2, ydep[1] // 2,
-                    min((ydep[0] + ydep[2] + 1) // 2, t.shape[2] // 2) - ydep[0] // 2,
-                    min((ydep[1] + ydep[3] + 1) // 2, t.shape[3] // 2) - ydep[1] // 2)
             if primed:
                 buf = session['pool%d' % (p + 1)]
-                qy0, qh = clip(dep[0] // 2, (dep[0] + dep[2] + 1) // 2, buf.shape[2])
-                qx0, qw = clip(dep[1] // 2, (dep[1] + dep[3] + 1) // 2, buf.shape[3])
-                dep = (qy0, qx0, qh, qw)
+                assert tuple(buf.shape[2:]) == (step.out_hw[0] // 2, step.out_hw[1] // 2)
                 t = buf if fused_pool is not None else \
-                    ops.maxpool2x2(t, out=buf, window=dep, mask=pool_mask)
+                    ops.maxpool2x2(t, out=buf, window=step.pooled, mask=pool_mask)
             else:
                 t = fused_pool if fused_pool is not None else ops.maxpool2x2(t, mask=pool_mask)   # :122
                 if session is not None:
                     session['pool%d' % (p + 1)] = t
             pool[p + 1] = t
-            if p < self.n_pool and pos < len(self.concat_h) and \
-                    self.concat_h[pos] == 'pool%d' % (p + 1):   # :131-134
-                pending_h, pos = h_list[pos], pos + 1
         if session is not None:
             session['primed'] = True
             session['h_fresh'] = False
-        if pending_h is not None:
-            raise NotImplementedError('h concatenated at the last pool feeds DePool2D directly '
-                                      '(additional_pool=0); not shape-consistent in the reference')
         # the hidden re-forward is stochastic whenever ANY stochastic layer is live: Gaussian noise
         # (noise > 0) or the DropoutLayers (dropout > 0, even at noise == 0 -- the configuration of
         # the reference's golden experiment name, plots.ipynb:84: dropout 0.5, z0)
@@ -435,44 +418,24 @@ class StandardDAE:
                 other = pool[p - 1]
                 uh, uw = conv.out_hw(t.shape[2], t.shape[3])
                 oh, ow = min(uh, other.shape[2]), min(uw, other.shape[3])
-                kw = dict(window=(_center(uh, oh), _center(uw, ow), oh, ow))
+                kw = dict(window=(center(uh, oh), center(uw, ow), oh, ow))
                 if self.skip and p > 1:
-                    kw.update(add=other, add_off=(_center(other.shape[2], oh),
-                                                  _center(other.shape[3], ow)))
+                    kw.update(add=other, add_off=(center(other.shape[2], oh),
+                                                  center(other.shape[3], ow)))
                 t = conv(t, **kw)
                 self._count(name, conv, t, full=(uh, uw))
             return t
         # ---- decoder, fcn_up.py:143-151 / UnpoolNet ------------------------------------------
         # Only the final center crop (fused_up1) is an output, so each level is computed just on
-        # the window that reaches it (dead-code elimination, bit-identical results): level p
-        # needs fused_up_{p+1} on [floor((lo-1)/2), ceil((hi+1)/2)).  Tensors keep their full-size
-        # addressing; windows are written in place (`place`), the rest is never read.
-        geom = {}
-        for p in range(self.total, 0, -1):
-            ph, pw = pre[p].shape[2], pre[p].shape[3]    # up_conv 'same' keeps the pre-pool size
-            other = pool[p - 1]                          # pre-concat pool (or the input for p=1)
-            oh, ow = min(ph, other.shape[2]), min(pw, other.shape[3])
-            geom[p] = (ph, pw, oh, ow, _center(ph, oh), _center(pw, ow))
-        win = {1: (0, 0, geom[1][2], geom[1][3])}        # (y0, x0, h, w) in fused_up_p coords
-        for p in range(1, self.total):
-            ph, pw, oh, ow, cy, cx = geom[p]
-            y0, x0, nh, nw = win[p]
-            uy0, ux0 = max(cy + y0 - 1, 0), max(cx + x0 - 1, 0)          # unpooled input rows/cols
-            uy1, ux1 = min(cy + y0 + nh + 1, ph), min(cx + x0 + nw + 1, pw)
-            qh, qw = geom[p + 1][2], geom[p + 1][3]                      # fused_up_{p+1} dims
-            ny0, nx0 = uy0 // 2, ux0 // 2
-            ny1, nx1 = min((uy1 + 1) // 2, qh), min((ux1 + 1) // 2, qw)
-            win[p + 1] = (ny0, nx0, ny1 - ny0, nx1 - nx0)
-        # with DCE off the full maps are computed, but the Winograd tiles stay anchored at the
-        # parity of the DCE windows so that both modes agree bit for bit
-        need = win if self.dce else {p: (0, 0, geom[p][2], geom[p][3]) for p in geom}
+        # the window that reaches it (dead-code elimination, bit-identical results;
+        # regions.decoder_windows).  Tensors keep their full-size addressing; windows are written
+        # in place (`place`), the rest is never read.
         for p in range(self.total, 0, -1):
             name = 'up_conv%d' % p
             conv = self.dec[name]
-            ph, pw, oh, ow, cy, cx = geom[p]
-            other = pool[p - 1]
-            y0, x0, nh, nw = need[p]
-            window = (cy + y0, cx + x0, nh, nw)
+            ph, pw, oh, ow, cy, cx = plan.geom[p]
+            other = pool[p - 1]                          # pre-concat pool (or the input for p=1)
+            y0, x0, nh, nw = plan.need[p]
             mpre, mpool = pre[p], pool[p]
             if mask_override and p in mask_override:
                 mpre, mpool = mask_override[p]
@@ -485,27 +448,26 @@ class StandardDAE:
                     (F64_FUSE_UNPOOL and (conv.KH, conv.KW, conv.dil) == (3, 3, 1) and not conv.transposed)
             if not fuse:
                 # materialise DePool2D with the HBM-bound kernel and run the plain conv
-                uy0, ux0 = max(cy + y0 - 1, 0), max(cx + x0 - 1, 0)
-                uy1, ux1 = min(cy + y0 + nh + 1, ph), min(cx + x0 + nw + 1, pw)
                 u = torch.empty_like(mpre)
-                t = ops.unpool_eqmask(t, mpre, mpool, out=u, window=(uy0, ux0, uy1 - uy0, ux1 - ux0))
+                t = ops.unpool_eqmask(t, mpre, mpool, out=u,
+                                      window=regions.unpool_reads(plan.geom[p], plan.need[p]))
                 mpre = mpool = None
             full = (nh, nw) == (oh, ow)
             out = None if full else torch.empty((y.shape[0], conv.Cout, oh, ow), dtype=y.dtype,
                                                 device=y.device)
-            kw = dict(pre=mpre, pooled=mpool, window=window, out=out,
+            kw = dict(pre=mpre, pooled=mpool, window=(cy + y0, cx + x0, nh, nw), out=out,
                       place=None if full else (y0, x0),
-                      anchor=(cy + win[p][0], cx + win[p][1]))
+                      anchor=(cy + plan.win[p][0], cx + plan.win[p][1]))
             if p in masks:
                 kw.update(pre=None, pooled=None, mask_in=masks[p], unpool_hw=(ph, pw))
             if self.skip and p > 1:                      # :96-102 ElemwiseSumLayer, center crop
-                kw.update(add=other, add_off=(_center(other.shape[2], oh) + y0,
-                                              _center(other.shape[3], ow) + x0))
+                kw.update(add=other, add_off=(center(other.shape[2], oh) + y0,
+                                              center(other.shape[3], ow) + x0))
             t = conv(t, **kw)                            # else :104-113 CroppingLayer
             self._count(name, conv, t, full=(ph, pw), computed=(nh, nw))
             if self.trace is not None:
                 self.trace['fused_up%d' % p] = t
-                self.trace['need%d' % p] = need[p]
+                self.trace['need%d' % p] = plan.need[p]
         if self.trace is not None:
             self.trace.update({'pre%d' % k: v for k, v in pre.items()})
             self.trace.update({'pool%d' % k: v for k, v in pool.items() if k > 0})
@@ -524,8 +486,8 @@ class StandardDAE:
 
     def _scores_c8(self, h_list, y, session):
         """`scores` with bf16 C8 activations between the layers (csrc/conv_c8_bf16.hip): the same
-        layer plan, windows (decoder dead-code elimination, loop-invariant encoder maps, border
-        stores) and fusions, in the form every level takes here --
+        plan (decoder dead-code elimination, loop-invariant encoder maps, border stores) and
+        fusions, in the form every level takes here --
           encoder level p : conv3x3 + ReLU whose epilogue writes pool_p (C8) and the DePool2D mask
                             bytes of its windows, taken from the fp32 results; the pre-pool map is
                             never stored (fcn_down.py:102-122);
@@ -541,10 +503,6 @@ class StandardDAE:
                                       "(conv_before_pool=1, bn=0, no trace / gradient mode / noise "
                                       "emulation): use mma='bf16' for those")
         B, dev = y.shape[0], y.device
-        pos, pending_h = 0, None
-        h_fresh = session is not None and session.get('h_fresh', False)
-        if self.concat_h[pos] == 'input':
-            pending_h, pos = h_list[pos], pos + 1
         primed = session is not None and session.get('primed', False) and self.licm
         if session is not None:
             if primed and session.get('masked') != 'c8':
@@ -554,46 +512,30 @@ class StandardDAE:
         # without records -- writes the tensors it already has)
         stable = session is not None and session.get('stable', False)
         realloc = session is not None and not primed and not stable
-        h_stale = stable and session.get('h_stale', False)
+        plan = self._plan(y.shape, primed, session['h_dep'] if session is not None and
+                          session.get('h_fresh', False) else None)
         # y as a C8 tensor: converted here, unless the refinement step that produced y has already
         # written it (`c8_feed`: api passes the session's buffer to ops.refine_update)
-        if session is not None and session.get('y8_fresh') and session.get('y8') is not None and \
-                tuple(session['y8'].shape[2:4]) == tuple(y.shape[2:4]):
-            t = session['y8']
+        y8 = session.get('y8') if session is not None else None
+        if y8 is not None and tuple(y8.shape[2:4]) != tuple(y.shape[2:4]):
+            y8 = None
+        if y8 is not None and session.get('y8_fresh'):
+            t = y8
         else:
-            t = ops.nchw_to_c8(y, out=session.get('y8') if session is not None and
-                               session.get('y8') is not None and
-                               tuple(session['y8'].shape[2:4]) == tuple(y.shape[2:4]) and
-                               session['y8'].shape[0] == B else None, x3=self.x3)
+            t = ops.nchw_to_c8(y, out=y8 if y8 is not None and y8.shape[0] == B else None, x3=self.x3)
             if session is not None:
                 session['y8'] = t
         if session is not None:
             session['y8_fresh'] = False
-        pre_hw, pool8, masks = {}, {}, {}
-        pool_hw = {0: (y.shape[2], y.shape[3])}
-        dep = (0, 0, y.shape[2], y.shape[3])
-
-        def clip(lo, hi, size):
-            lo, hi = max(lo, 0), min(hi, size)
-            return lo, max(hi - lo, 0)
-
-        for p in range(self.total):                      # fcn_down.py:77-136
+        to_c8 = lambda h: ops.nchw_to_c8(h, x3=self.x3)
+        pool8, masks = {}, {}
+        for step in plan.enc:                            # fcn_down.py:77-136
+            p, (fh, fw) = step.level, step.out_hw
             name = 'conv%d_1' % (p + 1)
             conv = self.enc[name]
-            fh, fw = conv.out_hw(t.shape[2], t.shape[3])
-            pre_hw[p + 1] = (fh, fw)
-            if primed and pending_h is not None and h_fresh:
-                hd = session['h_dep'][pos - 1]           # a new batch: h changed inside its region
-                y1 = max(dep[0] + dep[2], hd[0] + hd[2])
-                x1 = max(dep[1] + dep[3], hd[1] + hd[3])
-                dep = (min(dep[0], hd[0]), min(dep[1], hd[1]), 0, 0)
-                dep = (dep[0], dep[1], y1 - dep[0], x1 - dep[1])
             kw = {}
             if primed:
-                wy0, wh = clip(dep[0] + conv.pad - 2, dep[0] + dep[2] + conv.pad, fh)
-                wx0, ww = clip(dep[1] + conv.pad - 2, dep[1] + dep[3] + conv.pad, fw)
-                dep = (wy0, wx0, wh, ww)
-                kw['window'] = conv.pool_window(t.shape[2], t.shape[3], dep)
+                kw['window'] = conv.pool_window(t.shape[2], t.shape[3], step.dep)
                 pooled_t, m = session['pool%d' % (p + 1)], session['mask%d' % (p + 1)]
             else:
                 pooled_t = m = None
@@ -609,33 +551,16 @@ class StandardDAE:
                     m = ops.empty_c8(B, conv.Cout, fh // 2, fw // 2, dev, dtype=torch.uint8)
                     realloc = realloc or stable
             kw.update(pool_out=pooled_t, mask_out=m, store_out=False)
-            if pending_h is not None and name in self.hsplit:
-                conv_h, conv_y = self.hsplit[name]
-                keep = session is not None and self.licm
-                hb = session.get('hb_' + name) if keep else None
-                if hb is None:                           # loop-invariant: once per refine()
-                    hb = conv_h(ops.nchw_to_c8(pending_h, x3=self.x3), out_format='c8f32')
-                    if keep:
-                        session['hb_' + name] = hb
-                    realloc = realloc or stable
-                elif h_stale:                            # buffer-stable session, new batch: all of it again
-                    conv_h(ops.nchw_to_c8(pending_h, x3=self.x3), window=(0, 0, hb.shape[2], hb.shape[3]),
-                           out=hb, place=(0, 0), out_format='c8f32')
-                elif h_fresh:                            # reused session: only where h changed
-                    hd = session['h_dep'][pos - 1]
-                    hy0, hh = clip(hd[0] + conv_h.pad - 2, hd[0] + hd[2] + conv_h.pad, hb.shape[2])
-                    hx0, hw = clip(hd[1] + conv_h.pad - 2, hd[1] + hd[3] + conv_h.pad, hb.shape[3])
-                    conv_h(ops.nchw_to_c8(pending_h, x3=self.x3), window=(hy0, hx0, hh, hw), out=hb,
-                           place=(hy0, hx0), out_format='c8f32')
+            if step.h is not None and name in self.hsplit:
+                hb, fresh = self._h_half(name, h_list[step.h], step, session, to_c8, out_format='c8f32')
+                realloc = realloc or (fresh and stable)
                 off = (kw['window'][0], kw['window'][1]) if 'window' in kw else (0, 0)
-                conv_y(t, add=hb, add_off=off, **kw)
-                pending_h = None
-            elif pending_h is not None:                  # h first, then features (P13)
+                self.hsplit[name][1](t, add=hb, add_off=off, **kw)
+            elif step.h is not None:                     # h first, then features (P13)
                 if self.x3:
                     raise NotImplementedError("mma='bf16x3' needs the h-split form of a concat "
                                               "point (hsplit=True)")
-                conv(ops.nchw_to_c8(pending_h), x2=t, **kw)
-                pending_h = None
+                conv(ops.nchw_to_c8(h_list[step.h]), x2=t, **kw)
             else:
                 conv(t, **kw)
             if session is not None and not primed:
@@ -643,47 +568,20 @@ class StandardDAE:
             if self.conv_log is not None:
                 cw_ = kw['window'] if 'window' in kw else (0, 0, fh, fw)
                 self.conv_log.append((name, conv.flops(B, fh, fw), conv.flops(B, cw_[2], cw_[3])))
-            pool8[p + 1], masks[p + 1] = pooled_t, m
-            pool_hw[p + 1] = (fh // 2, fw // 2)
-            if primed:
-                qy0, qh = clip(dep[0] // 2, (dep[0] + dep[2] + 1) // 2, fh // 2)
-                qx0, qw = clip(dep[1] // 2, (dep[1] + dep[3] + 1) // 2, fw // 2)
-                dep = (qy0, qx0, qh, qw)
-            t = pooled_t
-            if p < self.n_pool and pos < len(self.concat_h) and \
-                    self.concat_h[pos] == 'pool%d' % (p + 1):   # :131-134
-                pending_h, pos = h_list[pos], pos + 1
+            t = pool8[p + 1] = pooled_t
+            masks[p + 1] = m
         if session is not None:
             session['primed'] = True
             session['h_fresh'] = False
             session['h_stale'] = False
             if realloc:
                 session['gen'] = session.get('gen', 0) + 1
-        if pending_h is not None:
-            raise NotImplementedError('h concatenated at the last pool feeds DePool2D directly '
-                                      '(additional_pool=0); not shape-consistent in the reference')
         # ---- decoder, fcn_up.py:143-151 (windows as in `scores`) -------------------------------
-        geom = {}
-        for p in range(self.total, 0, -1):
-            ph, pw = pre_hw[p]
-            oh, ow = min(ph, pool_hw[p - 1][0]), min(pw, pool_hw[p - 1][1])
-            geom[p] = (ph, pw, oh, ow, _center(ph, oh), _center(pw, ow))
-        win = {1: (0, 0, geom[1][2], geom[1][3])}
-        for p in range(1, self.total):
-            ph, pw, oh, ow, cy, cx = geom[p]
-            y0, x0, nh, nw = win[p]
-            uy0, ux0 = max(cy + y0 - 1, 0), max(cx + x0 - 1, 0)
-            uy1, ux1 = min(cy + y0 + nh + 1, ph), min(cx + x0 + nw + 1, pw)
-            qh, qw = geom[p + 1][2], geom[p + 1][3]
-            ny0, nx0 = uy0 // 2, ux0 // 2
-            ny1, nx1 = min((uy1 + 1) // 2, qh), min((ux1 + 1) // 2, qw)
-            win[p + 1] = (ny0, nx0, ny1 - ny0, nx1 - nx0)
-        need = win if self.dce else {p: (0, 0, geom[p][2], geom[p][3]) for p in geom}
         for p in range(self.total, 0, -1):
             name = 'up_conv%d' % p
             conv = self.dec[name]
-            ph, pw, oh, ow, cy, cx = geom[p]
-            y0, x0, nh, nw = need[p]
+            ph, pw, oh, ow, cy, cx = plan.geom[p]
+            y0, x0, nh, nw = plan.need[p]
             full = (nh, nw) == (oh, ow)
             out = None
             if not full:
@@ -693,8 +591,8 @@ class StandardDAE:
                       out=out, place=None if full else (y0, x0),
                       out_format='nchw' if p == 1 else 'c8')
             if self.skip and p > 1:                      # :96-102 ElemwiseSumLayer, center crop
-                oth = pool_hw[p - 1]
-                kw.update(add=pool8[p - 1], add_off=(_center(oth[0], oh) + y0, _center(oth[1], ow) + x0))
+                oth = pool8[p - 1].shape[2:4]
+                kw.update(add=pool8[p - 1], add_off=(center(oth[0], oh) + y0, center(oth[1], ow) + x0))
             if 0 < C8_UNPOOL_MIN_CIN <= conv.Cin and not self.x3 and conv.Cout > 16:
                 # Deep levels: DePool2D materialised first (a few tens of MB at these sizes), the conv then runs
                 # as a PLAIN layer -- LDS-DMA patch staging instead of up chunk + mask bytes selected through
@@ -706,10 +604,7 @@ class StandardDAE:
                     u = torch.zeros((B, t.shape[1], ph, pw, 8), dtype=torch.bfloat16, device=dev)
                     if session is not None:
                         session[skey] = u
-                wy0, wx0 = max(cy + y0 - 1, 0), max(cx + x0 - 1, 0)            # input rows / columns the window reads
-                wy1, wx1 = min(cy + y0 + nh + 1, 2 * (ph // 2)), min(cx + x0 + nw + 1, 2 * (pw // 2))
-                qy0, qx0 = wy0 // 2, wx0 // 2
-                ops.unpool_c8(t, masks[p], u, window=(qy0, qx0, (wy1 + 1) // 2 - qy0, (wx1 + 1) // 2 - qx0))
+                ops.unpool_c8(t, masks[p], u, window=regions.unpool_reads_pooled(plan.geom[p], plan.need[p]))
                 kw.pop('mask_in'); kw.pop('unpool_hw')
                 t = conv(u, **kw)
             else:
@@ -767,12 +662,12 @@ class StandardDAE:
             other_hw = (pool[p - 1].shape[2], pool[p - 1].shape[3]) if p > 1 else \
                 (y_shape[2], y_shape[3])
             oh, ow = min(ph, other_hw[0]), min(pw, other_hw[1])
-            cy, cx = _center(ph, oh), _center(pw, ow)
+            cy, cx = center(ph, oh), center(pw, ow)
             g_c = torch.zeros((B, g_f.shape[1], ph, pw), dtype=dt, device=dev)
             g_c[:, :, cy:cy + oh, cx:cx + ow].copy_(g_f)           # adjoint of the center crop
             if self.skip and p > 1:                                 # adjoint of the skip sum
                 gp = torch.zeros_like(pool[p - 1])
-                oy, ox = _center(other_hw[0], oh), _center(other_hw[1], ow)
+                oy, ox = center(other_hw[0], oh), center(other_hw[1], ow)
                 gp[:, :, oy:oy + oh, ox:ox + ow].copy_(g_f)
                 g_pool[p - 1] = gp
             g_u = bwd['up_conv%d' % p](g_c)
@@ -819,26 +714,21 @@ class StandardDAE:
             raise NotImplementedError('noise emulation with bn=1 (batch statistics in the hidden '
                                       'forward) is not supported')
         masks = {}
+        feeds = regions.concat_feeds(self.concat_h, self.total, self.n_pool)
         for p in range(self.total, 0, -1):
             # GaussianNoiseLayer(sigma=0) adds nothing (and draws nothing worth emulating)
             t = ops.add_noise(y, self._rand('noise', p, None, y.shape, y), self.noise) \
                 if self.noise > 0 else y
-            pos, pending = 0, None
-            if self.concat_h[0] == 'input':
-                pending, pos = h_list[0], 1
             for q in range(p):
                 for i in range(1, self.conv_before_pool + 1):
                     name = 'conv%d_%d' % (q + 1, i)
                     conv = self.enc[name]
-                    t = conv(pending, x2=t) if pending is not None else conv(t)
-                    pending = None
+                    h = feeds.get(q) if i == 1 else None
+                    t = conv(h_list[h], x2=t) if h is not None else conv(t)
                     if self.dropout > 0:
                         ops.dropout_apply(t, self._rand('dropout', p, name, t.shape, t), self.dropout)
                 pre_q = t
                 t = ops.maxpool2x2(t)
-                if q < self.n_pool and pos < len(self.concat_h) and \
-                        self.concat_h[pos] == 'pool%d' % (q + 1):
-                    pending, pos = h_list[pos], pos + 1
             masks[p] = (pre_q, t)
         return masks
 
@@ -874,7 +764,6 @@ def buildDAE(input_concat_h_vars=None, input_mask_var=None, n_classes=11,
     deterministic=True (P8, P9); the DePool2D masks are the deterministic ones unless
     `emulate_noise` asks for the reference's noisy hidden re-forward; the symbolic
     `input_*_var`, `trainable`, `ae_h`, `void_labels` are accepted and ignored."""
-    import os
     if params is None:
         if not (load_weights and path_weights):
             raise ValueError('buildDAE needs `params` or `path_weights`')

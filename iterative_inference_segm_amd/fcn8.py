@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .regions import center, conv_region, pool_region
 from .weights import load_param_list
 
 PARAM_ORDER = ['conv1_1', 'conv1_2', 'conv2_1', 'conv2_2', 'conv3_1', 'conv3_2', 'conv3_3',
@@ -24,29 +25,6 @@ _BLOCKS = [('conv1_1', 'conv1_2'), ('conv2_1', 'conv2_2'), ('conv3_1', 'conv3_2'
 
 
 _UID = itertools.count(1)   # identity of a net in the provenance tags (never reused, unlike id())
-
-
-def _center(big, small):
-    return (big - small) // 2  # lasagne autocrop 'center' (P6)
-
-
-def _clip(lo, hi, size):
-    lo, hi = max(lo, 0), min(hi, size)
-    return lo, max(hi - lo, 0)
-
-
-def _conv_region(dep, conv, fh, fw):
-    """Outputs (y0, x0, h, w) of a stride-1 conv whose receptive field meets input region dep."""
-    ey, ex = conv.dil * (conv.KH - 1), conv.dil * (conv.KW - 1)
-    y0, h = _clip(dep[0] + conv.pad - ey, dep[0] + dep[2] + conv.pad, fh)
-    x0, w = _clip(dep[1] + conv.pad - ex, dep[1] + dep[3] + conv.pad, fw)
-    return (y0, x0, h, w)
-
-
-def _pool_region(dep, ph, pw):
-    y0, h = _clip(dep[0] // 2, (dep[0] + dep[2] + 1) // 2, ph)
-    x0, w = _clip(dep[1] // 2, (dep[1] + dep[3] + 1) // 2, pw)
-    return (y0, x0, h, w)
 
 
 class FCN8:
@@ -132,7 +110,7 @@ class FCN8:
             for name in names:
                 conv = self.convs[name]
                 fh, fw = conv.out_hw(t.shape[2], t.shape[3])
-                dep = _conv_region(dep, conv, fh, fw)
+                dep = conv_region(dep, conv, fh, fw)
                 # Winograd tiles anchored at the parity of the region recomputed per batch
                 kw = dict(anchor=(dep[0], dep[1]))
                 if primed:
@@ -166,7 +144,7 @@ class FCN8:
                 if session is not None and not primed:
                     session[name] = t
             pname = 'pool%d' % (bi + 1)
-            dep = _pool_region(dep, fh // 2, fw // 2)
+            dep = pool_region(dep, fh // 2, fw // 2)
             if fused_pool is not None:
                 t = fused_pool
                 if session is not None and not primed:
@@ -203,7 +181,7 @@ class FCN8:
         H, W = x.shape[2], x.shape[3]
         uh, uw = self.upsample.out_hw(t.shape[2], t.shape[3])
         oh, ow = min(uh, H), min(uw, W)
-        score = self.upsample(t, window=(_center(uh, oh), _center(uw, ow), oh, ow))
+        score = self.upsample(t, window=(center(uh, oh), center(uw, ow), oh, ow))
         net['score'] = score
         net['probs_dimshuffle'] = ops.crop_softmax(score, oh, ow, off=(0, 0))  # :122-130,187-191
         # maps owned by the internal border store are overwritten by the next call: hand out
@@ -250,8 +228,8 @@ class FCN8:
         dh, dw = deconv.out_hw(t.shape[2], t.shape[3])
         sh, sw = pool.shape[2], pool.shape[3]          # 1x1 'valid'/'same' conv keeps the size
         oh, ow = min(dh, sh), min(dw, sw)
-        side = self._conv(score_name, pool, window=(_center(sh, oh), _center(sw, ow), oh, ow))
-        return deconv(t, add=side, window=(_center(dh, oh), _center(dw, ow), oh, ow))
+        side = self._conv(score_name, pool, window=(center(sh, oh), center(sw, ow), oh, ow))
+        return deconv(t, add=side, window=(center(dh, oh), center(dw, ow), oh, ow))
 
 
 class FCN8DAE:
