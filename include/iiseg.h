@@ -850,6 +850,57 @@ int iiseg_opt_step_f32(void* stream, int32_t kind, float* p, const float* g, flo
 int iiseg_opt_step_f64(void* stream, int32_t kind, double* p, const double* g, double* s1, double* s2,
                        const double* lr, double* state, int64_t n);
 
+/* ---------------------------------------------------------------------------------------
+ * True-gradient refinement through the context-module DAE: the backward pass w.r.t.
+ * the y channels.  Every entry checks its arguments and returns a status before any launch; sums have a fixed
+ * order (from 0, output-channel-major / tap-minor sequential FMAs); no atomics.  Tensors: device, NCHW.
+ *
+ * Masked data gradient of a 'valid' K x K layer (K = 1 or 3, dilation dil, at most 16 channels on either
+ * side) whose output map is (OH, OW) and whose input map is (OH + dil (K - 1), OW + dil (K - 1)):
+ *   g_z = out ? gout * [out > 0] : gout                       (relu'(0) = 0; out == NULL: a linear layer)
+ *   g_x[b][ci][y][x] = sum_{co,ky,kx} W[ci][co][ky][kx] g_z[b][co][y - ky dil][x - kx dil]
+ * g_z is formed while gout is read (no pass of its own); positions outside gout count as zero.
+ *   gout : (B, Cout, OH, OW), contiguous.
+ *   out  : the layer's rectified output, its (OH, OW) map at (out_y0, out_x0) of (B, Cout, out_H, out_W).
+ *   W    : the layer's parameter in its own layout: element (co, ci, tap) at co * so + ci * sc + tap with
+ *          (so, sc) = (Cin K K, K K) for W[out,in,k,k] or (K K, Cout K K) for W[in,out,k,k].
+ *   gx   : only the window (wy0, wx0, WH, WW) of g_x and the input channels [ci0, ci0 + nci) are computed;
+ *          they go to channels [gx_c0, gx_c0 + nci) of (B, gx_C, gx_H, gx_W) with the window's corner at
+ *          (gx_y0, gx_x0).  Nothing else of gx is touched.
+ * iiseg_conv_small_dgrad_blocks: the number of workgroups the launch would have (> 0), or the status the
+ * launch would return (host only).
+ *
+ * Head of the chain, one launch from the score map to the masked gradient at dilconv6's output:
+ *   r = softmax(score), g_r = 2 (r - y), g_s = r (g_r - <r, g_r>)   (the bits of iiseg_sqerr_softmax_bwd)
+ *   g6[ci] = [out6[ci] > 0] sum_co W7[ci][co] g_s[co]               (out6 == NULL: no mask)
+ * score, y, gs (may be NULL): (B, C, H, W); out6, g6: (B, Cin, H, W); W7 the 1x1 layer's parameter, (so, sc)
+ * = (Cin, 1) or (1, C); 2 <= C <= 16, Cin <= 16.
+ * ------------------------------------------------------------------------------------- */
+typedef struct iiseg_dgrad_desc {
+    int32_t B, Cin, Cout, K, dil;
+    int32_t OH, OW;
+    int32_t out_H, out_W, out_y0, out_x0;
+    int32_t wy0, wx0, WH, WW;
+    int32_t ci0, nci;
+    int32_t gx_C, gx_H, gx_W, gx_c0, gx_y0, gx_x0;
+    int32_t reserved;
+    int64_t so, sc;
+} iiseg_dgrad_desc;
+
+int iiseg_conv_small_dgrad_blocks(const iiseg_dgrad_desc* d);
+int iiseg_conv_small_dgrad_f32(void* stream, const iiseg_dgrad_desc* d, const float* gout, const float* out,
+                               const float* W, float* gx);
+int iiseg_conv_small_dgrad_f64(void* stream, const iiseg_dgrad_desc* d, const double* gout, const double* out,
+                               const double* W, double* gx);
+/* host only: number of workgroups, or a negative status */
+int iiseg_ctx_grad_head_blocks(int32_t B, int32_t C, int32_t Cin, int32_t H, int32_t W);
+int iiseg_ctx_grad_head_f32(void* stream, const float* score, const float* y, const float* out6, const float* W7,
+                            int64_t so, int64_t sc, float* gs, float* g6, int32_t B, int32_t C, int32_t Cin,
+                            int32_t H, int32_t W);
+int iiseg_ctx_grad_head_f64(void* stream, const double* score, const double* y, const double* out6,
+                            const double* W7, int64_t so, int64_t sc, double* gs, double* g6, int32_t B, int32_t C,
+                            int32_t Cin, int32_t H, int32_t W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ LOADPATH = os.environ.get('IISEG_LOADPATH', './iiseg_out/load/')
 WEIGHTS_PATH = os.environ.get('IISEG_WEIGHTS_PATH', './iiseg_out/load/')
 
 _EPSILON = EPSILON  # 1e-3, iterative_inference.py:53
+GRADIENT_KINDS = ('standard', 'contextmod')     # the DAE kinds with a backward pass w.r.t. y (`backward_y`)
 
 
 def _copy_tree(src, dst):
@@ -174,6 +175,12 @@ def inference(dataset, segm_net, learn_step=0.005, num_iter=500, dae_dict_update
                 'concat_h': ['input'], 'noise': 0.0, 'from_gt': True, 'temperature': 1.0,
                 'layer': 'probs_dimshuffle', 'exp_name': '', 'bn': 0}
     dae_dict.update(dae_dict_updates)
+    if update not in ('residual', 'gradient'):
+        raise ValueError("update must be 'residual' or 'gradient'")
+    if update == 'gradient' and dae_dict['kind'] not in GRADIENT_KINDS:
+        # before any directory is made or the GPU is touched
+        raise NotImplementedError("--update gradient needs the DAE's backward pass, which the DAE kind %r does not "
+                                  "have (built for: %s)" % (dae_dict['kind'], ', '.join(GRADIENT_KINDS)))
 
     # Prepare load/save directories (:84-104)
     name_kw = dict(dae_dict)

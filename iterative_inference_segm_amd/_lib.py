@@ -58,6 +58,13 @@ class WgradDesc(C.Structure):
                                          'gz_x0', 'reserved')] + [('so', C.c_int64), ('sc', C.c_int64)]
 
 
+class DgradDesc(C.Structure):
+    """struct iiseg_dgrad_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'K', 'dil', 'OH', 'OW', 'out_H', 'out_W', 'out_y0',
+                                         'out_x0', 'wy0', 'wx0', 'WH', 'WW', 'ci0', 'nci', 'gx_C', 'gx_H', 'gx_W',
+                                         'gx_c0', 'gx_y0', 'gx_x0', 'reserved')] + [('so', C.c_int64), ('sc', C.c_int64)]
+
+
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); mirrors include/iiseg.h one to one
@@ -216,6 +223,13 @@ SIGNATURES = {
     'iiseg_conv_small_wgrad_f64': (C.c_int, [_vp, C.POINTER(WgradDesc)] + [_vp] * 7),
     'iiseg_opt_step_f32': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
     'iiseg_opt_step_f64': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
+    # true-gradient refinement through the context-module DAE
+    'iiseg_conv_small_dgrad_blocks': (C.c_int, [C.POINTER(DgradDesc)]),
+    'iiseg_conv_small_dgrad_f32': (C.c_int, [_vp, C.POINTER(DgradDesc)] + [_vp] * 4),
+    'iiseg_conv_small_dgrad_f64': (C.c_int, [_vp, C.POINTER(DgradDesc)] + [_vp] * 4),
+    'iiseg_ctx_grad_head_blocks': (C.c_int, [_i32] * 5),
+    'iiseg_ctx_grad_head_f32': (C.c_int, [_vp] * 5 + [_i64] * 2 + [_vp] * 2 + [_i32] * 5),
+    'iiseg_ctx_grad_head_f64': (C.c_int, [_vp] * 5 + [_i64] * 2 + [_vp] * 2 + [_i32] * 5),
 }
 
 _lib = None

@@ -267,8 +267,10 @@ class IterativeInference:
         mode='gradient' (extension; the reference only has the residual form,
         F1): descends the true gradient of E(y) = sum (r(y|h) - y)^2,
             y = clip(y - step * (J_r^T 2(r - y) - 2(r - y)), 0, 1),
-        with a hand-written backward pass through the DAE (`StandardDAE.backward_y`); the stop
-        test uses mean_px ||grad||_2.
+        with a hand-written backward pass through the DAE (`StandardDAE.backward_y`, or
+        `ContextModDAE.sqerr_backward` -- the kind the driver defaults to); the stop test
+        uses mean_px ||grad||_2.  A DAE without `backward_y` (kind 'fcn8') is refused with
+        NotImplementedError before any launch.  The gradient loop is eager.
 
         `graph` (None = api.GRAPH_MODE): replay the steady-state step (everything after the first
         step has static shapes and static buffers: the session's encoder maps, y, h, the loop
@@ -291,6 +293,14 @@ class IterativeInference:
         the `valid_mat[:, :, it] += jacc_iter` of iterative_inference_valid.py:231,280-288 (the
         reference calls val_fn only when the loop did not break).
         """
+        if mode not in ('residual', 'gradient'):
+            raise ValueError('mode must be "residual" or "gradient"')
+        if mode == 'gradient' and not hasattr(self.dae, 'backward_y'):
+            # refused before any launch of the loop
+            raise NotImplementedError(
+                "mode='gradient' needs the DAE's backward pass (backward_y), which the DAE kind %r (%s) does "
+                "not have: it is built for the kinds 'standard' and 'contextmod'"
+                % (getattr(self.dae, 'kind', '?'), type(self.dae).__name__))
         H_in = list(H) if isinstance(H, (list, tuple)) else [H]
         want_graph = GRAPH_MODE if graph is None else ('1' if graph else '0')
         if inplace:
@@ -351,9 +361,12 @@ class IterativeInference:
             if it == 0 and first_reconstruction:
                 r0 = ops.crop_softmax(score, Hh, Ww, off=(0, 0))
             if mode == 'gradient':
-                g_score = ops.sqerr_softmax_bwd(score, y, off=(0, 0))
-                ops.grad_update(score, self.dae.backward_y(g_score, y.shape), y, st, step,
-                                off=(0, 0))
+                if hasattr(self.dae, 'sqerr_backward'):
+                    # (context module: the softmax backward, the last layer's adjoint and a mask are one launch)
+                    g_through = self.dae.sqerr_backward(score, y)
+                else:
+                    g_through = self.dae.backward_y(ops.sqerr_softmax_bwd(score, y, off=(0, 0)), y.shape)
+                ops.grad_update(score, g_through, y, st, step, off=(0, 0))
             elif mode == 'residual':
                 self._update(score, y, st, step, sess)
             else:

@@ -21,6 +21,8 @@ DILATIONS = [1, 2, 4, 8, 16, 1]                                     # contextmod
 
 
 class ContextModDAE:
+    kind = 'contextmod'
+
     def __init__(self, params, n_classes, concat_h=('input',), device='cuda',
                  dtype=torch.float32):
         assert all(el in ['input'] for el in concat_h)               # contextmod_dae.py:42
@@ -71,6 +73,19 @@ class ContextModDAE:
         self._train = {}            # training: buffers per geometry
         self._saved = None          # training: what `forward_train` kept for `backward`
         self._gflat = None
+        self._keep_pre, self._pre = False, None
+
+    @property
+    def keep_pre(self):
+        """True: `scores` keeps the seven rectified layer outputs and the score map of its latest call, which
+        `backward_y` / `sqerr_backward` read (api._refine sets it per call).  Setting it False drops them."""
+        return self._keep_pre
+
+    @keep_pre.setter
+    def keep_pre(self, on):
+        self._keep_pre = bool(on)
+        if not on:
+            self._pre = None
 
     def _shared_convs(self):
         return [self.conv1, self.conv1_valid, self.dil1_valid, self.last] + self.dil
@@ -139,6 +154,11 @@ class ContextModDAE:
     def scores(self, h_list, y, mask_override=None, session=None):
         if len(h_list) != 1:
             raise ValueError('expected 1 h tensor, got %d' % len(h_list))
+        if session is None and self.keep_pre:
+            # true-gradient mode outside a loop: the same 'valid' layers on the same per-geometry buffers as a
+            # loop's session, so the kept maps -- and the gradient -- have the same bits with and without one
+            # (the padded forms of conv1 / dilconv1 sum in another order in fp32)
+            session = self.new_session(h_list, y)
         if session is not None:
             if not session.get('y_in_cat'):
                 session['cat'][:, session['ch']:, 1:-1, 1:-1].copy_(y)
@@ -146,12 +166,59 @@ class ContextModDAE:
             self._first_layer(session)
             t = self.dil1_valid(session['pad32'])
             rest = self.dil[1:]
+            kept = [(session['pad32'], (32, 32)), (t, (0, 0))]       # conv1's map lives inside PadLayer(32)'s zeros
         else:
             t = self.conv1(h_list[0], x2=y)                          # h first (P13)
             rest = self.dil
+            kept = [(t, (0, 0))]
         for conv in rest:
             t = conv(t)
-        return self.last(t)
+            kept.append((t, (0, 0)))
+        score = self.last(t)
+        # true-gradient mode: the seven rectified outputs (tensor, where the map starts in it) and the score map
+        self._pre = {'outs': kept, 'score': score, 'ch': h_list[0].shape[1]} if self.keep_pre else None
+        return score
+
+    # ---- true-gradient refinement ----
+    def _chain(self, g, L_from, masked, y_shape):
+        pre = self._pre
+        if pre is None:
+            raise RuntimeError('backward_y needs the layer outputs of the forward pass: set dae.keep_pre = True '
+                               'before calling scores()')
+        outs, ch = pre['outs'], pre['ch']
+        B, Cy, H, W = (int(v) for v in y_shape)
+        if ch + Cy != self.conv1.Cin or g.shape[0] != B or tuple(g.shape[2:]) != (H, W):
+            raise RuntimeError('backward_y: gradient %s for y %s' % (tuple(g.shape), tuple(y_shape)))
+        for L in range(L_from, 0, -1):
+            # g is the gradient at dilconv L's output: masked by [out_L > 0] while it is read (dilconv7 is linear,
+            # and the head has applied dilconv6's mask already)
+            out, off = (None, (0, 0)) if (L == 7 or masked) else outs[L]
+            masked = False
+            d = 1 if L == 7 else DILATIONS[L - 1]
+            # PadLayer(32)'s adjoint is the crop at (32, 32): only that window of dilconv1's data gradient
+            g = ops.conv_small_dgrad(g, out, self._views['dilconv%d' % L][0], dil=d, layout='iohw', out_off=off,
+                                     window=(32, 32, H, W) if L == 1 else None)
+        # conv1 (pad 1) is a 'valid' layer on the bordered [h, y] buffer: its adjoint is the interior of that
+        # border, and only the y channels are needed (h is a constant of the loop)
+        out, off = outs[0]
+        return ops.conv_small_dgrad(g, out, self._views['conv1'][0], dil=1, layout='oihw', out_off=off,
+                                    window=(1, 1, H, W), ci=(ch, Cy))
+
+    def backward_y(self, g_score, y_shape):
+        """J^T g_score: the gradient w.r.t. the y channels of the input, for an upstream gradient on the score
+        map of the latest `scores` call (made with `keep_pre` set).  Eight launches; the ReLU masks are applied
+        while the gradient maps are read."""
+        return self._chain(g_score.contiguous(), 7, False, y_shape)
+
+    def sqerr_backward(self, score, y):
+        """`backward_y(ops.sqerr_softmax_bwd(score, y), y.shape)` with the softmax backward, dilconv7's adjoint
+        and dilconv6's mask as ONE launch (ops.ctx_grad_head): the same bits, one launch fewer."""
+        if self._pre is None:
+            raise RuntimeError('sqerr_backward needs the layer outputs of the forward pass: set dae.keep_pre = '
+                               'True before calling scores()')
+        out6, _ = self._pre['outs'][6]
+        g6 = ops.ctx_grad_head(score, y, out6, self._views['dilconv7'][0], layout='iohw')
+        return self._chain(g6, 6, True, y.shape)
 
     def y_updated(self, session, y):
         """The caller has just updated y outside `fused_step` (the first step of a loop, which also hands out

@@ -53,6 +53,8 @@ C8_UNPOOL_MIN_CIN = int(os.environ.get('IISEG_C8_UNPOOL_MIN_CIN', '1024'))
 class StandardDAE:
     """Callable with (h_1..h_k, y) like the compiled pred_dae_fn (iterative_inference.py:189-190)."""
 
+    kind = 'standard'
+
     def __init__(self, params, n_classes, concat_h=('pool4',), padding=100, n_filters=64,
                  conv_before_pool=1, additional_pool=2, skip=True, unpool_type='trackind', bn=0,
                  device='cuda', dtype=torch.float32, pad_multi_concat=False, noise=0.0,

@@ -236,6 +236,8 @@ class FCN8DAE:
     """dae kind 'fcn8' (models/fcn8_dae.py:19-171): an FCN-8 on y with h concatenated at
     `concat_h`.  Callable like pred_dae_fn(h..., y); `scores` gives the pre-softmax map."""
 
+    kind = 'fcn8'
+
     def __init__(self, params, n_classes, concat_h=('input',), pad=100, device='cuda',
                  dtype=torch.float32, mma=None):
         assert all(el in ['pool1', 'pool2', 'pool3', 'pool4', 'input'] for el in concat_h)  # :33-34

@@ -1871,3 +1871,95 @@ def opt_step(kind, p, g, s1, s2, lr, state):
         raise RuntimeError('opt_step: buffers of different sizes')
     _launch('opt_step_kernel', 0.0, _fn('opt_step', dt), OPTIMIZERS[kind], _ptr(p, dt), _ptr(g, dt), _ptr(s1, dt),
             _ptr(s2, dt), _ptr(lr, dt), _ptr(state, dt), p.numel())
+
+
+# ---- true-gradient refinement through the context-module DAE (csrc/ctx_grad.hip) ----
+def _param_strides(Wshape, layout):
+    """(Cin, Cout, K, so, sc) of a layer parameter in its own layout (include/iiseg.h: element (co, ci, tap) at
+    co so + ci sc + tap)."""
+    K = int(Wshape[2])
+    if layout == 'oihw':
+        Cout, Cin = int(Wshape[0]), int(Wshape[1])
+        return Cin, Cout, K, Cin * K * K, K * K
+    if layout == 'iohw':
+        Cin, Cout = int(Wshape[0]), int(Wshape[1])
+        return Cin, Cout, K, K * K, Cout * K * K
+    raise ValueError(layout)
+
+
+def dgrad_desc(gout_shape, Wshape, dil, layout, out_place=None, window=None, ci=None, gx_place=None):
+    """The iiseg_dgrad_desc of the masked data gradient of a 'valid' layer: gout (B,Cout,OH,OW); out_place =
+    (out_H, out_W, y0, x0) of the planes the layer's output lives in; window = (y0, x0, h, w) of g_x; ci =
+    (first, count) of the input channels; gx_place = (C, H, W, c0, y0, x0) of the destination (default: dense)."""
+    B, Cout, OH, OW = (int(v) for v in gout_shape)
+    Cin, Co, K, so, sc = _param_strides(Wshape, layout)
+    if Co != Cout:
+        raise RuntimeError('dgrad: gout has %d channels, the layer %d' % (Cout, Co))
+    d = _lib.DgradDesc()
+    d.B, d.Cin, d.Cout, d.K, d.dil, d.OH, d.OW = B, Cin, Cout, K, int(dil), OH, OW
+    d.out_H, d.out_W, d.out_y0, d.out_x0 = (OH, OW, 0, 0) if out_place is None else tuple(int(v) for v in out_place)
+    span = int(dil) * (K - 1)
+    d.wy0, d.wx0, d.WH, d.WW = (0, 0, OH + span, OW + span) if window is None else tuple(int(v) for v in window)
+    d.ci0, d.nci = (0, Cin) if ci is None else (int(ci[0]), int(ci[1]))
+    d.gx_C, d.gx_H, d.gx_W, d.gx_c0, d.gx_y0, d.gx_x0 = (d.nci, d.WH, d.WW, 0, 0, 0) if gx_place is None else \
+        tuple(int(v) for v in gx_place)
+    d.so, d.sc = so, sc
+    return d
+
+
+def conv_small_dgrad(gout, out, W, dil=1, layout='iohw', out_off=(0, 0), window=None, ci=None, gx=None,
+                     gx_off=(0, 0, 0)):
+    """g_x of the 'valid' layer with parameter W (its own `layout`) from gout = dL/d(layer output) and the
+    layer's rectified output `out` (None: a linear layer): g_z = gout [out > 0] is formed while gout is read.
+    `out` may be a larger tensor holding the (OH, OW) map at `out_off`.  Only `window` = (y0, x0, h, w) of g_x
+    and the input channels `ci` = (first, count) are computed; they go to a new dense tensor, or into `gx` at
+    gx_off = (c0, y0, x0) (the rest of `gx` is not touched).  Returns the tensor written."""
+    dt = gout.dtype
+    B, Cout, OH, OW = gout.shape
+    out_place = None
+    if out is not None:
+        if out.dim() != 4 or out.shape[0] != B or out.shape[1] != Cout:
+            raise RuntimeError('dgrad: out %s for gout %s' % (tuple(out.shape), tuple(gout.shape)))
+        out_place = (out.shape[2], out.shape[3], out_off[0], out_off[1])
+    d = dgrad_desc(tuple(gout.shape), tuple(W.shape), dil, layout, out_place, window, ci)
+    if gx is None:
+        gx = torch.empty((B, d.nci, d.WH, d.WW), dtype=dt, device=gout.device)
+    else:
+        if gx.dim() != 4 or gx.shape[0] != B:
+            raise RuntimeError('dgrad: gx %s' % (tuple(gx.shape),))
+        d.gx_C, d.gx_H, d.gx_W = gx.shape[1], gx.shape[2], gx.shape[3]
+        d.gx_c0, d.gx_y0, d.gx_x0 = (int(v) for v in gx_off)
+    lib = _lib.load()
+    nblk = lib.iiseg_conv_small_dgrad_blocks(C.byref(d))
+    if nblk < 0:
+        check(nblk, 'iiseg_conv_small_dgrad_blocks')
+    kern = 'conv_small_dgrad_kernel'
+    _launch(kern, 2.0 * d.nci * Cout * d.K * d.K * B * d.WH * d.WW, _fn('conv_small_dgrad', dt), C.byref(d),
+            _ptr(gout, dt), _ptr(out, dt), _ptr(W, dt), _ptr(gx, dt))
+    if CONV_PROFILE is not None:
+        # byte model: g_out (and out) read once, the window of g_x written
+        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + float(gout.element_size()) * B * \
+            ((2 if out is not None else 1) * Cout * OH * OW + d.nci * d.WH * d.WW)
+    return gx
+
+
+def ctx_grad_head(score, y, out6, W7, layout='iohw', want_gs=False):
+    """(score, y, out6) -> the masked gradient at dilconv6's output in one launch: r = softmax(score), g_s =
+    dE/dscore of E = sum (r - y)^2 (the bits of `sqerr_softmax_bwd`), g6 = [out6 > 0] W7^T g_s.  Returns g6, or
+    (g6, g_s) with want_gs."""
+    dt = y.dtype
+    B, Cc, H, W = y.shape
+    Cin, Cout, K, so, sc = _param_strides(tuple(W7.shape), layout)
+    if K != 1 or Cout != Cc or tuple(score.shape) != tuple(y.shape) or \
+            (out6 is not None and tuple(out6.shape) != (B, Cin, H, W)):
+        raise RuntimeError('ctx_grad_head: score %s y %s out6 %s W7 %s' % (
+            tuple(score.shape), tuple(y.shape), None if out6 is None else tuple(out6.shape), tuple(W7.shape)))
+    g6 = torch.empty((B, Cin, H, W), dtype=dt, device=y.device)
+    gs = torch.empty_like(y) if want_gs else None
+    kern = 'ctx_grad_head_kernel'
+    _launch(kern, 2.0 * Cin * Cc * B * H * W, _fn('ctx_grad_head', dt), _ptr(score, dt), _ptr(y, dt), _ptr(out6, dt),
+            _ptr(W7, dt), so, sc, _ptr(gs, dt), _ptr(g6, dt), B, Cc, Cin, H, W)
+    if CONV_PROFILE is not None:
+        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + float(y.element_size()) * B * H * W * \
+            ((3 if want_gs else 2) * Cc + (2 if out6 is not None else 1) * Cin)
+    return (g6, gs) if want_gs else g6
