@@ -165,6 +165,17 @@ int iiseg_conv_mask_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
                         const float* wp, const int32_t* ktab, const float* bias, const float* add,
                         float* out, float* pool_out, uint8_t* mask_out);
 
+/* Tiling of the fp32 halo-tile kernel (3x3, dil 1, 16 < Cout < 256).  By default its 32-column pixel tiles
+ * run across the seam between consecutive images of the batch (the B * OW columns of a row band laid end to
+ * end) wherever that takes fewer tiles than one tile grid per image, OW >= 32, and a fused pool has an even
+ * OW; every output is the same sum in the same order under both tilings, bit for bit.
+ *   iiseg_conv_halo_seam(on)         on = 0 / 1: per-image / seam tiling for the launches that follow (the
+ *                                    default is the environment's IISEG_HALO_SEAM, 1 when unset); on < 0 only
+ *                                    asks.  Returns the setting in force.  For A/B timing and tests.
+ *   iiseg_conv_halo_seam_launches    launches so far that ran the seam tiling (a scheduling fact) */
+int iiseg_conv_halo_seam(int on);
+int64_t iiseg_conv_halo_seam_launches(void);
+
 /* 3x3 convolution with at most 16 output channels whose INPUT is normalised and rectified while it
  * is staged: x <- max((x - mean[c]) * (gamma[c] * inv_std[c]) + beta[c], 0) per input channel --
  * BN_ReLU_Conv of FC-DenseNet (models/FCDenseNet.py:12,90,109,123) as one kernel instead of

@@ -83,6 +83,8 @@ SIGNATURES = {
     'iiseg_conv_small_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_pool_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_pool_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 10),
+    'iiseg_conv_halo_seam': (C.c_int, [C.c_int]),
+    'iiseg_conv_halo_seam_launches': (_i64, []),
     'iiseg_conv_mask_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_mask_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 12),
     'iiseg_conv_bnrelu_supported': (C.c_int, [C.POINTER(ConvDesc)]),

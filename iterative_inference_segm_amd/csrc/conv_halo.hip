@@ -10,6 +10,14 @@
 // The accumulation order over k is the same (channel-major, tap-minor, sequential 32x32x2 steps)
 // as conv_taps.hip / conv_igemm.hip, so results are bit-identical to those kernels.
 //
+// Column tiles across the image seam (SEAM): tile grids per image throw away the columns between OW and
+// the next multiple of 32 (113 -> 128, 116 -> 128, 226 -> 256: 10-13 % of the MFMAs).  With SEAM the
+// output columns of one row band of all B images are laid end to end, B*OW columns cut into 32-column
+// tiles; a tile may hold the last ns columns of image b and the first 32 - ns of image b + 1.  Its patch
+// is 36 columns wide: image b's columns and right halo, then image b + 1's left halo and columns, so
+// lanes right of the seam read at lane base + 2 and every tap offset stays the same immediate.  Which
+// tile computes a pixel changes; what is summed into it, and in what order, does not.
+//
 // Fusions: two-source channel concat (h first; needs C1 % 4 == 0), DePool2D equality-mask unpool
 // as the patch load (3 loads + compare per patch element instead of per im2col element:
 // layers/mylayers.py:88-115), bias / skip-add with crop / ReLU / window / placement epilogue.
@@ -18,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include "iiseg.h"
 #include "common.h"
 #include "conv_common.h"
@@ -47,11 +56,12 @@ __device__ __forceinline__ unsigned buf_ld_u8(__amdgpu_buffer_rsrc_t r, unsigned
 
 // MASKIN (with UNPOOL): the DePool2D mask comes as bytes (ConvParams::mask_in) instead of being
 // formed from pre == pooled: 2 loads (1 + 4 bytes) per patch element instead of 3 (12 bytes)
-template <int BM, int TH, int WM, int WN, bool UNPOOL, bool MASKIN = false>
+template <int BM, int TH, int WM, int WN, bool UNPOOL, bool MASKIN = false, bool SEAM = false>
 __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams p, const int tiles_y,
                                                                const int tiles_x) {
     constexpr int CPT = 4, BK = 9 * CPT, NCH = BK / 2;
-    constexpr int TW = 32, PH = TH + 2, PW = TW + 2, PP = PH * PW;
+    // SEAM: two more patch columns (the halo columns of both images on either side of the seam)
+    constexpr int TW = 32, PH = TH + 2, PW = TW + 2 + (SEAM ? 2 : 0), PP = PH * PW;
     constexpr int PE = CPT * PP;              // patch elements per k-tile
     constexpr int NE = (PE + 255) / 256;      // ... per thread
     constexpr int WTM = BM / WM, TM = WTM / 32;
@@ -60,7 +70,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
     static_assert(WM * WN == 4 && TH % WN == 0 && BM % (WM * 32) == 0 && WPT <= 5, "tile config");
     // MASKIN: a thread stages POOLED positions (`up` value + mask byte, 2 loads) and writes the up
     // to four patch elements of the 2x2 block -- a third of the loads of the per-pixel form
-    constexpr int QH = PH / 2 + 1, QW = PW / 2 + 1, QP = QH * QW, QE = CPT * QP;
+    // (SEAM: the two parts of the patch start at pooled columns of their own: one more each)
+    constexpr int QH = PH / 2 + 1, QW = PW / 2 + (SEAM ? 2 : 1), QP = QH * QW, QE = CPT * QP;
     constexpr int NQ = (QE + 255) / 256;
     static_assert(NQ <= NE, "staging registers");
 
@@ -70,12 +81,30 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
     int pt, mt;
     tile_of_block(blockIdx.x, gridDim.x, p.n_ptiles, p.n_mtiles, pt, mt);
     const int m0 = mt * BM;
-    const int tpi = tiles_y * tiles_x;
-    const int b = pt / tpi;
-    const int tr = pt - b * tpi;
-    const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
-    const int wy0 = ty * TH, wx0 = tx * TW;                        // tile origin, window coords
+    int b, ty, tx, wx0;
+    if constexpr (SEAM) {
+        // tiles_x counts the 32-column tiles of the B * OW columns of a row band; a column of tiles
+        // is walked top to bottom, so the tiles of one image stay together in the launch order
+        tx = pt / tiles_y;
+        ty = pt - tx * tiles_y;
+        b = (tx * TW) / p.OW;                                      // image of tile column 0 ...
+        wx0 = tx * TW - b * p.OW;                                  // ... and its window x there
+    } else {
+        const int tpi = tiles_y * tiles_x;
+        b = pt / tpi;
+        const int tr = pt - b * tpi;
+        ty = tr / tiles_x, tx = tr - ty * tiles_x;
+        wx0 = tx * TW;
+    }
+    const int wy0 = ty * TH;                                       // tile origin, window coords
     const int iy0 = p.oy0 + wy0 - p.pad, ix0 = p.ox0 + wx0 - p.pad;  // patch origin, input coords
+    // SEAM: tile columns [0, ns) belong to image b, [ns, 32) to image b + 1 (ns >= 32: no seam in
+    // this tile; host: OW >= 32, so never a second seam); `rimg`: that image exists and is needed
+    const int ns = SEAM ? p.OW - wx0 : TW;
+    const int nsc = SEAM ? min(ns, TW) : TW;
+    const bool rimg = SEAM && ns < TW && b + 1 < p.B;
+    const int nimg = rimg ? 2 : 1;                                 // images the descriptors span
+    const int ixr0 = p.ox0 - p.pad;                                // image b + 1's first patch column
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -84,55 +113,72 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
     const int C1 = p.C1, Ctot = p.C1 + p.C2;
 
     // ---- patch staging: element e = i*256 + tid  ->  (channel of the k-tile, patch y, patch x) ----
-    unsigned voff[NE], voff2[UNPOOL ? NE : 1];
+    // SEAM: patch columns [0, ns + 2) come from image b, [ns + 2, 36) from image b + 1; the elements
+    // of image b + 1 carry its distance from image b in their offset (of the first source; `rsel`
+    // lets the second source of a concat, whose images are C2 planes apart, correct it)
+    unsigned voff[NE], voff2[UNPOOL ? NE : 1], rsel[(SEAM && !UNPOOL) ? NE : 1];
     int cl[NE], bsel[UNPOOL ? NE : 1];
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
         const int e = i * 256 + tid;
         const int c = e / PP, rr = e - c * PP;
         const int py = rr / PW, px = rr - py * PW;
-        const int iy = iy0 + py, ix = ix0 + px;
+        const bool right = SEAM && px >= ns + 2;
+        const int iy = iy0 + py, ix = right ? ixr0 + px - (ns + 2) : ix0 + px;
         bool ok = e < PE && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+        if constexpr (SEAM) ok = ok && (right ? rimg : px < TW + 2);
         cl[i] = c;
-        voff[i] = ok ? 4u * (unsigned)(c * HW + iy * p.W + ix) : OOB;
+        voff[i] = ok ? 4u * (unsigned)(c * HW + iy * p.W + ix + (right ? C1 * HW : 0)) : OOB;
+        if constexpr (SEAM && !UNPOOL) rsel[i] = (ok && right) ? ~0u : 0u;
         if constexpr (UNPOOL) {
             // DePool2D (layers/mylayers.py:95-114): only the 2h x 2w region has pooling windows
             ok = ok && iy < 2 * p.h2 && ix < 2 * p.w2;
-            voff2[i] = ok ? 4u * (unsigned)(c * hw2 + (iy >> 1) * p.w2 + (ix >> 1)) : OOB;
+            voff2[i] = ok ? 4u * (unsigned)(c * hw2 + (iy >> 1) * p.w2 + (ix >> 1) + (right ? C1 * hw2 : 0))
+                          : OOB;
             bsel[i] = ((iy & 1) << 1) | (ix & 1);
         }
     }
     unsigned qv[MASKIN ? NQ : 1];
     int qs[MASKIN ? NQ : 1][4], qc[MASKIN ? NQ : 1];
     if constexpr (MASKIN) {
+        // SEAM: the first nql pooled columns of the grid cover image b's ns + 2 patch columns, the
+        // others image b + 1's 34 - ns, each part from the pooled column of its own first element
+        const int nql = ((ix0 + nsc + 1) >> 1) - (ix0 >> 1) + 1;
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int e = i * 256 + tid;
             const int c = e / QP, r = e - c * QP;
             const int qy = r / QW, qx = r - qy * QW;
-            const int Y2 = (iy0 >> 1) + qy, X2 = (ix0 >> 1) + qx;       // (arithmetic shifts: floor)
+            const bool right = SEAM && qx >= nql;
+            const int Y2 = (iy0 >> 1) + qy;                             // (arithmetic shifts: floor)
+            const int X2 = right ? (ixr0 >> 1) + qx - nql : (ix0 >> 1) + qx;
             const bool in = e < QE;
             qc[i] = c;
             // DePool2D (layers/mylayers.py:95-114): outside the h2 x w2 pooled map there is no
             // window (padding, the odd trailing row / column): the elements written there are zero
-            qv[i] = (in && (unsigned)Y2 < (unsigned)p.h2 && (unsigned)X2 < (unsigned)p.w2)
-                        ? 4u * (unsigned)(c * hw2 + Y2 * p.w2 + X2) : OOB;
+            // (and so are those of an image b + 1 past the batch)
+            qv[i] = (in && (unsigned)Y2 < (unsigned)p.h2 && (unsigned)X2 < (unsigned)p.w2 && (!right || rimg))
+                        ? 4u * (unsigned)(c * hw2 + Y2 * p.w2 + X2 + (right ? C1 * hw2 : 0)) : OOB;
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl) {
-                const int py = 2 * Y2 + (sl >> 1) - iy0, px = 2 * X2 + (sl & 1) - ix0;
-                qs[i][sl] = (in && (unsigned)py < (unsigned)PH && (unsigned)px < (unsigned)PW)
+                const int py = 2 * Y2 + (sl >> 1) - iy0;
+                // column inside the part, the part's width, its first patch column
+                const int pxp = 2 * X2 + (sl & 1) - (right ? ixr0 : ix0);
+                const int pw = SEAM ? (right ? max(TW + 2 - ns, 0) : nsc + 2) : PW;
+                const int px = right ? ns + 2 + pxp : pxp;
+                qs[i][sl] = (in && (unsigned)py < (unsigned)PH && (unsigned)pxp < (unsigned)pw)
                                 ? c * PP + py * PW + px : -1;
             }
         }
     }
-    // one image per tile: descriptors start at image b of each source
+    // descriptors start at image b of each source (SEAM: and span image b + 1 where the tile needs it)
     const unsigned char* basem = MASKIN ? p.mask_in + (size_t)b * C1 * hw2 : nullptr;
     const float* base1 = (UNPOOL && !MASKIN) ? p.pre + (size_t)b * C1 * HW : p.x1 + (size_t)b * C1 * HW;
     const float* base2 = p.C2 > 0 ? p.x2 + (size_t)b * p.C2 * HW : base1;
-    const int n1 = C1 * HW * 4, n2 = p.C2 > 0 ? p.C2 * HW * 4 : n1;
+    const int n1 = nimg * C1 * HW * 4, n2 = p.C2 > 0 ? nimg * p.C2 * HW * 4 : n1;
     const float* baseq = UNPOOL ? p.pooled + (size_t)b * C1 * hw2 : nullptr;
     const float* baseu = UNPOOL ? p.x1 + (size_t)b * C1 * hw2 : nullptr;
-    const int nq = C1 * hw2 * 4;
+    const int nq = nimg * C1 * hw2 * 4;
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -182,9 +228,13 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
             const bool s1 = c0 < C1;                                                               \
             const int crem = (s1 ? C1 : Ctot) - c0;                                                \
             const unsigned so = (unsigned)((s1 ? c0 : c0 - C1) * HW) * 4u;                         \
+            /* SEAM: images of the second source are C2, not C1, planes apart */                   \
+            const unsigned sd = s1 ? 0u : (unsigned)((p.C2 - C1) * HW) * 4u;                       \
             static_for<0, NE>([&](auto I) __attribute__((always_inline)) {                         \
                 constexpr int i = decltype(I)::value;                                              \
-                const unsigned vo = cl[i] < crem ? voff[i] : OOB;                                  \
+                unsigned vo = voff[i];                                                             \
+                if constexpr (SEAM) vo += rsel[i] & sd;   /* (rsel is 0 where voff is OOB) */      \
+                if (cl[i] >= crem) vo = OOB;                                                       \
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(                                          \
                     mk_rsrc(s1 ? base1 : base2, s1 ? n1 : n2),                                     \
                     (__attribute__((address_space(3))) void*)(&Ps[BUF][i * 256 + wave * 64]), 4,   \
@@ -234,7 +284,8 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    const int lbase = wn * RW * PW + l31;   // this lane's pixel inside the patch (tap 0,0)
+    // this lane's pixel inside the patch (tap 0,0); right of a seam the two halo columns lie between
+    const int lbase = wn * RW * PW + l31 + ((SEAM && l31 >= ns) ? 2 : 0);
     for (int kt = 0; kt < nkt; ++kt) {
         const int buf = kt & 1;
         const bool more = kt + 1 < nkt;
@@ -293,6 +344,10 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
     // consecutive x), then every thread moves 16-byte pieces of whole rows through buffer descriptors
     // of image b with 32-bit offsets computed once per thread; out-of-range pieces get the
     // out-of-bounds offset instead of a branch.  Same values in the same order of operations.
+    // SEAM: the descriptors span images b and b + 1; a piece (or pooling pair) right of the seam adds
+    // the distance to the same row of image b + 1, which is one image less OW columns -- tile column
+    // col is window x = wx0 + col left of the seam and wx0 + col - OW right of it.  The piece that
+    // holds the seam goes element by element, like the ragged right edge of the per-image tiling.
     constexpr int WSB = 2 * BK * BM * 4;                          // bytes of the weight ring
     constexpr int CHR = WSB >= 32 * TH * 128 ? 32 : (WSB >= 16 * TH * 128 ? 16 : 8);
     static_assert(CHR * TH * 128 <= WSB && 256 % (TH * 8) == 0, "staging tile must fit the weight ring");
@@ -305,31 +360,43 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
     const bool pooling = p.pool != nullptr;
     const __amdgpu_buffer_rsrc_t r_bias = mk_rsrc(p.bias, p.bias ? p.Cout * 4 : 0);
     const __amdgpu_buffer_rsrc_t r_out =
-        mk_rsrc(p.out ? p.out + (size_t)b * p.out_ctot * OPL : nullptr, p.out ? p.out_ctot * OPL * 4 : 0);
+        mk_rsrc(p.out ? p.out + (size_t)b * p.out_ctot * OPL : nullptr, p.out ? nimg * p.out_ctot * OPL * 4 : 0);
     const __amdgpu_buffer_rsrc_t r_add =
-        mk_rsrc(p.add ? p.add + (size_t)b * p.Cout * APL : nullptr, p.add ? p.Cout * APL * 4 : 0);
+        mk_rsrc(p.add ? p.add + (size_t)b * p.Cout * APL : nullptr, p.add ? nimg * p.Cout * APL * 4 : 0);
     const __amdgpu_buffer_rsrc_t r_pool =
-        mk_rsrc(pooling ? p.pool + (size_t)b * p.Cout * PPL : nullptr, pooling ? p.Cout * PPL * 4 : 0);
+        mk_rsrc(pooling ? p.pool + (size_t)b * p.Cout * PPL : nullptr, pooling ? nimg * p.Cout * PPL * 4 : 0);
     const __amdgpu_buffer_rsrc_t r_mask = mk_rsrc_b(
-        p.mask_out ? p.mask_out + (size_t)b * p.Cout * PPL : nullptr, p.mask_out ? p.Cout * PPL : 0);
+        p.mask_out ? p.mask_out + (size_t)b * p.Cout * PPL : nullptr, p.mask_out ? nimg * p.Cout * PPL : 0);
     const bool relu1 = p.relu && !p.add, relu2 = p.relu && p.add;   // (with a skip-add the ReLU comes
                                                                     //  after the sum)
     // store pass: thread -> (channel s_c of the pass, row, 4-pixel piece)
     const int s_c = tid / (TH * 8), s_rem = tid % (TH * 8);
     const int s_row = s_rem >> 3, s_x4 = (s_rem & 7) * 4;
     const int s_wy = wy0 + s_row, s_wx = wx0 + s_x4;
-    const int s_nv = min(4, p.OW - s_wx);
-    const bool s_ok = s_wy < p.OH && s_nv > 0;
+    // SEAM: columns are valid up to the last image's last (s_g: the piece's column among all B * OW);
+    // s_right: the whole piece lies right of the seam; the piece with the seam inside is not `s_whole`
+    const int GW = p.B * p.OW, s_g = tx * TW + s_x4;
+    const bool s_right = SEAM && s_x4 >= ns;
+    const int s_nv = SEAM ? ((s_x4 < ns && s_x4 + 4 > ns) ? 0 : min(4, GW - s_g)) : min(4, p.OW - s_wx);
+    const bool s_whole = s_nv == 4;
+    const bool s_ok = s_wy < p.OH && (SEAM ? s_g < GW : s_nv > 0);
+    const unsigned s_jo = SEAM ? 4u * (unsigned)(p.out_ctot * OPL - p.OW) : 0u;
+    const unsigned s_ja = SEAM ? 4u * (unsigned)(p.Cout * APL - p.OW) : 0u;
     const unsigned s_out0 = 4u * (unsigned)((p.out_c0 + m0 + s_c) * OPL + (p.out_y0 + s_wy) * p.out_W +
-                                            p.out_x0 + s_wx);
-    const unsigned s_add0 = 4u * (unsigned)((m0 + s_c) * APL + (p.ay0 + s_wy) * p.AW + p.ax0 + s_wx);
+                                            p.out_x0 + s_wx) + (s_right ? s_jo : 0u);
+    const unsigned s_add0 = 4u * (unsigned)((m0 + s_c) * APL + (p.ay0 + s_wy) * p.AW + p.ax0 + s_wx) +
+                            (s_right ? s_ja : 0u);
     // pool pass: thread -> (channel q_c of the pass, pooled row, pooled column) of the staged tile
     const int q_c = tid / ((TH / 2) * 16), q_rem = tid % ((TH / 2) * 16);
     const int q_row = q_rem >> 4, q_col = q_rem & 15;
-    const int q_wy = wy0 + 2 * q_row, q_wx = wx0 + 2 * q_col;
+    // (SEAM with a pool: OW is even -- host -- so wx0 and ns are even and a pair lies in one image)
+    const bool q_right = SEAM && 2 * q_col >= ns;
+    const int q_wy = wy0 + 2 * q_row, q_wx = wx0 + 2 * q_col - (q_right ? p.OW : 0);
     const int q_py = (p.oy0 + q_wy) >> 1, q_px = (p.ox0 + q_wx) >> 1;
-    const bool q_ok = pooling && q_wy + 1 < p.OH && q_wx + 1 < p.OW && q_py < p.pool_H && q_px < p.pool_W;
-    const unsigned q_off0 = (unsigned)((m0 + q_c) * PPL + q_py * p.pool_W + q_px);   // elements
+    const bool q_ok = pooling && q_wy + 1 < p.OH && q_wx + 1 < p.OW && q_py < p.pool_H && q_px < p.pool_W &&
+                      (!SEAM || tx * TW + 2 * q_col + 1 < GW);
+    const unsigned q_off0 = (unsigned)((m0 + q_c) * PPL + q_py * p.pool_W + q_px +
+                                       (q_right ? p.Cout * PPL : 0));   // elements
     const int lrow = wn * RW;
 #pragma unroll
     for (int wmr = 0; wmr < WM; ++wmr)
@@ -354,7 +421,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
                 for (int k = 0; k < NSP; ++k) {
                     const bool ok = s_ok && m0 + cb + CPP * k + s_c < p.Cout;
                     a4r[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        r_add, (int)((p.add && ok && s_nv == 4) ? s_add0 + 4u * (unsigned)((cb + CPP * k) * APL) : OOB), 0, 0));
+                        r_add, (int)((p.add && ok && s_whole) ? s_add0 + 4u * (unsigned)((cb + CPP * k) * APL) : OOB), 0, 0));
                 }
                 __syncthreads();                   // previous users of these LDS bytes are done
                 if (wm == wmr) {
@@ -377,7 +444,31 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
                     f32x4 v = *reinterpret_cast<const f32x4*>(Cs + (c * TH + s_row) * 32 + s_x4);
                     const unsigned oo = s_out0 + 4u * (unsigned)((cb + CPP * k) * OPL);
                     const unsigned ao = s_add0 + 4u * (unsigned)((cb + CPP * k) * APL);
-                    if (p.add) v += a4r[k];
+                    // (a piece that goes element by element adds its skip values there: adding the zero of
+                    // its out-of-range a4r first would turn a -0 + -0 into +0, unlike a whole piece)
+                    if (p.add && s_whole) v += a4r[k];
+                    if constexpr (SEAM) {
+                        if (ok && !s_whole) {      // the seam inside the piece, or the end of the last image
+                            // (the four skip-add loads first: one memory round trip, not one per element)
+                            float ad[4];
+                            bool jr[4], on[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                jr[e] = !s_right && s_x4 + e >= ns;            // this element is past the seam
+                                on[e] = s_g + e < GW;
+                                ad[e] = buf_ld(r_add, (p.add && on[e]) ? ao + 4u * e + (jr[e] ? s_ja : 0u) : OOB, 0);
+                            }
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                float t = v[e];
+                                if (p.add) t += ad[e];
+                                if (relu2) t = fmaxf(t, 0.f);
+                                __builtin_amdgcn_raw_buffer_store_b32(
+                                    __builtin_bit_cast(int, t), r_out,
+                                    (int)(on[e] ? oo + 4u * e + (jr[e] ? s_jo : 0u) : OOB), 0, 0);
+                            }
+                        }
+                    } else
                     if (ok && s_nv < 4) {          // ragged right edge of the window: element by element
                         for (int e = 0; e < s_nv; ++e) {
                             float t = v[e];
@@ -392,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
                         v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
                     }
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r_out,
-                                                           (int)((ok && s_nv == 4) ? oo : OOB), 0, 0);
+                                                           (int)((ok && s_whole) ? oo : OOB), 0, 0);
                 }
                 if (pooling) {
                     // fused 2x2 max-pool of these channels from the staged tile: window origin and TH
@@ -417,12 +508,58 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
             }
 }
 
+// IISEG_HALO_SEAM (default 1; iiseg_conv_halo_seam): 0 = per-image tile grids everywhere
+std::atomic<int> g_seam{-1};
+std::atomic<long long> g_seam_launches{0};
+
+int seam_setting() {
+    int v = g_seam.load();
+    if (v < 0) {
+        v = getenv("IISEG_HALO_SEAM") ? (atoi(getenv("IISEG_HALO_SEAM")) != 0) : 1;
+        g_seam.store(v);
+    }
+    return v;
+}
+
+// Column tiles across the image seam: where they save tiles, at most one seam can fall into a tile
+// (OW >= 32), the fused pool's column pairs cannot straddle it (even OW), and two consecutive images
+// of every tensor stay below the out-of-bounds offset of the kernel's 32-bit byte offsets.
+bool halo_seam_applies(const ConvParams& p) {
+    if (!seam_setting() || p.B < 2 || p.OW < 32) return false;
+    if (((int64_t)p.B * p.OW + 31) / 32 >= (int64_t)p.B * ((p.OW + 31) / 32)) return false;
+    if (p.pool && (p.OW & 1)) return false;
+    const int64_t lim = 1ll << 31, cmax = p.C1 > p.C2 ? p.C1 : p.C2;
+    if (2 * cmax * p.H * p.W * 4 >= lim) return false;
+    if (2 * ((int64_t)p.out_ctot + 128) * p.out_H * p.out_W * 4 >= lim) return false;
+    if (p.add && 2 * ((int64_t)p.Cout + 128) * p.AH * p.AW * 4 >= lim) return false;
+    if (p.pool && 2 * ((int64_t)p.Cout + 128) * p.pool_H * p.pool_W * 4 >= lim) return false;
+    return true;
+}
+
 template <int BM, int TH, int WM, int WN>
 int launch_halo(hipStream_t s, const ConvParams& cp, bool unpool) {
     ConvParams p = cp;
-    const int tiles_y = (p.OH + TH - 1) / TH, tiles_x = (p.OW + 31) / 32;
-    p.n_ptiles = p.B * tiles_y * tiles_x;
+    const int tiles_y = (p.OH + TH - 1) / TH;
     p.n_mtiles = p.Mpad / BM;
+    if (halo_seam_applies(p)) {
+        const int tiles_x = (p.B * p.OW + 31) / 32;       // of a row band of all B images
+        p.n_ptiles = tiles_y * tiles_x;
+        const int grid = p.n_ptiles * p.n_mtiles;
+        if (unpool && p.mask_in)
+            IISEG_LAUNCH((conv_halo_f32_kernel<BM, TH, WM, WN, true, true, true>), dim3(grid), dim3(256),
+                               0, s, p, tiles_y, tiles_x);
+        else if (unpool)
+            IISEG_LAUNCH((conv_halo_f32_kernel<BM, TH, WM, WN, true, false, true>), dim3(grid), dim3(256),
+                               0, s, p, tiles_y, tiles_x);
+        else
+            IISEG_LAUNCH((conv_halo_f32_kernel<BM, TH, WM, WN, false, false, true>), dim3(grid), dim3(256),
+                               0, s, p, tiles_y, tiles_x);
+        const int st = iiseg_check_launch();
+        if (st == IISEG_OK) g_seam_launches.fetch_add(1);
+        return st;
+    }
+    const int tiles_x = (p.OW + 31) / 32;
+    p.n_ptiles = p.B * tiles_y * tiles_x;
     const int grid = p.n_ptiles * p.n_mtiles;
     if (unpool && p.mask_in)
         IISEG_LAUNCH((conv_halo_f32_kernel<BM, TH, WM, WN, true, true>), dim3(grid), dim3(256),
@@ -753,6 +890,13 @@ bool iiseg_conv_halo_ok(const ConvParams& p, int KH, int KW) {
     if (p.add && ((int64_t)p.Cout + 128) * p.AH * p.AW * 4 >= (1ll << 31)) return false;
     return true;
 }
+
+extern "C" int iiseg_conv_halo_seam(int on) {
+    if (on >= 0) g_seam.store(on ? 1 : 0);
+    return seam_setting();
+}
+
+extern "C" int64_t iiseg_conv_halo_seam_launches(void) { return (int64_t)g_seam_launches.load(); }
 
 int iiseg_launch_conv_halo(hipStream_t s, const ConvParams& p, int bm, bool unpool) {
     static const int h16 = getenv("IISEG_CONV_HALO16") ? atoi(getenv("IISEG_CONV_HALO16")) : 1;

@@ -116,6 +116,20 @@ _scratch = {}
 _ws_tag = [0]
 
 
+# The fp32 halo kernel's column tiles across the image seam are switched in the library, not here:
+# IISEG_HALO_SEAM=0 in the environment, or `halo_seam(False)`, selects one tile grid per image.
+def halo_seam(on=None):
+    """The fp32 halo kernel's tiling for the launches that follow: True = 32-column tiles across the seam
+    between consecutive images (the default, IISEG_HALO_SEAM), False = one tile grid per image; None only
+    asks.  Returns the setting in force.  Both tilings give the same bits (A/B timing, tests)."""
+    return bool(_lib.load().iiseg_conv_halo_seam(-1 if on is None else int(bool(on))))
+
+
+def halo_seam_launches():
+    """Launches of the fp32 halo kernel so far that ran the seam tiling."""
+    return int(_lib.load().iiseg_conv_halo_seam_launches())
+
+
 class workspace_tag:
     """Context manager: launches inside use the scratch buffers of `tag` (an engine's id)."""
 
