@@ -220,6 +220,22 @@ int iiseg_conv_wino_pack_f32(void* stream, const iiseg_conv_desc* d, const float
 int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
                         const float* pre, const float* pooled, const float* U, const float* bias,
                         const float* add, float* workspace, float* out, uint32_t stages);
+/* The input transform of the fp32 Winograd calls.  By default plain and mask-byte inputs run the streaming
+ * kernel (four consecutive tiles per thread, 16-byte stores, a channel loop per workgroup).  The older
+ * per-tile (small maps) and LDS-staged kernels keep: the pre / pooled form of DePool2D; geometries whose
+ * staged rows or offsets do not fit the streaming kernel; and two classes that measured no gain on it --
+ * launches of fewer than 4096 tiles, and plain maps whose tiles per image fill the LDS-staged kernel's
+ * workgroups exactly.  V is the same under every choice, bit for bit.
+ *   iiseg_conv_wino_input_wide(on)   on = 0 / 1: never / by the rule above, for the launches that follow
+ *                                    (the default is the environment's IISEG_WINO_INPUT_WIDE, 1 when
+ *                                    unset); on = 2: also for the two no-gain classes (tests reach the
+ *                                    kernel on small maps); on < 0 only asks.  Returns the setting in
+ *                                    force.  For A/B timing and tests.
+ *   iiseg_conv_wino_input_path(d, mask_bytes)   the kernel a call with this descriptor would run under
+ *                                    the setting in force (mask_bytes: IISEG_CONV_UNPOOL from mask
+ *                                    bytes): 0 per-tile, 1 LDS-staged, 2 streaming; < 0 an IISEG_ERR_* */
+int iiseg_conv_wino_input_wide(int on);
+int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes);
 /* The Winograd call with the 2x2 max-pool and the DePool2D mask bytes (as iiseg_conv_mask_f32):
  *   pool_out   (may be NULL) the FULL pooled tensor (B, Cout, fullH/2, fullW/2); the pooled
  *              positions of the window are written in place by the output transform (or the fused

@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
+#include <type_traits>
 #include "iiseg.h"
 #include "common.h"
 #include "conv_common.h"
@@ -372,6 +374,184 @@ __global__ __launch_bounds__(NT) void wino_input_lds_kernel(const WinoParams p, 
             }
         }
     }
+}
+
+// Streaming input transform (plain and mask-byte inputs, every map size): a thread owns FOUR
+// consecutive tiles t = 4q .. 4q + 3 of V's tile axis, so each of the 16 xi values of a channel
+// leaves as one 16-byte store (1 KB per wave-instruction instead of 256 B), and a workgroup walks
+// `chw` channels with its integer prologue computed once.  t runs over tile rows of all images
+// laid end to end (t = gr * ntx + txl, gr = b * nty + tyl), so a workgroup's 4 * NT tiles may
+// cover part of one image or many small ones; it stages, per image it touches, the input rows of
+// the tile rows it holds (2 * rows + 2 each; element -> (image, iy, ix) is worked out once per
+// thread), double-buffered in LDS, and every thread reads its four 4x4 patches from there.
+// The next channel's loads are issued before the barrier and the previous channel's stores are
+// never waited for, so both stay in flight across it.  Values: the same d, the same B^T d B
+// expressions as the kernels above -- V is the same, bit for bit; nothing is written at t >= T.
+constexpr int IW_E = 24;   // staged elements per thread (capacity IW_E * NT floats per buffer)
+
+struct IwChunk {           // staged rows of the tiles [t0, t1): image b0 from tile row tyf, then whole images
+    int b0, tyf, R0, RI, NR;
+};
+
+__host__ __device__ inline IwChunk iw_chunk(int t0, int t1, int ntx, int nty) {
+    IwChunk k;
+    const int gr0 = t0 / ntx, gr1 = (t1 - 1) / ntx;
+    const int b1 = gr1 / nty, tyl = gr1 - b1 * nty;
+    k.b0 = gr0 / nty;
+    k.tyf = gr0 - k.b0 * nty;
+    k.RI = 2 * nty + 2;
+    if (k.b0 == b1) {
+        k.R0 = 2 * (tyl - k.tyf + 1) + 2;
+        k.NR = k.R0;
+    } else {
+        k.R0 = 2 * (nty - k.tyf) + 2;
+        k.NR = k.R0 + (b1 - k.b0 - 1) * k.RI + 2 * (tyl + 1) + 2;
+    }
+    return k;
+}
+
+// packed staging offset: bits 0..19 the offset inside one plane (mask bytes: (offset << 2) | bit),
+// bits 20.. the image relative to the chunk's first.  Elements that are zero (outside the map, not
+// staged) load offset 0 and have their bit clear in the thread's mask `okm`.
+constexpr int IW_PBITS = 20;
+static_assert(IW_E <= 32, "one validity bit per staged element");
+
+template <bool MB, int NT>
+__global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p, const int chw) {
+    __shared__ __attribute__((aligned(16))) float Ls[2][IW_E * NT];
+    const int tid = threadIdx.x;
+    const int tw0 = blockIdx.x * (4 * NT), tw1 = min(tw0 + 4 * NT, p.T);
+    const IwChunk k = iw_chunk(tw0, tw1, p.ntx, p.nty);
+    const int NC = 2 * p.ntx + 2, NE = k.NR * NC;
+    const int iyb = p.ty0 - p.pad, ixb = p.tx0 - p.pad;
+    uint32_t pk[IW_E], okm = 0;
+#pragma unroll
+    for (int i = 0; i < IW_E; ++i) {
+        const int e = i * NT + tid;
+        const int r = e / NC, c = e - r * NC;
+        int bi = 0, ry = 2 * k.tyf + r;
+        if (r >= k.R0) {
+            const int r2 = r - k.R0;
+            bi = r2 / k.RI;
+            ry = r2 - bi * k.RI;
+            bi += 1;
+        }
+        const int iy = iyb + ry, ix = ixb + c;
+        bool ok = e < NE && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+        int po = iy * p.W + ix;
+        if constexpr (MB) {
+            ok = ok && iy < 2 * p.h2 && ix < 2 * p.w2;
+            po = (((iy >> 1) * p.w2 + (ix >> 1)) << 2) | ((iy & 1) * 2 + (ix & 1));
+        }
+        pk[i] = ok ? ((uint32_t)bi << IW_PBITS) | (uint32_t)po : 0u;
+        okm |= (ok ? 1u : 0u) << i;
+    }
+    // the thread's four tiles: first staged element of each 4x4 patch
+    const int q4 = tw0 + 4 * tid;
+    int lbase[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int t = min(q4 + j, tw1 - 1);
+        const int gr = t / p.ntx, txl = t - gr * p.ntx;
+        const int b = gr / p.nty, ty = gr - b * p.nty;
+        const int row = b == k.b0 ? 2 * (ty - k.tyf) : k.R0 + (b - k.b0 - 1) * k.RI + 2 * ty;
+        lbase[j] = row * NC + 2 * txl;
+    }
+    const int nv = min(4, tw1 - q4);   // tiles of the quad below T (<= 0: none)
+    const int HW = p.H * p.W, hw2 = p.h2 * p.w2;
+    const size_t xis = (size_t)p.Kc * p.Tpad;
+    const int c0 = blockIdx.y * chw;
+    constexpr uint32_t PM = (1u << IW_PBITS) - 1;
+    float v[IW_E];
+    uint32_t mq[MB ? IW_E : 1];
+
+    // all loads of a channel unconditionally, one batch in flight (32-bit byte offsets from the
+    // plane of the chunk's first image); they are masked only where they are written to LDS, one
+    // barrier later, so nothing here waits for them
+    auto fetch = [&](int c) __attribute__((always_inline)) {
+        if constexpr (MB) {
+            const uint32_t ist = (uint32_t)(p.C1 * hw2);
+            const uint8_t* mp = p.mask_in + ((size_t)k.b0 * p.C1 + c) * hw2;
+            const char* upp = reinterpret_cast<const char*>(p.x1 + ((size_t)k.b0 * p.C1 + c) * hw2);
+#pragma unroll
+            for (int i = 0; i < IW_E; ++i) {
+                const uint32_t o = (pk[i] >> IW_PBITS) * ist + ((pk[i] & PM) >> 2);
+                mq[i] = mp[o];
+                v[i] = *reinterpret_cast<const float*>(upp + 4u * o);
+            }
+        } else {
+            const bool first = c < p.C1;
+            const uint32_t ist = (uint32_t)((first ? p.C1 : p.C2) * HW);
+            const char* src = reinterpret_cast<const char*>(
+                first ? p.x1 + ((size_t)k.b0 * p.C1 + c) * HW
+                      : p.x2 + ((size_t)k.b0 * p.C2 + (c - p.C1)) * HW);
+#pragma unroll
+            for (int i = 0; i < IW_E; ++i)
+                v[i] = *reinterpret_cast<const float*>(src + 4u * ((pk[i] >> IW_PBITS) * ist + (pk[i] & PM)));
+        }
+    };
+
+    // FULL: every quad of the workgroup lies below T (all workgroups but the last along x).  Its
+    // loop has no branch between a channel's loads and the stores that follow them, so the wait
+    // before the LDS writes counts those 16 stores out and leaves them in flight; the other form's
+    // store count depends on the lane, and its waits are for everything.
+    auto run = [&](auto FULLC) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(FULLC)::value;
+    fetch(c0);
+    for (int cc = 0; cc < chw; ++cc) {
+        const int c = c0 + cc;
+        float* L = Ls[cc & 1];
+#pragma unroll
+        for (int i = 0; i < IW_E; ++i) {   // (every slot of the buffer: those past the staged rows get 0)
+            bool on = (okm >> i) & 1u;
+            if constexpr (MB) on = on && ((mq[i] >> (pk[i] & 3u)) & 1u);
+            L[i * NT + tid] = on ? v[i] : 0.f;
+        }
+        if (cc + 1 < chw) fetch(c + 1);
+        __syncthreads();
+        if constexpr (!FULL)
+            if (nv <= 0) continue;
+        // row i of B^T d needs two rows of d only (d0 - d2, d1 + d2, d2 - d1, d1 - d3): the four
+        // xi planes of one i at a time keep the live values of a thread's four tiles small
+        float* vo = p.V + (size_t)c * p.Tpad + q4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            constexpr int RA[4] = {0, 1, 2, 1}, RB[4] = {2, 2, 1, 3};
+            float o[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float* La = L + lbase[j] + RA[i] * NC;
+                const float* Lb = L + lbase[j] + RB[i] * NC;
+                const float2 alo = *reinterpret_cast<const float2*>(La);
+                const float2 ahi = *reinterpret_cast<const float2*>(La + 2);
+                const float2 blo = *reinterpret_cast<const float2*>(Lb);
+                const float2 bhi = *reinterpret_cast<const float2*>(Lb + 2);
+                const float da[4] = {alo.x, alo.y, ahi.x, ahi.y}, db[4] = {blo.x, blo.y, bhi.x, bhi.y};
+                float e[4];
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) e[jj] = i == 1 ? da[jj] + db[jj] : da[jj] - db[jj];   // B^T d
+                o[0][j] = e[0] - e[2];   // (B^T d) B
+                o[1][j] = e[1] + e[2];
+                o[2][j] = e[2] - e[1];
+                o[3][j] = e[1] - e[3];
+            }
+            if (FULL || nv == 4) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+                    *reinterpret_cast<float4*>(vo + (size_t)(i * 4 + x) * xis) =
+                        make_float4(o[x][0], o[x][1], o[x][2], o[x][3]);
+            } else {   // the quad that holds T: the tiles below T, one by one
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j)
+                        if (j < nv) vo[(size_t)(i * 4 + x) * xis + j] = o[x][j];
+            }
+        }
+    }
+    };
+    if (tw0 + 4 * NT <= p.T) run(std::true_type{});
+    else run(std::false_type{});
 }
 
 // ---- 2. the 16 GEMMs ---------------------------------------------------------------------------
@@ -874,8 +1054,61 @@ int wino_geom(const iiseg_conv_desc* d, WinoGeom& g) {
     return IISEG_OK;
 }
 
-void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
-    const bool mb = unpool && p.mask_in;
+// IISEG_WINO_INPUT_WIDE (default 1; iiseg_conv_wino_input_wide): 0 = the per-tile / LDS-staged kernels
+// with one-dword stores everywhere (same bits: A/B timing, tests); 2 = also for the classes iw_shape leaves out
+std::atomic<int> g_input_wide{-1};
+
+int input_wide_setting() {
+    int v = g_input_wide.load();
+    if (v < 0) {
+        v = getenv("IISEG_WINO_INPUT_WIDE") ? (atoi(getenv("IISEG_WINO_INPUT_WIDE")) != 0) : 1;
+        g_input_wide.store(v);
+    }
+    return v;
+}
+
+// every workgroup's staged rows fit its LDS buffer (exact: the same iw_chunk the kernel runs)
+bool iw_fits(const WinoParams& p, int nt) {
+    const int NC = 2 * p.ntx + 2;
+    for (int t0 = 0; t0 < p.T; t0 += 4 * nt) {
+        const int t1 = t0 + 4 * nt < p.T ? t0 + 4 * nt : p.T;
+        if ((int64_t)iw_chunk(t0, t1, p.ntx, p.nty).NR * NC > (int64_t)IW_E * nt) return false;
+    }
+    return true;
+}
+
+int ilds_nt(const WinoParams& p);
+constexpr int IW_NT = 256;   // threads per workgroup of the streaming kernel
+
+// Channels per workgroup of the streaming kernel for this call, 0 = it does not apply.  It takes
+// plain and mask-byte inputs (`mb`; the pre / pooled form of DePool2D keeps the kernels above)
+// whose planes and image strides fit its packed 32-bit offsets.  Two classes measured no gain at
+// batch 64 and keep their kernels unless the setting is 2 (profiles/r09_wino_input_ab.txt):
+//  - launches of fewer than 4096 tiles, too few quads to fill the chip (2048 channels of 5 x 5
+//    tiles, T = 1600: 0.045 -> 0.064 ms; 1024 of 7 x 7, T = 3136: 0.048 -> 0.057 ms; from T = 5184 up
+//    it gains);
+//  - plain maps whose tiles per image fill the LDS-staged kernel's workgroups exactly: that kernel
+//    then already stores at this one's rate (256 channels of 32 x 32 tiles: 0.287 -> 0.299 ms).
+int iw_shape(const WinoParams& p, bool unpool, bool mb) {
+    const int setting = input_wide_setting();
+    if (!setting || (unpool && !mb)) return 0;
+    if (setting != 2) {
+        if (p.T < 4096) return 0;
+        const int lnt = mb ? 0 : ilds_nt(p);
+        if (lnt && (p.nty * p.ntx) % lnt == 0) return 0;
+    }
+    const int64_t HW = (int64_t)p.H * p.W, cmax = p.C1 > p.C2 ? p.C1 : p.C2;
+    if (HW > (1 << IW_PBITS) || (int64_t)p.B * cmax * HW >= (int64_t)1 << 30) return 0;
+    // channels per workgroup: as many as still leave about 8 waves for each of the 256 CUs
+    const int64_t waves1 = ((int64_t)p.T + 255) / 256 * p.Kc;   // with one channel per workgroup
+    int ch = 8;
+    if (p.Kc % 32 == 0 && waves1 / 32 >= 2048) ch = 32;
+    else if (waves1 / 16 >= 2048) ch = 16;
+    return iw_fits(p, IW_NT) ? ch : 0;
+}
+
+// tiles per workgroup of the LDS-staged kernel (one image per workgroup), 0 = the per-tile kernel
+int ilds_nt(const WinoParams& p) {
     static const int lds = getenv("IISEG_WINO_INPUT_LDS") ? atoi(getenv("IISEG_WINO_INPUT_LDS")) : 1;
     const int ntt = p.nty * p.ntx;
     // tiles per workgroup (one image per workgroup): the size that leaves the fewest idle lanes
@@ -889,7 +1122,20 @@ void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
         const double util = (double)ntt / (((ntt + cand - 1) / cand) * cand);
         if (util > best + 0.02) { best = util; nt = cand; }
     }
-    if (lds && nt && best >= 0.8 && p.Kc % ILDS_CH == 0) {
+    return lds && nt && best >= 0.8 && p.Kc % ILDS_CH == 0 ? nt : 0;
+}
+
+void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
+    const bool mb = unpool && p.mask_in;
+    if (const int chw = iw_shape(p, unpool, mb)) {
+        const dim3 g2((p.T + 4 * IW_NT - 1) / (4 * IW_NT), p.Kc / chw);
+        if (mb) IISEG_LAUNCH((wino_input_wide_kernel<true, IW_NT>), g2, dim3(IW_NT), 0, s, p, chw);
+        else IISEG_LAUNCH((wino_input_wide_kernel<false, IW_NT>), g2, dim3(IW_NT), 0, s, p, chw);
+        return;
+    }
+    const int nt = ilds_nt(p);
+    const int ntt = p.nty * p.ntx;
+    if (nt) {
         const int chunks = (ntt + nt - 1) / nt;
         const dim3 g2(p.B * chunks, p.Kc / ILDS_CH);
 #define WINO_ILDS(U, N, ...) IISEG_LAUNCH((wino_input_lds_kernel<U, N, ##__VA_ARGS__>), g2, dim3(N), 0, s, p, chunks)
@@ -952,6 +1198,24 @@ int iiseg_wino_output_launch(hipStream_t s, const iiseg_conv_desc* d, const floa
 extern "C" int iiseg_conv_wino_supported(const iiseg_conv_desc* d) {
     WinoGeom g;
     return wino_geom(d, g) == IISEG_OK ? 1 : 0;
+}
+
+extern "C" int iiseg_conv_wino_input_wide(int on) {
+    if (on >= 0) g_input_wide.store(on > 1 ? 2 : on);
+    return input_wide_setting();
+}
+
+extern "C" int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes) {
+    WinoGeom g;
+    const int st = wino_geom(d, g);
+    if (st) return st;
+    WinoParams p = {};
+    const bool unpool = (d->flags & IISEG_CONV_UNPOOL) != 0;
+    if (mask_bytes && !unpool) return IISEG_ERR_UNSUPPORTED;
+    p.B = d->B; p.C1 = d->C1; p.C2 = d->C2; p.H = d->H; p.W = d->W;
+    p.nty = g.nty; p.ntx = g.ntx; p.T = g.T; p.Tpad = g.Tpad; p.Kc = g.Kc;
+    if (iw_shape(p, unpool, mask_bytes != 0)) return 2;
+    return ilds_nt(p) ? 1 : 0;
 }
 
 extern "C" int64_t iiseg_conv_wino_weight_elems(const iiseg_conv_desc* d) {

@@ -130,6 +130,17 @@ def halo_seam_launches():
     return int(_lib.load().iiseg_conv_halo_seam_launches())
 
 
+# The fp32 Winograd input transform's streaming kernel is switched in the library too:
+# IISEG_WINO_INPUT_WIDE=0 in the environment, or `wino_input_wide(False)`, keeps the one-dword-store kernels.
+def wino_input_wide(on=None, force=False):
+    """The fp32 Winograd input transform for the launches that follow: True = the streaming kernel with
+    16-byte stores wherever it applies (the default, IISEG_WINO_INPUT_WIDE), False = the per-tile and
+    LDS-staged kernels; None only asks.  `force` (with True): also for the two classes that measured no gain
+    and keep the older kernels otherwise (include/iiseg.h: under 4096 tiles; plain maps that fill the
+    LDS-staged kernel's workgroups).  Returns the setting in force.  Same bits (A/B timing, tests)."""
+    return bool(_lib.load().iiseg_conv_wino_input_wide(-1 if on is None else (2 if on and force else int(bool(on)))))
+
+
 class workspace_tag:
     """Context manager: launches inside use the scratch buffers of `tag` (an engine's id)."""
 
