@@ -928,6 +928,42 @@ int iiseg_ctx_grad_head_f64(void* stream, const double* score, const double* y, 
                             const double* W7, int64_t so, int64_t sc, double* gs, double* g6, int32_t B, int32_t C,
                             int32_t Cin, int32_t H, int32_t W);
 
+/* ---------------------------------------------------------------------------------------
+ * 16-bit leg of the context-module DAE: a 'valid' K x K layer, K = 1 or 3, dilation
+ * dil in {1, 2, 4, 8, 16}, at most 16 channels on either side, on bf16 C8 activations with
+ * v_mfma_f32_16x16x32_bf16 (bf16 operands, fp32 accumulation; csrc/conv_c8_dil.hip).  The B operand comes
+ * straight from global memory (one 16-byte chunk entry per lane and MFMA, no LDS).  Every output is ONE
+ * fixed-order sum: the MFMA chain from zero over the tap pairs (0,1) (2,3) (4,5) (6,7) (8,-), then in fp32
+ * + bias, + addend, ReLU, store.  No atomics.  Every entry checks its arguments before any launch.
+ *   x8     : (B, 2, H, W, 8) bf16, channels >= Cin are zeros by contract.
+ *   wpack  : the packed A operand, iiseg_conv_c8_dil_pack_bytes(K) bytes, 16-byte aligned: image m (tap pair m;
+ *            K = 1: one image) as [lane group g][row co][j] bf16 = W[co][ci = 8 (g & 1) + j][tap 2 m + (g >> 1)],
+ *            rounded to nearest-even; zero where co >= Cout, ci >= Cin or the tap does not exist.
+ *   bias   : Cout floats or NULL.   addend : fp32 (B, Cout, OH, OW) or NULL, (OH, OW) = (H, W) - dil (K - 1).
+ *   out    : bf16 C8 (B, 2, out_H, out_W, 8) with the (OH, OW) map at (out_y0, out_x0) -- channels >= Cout are
+ *            written as zeros, nothing outside the window is touched -- or, with IISEG_C8DIL_OUT_NCHW, fp32
+ *            (B, Cout, out_H, out_W).  out_H == 0: a dense (OH, OW) output.
+ * W of the packers: element (co, ci, tap) at co * so + ci * sc + tap (see iiseg_dgrad_desc).
+ * ------------------------------------------------------------------------------------- */
+#define IISEG_C8DIL_OUT_NCHW 0x100u   /* flags, beside IISEG_CONV_RELU */
+typedef struct iiseg_c8dil_desc {
+    int32_t B, Cin, Cout, H, W, K, dil;
+    int32_t out_H, out_W, out_y0, out_x0;
+    uint32_t flags;
+} iiseg_c8dil_desc;
+
+/* host only: IISEG_OK or the status a launch of `d` would return */
+int iiseg_conv_c8_dil_check(const iiseg_c8dil_desc* d);
+/* host only: bytes of the packed operand for K (1 or 3), or a negative status */
+int64_t iiseg_conv_c8_dil_pack_bytes(int32_t K);
+/* host only: packs host weights into host memory (the arithmetic of the device packer; tests, tools) */
+int iiseg_conv_c8_dil_pack_host(const iiseg_c8dil_desc* d, const float* W, int64_t so, int64_t sc, void* wpack);
+/* device: W and wpack in device memory; one small launch */
+int iiseg_conv_c8_dil_pack(void* stream, const iiseg_c8dil_desc* d, const float* W, int64_t so, int64_t sc,
+                           void* wpack);
+int iiseg_conv_c8_dil(void* stream, const iiseg_c8dil_desc* d, const void* x8, const void* wpack,
+                      const float* bias, const float* addend, void* out);
+
 #ifdef __cplusplus
 }
 #endif

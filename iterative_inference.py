@@ -25,6 +25,7 @@ from iterative_inference_segm_amd import dist as iidist
 from iterative_inference_segm_amd import synthetic as S
 from iterative_inference_segm_amd.api import EPSILON, EnginePool, IterativeInference
 from iterative_inference_segm_amd.dae import buildDAE, param_order
+from iterative_inference_segm_amd import ops as _ops
 from iterative_inference_segm_amd.data_loader import load_data
 from iterative_inference_segm_amd.fcn8 import buildFCN8
 from iterative_inference_segm_amd.helpers import build_experiment_name, print_results, results_line
@@ -144,7 +145,9 @@ def build_networks(dataset, segm_net, dae_dict, loadpath, weights_path, which_se
                                   model_name='dae_model_best.npz', trainable=True,
                                   load_weights=True, out_nonlin='softmax',
                                   noise=dae_dict['noise'], concat_h=dae_dict['concat_h'],
-                                  params=dae_params, device=device)
+                                  params=dae_params, device=device,
+                                  # the chosen matrix-pipe mode (--mma / IISEG_MMA): 'bf16c8' = its 16-bit leg
+                                  mma=_ops.DEFAULT_MMA)
     else:
         raise ValueError('Unknown dae kind')                     # :178-179
 
@@ -181,6 +184,11 @@ def inference(dataset, segm_net, learn_step=0.005, num_iter=500, dae_dict_update
         # before any directory is made or the GPU is touched
         raise NotImplementedError("--update gradient needs the DAE's backward pass, which the DAE kind %r does not "
                                   "have (built for: %s)" % (dae_dict['kind'], ', '.join(GRADIENT_KINDS)))
+    if update == 'gradient' and dae_dict['kind'] == 'contextmod' and _ops.DEFAULT_MMA == 'bf16c8' and not dry_run:
+        # (the same: before any directory is made or the GPU is touched)
+        # (keyed on the process-wide default alone -- what `build_networks` hands the DAE; --mma / IISEG_MMA set it)
+        raise NotImplementedError("--update gradient with --mma bf16c8: the context module's 16-bit leg "
+                                  "(mma='bf16c8') runs the forward pass only, its backward pass needs --mma f32")
 
     # Prepare load/save directories (:84-104)
     name_kw = dict(dae_dict)
@@ -390,7 +398,6 @@ def main():
                              "pairs: fp32-class, DESIGN 3.8)")
     args = parser.parse_args()
     if args.mma is not None and not args.dry_run:
-        from iterative_inference_segm_amd import ops as _ops
         _ops.DEFAULT_MMA = args.mma
 
     inference(args.dataset, args.segmentation_net, float(args.step), int(args.num_iter),

@@ -65,6 +65,15 @@ class DgradDesc(C.Structure):
                                          'gx_c0', 'gx_y0', 'gx_x0', 'reserved')] + [('so', C.c_int64), ('sc', C.c_int64)]
 
 
+C8DIL_OUT_NCHW = 0x100
+
+
+class C8DilDesc(C.Structure):
+    """struct iiseg_c8dil_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'dil', 'out_H', 'out_W', 'out_y0',
+                                         'out_x0')] + [('flags', C.c_uint32)]
+
+
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); mirrors include/iiseg.h one to one
@@ -234,6 +243,12 @@ SIGNATURES = {
     'iiseg_ctx_grad_head_blocks': (C.c_int, [_i32] * 5),
     'iiseg_ctx_grad_head_f32': (C.c_int, [_vp] * 5 + [_i64] * 2 + [_vp] * 2 + [_i32] * 5),
     'iiseg_ctx_grad_head_f64': (C.c_int, [_vp] * 5 + [_i64] * 2 + [_vp] * 2 + [_i32] * 5),
+    # 16-bit leg of the context-module DAE
+    'iiseg_conv_c8_dil_check': (C.c_int, [C.POINTER(C8DilDesc)]),
+    'iiseg_conv_c8_dil_pack_bytes': (_i64, [_i32]),
+    'iiseg_conv_c8_dil_pack_host': (C.c_int, [C.POINTER(C8DilDesc), _vp, _i64, _i64, _vp]),
+    'iiseg_conv_c8_dil_pack': (C.c_int, [_vp, C.POINTER(C8DilDesc), _vp, _i64, _i64, _vp]),
+    'iiseg_conv_c8_dil': (C.c_int, [_vp, C.POINTER(C8DilDesc)] + [_vp] * 5),
 }
 
 _lib = None

@@ -3,7 +3,11 @@ conv3x3(+ReLU) on [h=image, y] -> pad 32 -> six dilated 3x3 convs (dilation 1,2,
 -> 1x1 linear -> softmax, 11 channels throughout.  The PadLayer is the `pad` of the first dilated
 conv; the 3x3 layers (dilation 1..16) run on the 16-channel halo kernel (`conv_halo16`, 16x16x4
 MFMA; DilatedConv2DLayer weight layout W[in,out,k,k], P11); inside a refinement loop the concat is
-a buffer whose y channels are refreshed per step, outside it the two-source gather."""
+a buffer whose y channels are refreshed per step, outside it the two-source gather.
+
+`mma='bf16c8'` (float32 only) is the 16-bit leg: bf16 C8 activations between the layers,
+every layer but the image half of conv1 on `ops.ConvC8Dil` (csrc/conv_c8_dil.hip), the score map in fp32.  The
+other modes ('f32', 'bf16', 'bf16x3') run the fp32 kernels below: layers this narrow have no other 16-bit form."""
 import os
 
 import torch
@@ -24,8 +28,15 @@ class ContextModDAE:
     kind = 'contextmod'
 
     def __init__(self, params, n_classes, concat_h=('input',), device='cuda',
-                 dtype=torch.float32):
+                 dtype=torch.float32, mma=None):
+        """mma: None (ops.DEFAULT_MMA) | 'f32' | 'bf16' | 'bf16x3' | 'bf16c8'.  Only 'bf16c8' changes anything
+        here, and only for float32 (`self.c8`): float64 ignores it."""
         assert all(el in ['input'] for el in concat_h)               # contextmod_dae.py:42
+        mma = (mma or ops.DEFAULT_MMA) if dtype == torch.float32 else 'f32'
+        if mma not in ('f32', 'bf16', 'bf16c8', 'bf16x3'):
+            raise ValueError("mma must be 'f32', 'bf16', 'bf16c8' or 'bf16x3'")
+        self.mma = mma
+        self.c8 = mma == 'bf16c8' and dtype == torch.float32
         if len(concat_h) != 1:
             raise NotImplementedError('one h (the image) is concatenated at the input')
         self.concat_h = list(concat_h)
@@ -74,6 +85,22 @@ class ContextModDAE:
         self._saved = None          # training: what `forward_train` kept for `backward`
         self._gflat = None
         self._keep_pre, self._pre = False, None
+        if self.c8:
+            # the 16-bit leg's layers: views of `flat` read through their strides, packed to bf16 operand images
+            if max(self.conv1.Cout, self.last.Cout, *(c.Cout for c in self.dil)) > 16:
+                raise NotImplementedError("mma='bf16c8': the context module's layers have at most 16 channels")
+            self._c8_first = {}     # h channels -> the y half of conv1 (its image half: `_split_convs`)
+            self._c8_dil = [ops.ConvC8Dil(params['dilconv%d' % (i + 1)][0], params['dilconv%d' % (i + 1)][1],
+                                          relu=True, dil=d, layout='iohw', device=device)
+                            for i, d in enumerate(DILATIONS)]
+            self._c8_last = ops.ConvC8Dil(params['dilconv7'][0], params['dilconv7'][1], relu=False, dil=1,
+                                          layout='iohw', device=device)
+
+    def _refuse_c8(self, what):
+        if self.c8:
+            raise NotImplementedError("mma='bf16c8' runs the context module's forward pass only (no keep_pre / "
+                                      "backward_y / sqerr_backward, no forward_train / backward): %s needs "
+                                      "mma='f32'" % what)
 
     @property
     def keep_pre(self):
@@ -83,6 +110,8 @@ class ContextModDAE:
 
     @keep_pre.setter
     def keep_pre(self, on):
+        if on:
+            self._refuse_c8('keep_pre (true-gradient mode)')
         self._keep_pre = bool(on)
         if not on:
             self._pre = None
@@ -103,6 +132,8 @@ class ContextModDAE:
             return None
         h = h_list[0]
         B, ch, H, W = h.shape[0], h.shape[1], y.shape[2], y.shape[3]
+        if self.c8:
+            return self._new_session_c8(h, y)
         # The buffers are kept per geometry and handed out again (a captured refinement step points into them:
         # a new batch replays the same graph); what a call changes: the h channels (copied here) and the y
         # channels (every step).  The zero borders are written once.
@@ -137,10 +168,72 @@ class ContextModDAE:
         if pair is None:
             W, b, device, dtype = self._conv1_params
             W = torch.as_tensor(W)
+            kw = {'mma': 'f32'} if self.c8 else {}      # (the 16-bit leg keeps the image half in fp32)
             pair = self._hsplit[ch] = (
-                ops.Conv(W[:, :ch].contiguous(), b, pad=0, relu=False, device=device, dtype=dtype),
-                ops.Conv(W[:, ch:].contiguous(), None, pad=0, relu=True, device=device, dtype=dtype))
+                ops.Conv(W[:, :ch].contiguous(), b, pad=0, relu=False, device=device, dtype=dtype, **kw),
+                ops.Conv(W[:, ch:].contiguous(), None, pad=0, relu=True, device=device, dtype=dtype, **kw))
         return pair
+
+    # ---- the 16-bit leg (mma='bf16c8') ----
+    def _new_session_c8(self, h, y):
+        """The C8 form of a session, per geometry and handed out again like the fp32 one: `y8` (the y channels
+        as a dense C8 map: what `c8_feed` hands to ops.refine_update), `y8cat` (the same inside conv1's one-pixel
+        zero border), `hb` (the image half W_h * h + b in fp32, once per batch), `pad32_8` (conv1's output inside
+        PadLayer(32)'s zeros) and the six dilated layers' outputs."""
+        B, ch, Cy, H, W = h.shape[0], h.shape[1], y.shape[1], y.shape[2], y.shape[3]
+        if ch + Cy != self.conv1.Cin or Cy > 16:
+            raise RuntimeError('context module: h %s, y %s' % (tuple(h.shape), tuple(y.shape)))
+        key = (B, ch, Cy, H, W, 'c8', str(y.device))
+        sess = self._sessions.get(key)
+        if sess is None:
+            dev = y.device
+            z8 = lambda hh, ww: torch.zeros((B, 2, hh, ww, 8), dtype=torch.bfloat16, device=dev)
+            acts, hh, ww = [], H + 64, W + 64
+            for d in DILATIONS:
+                hh, ww = hh - 2 * d, ww - 2 * d
+                acts.append(ops.empty_c8(B, 16, hh, ww, dev))
+            while len(self._sessions) >= 4:
+                self._sessions.pop(next(iter(self._sessions)))
+            sess = self._sessions[key] = {
+                'c8': True, 'ch': ch, 'split': self._split_convs(ch), 'first': self._c8_first_layer(ch),
+                'hpad': torch.zeros((B, ch, H + 2, W + 2), dtype=y.dtype, device=dev),
+                'hb': torch.empty((B, self.conv1.Cout, H, W), dtype=y.dtype, device=dev),
+                'y8': ops.empty_c8(B, Cy, H, W, dev), 'y8cat': z8(H + 2, W + 2), 'pad32_8': z8(H + 64, W + 64),
+                'acts': acts}
+        sess['hpad'][:, :, 1:-1, 1:-1].copy_(h)
+        sess['split'][0](sess['hpad'], out=sess['hb'])
+        sess['y8_fresh'] = False        # y8 holds another loop's map
+        return sess
+
+    def _c8_first_layer(self, ch):
+        conv = self._c8_first.get(ch)
+        if conv is None:
+            # conv1's y half: a slice of the parameter along its input channels, no bias (it is in `hb`)
+            conv = self._c8_first[ch] = ops.ConvC8Dil(self._views['conv1'][0][:, ch:], None, relu=True, dil=1,
+                                                      layout='oihw', device=self.device)
+        return conv
+
+    def c8_feed(self, session):
+        """The C8 buffer a fused refinement update may write the new y into for the NEXT `scores` call of this
+        session (ops.refine_update(..., y8=)), or None; `c8_fed(session)` afterwards."""
+        if not self.c8 or not isinstance(session, dict) or not session.get('c8'):
+            return None
+        return session['y8']
+
+    def c8_fed(self, session):
+        session['y8_fresh'] = True
+
+    def _scores_c8(self, y, session):
+        if not session.get('y8_fresh'):
+            ops.nchw_to_c8(y, out=session['y8'])
+        session['y8_fresh'] = False
+        # (ops.refine_update writes dense maps: y8 goes inside conv1's zero border with one strided device copy)
+        session['y8cat'][:, :, 1:-1, 1:-1].copy_(session['y8'])
+        session['first'](session['y8cat'], add=session['hb'], out=session['pad32_8'], place=(32, 32))
+        t = session['pad32_8']
+        for conv, out in zip(self._c8_dil, session['acts']):
+            t = conv(t, out=out)
+        return self._c8_last(t, out_format='nchw')
 
     def _first_layer(self, session):
         """conv1 of a session step into the PadLayer(32) buffer: the whole layer on [h, y], or its y half
@@ -154,6 +247,11 @@ class ContextModDAE:
     def scores(self, h_list, y, mask_override=None, session=None):
         if len(h_list) != 1:
             raise ValueError('expected 1 h tensor, got %d' % len(h_list))
+        if self.c8:
+            # (without a session: the same layers on the same per-geometry buffers)
+            if not isinstance(session, dict) or not session.get('c8'):
+                session = self.new_session(h_list, y)
+            return self._scores_c8(y, session)
         if session is None and self.keep_pre:
             # true-gradient mode outside a loop: the same 'valid' layers on the same per-geometry buffers as a
             # loop's session, so the kept maps -- and the gradient -- have the same bits with and without one
@@ -208,11 +306,13 @@ class ContextModDAE:
         """J^T g_score: the gradient w.r.t. the y channels of the input, for an upstream gradient on the score
         map of the latest `scores` call (made with `keep_pre` set).  Eight launches; the ReLU masks are applied
         while the gradient maps are read."""
+        self._refuse_c8('backward_y')
         return self._chain(g_score.contiguous(), 7, False, y_shape)
 
     def sqerr_backward(self, score, y):
         """`backward_y(ops.sqerr_softmax_bwd(score, y), y.shape)` with the softmax backward, dilconv7's adjoint
         and dilconv6's mask as ONE launch (ops.ctx_grad_head): the same bits, one launch fewer."""
+        self._refuse_c8('sqerr_backward')
         if self._pre is None:
             raise RuntimeError('sqerr_backward needs the layer outputs of the forward pass: set dae.keep_pre = '
                                'True before calling scores()')
@@ -224,6 +324,8 @@ class ContextModDAE:
         """The caller has just updated y outside `fused_step` (the first step of a loop, which also hands out
         the score map): refresh the y channels of the concat buffer, so that every later step -- eager or
         replayed from a captured graph -- starts with the buffer equal to y."""
+        if session.get('c8'):
+            return                       # (the 16-bit leg's y arrives through `c8_feed`, or is converted by `scores`)
         session['cat'][:, session['ch']:, 1:-1, 1:-1].copy_(y)
         session['y_in_cat'] = True
 
@@ -233,8 +335,8 @@ class ContextModDAE:
         ctx_tail_kernel): bit-identical y, three launches and the per-step copy of y fewer.  Returns the number
         of norm partials per image written (for ops.refine_finalize), or None when this geometry / dtype has no
         fused form (the caller then runs scores + refine_update)."""
-        if session is None or not ops.ctx_tail_supported(self.dil[-1], self.last, y):
-            return None
+        if self.c8 or session is None or not ops.ctx_tail_supported(self.dil[-1], self.last, y):
+            return None                  # (a fused bf16 tail is not built: the caller runs scores + refine_update)
         if not session.get('y_in_cat'):
             session['cat'][:, session['ch']:, 1:-1, 1:-1].copy_(y)
         self._first_layer(session)
@@ -272,7 +374,11 @@ class ContextModDAE:
         """The parameters (`self.flat`) have been changed in place: every layer object that holds them -- the
         padded and 'valid' forms of conv1 / dilconv1, the image / y halves of conv1 a session uses, the
         data-gradient layers -- packs its weights again into the buffers it already has, and every session's cached
-        image half (`hb`) is computed again from the image it holds.  No host wait."""
+        image half (`hb`) is computed again from the image it holds.  The 16-bit leg's layers pack their bf16
+        operand images again from `flat`.  No host wait."""
+        if self.c8:
+            for conv in self._c8_dil + [self._c8_last] + list(self._c8_first.values()):
+                conv.refresh()
         for conv in self._shared_convs():
             conv.refresh()
         W1 = self._views['conv1'][0]
@@ -309,6 +415,7 @@ class ContextModDAE:
         """The training-mode forward pass: GaussianNoiseLayer on y (contextmod_dae.py:50-57: y + noise * N(0, 1),
         `eps` = the caller's standard-normal sample, else drawn from `generator`), then the eight layers, whose
         outputs are kept for `backward`.  Returns the score map (B,C,H,W) before the softmax."""
+        self._refuse_c8('forward_train')
         B, ch, H, W = h.shape
         if tuple(y.shape[2:]) != (H, W) or y.shape[0] != B or ch + y.shape[1] != self.conv1.Cin:
             raise RuntimeError('forward_train: h %s, y %s' % (tuple(h.shape), tuple(y.shape)))
@@ -337,6 +444,7 @@ class ContextModDAE:
         """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
         g_score, after `forward_train`.  Per layer, last to first: the weight-gradient kernel (which applies
         the ReLU mask and stores g_z inside its zero border), then the data gradient as a 'valid' layer."""
+        self._refuse_c8('backward')
         s = self._saved
         if s is None:
             raise RuntimeError('backward() needs forward_train() first')
@@ -376,10 +484,11 @@ class ContextModDAE:
 def buildDAE_contextmod(input_concat_h_vars=None, input_mask_var=None, n_classes=11,
                         path_weights=None, model_name='dae_model.npz', trainable=False,
                         load_weights=False, out_nonlin='softmax', concat_h=('input',), noise=0.1,
-                        params=None, device='cuda', dtype=torch.float32):
-    """Mirror of models/contextmod_dae.py:19-23 (inference only: noise is the identity)."""
+                        params=None, device='cuda', dtype=torch.float32, mma=None):
+    """Mirror of models/contextmod_dae.py:19-23 (inference only: noise is the identity).  mma: see
+    ContextModDAE (None = ops.DEFAULT_MMA; 'bf16c8' = the 16-bit leg)."""
     if params is None:
         if not (load_weights and path_weights):
             raise ValueError('buildDAE_contextmod needs `params` or `path_weights`')
         params = load_param_list(os.path.join(path_weights, model_name), PARAM_ORDER)  # :127-132
-    return ContextModDAE(params, n_classes, concat_h=concat_h, device=device, dtype=dtype)
+    return ContextModDAE(params, n_classes, concat_h=concat_h, device=device, dtype=dtype, mma=mma)

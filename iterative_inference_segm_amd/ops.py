@@ -1395,6 +1395,120 @@ def c8_to_nchw(x8, channels, out=None, x3=False):
     return out
 
 
+class ConvC8Dil:
+    """One 'valid' K x K layer (K = 1 or 3, dilation 1, 2, 4, 8 or 16, at most 16 channels on either side) on
+    bf16 C8 activations: the context module's 16-bit leg (csrc/conv_c8_dil.hip).  `W` is
+    the layer's float32 parameter on the device in layout 'oihw' (W[out,in,k,k]) or 'iohw' (W[in,out,k,k]); it may
+    be a VIEW of a larger buffer, and a slice of it along the input channels (conv1's y half): it is read
+    through its strides and never copied.  The bf16 operand images are packed once, here; `refresh()` packs
+    them again, into the same buffer, after `W` has been changed in place."""
+    kernel = 'conv_c8_dil_kernel'
+
+    def __init__(self, W, b, relu, dil=1, layout='oihw', device='cuda'):
+        self.lib = _lib.load()
+        if layout not in ('oihw', 'iohw'):
+            raise ValueError(layout)
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.dim() != 4 or W.shape[2] != W.shape[3] \
+                or (b is not None and (not isinstance(b, torch.Tensor) or b.dtype != torch.float32)):
+            raise RuntimeError('ConvC8Dil needs float32 tensors W (4-d, square filter) and b')
+        if not bool(torch.isfinite(W).all()) or (b is not None and not bool(torch.isfinite(b).all())):
+            raise ValueError('non-finite convolution parameters (NaN / Inf in W or b)')
+        self.W = W.to(device)
+        self.b = None if b is None else b.to(device).contiguous()
+        self.layout, self.relu, self.dil = layout, bool(relu), int(dil)
+        self.K = int(W.shape[2])
+        st = self.W.stride()
+        if st[3] != 1 or st[2] != self.K:
+            raise RuntimeError('ConvC8Dil: the filter taps of W must be contiguous (strides %s)' % (st,))
+        if layout == 'oihw':
+            (self.Cout, self.Cin), (self.so, self.sc) = W.shape[:2], st[:2]
+        else:
+            (self.Cin, self.Cout), (self.sc, self.so) = W.shape[:2], st[:2]
+        # (the smallest legal map: what the packer's argument check needs of a geometry)
+        self._pack_desc = self._desc(1, self.dil * (self.K - 1) + 1, self.dil * (self.K - 1) + 1, None, False)
+        nbytes = self.lib.iiseg_conv_c8_dil_pack_bytes(self.K)
+        if nbytes < 0:
+            check(int(nbytes), 'iiseg_conv_c8_dil_pack_bytes')
+        self.wpack = torch.empty(int(nbytes) // 2, dtype=torch.bfloat16, device=device)
+        self._descs = {}
+        self.refresh()
+
+    def _desc(self, B, H, W, place, nchw):
+        d = _lib.C8DilDesc()
+        d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.dil = int(B), self.Cin, self.Cout, int(H), int(W), self.K, self.dil
+        if place is not None:
+            d.out_H, d.out_W, d.out_y0, d.out_x0 = (int(v) for v in place)
+        d.flags = (CONV_RELU if self.relu else 0) | (_lib.C8DIL_OUT_NCHW if nchw else 0)
+        check(self.lib.iiseg_conv_c8_dil_check(C.byref(d)), 'iiseg_conv_c8_dil_check')
+        return d
+
+    def refresh(self):
+        """Packs the bf16 operand images again from `self.W`, into the buffer it already has (launches that
+        hold its address -- a captured graph -- see the new weights).  No host wait."""
+        check(self.lib.iiseg_conv_c8_dil_pack(_stream(), C.byref(self._pack_desc), _ptr_strided(self.W),
+                                              self.so, self.sc, C.c_void_p(self.wpack.data_ptr())),
+              'iiseg_conv_c8_dil_pack')
+
+    def out_hw(self, H, W):
+        return H - self.dil * (self.K - 1), W - self.dil * (self.K - 1)
+
+    def flops(self, B, OH, OW):
+        """Nominal 2*Cin*Cout*k*k*OH*OW*B (SURVEY 6.2 convention)."""
+        return 2.0 * self.Cin * self.Cout * self.K * self.K * OH * OW * B
+
+    def __call__(self, x8, add=None, out=None, place=None, out_format='c8'):
+        """x8: bf16 C8 (B, 2, H, W, 8), channels >= Cin zeros.  add: fp32 (B, Cout, OH, OW), added behind the
+        bias.  out_format 'c8': a bf16 C8 tensor of two chunks -- `out` with `place=(y0, x0)`: the map goes to
+        that offset of the larger `out`, whose other elements are not touched -- or 'nchw': fp32
+        (B, Cout, OH, OW)."""
+        if out_format not in ('c8', 'nchw'):
+            raise ValueError("out_format must be 'c8' or 'nchw'")
+        nchw = out_format == 'nchw'
+        if not is_c8(x8) or x8.shape[1] != 2 or not x8.is_contiguous():
+            raise RuntimeError('ConvC8Dil needs a contiguous bf16 C8 tensor of two chunks, got %s'
+                               % (tuple(x8.shape),))
+        B, _, H, W, _ = x8.shape
+        OH, OW = self.out_hw(H, W)
+        if place is not None and (out is None or nchw):
+            raise RuntimeError('ConvC8Dil: `place` needs a C8 `out`')
+        geom = None if place is None else (out.shape[2], out.shape[3], place[0], place[1])
+        key = (B, H, W, geom, nchw)
+        d = self._descs.get(key)
+        if d is None:
+            d = self._descs[key] = self._desc(B, H, W, geom, nchw)
+        if nchw:
+            if out is None:
+                out = torch.empty((B, self.Cout, OH, OW), dtype=torch.float32, device=x8.device)
+            if tuple(out.shape) != (B, self.Cout, OH, OW):
+                raise RuntimeError('ConvC8Dil: out %s' % (tuple(out.shape),))
+            optr = _ptr(out)
+        else:
+            if out is None:
+                out = empty_c8(B, 16, OH, OW, x8.device)
+            want = (B, 2, OH, OW, 8) if place is None else (B, 2, out.shape[2], out.shape[3], 8)
+            if not is_c8(out) or tuple(out.shape) != want or not out.is_contiguous():
+                raise RuntimeError('ConvC8Dil: out %s' % (tuple(out.shape),))
+            optr = _c8ptr(out)
+        if add is not None and tuple(add.shape) != (B, self.Cout, OH, OW):
+            raise RuntimeError('ConvC8Dil: add %s for an output (%d, %d, %d, %d)'
+                               % (tuple(add.shape), B, self.Cout, OH, OW))
+        if CONV_PROFILE is not None:
+            KERNEL_BYTES[self.kernel] = KERNEL_BYTES.get(self.kernel, 0) + \
+                B * (32 * H * W + (4 * self.Cout if nchw else 32) * OH * OW)
+        _launch(self.kernel, self.flops(B, OH, OW), self.lib.iiseg_conv_c8_dil, C.byref(d), _c8ptr(x8),
+                C.c_void_p(self.wpack.data_ptr()), _ptr(self.b), _ptr(add), optr)
+        return out
+
+
+def _ptr_strided(t):
+    """Device address of a float32 tensor that is read through explicit strides (a view of a parameter)."""
+    if not t.is_cuda:
+        raise RuntimeError('iiseg ops need device tensors (got %s)' % t.device)
+    if t.dtype != torch.float32:
+        raise RuntimeError('expected %s, got %s' % (torch.float32, t.dtype))
+    return C.c_void_p(t.data_ptr())
+
+
 def unpool_c8(up, mask, out, window=None):
     """DePool2D materialised on C8 tensors (include/iiseg.h iiseg_unpool_c8): `out` (B, C8, H, W, 8) <- up
     (B, C8, H/2, W/2, 8) under the mask bytes, for the pooled-coordinate `window` (y0, x0, h, w) (default: all);
