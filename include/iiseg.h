@@ -964,6 +964,50 @@ int iiseg_conv_c8_dil_pack(void* stream, const iiseg_c8dil_desc* d, const float*
 int iiseg_conv_c8_dil(void* stream, const iiseg_c8dil_desc* d, const void* x8, const void* wpack,
                       const float* bias, const float* addend, void* out);
 
+/* ---------------------------------------------------------------------------------------
+ * Training the standard pool / unpool DAE (backward-compatible addition).
+ *
+ * Weight and bias gradient of a zero-padded 3x3 stride-1 layer out = conv(xpad, W) + b, any channel counts up
+ * to 65535 (csrc/conv_wgrad.hip; float on v_mfma_f32_32x32x2_f32, double on the vector ALU):
+ *   dW[co][ci0 + ci][ky][kx] = sum_{b,y,x} gz[b,co,y,x] xpad[b,ci,y + ky,x + kx],   db[co] = sum_{b,y,x} gz[b,co,y,x]
+ *   x  : (B, Cin, H, W), contiguous; the zero padding `pad` >= 0 on every side is implicit.
+ *   gz : (B, Cout, OH, OW) = dL/dout with the ReLU mask already applied, OH = H + 2 pad - 2.
+ *   dW : the layer's parameter array with Cin_tot >= ci0 + Cin input channels; element (co, ci0 + ci, tap) at
+ *        co * so + (ci0 + ci) * sc + tap, (so, sc) = (Cin_tot 9, 9) for W[out,in,3,3] or (9, Cout 9) for
+ *        W[in,out,3,3].  Only those Cout * Cin * 9 elements are written: the two sources of a concat layer are
+ *        two calls with their channel offsets.
+ *   db : Cout elements, or NULL (the second call of a concat layer).
+ *   ws : iiseg_conv_wgrad_workspace_elems(d, sizeof element) elements of scratch (0: may be NULL).
+ * The pixel range is split into iiseg_conv_wgrad_slabs(d, ...) slabs, one workgroup per slab and 64 x 64 (double:
+ * 32 x 32) channel block; with more than one slab a second launch adds the slabs in slab order.  No atomics:
+ * the same inputs give the same bits.  Output pixels whose 3x3 patch lies wholly inside the zero padding (wide
+ * pads) contribute to db only and are not multiplied.
+ *
+ * Grid form of iiseg_opt_step_*: the same arithmetic per element (the same bits), many workgroups; adam's state
+ * is read by every workgroup and advanced by a one-thread launch AFTER the grid launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct iiseg_conv_wgrad_desc {
+    int32_t B, Cin, Cout, H, W, K, pad;   /* K must be 3 */
+    int32_t ci0, Cin_tot;
+    int32_t reserved[3];
+    int64_t so, sc;
+} iiseg_conv_wgrad_desc;
+
+/* host only: IISEG_OK or the status a launch of `d` would return */
+int iiseg_conv_wgrad_check(const iiseg_conv_wgrad_desc* d);
+/* host only: number of pixel slabs (>= 1) for elements of elem_bytes (4 or 8), or a negative status */
+int iiseg_conv_wgrad_slabs(const iiseg_conv_wgrad_desc* d, int32_t elem_bytes);
+/* host only: elements of `ws` (0 with one slab, else slabs * (Cout Cin 9 + Cout)), or a negative status */
+int64_t iiseg_conv_wgrad_workspace_elems(const iiseg_conv_wgrad_desc* d, int32_t elem_bytes);
+int iiseg_conv_wgrad_f32(void* stream, const iiseg_conv_wgrad_desc* d, const float* x, const float* gz, float* ws,
+                         float* dW, float* db);
+int iiseg_conv_wgrad_f64(void* stream, const iiseg_conv_wgrad_desc* d, const double* x, const double* gz, double* ws,
+                         double* dW, double* db);
+int iiseg_opt_step_grid_f32(void* stream, int32_t kind, float* p, const float* g, float* s1, float* s2,
+                            const float* lr, float* state, int64_t n);
+int iiseg_opt_step_grid_f64(void* stream, int32_t kind, double* p, const double* g, double* s1, double* s2,
+                            const double* lr, double* state, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,12 @@ class DgradDesc(C.Structure):
                                          'gx_c0', 'gx_y0', 'gx_x0', 'reserved')] + [('so', C.c_int64), ('sc', C.c_int64)]
 
 
+class ConvWgradDesc(C.Structure):
+    """struct iiseg_conv_wgrad_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'pad', 'ci0', 'Cin_tot')] + \
+               [('reserved', C.c_int32 * 3), ('so', C.c_int64), ('sc', C.c_int64)]
+
+
 C8DIL_OUT_NCHW = 0x100
 
 
@@ -249,6 +255,14 @@ SIGNATURES = {
     'iiseg_conv_c8_dil_pack_host': (C.c_int, [C.POINTER(C8DilDesc), _vp, _i64, _i64, _vp]),
     'iiseg_conv_c8_dil_pack': (C.c_int, [_vp, C.POINTER(C8DilDesc), _vp, _i64, _i64, _vp]),
     'iiseg_conv_c8_dil': (C.c_int, [_vp, C.POINTER(C8DilDesc)] + [_vp] * 5),
+    # training the standard DAE
+    'iiseg_conv_wgrad_check': (C.c_int, [C.POINTER(ConvWgradDesc)]),
+    'iiseg_conv_wgrad_slabs': (C.c_int, [C.POINTER(ConvWgradDesc), _i32]),
+    'iiseg_conv_wgrad_workspace_elems': (_i64, [C.POINTER(ConvWgradDesc), _i32]),
+    'iiseg_conv_wgrad_f32': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
+    'iiseg_conv_wgrad_f64': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
+    'iiseg_opt_step_grid_f32': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
+    'iiseg_opt_step_grid_f64': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
 }
 
 _lib = None

@@ -325,6 +325,55 @@ __global__ __launch_bounds__(1024) void opt_step_kernel(int kind, T* __restrict_
     }
 }
 
+// ---- grid form of the optimizer step (the standard DAE: tens of millions of scalars).  The per-element
+//      arithmetic of opt_step_kernel, so the same bits; every workgroup reads adam's state as the previous step
+//      left it and forms the advanced values locally; opt_state_advance_kernel stores them afterwards. ----
+constexpr int OPT_GRID_BLOCK = 256;
+
+template <typename T>
+__global__ __launch_bounds__(OPT_GRID_BLOCK) void opt_step_grid_kernel(int kind, T* __restrict__ p, const T* __restrict__ g,
+                                                                       T* __restrict__ s1, T* __restrict__ s2,
+                                                                       const T* __restrict__ lr_p,
+                                                                       const T* __restrict__ state, long long n) {
+#pragma clang fp contract(off)
+    const T lr = lr_p[0];
+    const T one = (T)1;
+    const long long stride = (long long)gridDim.x * OPT_GRID_BLOCK;
+    const long long i0 = (long long)blockIdx.x * OPT_GRID_BLOCK + threadIdx.x;
+    if (kind == IISEG_OPT_RMSPROP) {
+        const T rho = (T)0.9, eps = (T)1e-6;
+        const T omr = one - rho;
+        for (long long i = i0; i < n; i += stride) {
+            const T gi = g[i];
+            const T a = rho * s1[i] + omr * (gi * gi);
+            s1[i] = a;
+            p[i] = p[i] - (lr * gi) / sqrt_t(a + eps);
+        }
+        return;
+    }
+    const T b1 = (T)0.9, b2 = (T)0.999, eps = (T)1e-8;
+    const T p1 = state[1] * b1, p2 = state[2] * b2;
+    const T alpha = (lr * sqrt_t(one - p2)) / (one - p1);
+    const T omb1 = one - b1, omb2 = one - b2;
+    for (long long i = i0; i < n; i += stride) {
+        const T gi = g[i];
+        const T m = b1 * s1[i] + omb1 * gi;
+        const T v = b2 * s2[i] + omb2 * (gi * gi);
+        s1[i] = m;
+        s2[i] = v;
+        p[i] = p[i] - (alpha * m) / (sqrt_t(v) + eps);
+    }
+}
+
+template <typename T>
+__global__ void opt_state_advance_kernel(T* __restrict__ state) {
+#pragma clang fp contract(off)
+    const T t1 = state[0] + (T)1, p1 = state[1] * (T)0.9, p2 = state[2] * (T)0.999;
+    state[0] = t1;
+    state[1] = p1;
+    state[2] = p2;
+}
+
 // ---- host side ----
 int loss_check(int B, int C, int H, int W) {
     if (B < 1 || B > 65535 || C < 2 || C > 16 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return IISEG_ERR_SHAPE;
@@ -427,6 +476,21 @@ int opt_step(void* stream, int kind, T* p, const T* g, T* s1, T* s2, const T* lr
     return iiseg_check_launch();
 }
 
+template <typename T>
+int opt_step_grid(void* stream, int kind, T* p, const T* g, T* s1, T* s2, const T* lr, T* state, int64_t n) {
+    if (kind != IISEG_OPT_RMSPROP && kind != IISEG_OPT_ADAM) return IISEG_ERR_SHAPE;
+    if (!p || !g || !s1 || !lr) return IISEG_ERR_NULL;
+    if (kind == IISEG_OPT_ADAM && (!s2 || !state)) return IISEG_ERR_NULL;
+    if (n < 1 || n > (int64_t)1 << 30) return IISEG_ERR_SHAPE;
+    int64_t blocks = (n + OPT_GRID_BLOCK - 1) / OPT_GRID_BLOCK;
+    if (blocks > 2048) blocks = 2048;                       // 8 workgroups per CU, grid-stride beyond
+    hipStream_t s = (hipStream_t)stream;
+    IISEG_LAUNCH(opt_step_grid_kernel<T>, dim3((unsigned)blocks), dim3(OPT_GRID_BLOCK), 0, s, kind, p, g, s1, s2, lr,
+                 (const T*)state, (long long)n);
+    if (kind == IISEG_OPT_ADAM) IISEG_LAUNCH(opt_state_advance_kernel<T>, dim3(1), dim3(1), 0, s, state);
+    return iiseg_check_launch();
+}
+
 }  // namespace
 
 extern "C" int iiseg_ctx_loss_partials(int32_t B, int32_t H, int32_t W) {
@@ -471,4 +535,12 @@ extern "C" int iiseg_opt_step_f32(void* stream, int32_t kind, float* p, const fl
 extern "C" int iiseg_opt_step_f64(void* stream, int32_t kind, double* p, const double* g, double* s1, double* s2,
                                   const double* lr, double* state, int64_t n) {
     return opt_step<double>(stream, kind, p, g, s1, s2, lr, state, n);
+}
+extern "C" int iiseg_opt_step_grid_f32(void* stream, int32_t kind, float* p, const float* g, float* s1, float* s2,
+                                       const float* lr, float* state, int64_t n) {
+    return opt_step_grid<float>(stream, kind, p, g, s1, s2, lr, state, n);
+}
+extern "C" int iiseg_opt_step_grid_f64(void* stream, int32_t kind, double* p, const double* g, double* s1, double* s2,
+                                       const double* lr, double* state, int64_t n) {
+    return opt_step_grid<double>(stream, kind, p, g, s1, s2, lr, state, n);
 }

@@ -58,11 +58,35 @@ class StandardDAE:
     def __init__(self, params, n_classes, concat_h=('pool4',), padding=100, n_filters=64,
                  conv_before_pool=1, additional_pool=2, skip=True, unpool_type='trackind', bn=0,
                  device='cuda', dtype=torch.float32, pad_multi_concat=False, noise=0.0,
-                 dropout=0.0, emulate_noise=False, seed=0, mma=None):
+                 dropout=0.0, emulate_noise=False, seed=0, mma=None, trainable=False):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
-        'bf16' = 16-bit MFMA operands with fp32 accumulation; ops.Conv)."""
+        'bf16' = 16-bit MFMA operands with fp32 accumulation; ops.Conv).
+        trainable=True: the parameters live in ONE flat buffer in `param_order` (W then b per layer), every
+        layer holds views of it and runs on the direct / halo kernels only, so that `refresh()` can pack
+        them again in place after an optimizer step."""
         concat_h = list(concat_h)
         mma = mma or ops.DEFAULT_MMA
+        self.trainable = bool(trainable)
+        self.flat, self._views, self._gflat, self._gviews, self._tsaved = None, None, None, None, None
+        if trainable:
+            if conv_before_pool != 1 or bn or dropout > 0 or unpool_type not in ('trackind', 'inverse'):
+                raise NotImplementedError('training the standard DAE: conv_before_pool=1, bn=0, dropout=0, '
+                                          'unpool_type in {trackind, inverse}')
+            if dtype not in (torch.float32, torch.float64) or (dtype == torch.float32 and mma != 'f32'):
+                raise NotImplementedError("training the standard DAE: float32 (mma='f32') or float64; the "
+                                          '16-bit legs are not trained')
+            order = param_order(concat_h, conv_before_pool, additional_pool, unpool_type, bn)
+            host = [(n, torch.as_tensor(params[n][0]), torch.as_tensor(params[n][1])) for n in order]
+            self.flat = torch.empty(sum(W.numel() + b.numel() for _, W, b in host), dtype=dtype, device=device)
+            self._views, off = {}, 0
+            for n, W, b in host:
+                Wv = self.flat[off:off + W.numel()].view(W.shape)
+                bv = self.flat[off + W.numel():off + W.numel() + b.numel()]
+                Wv.copy_(W.to(dtype))
+                bv.copy_(b.to(dtype))
+                self._views[n] = (Wv, bv)
+                off += W.numel() + b.numel()
+            params = self._views
         self.mma = mma
         # bf16 C8 activations between the layers (ops.Conv mma='bf16c8', `_scores_c8`)
         # ('bf16x3': the same plan on hi / lo pairs, the fp32-class mode of that kernel)
@@ -119,7 +143,8 @@ class StandardDAE:
         # epilogue.  Same association with or without a session, float32 only (float64 keeps the
         # single-sum form of the oracle).
         self.hsplit = {}
-        if dtype == torch.float32 and os.environ.get('IISEG_H_SPLIT', '1') != '0':
+        # (a trainable DAE keeps the two-source form: one parameter view per layer)
+        if dtype == torch.float32 and os.environ.get('IISEG_H_SPLIT', '1') != '0' and not trainable:
             prev = n_classes
             for p in range(self.total):
                 name = 'conv%d_1' % (p + 1)
@@ -172,6 +197,11 @@ class StandardDAE:
         # pool + one mask byte per pooled element, the decoder reads up + that byte (`_mask_levels`)
         self.use_masks = os.environ.get('IISEG_DEPOOL_MASKS', '1') != '0'
         self.keep_pre = False   # True: the pre-pool maps are needed afterwards (backward_y)
+        if trainable:
+            lo, hi = self.flat.data_ptr(), self.flat.data_ptr() + self.flat.numel() * self.flat.element_size()
+            for conv in self.conv_layers().values():
+                assert lo <= conv.W.data_ptr() < hi and lo <= conv.b.data_ptr() < hi      # views, not copies
+                conv.wino = conv.wino_f64 = False     # no weight transform to keep in step (Conv.refresh)
 
     def _mask_levels(self, overridden):
         """Levels (1-based) whose DePool2D mask travels as bytes in this call."""
@@ -640,6 +670,9 @@ class StandardDAE:
                 W = self.dec[name].W
                 bwd[name] = ops.Conv(W.transpose(0, 1).flip(2, 3).contiguous(), None, pad=1,
                                      relu=False, device=W.device, dtype=self.dtype)
+            if self.trainable:
+                for conv in bwd.values():
+                    conv.wino = conv.wino_f64 = False
             self._bwd = bwd
         return self._bwd
 
@@ -692,6 +725,137 @@ class StandardDAE:
                 else:
                     g_in = conv(g_z)
         return g_in
+
+    # ---- training (reference train_dae.py with dae kind 'standard') ----------
+    def parameters(self):
+        """{name: (W, b)} in `param_order`: views of `self.flat`.  After changing them in place call
+        `refresh()`."""
+        return dict(self._views)
+
+    def state_arrays(self):
+        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
+        return {n: (W.detach().cpu().float().numpy(), b.detach().cpu().float().numpy())
+                for n, (W, b) in self._views.items()}
+
+    def _need_trainable(self, what):
+        if not self.trainable:
+            raise RuntimeError('%s needs a StandardDAE built with trainable=True' % what)
+
+    def forward_train(self, h_list, y, noise=0.0, generator=None, eps=None):
+        """The training-mode forward: GaussianNoiseLayer on y (y + noise * N(0, 1) formed ONCE, `eps` = the
+        caller's standard-normal sample, else drawn from `generator`), then `scores` on full maps with the
+        pre-pool maps kept; the DePool2D masks are those of this same noisy forward (one sample per step:
+        DESIGN.md section 4).  Returns the score map before the softmax."""
+        self._need_trainable('forward_train')
+        h_list = list(h_list)
+        if noise > 0:
+            if eps is None:
+                eps = torch.randn(y.shape, generator=generator, device=y.device, dtype=y.dtype)
+            y = ops.add_noise(y, eps, float(noise))
+        keep, dce, trace = self.keep_pre, self.dce, self.trace
+        # full decoder maps: the weight gradient reads every layer input whole
+        self.keep_pre, self.dce, self.trace = True, False, {}
+        try:
+            score = self.scores(h_list, y)
+            fused = self.trace
+        finally:
+            self.keep_pre, self.dce, self.trace = keep, dce, trace
+        self._tsaved = (h_list, tuple(y.shape), fused)
+        return score
+
+    def saved_maps(self):
+        """What the last `forward_train` kept, under the names of oracle/dae.py's net: 'input' (the noisy y),
+        'pre%d', 'pool%d', 'fused_up%d'; for tests."""
+        _, pre, pool = self._saved
+        out = {'input': pool[0]}
+        out.update({'pre%d' % k: v for k, v in pre.items()})
+        out.update({'pool%d' % k: v for k, v in pool.items() if k > 0})
+        out.update({k: v for k, v in self._tsaved[2].items() if k.startswith('fused_up')})
+        return out
+
+    def _grad_views(self):
+        if self._gflat is None:
+            self._gflat = torch.zeros_like(self.flat)
+            self._gviews, off = {}, 0
+            for n, (W, b) in self._views.items():
+                self._gviews[n] = (self._gflat[off:off + W.numel()].view(W.shape),
+                                   self._gflat[off + W.numel():off + W.numel() + b.numel()])
+                off += W.numel() + b.numel()
+        return self._gviews
+
+    def backward(self, g_score):
+        """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
+        g_score, after `forward_train`: the chain of `backward_y` with ops.conv_wgrad at every layer, fed the
+        g_z the chain forms and the layer's saved input.  DePool2D's output is materialised here for the
+        up_conv layers (ops.unpool_eqmask); a concat layer is two calls into one dW (h first).  The data
+        gradient of the first layer is not formed."""
+        self._need_trainable('backward')
+        if self._tsaved is None or self._saved is None:
+            raise RuntimeError('backward() needs forward_train() first')
+        h_list, y_shape, fused = self._tsaved
+        gv, bwd = self._grad_views(), self._bwd_convs()
+        _, pre, pool = self._saved
+        feeds = regions.concat_feeds(self.concat_h, self.total, self.n_pool)
+        B, dev, dt = g_score.shape[0], g_score.device, g_score.dtype
+        g_pool = {}
+        g_f = g_score
+        for p in range(1, self.total + 1):               # decoder, output to input
+            ph, pw = pre[p].shape[2], pre[p].shape[3]
+            other_hw = (pool[p - 1].shape[2], pool[p - 1].shape[3]) if p > 1 else (y_shape[2], y_shape[3])
+            oh, ow = min(ph, other_hw[0]), min(pw, other_hw[1])
+            cy, cx = center(ph, oh), center(pw, ow)
+            g_c = torch.zeros((B, g_f.shape[1], ph, pw), dtype=dt, device=dev)
+            g_c[:, :, cy:cy + oh, cx:cx + ow].copy_(g_f)           # adjoint of the center crop
+            if self.skip and p > 1:                                 # adjoint of the skip sum
+                gp = torch.zeros_like(pool[p - 1])
+                oy, ox = center(other_hw[0], oh), center(other_hw[1], ow)
+                gp[:, :, oy:oy + oh, ox:ox + ow].copy_(g_f)
+                g_pool[p - 1] = gp
+            t_in = pool[self.total] if p == self.total else fused['fused_up%d' % (p + 1)]
+            u = ops.unpool_eqmask(t_in, pre[p], pool[p])
+            ops.conv_wgrad(u, g_c, *gv['up_conv%d' % p], pad=1)
+            g_u = bwd['up_conv%d' % p](g_c)
+            g_f = ops.depool_bwd(g_u, pre[p], pool[p])
+        g_pool[self.total] = g_f
+        for p in range(self.total, 0, -1):               # encoder, deep to shallow
+            gp = g_pool.get(p)
+            if gp is None:
+                gp = torch.zeros_like(pool[p])
+            g_z = ops.pool_relu_bwd(gp, pre[p], pool[p])
+            name = 'conv%d_1' % p
+            dW, db = gv[name]
+            pad, ch = self.enc[name].pad, 0
+            if (p - 1) in feeds:                         # h first (P13), then the features
+                h = h_list[feeds[p - 1]]
+                ch = h.shape[1]
+                ops.conv_wgrad(h, g_z, dW, None, pad=pad, ci0=0)
+            ops.conv_wgrad(pool[p - 1], g_z, dW, db, pad=pad, ci0=ch)
+            if p > 1:
+                acc = g_pool.get(p - 1)
+                g_pool[p - 1] = bwd[name](g_z) if acc is None else bwd[name](g_z, add=acc, out=acc)
+        return dict(gv)
+
+    def refresh(self):
+        """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into
+        the buffers it already has, the data-gradient layers take the flipped filters again, and sessions
+        that cached maps of the old weights are dropped.  No host wait."""
+        self._need_trainable('refresh')
+        for conv in self.conv_layers().values():
+            conv.refresh()
+        if self._bwd is not None:
+            prev = self.n_classes
+            for p in range(self.total):
+                name = 'conv%d_1' % (p + 1)
+                W = self.enc[name].W
+                self._bwd[name].W.copy_(W[:, W.shape[1] - prev:].transpose(0, 1).flip(2, 3))
+                prev = W.shape[0]
+            for p in range(self.total, 0, -1):
+                name = 'up_conv%d' % p
+                self._bwd[name].W.copy_(self.dec[name].W.transpose(0, 1).flip(2, 3))
+            for conv in self._bwd.values():
+                conv.refresh()
+        self._store = None
+        self._scratch_sessions.clear()
 
     def _rand(self, kind, level, name, shape, like):
         if self.random_source is not None:

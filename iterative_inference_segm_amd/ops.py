@@ -2002,14 +2002,62 @@ def conv_small_wgrad(x, gout, out, dW, db, dil=1, layout='oihw', gz=None, gz_off
             float(dW.element_size()) * (x.shape[1] + 2 * Cout) * x.shape[0] * x.shape[2] * x.shape[3]
 
 
-def opt_step(kind, p, g, s1, s2, lr, state):
+def opt_step(kind, p, g, s1, s2, lr, state, grid=False):
     """One optimizer step on the flat buffers p, g, s1 (, s2) in place; lr: one element on the device;
-    state (adam): [t, 0.9^t, 0.999^t], start [0, 1, 1]."""
+    state (adam): [t, 0.9^t, 0.999^t], start [0, 1, 1].  grid=True: the many-workgroup form (the same bits;
+    adam's state advanced by a one-thread launch after it) for buffers of millions of scalars."""
     dt = p.dtype
     if not (p.numel() == g.numel() == s1.numel()) or (s2 is not None and s2.numel() != p.numel()):
         raise RuntimeError('opt_step: buffers of different sizes')
-    _launch('opt_step_kernel', 0.0, _fn('opt_step', dt), OPTIMIZERS[kind], _ptr(p, dt), _ptr(g, dt), _ptr(s1, dt),
+    kern, fn = ('opt_step_grid_kernel', 'opt_step_grid') if grid else ('opt_step_kernel', 'opt_step')
+    _launch(kern, 0.0, _fn(fn, dt), OPTIMIZERS[kind], _ptr(p, dt), _ptr(g, dt), _ptr(s1, dt),
             _ptr(s2, dt), _ptr(lr, dt), _ptr(state, dt), p.numel())
+
+
+# ---- training the standard DAE (csrc/conv_wgrad.hip, DESIGN.md section 12) ----
+def conv_wgrad_desc(x_shape, Cout, pad, Cin_tot=None, ci0=0, layout='oihw'):
+    """The iiseg_conv_wgrad_desc of a zero-padded 3x3 layer on x (B,Cin,H,W) whose parameter array has Cin_tot
+    input channels, this source's at [ci0, ci0 + Cin)."""
+    B, Cin, H, W = (int(v) for v in x_shape)
+    Cin_tot = Cin if Cin_tot is None else int(Cin_tot)
+    d = _lib.ConvWgradDesc()
+    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin, int(Cout), H, W, 3, int(pad)
+    d.ci0, d.Cin_tot = int(ci0), Cin_tot
+    if layout == 'oihw':
+        d.so, d.sc = Cin_tot * 9, 9
+    elif layout == 'iohw':
+        d.so, d.sc = 9, int(Cout) * 9
+    else:
+        raise ValueError(layout)
+    return d
+
+
+def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw'):
+    """dW[:, ci0:ci0 + Cin] (and db, unless None) of the zero-padded 3x3 layer out = conv(xpad, W) + b, written
+    in place into the layer's own parameter layout, from its input x (B,Cin,H,W) and gz = dL/dout (ReLU mask
+    applied) (B,Cout,H + 2 pad - 2,W + 2 pad - 2).  The other input channels of dW are not touched (the second
+    source of a concat layer is a second call).  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU."""
+    dt = x.dtype
+    if dW.dim() != 4 or tuple(dW.shape[2:]) != (3, 3):
+        raise RuntimeError('conv_wgrad: dW %s is not a 3x3 parameter' % (tuple(dW.shape),))
+    Cout, Cin_tot = (dW.shape[0], dW.shape[1]) if layout == 'oihw' else (dW.shape[1], dW.shape[0])
+    B, Cin, H, W = x.shape
+    OH, OW = H + 2 * pad - 2, W + 2 * pad - 2
+    if tuple(gz.shape) != (B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
+        raise RuntimeError('conv_wgrad: shapes x %s gz %s dW %s' % (tuple(x.shape), tuple(gz.shape), tuple(dW.shape)))
+    d = conv_wgrad_desc(tuple(x.shape), Cout, pad, Cin_tot, ci0, layout)
+    lib = _lib.load()
+    n = lib.iiseg_conv_wgrad_workspace_elems(C.byref(d), dW.element_size())
+    if n < 0:
+        check(int(n), 'iiseg_conv_wgrad_workspace_elems')
+    ws = _workspace(_SUFFIX[dt], n, x.device) if n else None
+    kern = 'conv_wgrad_kernel'
+    _launch(kern, 2.0 * Cin * Cout * 9 * B * OH * OW, _fn('conv_wgrad', dt), C.byref(d), _ptr(x, dt), _ptr(gz, dt),
+            _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))
+    if CONV_PROFILE is not None:
+        # byte model: x and g_z read once, the slabs written and read once
+        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
+            float(dW.element_size()) * (x.numel() + gz.numel() + 2 * n)
 
 
 # ---- true-gradient refinement through the context-module DAE (csrc/ctx_grad.hip, DESIGN.md section 10) ----

@@ -1,29 +1,49 @@
-"""Training the context-module DAE on MI355X: the two compiled functions of the reference's
+"""Training the DAE on MI355X: the two compiled functions of the reference's
 train_dae.py:334-338,
 
     train_fn(H..., Y_in, T) -> loss          (+ the optimizer's updates)
     val_fn(H..., Y_in, T)   -> [loss, jacc(2, C), mse]
 
-for dae kind 'contextmod' (DESIGN.md section 9).  Forward and data gradient run on the inference layers
-(ops.Conv), the loss, the weight gradients and the optimizer step on csrc/ctx_train.hip.  Everything is
-enqueued on the current stream; nothing here waits for the device.
+for dae kind 'contextmod'  and kind 'standard' with h at a pool point (section 12).
+Forward and data gradient run on the inference layers (ops.Conv), the loss and the optimizer step on
+csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_wgrad.hip (standard DAE).
+Everything is enqueued on the current stream; nothing here waits for the device.
 """
 import torch
 
 from . import ops
 from .api import Metrics
 from .contextmod import ContextModDAE
+from .dae import StandardDAE
 
 SUPPORTED_LOSSES = ('crossentropy', 'squared_error')
 
 
 def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
-                    optimizer='rmsprop'):
+                    optimizer='rmsprop', dae_dict=None):
     """Raises NotImplementedError / ValueError with the reason for everything this slice does not train
-    (host only: callable before any GPU work)."""
-    if kind != 'contextmod':
-        raise NotImplementedError("training is built for dae kind 'contextmod' only (got %r): the standard "
-                                  'and fcn8 kinds need weight gradients at 64-2048 channels' % (kind,))
+    (host only: callable before any GPU work).  dae_dict: the standard kind's options (concat_h, bn, dropout,
+    conv_before_pool, unpool_type)."""
+    if kind not in ('contextmod', 'standard'):
+        raise NotImplementedError("training is built for dae kinds 'contextmod' and 'standard' (got %r): the "
+                                  'fcn8 kind (strided 4x4 transposed convolutions) has no weight-gradient '
+                                  'kernel' % (kind,))
+    if kind == 'standard':
+        dd = dae_dict or {}
+        concat_h = list(dd.get('concat_h', ['input']))
+        if not concat_h or 'pool' not in concat_h[-1]:
+            raise NotImplementedError("dae kind 'standard' trains with h at a pool point (concat_h ending in "
+                                      "'pool*', e.g. ['pool4']); 'contextmod' is the kind that trains with "
+                                      "concat_h=['input'] (got concat_h=%r)" % (concat_h,))
+        if dd.get('bn', 0):
+            raise NotImplementedError("training dae kind 'standard': bn=1 (batch statistics) is not built")
+        if float(dd.get('dropout', 0) or 0) > 0:
+            raise NotImplementedError("training dae kind 'standard': dropout > 0 is not built")
+        if int(dd.get('conv_before_pool', 1)) != 1:
+            raise NotImplementedError("training dae kind 'standard': conv_before_pool must be 1")
+        if dd.get('unpool_type', 'trackind') not in ('trackind', 'inverse'):
+            raise NotImplementedError("training dae kind 'standard': unpool_type must be 'trackind' or 'inverse' "
+                                      "(unpool_type='standard', the 4x4 transposed convolution, is not built)")
     for name in training_loss:
         if name not in SUPPORTED_LOSSES:
             raise NotImplementedError('training loss %r is not built (supported: %s)'
@@ -31,7 +51,7 @@ def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=Fal
     if not training_loss:
         raise ValueError('training_loss is empty')
     if ae_h:
-        raise NotImplementedError("ae_h (Plug&Play) needs dae kind 'standard' (train_dae.py:177-178)")
+        raise NotImplementedError('ae_h (Plug&Play: the DAE on h itself, train_dae.py:177-178) is not built')
     if full_im_ft:
         raise NotImplementedError('full_im_ft (full-image fine-tuning) is not built')
     if optimizer not in ops.OPTIMIZERS:
@@ -40,13 +60,19 @@ def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=Fal
 
 class DAETrainer:
     """fcn: the segmentation net (callable X -> [H..., Y]; may be None when the caller brings H and Y);
-    dae: a ContextModDAE, trained in place."""
+    dae: a ContextModDAE, or a StandardDAE built with trainable=True; trained in place."""
 
     def __init__(self, fcn, dae, n_classes, void_labels=(11,), optimizer='rmsprop', learning_rate=1e-4,
                  training_loss=('crossentropy',), lmb=1.0, noise=0.0, seed=None):
-        if not isinstance(dae, ContextModDAE):
-            raise NotImplementedError("training is built for dae kind 'contextmod' only")
-        check_supported('contextmod', training_loss, optimizer=optimizer)
+        self.standard = isinstance(dae, StandardDAE)
+        if self.standard:
+            if not dae.trainable:
+                raise NotImplementedError('training a StandardDAE needs one built with trainable=True')
+            check_supported('standard', training_loss, optimizer=optimizer, dae_dict={'concat_h': dae.concat_h})
+        elif isinstance(dae, ContextModDAE):
+            check_supported('contextmod', training_loss, optimizer=optimizer)
+        else:
+            raise NotImplementedError("training is built for dae kinds 'contextmod' and 'standard'")
         if list(void_labels) not in ([n_classes], []):
             raise NotImplementedError('void_labels must be [n_classes] (the last target channel) or empty')
         self.fcn, self.dae, self.C = fcn, dae, int(n_classes)
@@ -69,6 +95,8 @@ class DAETrainer:
         self.lr.mul_(float(factor))
 
     def _h(self, H):
+        if self.standard:                 # a list of h maps, one per concat point
+            return list(H) if isinstance(H, (list, tuple)) else [H]
         if isinstance(H, (list, tuple)):
             if len(H) != 1:
                 raise ValueError('expected 1 h tensor, got %d' % len(H))
@@ -81,7 +109,9 @@ class DAETrainer:
         score = dae.forward_train(self._h(H), Y_in, noise=self.noise, generator=self.generator, eps=eps)
         res, g, _ = ops.ctx_loss(score, T, self.losses, self.lmb, grad=True)
         dae.backward(g)
-        ops.opt_step(self.optimizer, dae.flat, dae._gflat, self.s1, self.s2, self.lr, self.state)
+        # (the standard DAE has millions of parameters: the many-workgroup form, same bits)
+        ops.opt_step(self.optimizer, dae.flat, dae._gflat, self.s1, self.s2, self.lr, self.state,
+                     grid=self.standard)
         dae.refresh()
         return res[0]
 

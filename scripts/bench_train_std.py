@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""One training step of the headline standard DAE (BASELINE configs[1]: 64 filters, concat_h=['pool4'],
+additional_pool=2, pad 100, trackind, skip) at batch 10, 224x224, from_gt, noise 0.1: one JSON line.
+
+    python scripts/bench_train_std.py [--batch 10] [--size 224x224] [--reps 15] [--dtypes float32 float64]
+
+Per precision: step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, RMSprop,
+refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch profile, per
+layer the weight-gradient launches' ms (kernel + finalize; both sources of the concat layer) next to the forward
+launch's ms of that same layer in that same step, their ratio, and the weight gradient's fraction of
+`--peak_tflops` (157.3: the fp32 matrix-pipe peak) on the nominal 2 Cin Cout 9 OH OW B.  A trainable StandardDAE
+runs its forward layers on the direct / halo kernels (no Winograd form: DESIGN section 12).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from iterative_inference_segm_amd import ops, synthetic as S              # noqa: E402
+from iterative_inference_segm_amd.dae import StandardDAE, param_order     # noqa: E402
+from iterative_inference_segm_amd.train import DAETrainer                 # noqa: E402
+
+
+def one(B, H, W, dt, reps, peak):
+    params = S.make_dae_params(seed=4321)
+    dae = StandardDAE(params, 11, dtype=dt, mma='f32', trainable=True)
+    tr = DAETrainer(None, dae, 11, [11], noise=0.1, seed=1)
+    T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
+    y = T[:, :11].contiguous()
+    hh, hw = H + 198, W + 198
+    for _ in range(4):
+        hh, hw = hh // 2, hw // 2
+    gen = torch.Generator(device='cuda').manual_seed(1)
+    h = [torch.randn((B, 512, hh, hw), generator=gen, device='cuda', dtype=dt)]
+    for _ in range(3):
+        tr.train_step(h, y, T)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tr.train_step(h, y, T)
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    step = float(np.median(ms))
+    # one profiled step: every launch of the library between two marks, in launch order
+    prof = []
+    ops.profile_begin()
+    ops.CONV_PROFILE = prof
+    try:
+        score = dae.forward_train(h, y, noise=0.1, generator=tr.generator)
+        n_fwd = len(prof)
+        _, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0)
+        dae.backward(g)
+        torch.cuda.synchronize()
+    finally:
+        ops.CONV_PROFILE = None
+        ops.profile_end()
+    order = param_order()
+    total = len(order) // 2
+    fwd = [(k, f, a.elapsed_time(b)) for k, f, a, b in prof[:n_fwd] if f > 0]
+    if len(fwd) != len(order):
+        raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fwd],))
+    fwd_ms = dict(zip(order, [t for _, _, t in fwd]))
+    fwd_kernel = dict(zip(order, [k for k, _, _ in fwd]))
+    wg = [(f, a.elapsed_time(b)) for k, f, a, b in prof[n_fwd:] if k == 'conv_wgrad_kernel']
+    # backward's order: up_conv1..total, then conv<total>_1..conv1_1, the concat layer (h behind pool4) twice
+    names = ['up_conv%d' % p for p in range(1, total + 1)]
+    for p in range(total, 0, -1):
+        names += ['conv%d_1' % p] * (2 if p == 5 else 1)
+    if len(wg) != len(names):
+        raise RuntimeError('expected %d weight-gradient calls, got %d' % (len(names), len(wg)))
+    rows = {}
+    for n, (f, t) in zip(names, wg):
+        r = rows.setdefault(n, {'layer': n, 'flops': 0.0, 'wgrad_ms': 0.0})
+        r['flops'] += f
+        r['wgrad_ms'] += t
+    out = []
+    for n in order:
+        r = rows[n]
+        out.append({'layer': n, 'cout': int(params[n][0].shape[0]), 'cin': int(params[n][0].shape[1]),
+                    'forward_kernel': fwd_kernel[n], 'wgrad_ms': round(r['wgrad_ms'], 4),
+                    'forward_ms': round(fwd_ms[n], 4), 'wgrad_over_forward': round(r['wgrad_ms'] / fwd_ms[n], 3),
+                    'wgrad_fraction_of_peak': round(r['flops'] / (r['wgrad_ms'] * 1e-3) / (peak * 1e12), 4)})
+    all_ms = float(sum(a.elapsed_time(b) for _, _, a, b in prof))
+    tw, tf = sum(r['wgrad_ms'] for r in out), sum(r['forward_ms'] for r in out)
+    return {'dtype': str(dt).replace('torch.', ''), 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+            'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 1),
+            'parameters': int(dae.flat.numel()), 'profiled_launch_ms': round(all_ms, 3),
+            'wgrad_ms_total': round(tw, 3), 'forward_conv_ms_total': round(tf, 3),
+            'wgrad_over_forward': round(tw / tf, 3), 'layers': out}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=10)
+    ap.add_argument('--size', default='224x224')
+    ap.add_argument('--reps', type=int, default=15)
+    ap.add_argument('--dtypes', nargs='+', default=['float32', 'float64'])
+    ap.add_argument('--peak_tflops', type=float, default=157.3)
+    a = ap.parse_args()
+    H, W = (int(v) for v in a.size.split('x'))
+    rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops) for name in a.dtypes]
+    print(json.dumps({'bench': 'train_std', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
+                      'reps': a.reps, 'results': rows}))
+
+
+if __name__ == '__main__':
+    main()

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Training the DAE on MI355X -- counterpart of the reference's train_dae.py for the DAE kind it defaults to,
-'contextmod' (train_dae.py:479-488).
+'contextmod' (train_dae.py:479-488), and for kind 'standard' with h at a pool point (e.g. -dae_dict
+'{"kind": "standard", "concat_h": ["pool4"]}' -segmentation_net fcn8; checkpoint in dae.param_order).
 
 Same arguments and defaults (`-dataset`, `-segmentation_net`, `-train_dict`, `-dae_dict`,
 `-data_augmentation`, `-train_from_0_255`; the dict arguments are JSON), the same epoch loop
@@ -10,7 +11,8 @@ helpers.build_experiment_name: `dae_model_best.npz` / `dae_model_last.npz` (np.s
 contextmod.PARAM_ORDER), `dae_errors_best.npz` / `dae_errors_last.npz`, `output.log`, `config.txt`.
 The lab paths keyed on getuser() become `--savepath / --loadpath / --weights_path`; `--synthetic` supplies the
 seeded synthetic split and initial weights.  What is not built is refused before any GPU work, with the
-reason: dae kinds other than 'contextmod', the 'dice' and 'squared_error_h' losses, `ae_h`, `full_im_ft`.
+reason: kind 'fcn8', kind 'standard' with bn / dropout / conv_before_pool != 1 / unpool_type 'standard' or with
+the image concatenated at the input, the 'dice' and 'squared_error_h' losses, `ae_h`, `full_im_ft`.
 All arithmetic runs in the HIP kernels of libiiseg_hip.so.
 """
 import argparse
@@ -45,17 +47,17 @@ def _json_dict(s):
 def check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer):
     """Everything this build does not train, refused with the reason (host only)."""
     from iterative_inference_segm_amd.train import check_supported as chk
-    chk(dae_dict['kind'], training_loss, ae_h, full_im_ft, optimizer)
-    if list(dae_dict['concat_h']) != ['input']:
+    chk(dae_dict['kind'], training_loss, ae_h, full_im_ft, optimizer, dae_dict=dae_dict)
+    if dae_dict['kind'] == 'contextmod' and list(dae_dict['concat_h']) != ['input']:
         raise NotImplementedError("the context module concatenates the image: concat_h must be ['input']")
 
 
-def save_checkpoint(savepath, tag, params, errors):
-    """dae_model_<tag>.npz (weights.save_param_list in contextmod.PARAM_ORDER: what
+def save_checkpoint(savepath, tag, params, errors, order=None):
+    """dae_model_<tag>.npz (weights.save_param_list in `order`, default contextmod.PARAM_ORDER: what
     np.savez(*get_all_param_values(dae)) wrote, train_dae.py:436-445) and dae_errors_<tag>.npz."""
     from iterative_inference_segm_amd.contextmod import PARAM_ORDER
     from iterative_inference_segm_amd.weights import save_param_list
-    save_param_list(os.path.join(savepath, 'dae_model_%s.npz' % tag), params, PARAM_ORDER)
+    save_param_list(os.path.join(savepath, 'dae_model_%s.npz' % tag), params, order or PARAM_ORDER)
     np.savez(os.path.join(savepath, 'dae_errors_%s.npz' % tag), *[np.asarray(e) for e in errors])
 
 
@@ -147,19 +149,37 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
     void = n_classes if any(void_labels) else n_classes + 1
 
     fcn_fn = None
-    if not dae_dict['from_gt']:
+    if not dae_dict['from_gt'] or dae_dict['kind'] == 'standard':       # (the standard kind's h: its feature maps)
         say('Building segmentation network')
         fcn_fn = build_segmentation_net(dataset, segm_net, dae_dict, weights_path, n_classes, void_labels,
                                         nb_in_channels, synthetic)
 
     say('Building DAE network')
     init = os.path.join(loadpath_init, 'dae_model_best.npz')
-    if resume:
-        params = load_param_list(init, PARAM_ORDER)
+    standard = dae_dict['kind'] == 'standard'
+    if standard:
+        from iterative_inference_segm_amd.dae import StandardDAE, param_order
+        arch = dict(concat_h=list(dae_dict['concat_h']), conv_before_pool=dae_dict['conv_before_pool'],
+                    additional_pool=dae_dict['additional_pool'], unpool_type=dae_dict['unpool_type'])
+        order = param_order(bn=0, **arch)
+        if resume:
+            params = load_param_list(init, order)
+        else:
+            # channels of the h maps: one forward of the frozen net on a blank image
+            probe = torch.zeros((1, nb_in_channels) + tuple(size), dtype=torch.float32, device='cuda')
+            h_channels = tuple(int(h.shape[1]) for h in fcn_fn(probe)[:-1])
+            params = S.make_dae_params(n_classes, h_channels, n_filters=dae_dict['n_filters'],
+                                       seed=4321 + int(seed), **arch)
+        dae = StandardDAE(params, n_classes, padding=100, n_filters=dae_dict['n_filters'],
+                          skip=dae_dict['skip'], noise=dae_dict['noise'], dtype=tdt, mma='f32', trainable=True, **arch)
     else:
-        params = S.make_contextmod_params(n_classes, nb_in_channels, seed=777 + int(seed))
-    dae = buildDAE_contextmod(n_classes=n_classes, trainable=True, noise=dae_dict['noise'],
-                              concat_h=dae_dict['concat_h'], params=params, dtype=tdt)
+        order = PARAM_ORDER
+        if resume:
+            params = load_param_list(init, PARAM_ORDER)
+        else:
+            params = S.make_contextmod_params(n_classes, nb_in_channels, seed=777 + int(seed))
+        dae = buildDAE_contextmod(n_classes=n_classes, trainable=True, noise=dae_dict['noise'],
+                                  concat_h=dae_dict['concat_h'], params=params, dtype=tdt)
     trainer = DAETrainer(fcn_fn, dae, n_classes, void_labels, optimizer=optimizer, learning_rate=learning_rate,
                          training_loss=training_loss, lmb=lmb, noise=float(dae_dict['noise']), seed=seed)
 
@@ -169,8 +189,14 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
         Ld = torch.from_numpy(np.ascontiguousarray(L)).cuda().to(tdt).contiguous()
         if dae_dict['from_gt']:
             Y = Ld[:, :void].contiguous()                                               # :371-372
-        else:
+        elif not standard:
             Y = fcn_fn(Xd)[-1].to(tdt).contiguous()                                     # :374
+        else:
+            Y = None
+        if standard:
+            out = fcn_fn(Xd)
+            H = [h.to(tdt).contiguous() for h in out[:-1]]
+            return H, (Y if dae_dict['from_gt'] else out[-1].to(tdt).contiguous()), Ld
         return Xd.to(tdt).contiguous(), Y, Ld
 
     err_train, err_valid, jacc_val_arr, mse_val_arr = [], [], [], []
@@ -213,17 +239,17 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
             best_err_val = err_valid[epoch]
             # the reference writes no checkpoint for epoch 0; this build does, so that a run of one epoch
             # leaves a model behind
-            save_checkpoint(savepath, 'best', dae.state_arrays(), errors)
+            save_checkpoint(savepath, 'best', dae.state_arrays(), errors, order)
         elif err_valid[epoch] < best_err_val:
             best_err_val = err_valid[epoch]
             patience = 0
-            save_checkpoint(savepath, 'best', dae.state_arrays(), errors)
+            save_checkpoint(savepath, 'best', dae.state_arrays(), errors, order)
         else:
             patience += 1
-            save_checkpoint(savepath, 'last', dae.state_arrays(), errors)
+            save_checkpoint(savepath, 'last', dae.state_arrays(), errors, order)
 
         if patience == max_patience or epoch == num_epochs - 1:
-            save_checkpoint(savepath, 'last', dae.state_arrays(), errors)
+            save_checkpoint(savepath, 'last', dae.state_arrays(), errors, order)
             if os.path.abspath(savepath) != os.path.abspath(loadpath):
                 say('Copying model and other training files to {}'.format(loadpath))
                 shutil.copytree(savepath, loadpath, dirs_exist_ok=True)
@@ -242,12 +268,15 @@ def make_parser():
                              'only enters the experiment name, as in the reference: no regulariser is added '
                              'to the loss')
     parser.add_argument('-dae_dict', type=_json_dict, default=dict(DAE_DICT),
-                        help="DAE kind and parameters (JSON).  Only kind 'contextmod' is trained here")
+                        help="DAE kind and parameters (JSON).  Kinds 'contextmod' and 'standard' (h at a pool point) are "
+                             "trained here")
     parser.add_argument('-data_augmentation', type=_json_dict, default=dict(DATA_AUGMENTATION),
                         help='Dictionary of data augmentation (JSON): accepted and recorded in the experiment '
                              'name; crop_size sets the synthetic image size')
     parser.add_argument('-train_from_0_255', type=lambda s: str(s).lower() in ('1', 'true', 'yes'),
                         default=False, help='Whether to train from images within 0-255 range')
+    parser.add_argument('-ae_h', type=lambda s: str(s).lower() in ('1', 'true', 'yes'), default=False,
+                        help='Plug&Play DAE on h (refused: not built)')
     parser.add_argument('--synthetic', action='store_true',
                         help='seeded synthetic split and initial weights (no dataset here)')
     parser.add_argument('--savepath', type=str, default=SAVEPATH)
@@ -277,12 +306,12 @@ def parse_args(argv=None):
 def main(argv=None):
     args, train_dict, dae_dict = parse_args(argv)
     try:
-        check_supported(dae_dict, train_dict['training_loss'], False, train_dict.get('full_im_ft', False),
+        check_supported(dae_dict, train_dict['training_loss'], args.ae_h, train_dict.get('full_im_ft', False),
                         train_dict['optimizer'])
     except (NotImplementedError, ValueError) as e:
         print('train_dae.py: ' + str(e), file=sys.stderr)
         return 2
-    train(dataset=args.dataset, segm_net=args.segmentation_net, dae_dict_updates=dae_dict,
+    train(dataset=args.dataset, segm_net=args.segmentation_net, dae_dict_updates=dae_dict, ae_h=args.ae_h,
           data_augmentation=args.data_augmentation, train_from_0_255=args.train_from_0_255, resume=args.resume,
           savepath=args.savepath, loadpath=args.loadpath, weights_path=args.weights_path,
           synthetic=args.synthetic, n_images=args.n_images, image_size=args.image_size, seed=args.seed,
