@@ -13,6 +13,7 @@ import os
 import torch
 
 from . import ops
+from .params import ParamStore
 from .weights import load_param_list
 
 # inside a refinement loop the image half of the first layer (3 of its 14 input channels; h is the image and does not
@@ -43,17 +44,9 @@ class ContextModDAE:
         # ONE flat parameter buffer in PARAM_ORDER (W then b per layer): every ops.Conv below holds VIEWS of it,
         # so an optimizer step on `flat` followed by `refresh()` reaches every path (training, section 9)
         self.device, self.dtype = device, dtype
-        host = [(n, torch.as_tensor(params[n][0]), torch.as_tensor(params[n][1])) for n in PARAM_ORDER]
-        self.flat = torch.empty(sum(W.numel() + b.numel() for _, W, b in host), dtype=dtype, device=device)
-        self._views, off = {}, 0
-        for n, W, b in host:
-            Wv = self.flat[off:off + W.numel()].view(W.shape)
-            bv = self.flat[off + W.numel():off + W.numel() + b.numel()]
-            Wv.copy_(W.to(dtype))
-            bv.copy_(b.to(dtype))
-            self._views[n] = (Wv, bv)
-            off += W.numel() + b.numel()
-        params = self._views
+        self._params = ParamStore(params, PARAM_ORDER, dtype, device)
+        self.flat, params = self._params.flat, self._params.views
+        self._views = params
         self.conv1 = ops.Conv(params['conv1'][0], params['conv1'][1], pad=1, relu=True,
                               device=device, dtype=dtype)                         # :74-76
         self.dil = []
@@ -74,16 +67,14 @@ class ContextModDAE:
         W, b = params['dilconv1']
         self.dil1_valid = ops.Conv(W, b, pad=0, relu=True, dil=DILATIONS[0], layout='iohw', device=device,
                                    dtype=dtype)
-        lo, hi = self.flat.data_ptr(), self.flat.data_ptr() + self.flat.numel() * self.flat.element_size()
         for conv in self._shared_convs():
-            assert lo <= conv.W.data_ptr() < hi and lo <= conv.b.data_ptr() < hi      # views, not copies
+            assert self._params.holds(conv.W) and self._params.holds(conv.b)              # views, not copies
         self._sessions = {}
         self._conv1_params = (params['conv1'][0], params['conv1'][1], device, dtype)
         self._hsplit = {}           # h channels -> (image-half conv, y-half conv) of the first layer
         self._adj = None            # training: the data-gradient layers (`_adjoints`)
         self._train = {}            # training: buffers per geometry
         self._saved = None          # training: what `forward_train` kept for `backward`
-        self._gflat = None
         self._keep_pre, self._pre = False, None
         if self.c8:
             # the 16-bit leg's layers: views of `flat` read through their strides, packed to bf16 operand images
@@ -235,14 +226,18 @@ class ContextModDAE:
             t = conv(t, out=out)
         return self._c8_last(t, out_format='nchw')
 
-    def _first_layer(self, session):
-        """conv1 of a session step into the PadLayer(32) buffer: the whole layer on [h, y], or its y half
-        continuing from the cached image half."""
+    def _front(self, session, y):
+        """The first two layers of a session step: y into the concat buffer unless a fused step has left it
+        there, conv1 into the PadLayer(32) buffer (the whole layer on [h, y], or its y half continuing from the
+        cached image half), dilconv1 as a 'valid' layer on that buffer.  Returns dilconv1's output."""
+        if not session.get('y_in_cat'):
+            session['cat'][:, session['ch']:, 1:-1, 1:-1].copy_(y)
         if session['split'] is not None:
             session['split'][1](session['cat'], add=session['hb'], add_off=(0, 0), out=session['pad32'],
                                 place=(32, 32))
         else:
             self.conv1_valid(session['cat'], out=session['pad32'], place=(32, 32))
+        return self.dil1_valid(session['pad32'])
 
     def scores(self, h_list, y, mask_override=None, session=None):
         if len(h_list) != 1:
@@ -258,11 +253,8 @@ class ContextModDAE:
             # (the padded forms of conv1 / dilconv1 sum in another order in fp32)
             session = self.new_session(h_list, y)
         if session is not None:
-            if not session.get('y_in_cat'):
-                session['cat'][:, session['ch']:, 1:-1, 1:-1].copy_(y)
+            t = self._front(session, y)
             session['y_in_cat'] = False      # (the caller's update changes y, not the buffer: see `fused_step`)
-            self._first_layer(session)
-            t = self.dil1_valid(session['pad32'])
             rest = self.dil[1:]
             kept = [(session['pad32'], (32, 32)), (t, (0, 0))]       # conv1's map lives inside PadLayer(32)'s zeros
         else:
@@ -337,10 +329,7 @@ class ContextModDAE:
         fused form (the caller then runs scores + refine_update)."""
         if self.c8 or session is None or not ops.ctx_tail_supported(self.dil[-1], self.last, y):
             return None                  # (a fused bf16 tail is not built: the caller runs scores + refine_update)
-        if not session.get('y_in_cat'):
-            session['cat'][:, session['ch']:, 1:-1, 1:-1].copy_(y)
-        self._first_layer(session)
-        t = self.dil1_valid(session['pad32'])
+        t = self._front(session, y)
         for conv in self.dil[1:-1]:
             t = conv(t)
         nblk = ops.ctx_tail(self.dil[-1], self.last, t, y, state, step, ycat=session['cat'],
@@ -356,18 +345,25 @@ class ContextModDAE:
 
     def state_arrays(self):
         """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
-        return {n: (W.detach().cpu().float().numpy(), b.detach().cpu().float().numpy())
-                for n, (W, b) in self._views.items()}
+        return self._params.state_arrays()
+
+    @property
+    def gflat(self):
+        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
+        return self._params.gflat
+
+    def _adjoint_filters(self):
+        """(filter, dilation) of the data-gradient layer of dilconv1..7: the adjoint of a 'valid' dilated 3x3
+        layer is the same layer with the channel-transposed, spatially flipped filter on g_z inside a zero border
+        of 2 d -- W[in,out,k,k] flipped and READ as W[out,in,k,k] is exactly that filter."""
+        for i, d in enumerate(DILATIONS + [1]):
+            yield self._views['dilconv%d' % (i + 1)][0].flip(2, 3), d
 
     def _adjoints(self):
-        """The data-gradient layers: the adjoint of a 'valid' dilated 3x3 layer is the same layer with the
-        channel-transposed, spatially flipped filter on g_z inside a zero border of 2 d -- W[in,out,k,k]
-        flipped and READ as W[out,in,k,k] is exactly that filter."""
+        """The data-gradient layers (`_adjoint_filters`), built at first use."""
         if self._adj is None:
-            mk = lambda W, d: ops.Conv(W.flip(2, 3).contiguous(), None, pad=0, relu=False, dil=d, layout='oihw',
-                                       device=self.device, dtype=self.dtype)
-            self._adj = [mk(self._views['dilconv%d' % (i + 1)][0], d) for i, d in enumerate(DILATIONS)]
-            self._adj.append(mk(self._views['dilconv7'][0], 1))
+            self._adj = [ops.Conv(Wf.contiguous(), None, pad=0, relu=False, dil=d, layout='oihw',
+                                  device=self.device, dtype=self.dtype) for Wf, d in self._adjoint_filters()]
         return self._adj
 
     def refresh(self):
@@ -391,8 +387,8 @@ class ContextModDAE:
             if sess['split'] is not None:
                 sess['split'][0](sess['hpad'], out=sess['hb'])
         if self._adj is not None:
-            for i, adj in enumerate(self._adj):
-                adj.W.copy_(self._views['dilconv%d' % (i + 1)][0].flip(2, 3))
+            for adj, (Wf, _) in zip(self._adj, self._adjoint_filters()):
+                adj.W.copy_(Wf)
                 adj.refresh()
 
     def _train_buffers(self, B, ch, Cy, H, W, device):
@@ -411,19 +407,23 @@ class ContextModDAE:
             self._train[key] = buf
         return buf
 
-    def forward_train(self, h, y, noise=0.0, generator=None, eps=None):
+    def forward_train(self, h_list, y, noise=0.0, generator=None, eps=None):
         """The training-mode forward pass: GaussianNoiseLayer on y (contextmod_dae.py:50-57: y + noise * N(0, 1),
         `eps` = the caller's standard-normal sample, else drawn from `generator`), then the eight layers, whose
-        outputs are kept for `backward`.  Returns the score map (B,C,H,W) before the softmax."""
+        outputs are kept for `backward`.  h_list: the one h map in a list, as `scores` takes it; the bare tensor,
+        which this method took before it took a list, is still accepted.  Returns the score map (B,C,H,W) before
+        the softmax."""
         self._refuse_c8('forward_train')
+        if isinstance(h_list, torch.Tensor):
+            h_list = [h_list]
+        if len(h_list) != 1:
+            raise ValueError('expected 1 h tensor, got %d' % len(h_list))
+        h = h_list[0]
         B, ch, H, W = h.shape
         if tuple(y.shape[2:]) != (H, W) or y.shape[0] != B or ch + y.shape[1] != self.conv1.Cin:
             raise RuntimeError('forward_train: h %s, y %s' % (tuple(h.shape), tuple(y.shape)))
         buf = self._train_buffers(B, ch, y.shape[1], H, W, y.device)
-        if noise > 0:
-            if eps is None:
-                eps = torch.randn(y.shape, generator=generator, device=y.device, dtype=y.dtype)
-            y = ops.add_noise(y, eps, float(noise))
+        y = ops.gaussian_noise(y, noise, generator, eps)
         buf['cat'][:, :ch, 1:-1, 1:-1].copy_(h)                      # h first (P13)
         buf['cat'][:, ch:, 1:-1, 1:-1].copy_(y)
         self.conv1_valid(buf['cat'], out=buf['pad32'], place=(32, 32))
@@ -448,15 +448,7 @@ class ContextModDAE:
         s = self._saved
         if s is None:
             raise RuntimeError('backward() needs forward_train() first')
-        if self._gflat is None:
-            self._gflat = torch.zeros_like(self.flat)
-            self._gviews, off = {}, 0
-            for n in PARAM_ORDER:
-                W, b = self._views[n]
-                self._gviews[n] = (self._gflat[off:off + W.numel()].view(W.shape),
-                                   self._gflat[off + W.numel():off + W.numel() + b.numel()])
-                off += W.numel() + b.numel()
-        gv, adj, acts, buf = self._gviews, self._adjoints(), s['acts'], s['buf']
+        gv, adj, acts, buf = self._params.grad_views(), self._adjoints(), s['acts'], s['buf']
         H, W = s['hw']
         ops.conv_small_wgrad(acts[6], g_score, None, *gv['dilconv7'], dil=1, layout='iohw')
         g = adj[6](g_score)
@@ -469,7 +461,7 @@ class ContextModDAE:
             g = adj[L - 1](gz, window=(32, 32, H, W)) if L == 1 else adj[L - 1](gz)
         c1 = acts[0][:, :, 32:32 + H, 32:32 + W].contiguous()
         ops.conv_small_wgrad(buf['cat'], g, c1, *gv['conv1'], dil=1, layout='oihw')
-        return dict(gv)
+        return gv
 
     def __call__(self, *args):
         score = self.scores(args[:-1], args[-1])

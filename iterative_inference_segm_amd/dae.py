@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import ops, regions
+from .params import ParamStore
 from .regions import center
 from .weights import load_param_list
 
@@ -67,7 +68,7 @@ class StandardDAE:
         concat_h = list(concat_h)
         mma = mma or ops.DEFAULT_MMA
         self.trainable = bool(trainable)
-        self.flat, self._views, self._gflat, self._gviews, self._tsaved = None, None, None, None, None
+        self.flat, self._params, self._tsaved = None, None, None
         if trainable:
             if conv_before_pool != 1 or bn or dropout > 0 or unpool_type not in ('trackind', 'inverse'):
                 raise NotImplementedError('training the standard DAE: conv_before_pool=1, bn=0, dropout=0, '
@@ -75,18 +76,13 @@ class StandardDAE:
             if dtype not in (torch.float32, torch.float64) or (dtype == torch.float32 and mma != 'f32'):
                 raise NotImplementedError("training the standard DAE: float32 (mma='f32') or float64; the "
                                           '16-bit legs are not trained')
-            order = param_order(concat_h, conv_before_pool, additional_pool, unpool_type, bn)
-            host = [(n, torch.as_tensor(params[n][0]), torch.as_tensor(params[n][1])) for n in order]
-            self.flat = torch.empty(sum(W.numel() + b.numel() for _, W, b in host), dtype=dtype, device=device)
-            self._views, off = {}, 0
-            for n, W, b in host:
-                Wv = self.flat[off:off + W.numel()].view(W.shape)
-                bv = self.flat[off + W.numel():off + W.numel() + b.numel()]
-                Wv.copy_(W.to(dtype))
-                bv.copy_(b.to(dtype))
-                self._views[n] = (Wv, bv)
-                off += W.numel() + b.numel()
-            params = self._views
+            if emulate_noise:
+                raise NotImplementedError('training the standard DAE: emulate_noise (DePool2D masks of a hidden '
+                                          'noisy re-forward) is not built: the weight gradients take the masks of '
+                                          'the training forward itself')
+            self._params = ParamStore(params, param_order(concat_h, conv_before_pool, additional_pool, unpool_type,
+                                                          bn), dtype, device)
+            self.flat, params = self._params.flat, self._params.views
         self.mma = mma
         # bf16 C8 activations between the layers (ops.Conv mma='bf16c8', `_scores_c8`)
         # ('bf16x3': the same plan on hi / lo pairs, the fp32-class mode of that kernel)
@@ -198,9 +194,8 @@ class StandardDAE:
         self.use_masks = os.environ.get('IISEG_DEPOOL_MASKS', '1') != '0'
         self.keep_pre = False   # True: the pre-pool maps are needed afterwards (backward_y)
         if trainable:
-            lo, hi = self.flat.data_ptr(), self.flat.data_ptr() + self.flat.numel() * self.flat.element_size()
             for conv in self.conv_layers().values():
-                assert lo <= conv.W.data_ptr() < hi and lo <= conv.b.data_ptr() < hi      # views, not copies
+                assert self._params.holds(conv.W) and self._params.holds(conv.b)          # views, not copies
                 conv.wino = conv.wino_f64 = False     # no weight transform to keep in step (Conv.refresh)
 
     def _mask_levels(self, overridden):
@@ -647,52 +642,56 @@ class StandardDAE:
         return t
 
     # ---- true-gradient mode (not in the reference, F1) -----------------------
+    def _flipped_filters(self):
+        """(name, filter) of every layer's backward-data conv: the channel-transposed, spatially flipped filter.
+        After a concat only the filters of the non-h channels are kept: h is a constant of the loop."""
+        prev = self.n_classes
+        for p in range(self.total):
+            name = 'conv%d_1' % (p + 1)
+            W = self.enc[name].W                         # (Cout, ch + prev, 3, 3), on the device
+            yield name, W[:, W.shape[1] - prev:].transpose(0, 1).flip(2, 3)
+            prev = W.shape[0]
+        for p in range(self.total, 0, -1):
+            name = 'up_conv%d' % p
+            yield name, self.dec[name].W.transpose(0, 1).flip(2, 3)
+
     def _bwd_convs(self):
-        """Backward-data of a 3x3 stride-1 conv = the forward conv of the gradient with the
-        channel-transposed, spatially flipped filter ('same' for pad 1; for the pad-100 first layer
-        the window at offset pad-1 of that 'same' result).  After a concat only the filters of the
-        non-h channels are kept: h is a constant of the loop."""
+        """Backward-data of a 3x3 stride-1 conv = the forward conv of the gradient with the flipped filter
+        (`_flipped_filters`; 'same' for pad 1; for the pad-100 first layer the window at offset pad-1 of that
+        'same' result)."""
         if self._bwd is None:
             if self.conv_before_pool != 1 or self.bn or self.unpool_type == 'standard':
                 raise NotImplementedError('gradient mode: conv_before_pool=1, bn=0, unpool_type in '
                                           '{trackind, inverse}')
-            bwd = {}
-            prev = self.n_classes
-            for p in range(self.total):
-                name = 'conv%d_1' % (p + 1)
-                W = self.enc[name].W                     # (Cout, ch + prev, 3, 3), on the device
-                ch = W.shape[1] - prev
-                Wt = W[:, ch:].transpose(0, 1).flip(2, 3).contiguous()
-                bwd[name] = ops.Conv(Wt, None, pad=1, relu=False, device=W.device, dtype=self.dtype)
-                prev = W.shape[0]
-            for p in range(self.total, 0, -1):
-                name = 'up_conv%d' % p
-                W = self.dec[name].W
-                bwd[name] = ops.Conv(W.transpose(0, 1).flip(2, 3).contiguous(), None, pad=1,
-                                     relu=False, device=W.device, dtype=self.dtype)
+            bwd = {name: ops.Conv(Wt.contiguous(), None, pad=1, relu=False, device=Wt.device, dtype=self.dtype)
+                   for name, Wt in self._flipped_filters()}
             if self.trainable:
                 for conv in bwd.values():
                     conv.wino = conv.wino_f64 = False
             self._bwd = bwd
         return self._bwd
 
-    def backward_y(self, g_score, y_shape):
-        """dE/dy THROUGH the DAE for an upstream gradient g_score w.r.t. the (cropped) score map
-        of the latest `scores()` call; adjoint of that forward, level by level (oracle/dae_grad.py).
-        Full maps (the decoder / encoder windows of the forward are not exploited here)."""
+    def _adjoint_walk(self, g_score, y_shape, override=None, gv=None, first_layer=True):
+        """The adjoint of the latest `scores()` call, level by level (oracle/dae_grad.py), on full maps (the
+        decoder / encoder windows of the forward are not exploited here): `backward_y` and `backward` are its two
+        callers.  override: the forward's {level: (pre, pooled)} DePool2D mask tensors.  gv: {name: (dW, db)} to
+        take the weight gradients into (ops.conv_wgrad on the g_z the chain forms and the layer input that
+        `forward_train` saved; DePool2D's output is materialised for the up_conv layers, a concat layer is two
+        calls into one dW, h first).  first_layer: form (and return) the first layer's data gradient."""
         bwd = self._bwd_convs()
-        override, pre, pool = self._saved
+        _, pre, pool = self._saved
         if any(t.device.type == 'meta' for t in pre.values()):
             raise RuntimeError('backward_y needs the pre-pool maps of the forward pass: set '
                                'dae.keep_pre = True before calling scores()')
+        if gv is not None:
+            h_list, _, fused = self._tsaved
+            feeds = regions.concat_feeds(self.concat_h, self.total, self.n_pool)
         B = g_score.shape[0]
         dev, dt = g_score.device, g_score.dtype
         g_pool = {}
         g_f = g_score
         for p in range(1, self.total + 1):               # decoder, output to input
-            mpre, mpool = pre[p], pool[p]
-            if override and p in override:
-                mpre, mpool = override[p]
+            mpre, mpool = override[p] if override and p in override else (pre[p], pool[p])
             ph, pw = pre[p].shape[2], pre[p].shape[3]
             other_hw = (pool[p - 1].shape[2], pool[p - 1].shape[3]) if p > 1 else \
                 (y_shape[2], y_shape[3])
@@ -705,6 +704,9 @@ class StandardDAE:
                 oy, ox = center(other_hw[0], oh), center(other_hw[1], ow)
                 gp[:, :, oy:oy + oh, ox:ox + ow].copy_(g_f)
                 g_pool[p - 1] = gp
+            if gv is not None:
+                t_in = pool[self.total] if p == self.total else fused['fused_up%d' % (p + 1)]
+                ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *gv['up_conv%d' % p], pad=1)
             g_u = bwd['up_conv%d' % p](g_c)
             g_f = ops.depool_bwd(g_u, mpre, mpool)
         g_pool[self.total] = g_f
@@ -714,28 +716,45 @@ class StandardDAE:
             if gp is None:
                 gp = torch.zeros_like(pool[p])
             g_z = ops.pool_relu_bwd(gp, pre[p], pool[p])
-            conv = bwd['conv%d_1' % p]
+            name = 'conv%d_1' % p
+            conv, fwd = bwd[name], self.enc[name]
+            if gv is not None:
+                dW, db = gv[name]
+                ch = 0
+                if (p - 1) in feeds:                     # h first (P13), then the features
+                    h = h_list[feeds[p - 1]]
+                    ch = h.shape[1]
+                    ops.conv_wgrad(h, g_z, dW, None, pad=fwd.pad, ci0=0)
+                ops.conv_wgrad(pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch)
             if p > 1:
                 acc = g_pool.get(p - 1)
                 g_pool[p - 1] = conv(g_z) if acc is None else conv(g_z, add=acc, out=acc)
-            else:
-                fwd = self.enc['conv1_1']
+            elif first_layer:
                 if fwd.pad != 1:      # pad-100 first layer: crop at offset pad - 1
                     g_in = conv(g_z, window=(fwd.pad - 1, fwd.pad - 1, y_shape[2], y_shape[3]))
                 else:
                     g_in = conv(g_z)
         return g_in
 
+    def backward_y(self, g_score, y_shape):
+        """dE/dy THROUGH the DAE for an upstream gradient g_score w.r.t. the (cropped) score map
+        of the latest `scores()` call (`_adjoint_walk` under the mask override of that call)."""
+        return self._adjoint_walk(g_score, y_shape, override=self._saved[0])
+
     # ---- training (DESIGN.md section 12; reference train_dae.py with dae kind 'standard') ----------
     def parameters(self):
         """{name: (W, b)} in `param_order`: views of `self.flat`.  After changing them in place call
         `refresh()`."""
-        return dict(self._views)
+        return dict(self._params.views)
 
     def state_arrays(self):
         """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
-        return {n: (W.detach().cpu().float().numpy(), b.detach().cpu().float().numpy())
-                for n, (W, b) in self._views.items()}
+        return self._params.state_arrays()
+
+    @property
+    def gflat(self):
+        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
+        return self._params.gflat
 
     def _need_trainable(self, what):
         if not self.trainable:
@@ -748,10 +767,7 @@ class StandardDAE:
         DESIGN.md section 4).  Returns the score map before the softmax."""
         self._need_trainable('forward_train')
         h_list = list(h_list)
-        if noise > 0:
-            if eps is None:
-                eps = torch.randn(y.shape, generator=generator, device=y.device, dtype=y.dtype)
-            y = ops.add_noise(y, eps, float(noise))
+        y = ops.gaussian_noise(y, noise, generator, eps)
         keep, dce, trace = self.keep_pre, self.dce, self.trace
         # full decoder maps: the weight gradient reads every layer input whole
         self.keep_pre, self.dce, self.trace = True, False, {}
@@ -773,67 +789,16 @@ class StandardDAE:
         out.update({k: v for k, v in self._tsaved[2].items() if k.startswith('fused_up')})
         return out
 
-    def _grad_views(self):
-        if self._gflat is None:
-            self._gflat = torch.zeros_like(self.flat)
-            self._gviews, off = {}, 0
-            for n, (W, b) in self._views.items():
-                self._gviews[n] = (self._gflat[off:off + W.numel()].view(W.shape),
-                                   self._gflat[off + W.numel():off + W.numel() + b.numel()])
-                off += W.numel() + b.numel()
-        return self._gviews
-
     def backward(self, g_score):
         """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
-        g_score, after `forward_train`: the chain of `backward_y` with ops.conv_wgrad at every layer, fed the
-        g_z the chain forms and the layer's saved input.  DePool2D's output is materialised here for the
-        up_conv layers (ops.unpool_eqmask); a concat layer is two calls into one dW (h first).  The data
-        gradient of the first layer is not formed."""
+        g_score, after `forward_train`: `_adjoint_walk` with ops.conv_wgrad at every layer.  The data gradient
+        of the first layer is not formed."""
         self._need_trainable('backward')
         if self._tsaved is None or self._saved is None:
             raise RuntimeError('backward() needs forward_train() first')
-        h_list, y_shape, fused = self._tsaved
-        gv, bwd = self._grad_views(), self._bwd_convs()
-        _, pre, pool = self._saved
-        feeds = regions.concat_feeds(self.concat_h, self.total, self.n_pool)
-        B, dev, dt = g_score.shape[0], g_score.device, g_score.dtype
-        g_pool = {}
-        g_f = g_score
-        for p in range(1, self.total + 1):               # decoder, output to input
-            ph, pw = pre[p].shape[2], pre[p].shape[3]
-            other_hw = (pool[p - 1].shape[2], pool[p - 1].shape[3]) if p > 1 else (y_shape[2], y_shape[3])
-            oh, ow = min(ph, other_hw[0]), min(pw, other_hw[1])
-            cy, cx = center(ph, oh), center(pw, ow)
-            g_c = torch.zeros((B, g_f.shape[1], ph, pw), dtype=dt, device=dev)
-            g_c[:, :, cy:cy + oh, cx:cx + ow].copy_(g_f)           # adjoint of the center crop
-            if self.skip and p > 1:                                 # adjoint of the skip sum
-                gp = torch.zeros_like(pool[p - 1])
-                oy, ox = center(other_hw[0], oh), center(other_hw[1], ow)
-                gp[:, :, oy:oy + oh, ox:ox + ow].copy_(g_f)
-                g_pool[p - 1] = gp
-            t_in = pool[self.total] if p == self.total else fused['fused_up%d' % (p + 1)]
-            u = ops.unpool_eqmask(t_in, pre[p], pool[p])
-            ops.conv_wgrad(u, g_c, *gv['up_conv%d' % p], pad=1)
-            g_u = bwd['up_conv%d' % p](g_c)
-            g_f = ops.depool_bwd(g_u, pre[p], pool[p])
-        g_pool[self.total] = g_f
-        for p in range(self.total, 0, -1):               # encoder, deep to shallow
-            gp = g_pool.get(p)
-            if gp is None:
-                gp = torch.zeros_like(pool[p])
-            g_z = ops.pool_relu_bwd(gp, pre[p], pool[p])
-            name = 'conv%d_1' % p
-            dW, db = gv[name]
-            pad, ch = self.enc[name].pad, 0
-            if (p - 1) in feeds:                         # h first (P13), then the features
-                h = h_list[feeds[p - 1]]
-                ch = h.shape[1]
-                ops.conv_wgrad(h, g_z, dW, None, pad=pad, ci0=0)
-            ops.conv_wgrad(pool[p - 1], g_z, dW, db, pad=pad, ci0=ch)
-            if p > 1:
-                acc = g_pool.get(p - 1)
-                g_pool[p - 1] = bwd[name](g_z) if acc is None else bwd[name](g_z, add=acc, out=acc)
-        return dict(gv)
+        gv = self._params.grad_views()
+        self._adjoint_walk(g_score, self._tsaved[1], gv=gv, first_layer=False)
+        return gv
 
     def refresh(self):
         """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into
@@ -843,15 +808,8 @@ class StandardDAE:
         for conv in self.conv_layers().values():
             conv.refresh()
         if self._bwd is not None:
-            prev = self.n_classes
-            for p in range(self.total):
-                name = 'conv%d_1' % (p + 1)
-                W = self.enc[name].W
-                self._bwd[name].W.copy_(W[:, W.shape[1] - prev:].transpose(0, 1).flip(2, 3))
-                prev = W.shape[0]
-            for p in range(self.total, 0, -1):
-                name = 'up_conv%d' % p
-                self._bwd[name].W.copy_(self.dec[name].W.transpose(0, 1).flip(2, 3))
+            for name, Wt in self._flipped_filters():
+                self._bwd[name].W.copy_(Wt)
             for conv in self._bwd.values():
                 conv.refresh()
         self._store = None

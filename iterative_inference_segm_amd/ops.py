@@ -297,6 +297,18 @@ def _launch_staged(fn, args, whole, stages):
         ev0 = ev1
 
 
+def _count(n, what):
+    """The result of a query of the library that returns a count, or a negative status (raised here)."""
+    if n < 0:
+        check(int(n), what)
+    return int(n)
+
+
+def _add_bytes(kernel, nbytes):
+    """Algorithmic bytes of one launch, summed per kernel name (KERNEL_BYTES; callers do it under CONV_PROFILE)."""
+    KERNEL_BYTES[kernel] = KERNEL_BYTES.get(kernel, 0.0) + nbytes
+
+
 # the descriptor and operands of one NCHW launch of a Conv, as its `_run_<form>` methods take them
 _Launch = collections.namedtuple('_Launch', 'd x1 x2 pre pooled add out pool_out mask_in mask_out')
 
@@ -567,8 +579,8 @@ class Conv:
                 kern = 'conv_halo_f64_kernel'
         elif (add is None or self.b is None) and self.lib.iiseg_conv_small_supported(C.byref(d)):
             kern = 'conv_small_f32_kernel'         # vector ALU, HBM-bound: algorithmic bytes for the roofline
-            KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
-                4.0 * d.B * (self.Cin * d.H * d.W + (2 if add is not None else 1) * self.Cout * d.OH * d.OW)
+            _add_bytes(kern, 4.0 * d.B * (self.Cin * d.H * d.W +
+                                          (2 if add is not None else 1) * self.Cout * d.OH * d.OW))
         if kern == 'conv_halo_f32_kernel' and d.C2 > 0 and d.C1 % 4:
             kern = 'conv_taps_f32_kernel'      # a k-tile would straddle the two sources
         return kern
@@ -1426,10 +1438,8 @@ class ConvC8Dil:
             (self.Cin, self.Cout), (self.sc, self.so) = W.shape[:2], st[:2]
         # (the smallest legal map: what the packer's argument check needs of a geometry)
         self._pack_desc = self._desc(1, self.dil * (self.K - 1) + 1, self.dil * (self.K - 1) + 1, None, False)
-        nbytes = self.lib.iiseg_conv_c8_dil_pack_bytes(self.K)
-        if nbytes < 0:
-            check(int(nbytes), 'iiseg_conv_c8_dil_pack_bytes')
-        self.wpack = torch.empty(int(nbytes) // 2, dtype=torch.bfloat16, device=device)
+        nbytes = _count(self.lib.iiseg_conv_c8_dil_pack_bytes(self.K), 'iiseg_conv_c8_dil_pack_bytes')
+        self.wpack = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=device)
         self._descs = {}
         self.refresh()
 
@@ -1493,8 +1503,7 @@ class ConvC8Dil:
             raise RuntimeError('ConvC8Dil: add %s for an output (%d, %d, %d, %d)'
                                % (tuple(add.shape), B, self.Cout, OH, OW))
         if CONV_PROFILE is not None:
-            KERNEL_BYTES[self.kernel] = KERNEL_BYTES.get(self.kernel, 0) + \
-                B * (32 * H * W + (4 * self.Cout if nchw else 32) * OH * OW)
+            _add_bytes(self.kernel, B * (32 * H * W + (4 * self.Cout if nchw else 32) * OH * OW))
         _launch(self.kernel, self.flops(B, OH, OW), self.lib.iiseg_conv_c8_dil, C.byref(d), _c8ptr(x8),
                 C.c_void_p(self.wpack.data_ptr()), _ptr(self.b), _ptr(add), optr)
         return out
@@ -1748,8 +1757,7 @@ def ctx_tail(conv6, conv7, x, y, state, step, ycat=None, cat_c0=0, cat_off=(0, 0
             float(step))
     if CONV_PROFILE is not None:
         # algorithmic bytes: x planes read, y read and written, the mirror written
-        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
-            4.0 * B * Cc * ((H + 2) * (W + 2) + (3 if ycat is not None else 2) * H * W)
+        _add_bytes(kern, 4.0 * B * Cc * ((H + 2) * (W + 2) + (3 if ycat is not None else 2) * H * W))
     return nblk
 
 
@@ -1908,6 +1916,16 @@ def add_noise(x, eps, sigma):
     return out
 
 
+def gaussian_noise(y, noise, generator=None, eps=None):
+    """GaussianNoiseLayer in training mode: y + noise * eps, formed ONCE (`add_noise`); eps = the caller's
+    standard-normal sample, else drawn from `generator`.  noise = 0: y itself."""
+    if not noise > 0:
+        return y
+    if eps is None:
+        eps = torch.randn(y.shape, generator=generator, device=y.device, dtype=y.dtype)
+    return add_noise(y, eps, float(noise))
+
+
 def dropout_apply(x, keep, p):
     """In place x * keep / (1 - p) (DropoutLayer, rescale=True, with the caller's 0/1 mask)."""
     dt = x.dtype
@@ -1919,6 +1937,16 @@ def dropout_apply(x, keep, p):
 # ---- training the context-module DAE (csrc/ctx_train.hip) ----
 LOSS_FLAGS = {'crossentropy': _lib.LOSS_CROSSENTROPY, 'squared_error': _lib.LOSS_SQUARED_ERROR}
 OPTIMIZERS = {'rmsprop': _lib.OPT_RMSPROP, 'adam': _lib.OPT_ADAM}
+
+
+def layout_strides(Cin, Cout, K, layout):
+    """(so, sc) of a layer parameter with K x K taps stored as `layout` ('oihw': W[out,in,k,k]; 'iohw':
+    W[in,out,k,k]): element (co, ci, tap) lies at co so + ci sc + tap (include/iiseg.h)."""
+    if layout == 'oihw':
+        return Cin * K * K, K * K
+    if layout == 'iohw':
+        return K * K, Cout * K * K
+    raise ValueError(layout)
 
 
 def ctx_loss(score, target, losses=('crossentropy',), lmb=1.0, grad=True, res=None, cnt=None, g=None):
@@ -1937,10 +1965,7 @@ def ctx_loss(score, target, losses=('crossentropy',), lmb=1.0, grad=True, res=No
         if name not in LOSS_FLAGS:
             raise ValueError('ctx_loss: loss %r is not built (crossentropy, squared_error)' % (name,))
         flags |= LOSS_FLAGS[name]
-    lib = _lib.load()
-    nblk = lib.iiseg_ctx_loss_partials(B, H, W)
-    if nblk < 0:
-        check(nblk, 'iiseg_ctx_loss_partials')
+    nblk = _count(_lib.load().iiseg_ctx_loss_partials(B, H, W), 'iiseg_ctx_loss_partials')
     partial = _workspace('bn', 2 * nblk, score.device)
     f64 = torch.float64
     if cnt is None:
@@ -1963,13 +1988,7 @@ def wgrad_desc(x_shape, Cout, K, dil, layout, gz_place=None):
     d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.dil = int(B), int(Cin), int(Cout), int(H), int(W), int(K), int(dil)
     OH, OW = H - dil * (K - 1), W - dil * (K - 1)
     d.gz_H, d.gz_W, d.gz_y0, d.gz_x0 = (OH, OW, 0, 0) if gz_place is None else tuple(int(v) for v in gz_place)
-    kk = K * K
-    if layout == 'oihw':
-        d.so, d.sc = Cin * kk, kk
-    elif layout == 'iohw':
-        d.so, d.sc = kk, Cout * kk
-    else:
-        raise ValueError(layout)
+    d.so, d.sc = layout_strides(Cin, Cout, K, layout)
     return d
 
 
@@ -1988,18 +2007,15 @@ def conv_small_wgrad(x, gout, out, dW, db, dil=1, layout='oihw', gz=None, gz_off
             or db.numel() != Cout:
         raise RuntimeError('conv_small_wgrad: shapes x %s gout %s dW %s' % (tuple(x.shape), tuple(gout.shape),
                                                                             tuple(dW.shape)))
-    lib = _lib.load()
-    nslab = lib.iiseg_conv_small_wgrad_partials(C.byref(d), dW.element_size())
-    if nslab < 0:
-        check(nslab, 'iiseg_conv_small_wgrad_partials')
+    nslab = _count(_lib.load().iiseg_conv_small_wgrad_partials(C.byref(d), dW.element_size()),
+                   'iiseg_conv_small_wgrad_partials')
     slab = _workspace(_SUFFIX[dt], nslab * (dW.numel() + Cout), x.device)
     kern = 'conv_small_wgrad_kernel'
     _launch(kern, 2.0 * dW.numel() * x.shape[0] * OH * OW, _fn('conv_small_wgrad', dt), C.byref(d), _ptr(x, dt),
             _ptr(gout, dt), _ptr(out, dt), _ptr(gz, dt), _ptr(slab, dt), _ptr(dW, dt), _ptr(db, dt))
     if CONV_PROFILE is not None:
         # byte model: x and g_out read, g_z written, once each
-        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
-            float(dW.element_size()) * (x.shape[1] + 2 * Cout) * x.shape[0] * x.shape[2] * x.shape[3]
+        _add_bytes(kern, float(dW.element_size()) * (x.shape[1] + 2 * Cout) * x.shape[0] * x.shape[2] * x.shape[3])
 
 
 def opt_step(kind, p, g, s1, s2, lr, state, grid=False):
@@ -2023,12 +2039,7 @@ def conv_wgrad_desc(x_shape, Cout, pad, Cin_tot=None, ci0=0, layout='oihw'):
     d = _lib.ConvWgradDesc()
     d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin, int(Cout), H, W, 3, int(pad)
     d.ci0, d.Cin_tot = int(ci0), Cin_tot
-    if layout == 'oihw':
-        d.so, d.sc = Cin_tot * 9, 9
-    elif layout == 'iohw':
-        d.so, d.sc = 9, int(Cout) * 9
-    else:
-        raise ValueError(layout)
+    d.so, d.sc = layout_strides(Cin_tot, int(Cout), 3, layout)
     return d
 
 
@@ -2046,32 +2057,23 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw'):
     if tuple(gz.shape) != (B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
         raise RuntimeError('conv_wgrad: shapes x %s gz %s dW %s' % (tuple(x.shape), tuple(gz.shape), tuple(dW.shape)))
     d = conv_wgrad_desc(tuple(x.shape), Cout, pad, Cin_tot, ci0, layout)
-    lib = _lib.load()
-    n = lib.iiseg_conv_wgrad_workspace_elems(C.byref(d), dW.element_size())
-    if n < 0:
-        check(int(n), 'iiseg_conv_wgrad_workspace_elems')
+    n = _count(_lib.load().iiseg_conv_wgrad_workspace_elems(C.byref(d), dW.element_size()),
+               'iiseg_conv_wgrad_workspace_elems')
     ws = _workspace(_SUFFIX[dt], n, x.device) if n else None
     kern = 'conv_wgrad_kernel'
     _launch(kern, 2.0 * Cin * Cout * 9 * B * OH * OW, _fn('conv_wgrad', dt), C.byref(d), _ptr(x, dt), _ptr(gz, dt),
             _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))
     if CONV_PROFILE is not None:
         # byte model: x and g_z read once, the slabs written and read once
-        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + \
-            float(dW.element_size()) * (x.numel() + gz.numel() + 2 * n)
+        _add_bytes(kern, float(dW.element_size()) * (x.numel() + gz.numel() + 2 * n))
 
 
 # ---- true-gradient refinement through the context-module DAE (csrc/ctx_grad.hip) ----
 def _param_strides(Wshape, layout):
-    """(Cin, Cout, K, so, sc) of a layer parameter in its own layout (include/iiseg.h: element (co, ci, tap) at
-    co so + ci sc + tap)."""
+    """(Cin, Cout, K, so, sc) of a layer parameter in its own layout."""
+    Cout, Cin = (int(Wshape[0]), int(Wshape[1])) if layout == 'oihw' else (int(Wshape[1]), int(Wshape[0]))
     K = int(Wshape[2])
-    if layout == 'oihw':
-        Cout, Cin = int(Wshape[0]), int(Wshape[1])
-        return Cin, Cout, K, Cin * K * K, K * K
-    if layout == 'iohw':
-        Cin, Cout = int(Wshape[0]), int(Wshape[1])
-        return Cin, Cout, K, K * K, Cout * K * K
-    raise ValueError(layout)
+    return (Cin, Cout, K) + layout_strides(Cin, Cout, K, layout)
 
 
 def dgrad_desc(gout_shape, Wshape, dil, layout, out_place=None, window=None, ci=None, gx_place=None):
@@ -2116,17 +2118,14 @@ def conv_small_dgrad(gout, out, W, dil=1, layout='iohw', out_off=(0, 0), window=
             raise RuntimeError('dgrad: gx %s' % (tuple(gx.shape),))
         d.gx_C, d.gx_H, d.gx_W = gx.shape[1], gx.shape[2], gx.shape[3]
         d.gx_c0, d.gx_y0, d.gx_x0 = (int(v) for v in gx_off)
-    lib = _lib.load()
-    nblk = lib.iiseg_conv_small_dgrad_blocks(C.byref(d))
-    if nblk < 0:
-        check(nblk, 'iiseg_conv_small_dgrad_blocks')
+    _count(_lib.load().iiseg_conv_small_dgrad_blocks(C.byref(d)), 'iiseg_conv_small_dgrad_blocks')
     kern = 'conv_small_dgrad_kernel'
     _launch(kern, 2.0 * d.nci * Cout * d.K * d.K * B * d.WH * d.WW, _fn('conv_small_dgrad', dt), C.byref(d),
             _ptr(gout, dt), _ptr(out, dt), _ptr(W, dt), _ptr(gx, dt))
     if CONV_PROFILE is not None:
         # byte model: g_out (and out) read once, the window of g_x written
-        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + float(gout.element_size()) * B * \
-            ((2 if out is not None else 1) * Cout * OH * OW + d.nci * d.WH * d.WW)
+        _add_bytes(kern, float(gout.element_size()) * B *
+                   ((2 if out is not None else 1) * Cout * OH * OW + d.nci * d.WH * d.WW))
     return gx
 
 
@@ -2147,6 +2146,6 @@ def ctx_grad_head(score, y, out6, W7, layout='iohw', want_gs=False):
     _launch(kern, 2.0 * Cin * Cc * B * H * W, _fn('ctx_grad_head', dt), _ptr(score, dt), _ptr(y, dt), _ptr(out6, dt),
             _ptr(W7, dt), so, sc, _ptr(gs, dt), _ptr(g6, dt), B, Cc, Cin, H, W)
     if CONV_PROFILE is not None:
-        KERNEL_BYTES[kern] = KERNEL_BYTES.get(kern, 0.0) + float(y.element_size()) * B * H * W * \
-            ((3 if want_gs else 2) * Cc + (2 if out6 is not None else 1) * Cin)
+        _add_bytes(kern, float(y.element_size()) * B * H * W *
+                   ((3 if want_gs else 2) * Cc + (2 if out6 is not None else 1) * Cin))
     return (g6, gs) if want_gs else g6

@@ -13,8 +13,6 @@ import torch
 
 from . import ops
 from .api import Metrics
-from .contextmod import ContextModDAE
-from .dae import StandardDAE
 
 SUPPORTED_LOSSES = ('crossentropy', 'squared_error')
 
@@ -64,15 +62,11 @@ class DAETrainer:
 
     def __init__(self, fcn, dae, n_classes, void_labels=(11,), optimizer='rmsprop', learning_rate=1e-4,
                  training_loss=('crossentropy',), lmb=1.0, noise=0.0, seed=None):
-        self.standard = isinstance(dae, StandardDAE)
-        if self.standard:
-            if not dae.trainable:
-                raise NotImplementedError('training a StandardDAE needs one built with trainable=True')
-            check_supported('standard', training_loss, optimizer=optimizer, dae_dict={'concat_h': dae.concat_h})
-        elif isinstance(dae, ContextModDAE):
-            check_supported('contextmod', training_loss, optimizer=optimizer)
-        else:
-            raise NotImplementedError("training is built for dae kinds 'contextmod' and 'standard'")
+        kind = getattr(dae, 'kind', None)
+        if kind == 'standard' and not dae.trainable:
+            raise NotImplementedError('training a StandardDAE needs one built with trainable=True')
+        check_supported(kind, training_loss, optimizer=optimizer, dae_dict={'concat_h': getattr(dae, 'concat_h', ())})
+        self.grid = kind == 'standard'     # millions of parameters: the many-workgroup optimizer step, same bits
         if list(void_labels) not in ([n_classes], []):
             raise NotImplementedError('void_labels must be [n_classes] (the last target channel) or empty')
         self.fcn, self.dae, self.C = fcn, dae, int(n_classes)
@@ -94,24 +88,15 @@ class DAETrainer:
         """lr <- lr * factor on the device (train_dae.py:424)."""
         self.lr.mul_(float(factor))
 
-    def _h(self, H):
-        if self.standard:                 # a list of h maps, one per concat point
-            return list(H) if isinstance(H, (list, tuple)) else [H]
-        if isinstance(H, (list, tuple)):
-            if len(H) != 1:
-                raise ValueError('expected 1 h tensor, got %d' % len(H))
-            return H[0]
-        return H
-
     def train_step(self, H, Y_in, T, eps=None):
-        """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64)."""
+        """One step of train_fn (H: the h maps, one per concat point, or the only one): returns the loss BEFORE
+        the update as a device scalar (float64)."""
         dae = self.dae
-        score = dae.forward_train(self._h(H), Y_in, noise=self.noise, generator=self.generator, eps=eps)
+        score = dae.forward_train(H if isinstance(H, (list, tuple)) else [H], Y_in, noise=self.noise,
+                                  generator=self.generator, eps=eps)
         res, g, _ = ops.ctx_loss(score, T, self.losses, self.lmb, grad=True)
         dae.backward(g)
-        # (the standard DAE has millions of parameters: the many-workgroup form, same bits)
-        ops.opt_step(self.optimizer, dae.flat, dae._gflat, self.s1, self.s2, self.lr, self.state,
-                     grid=self.standard)
+        ops.opt_step(self.optimizer, dae.flat, dae.gflat, self.s1, self.s2, self.lr, self.state, grid=self.grid)
         dae.refresh()
         return res[0]
 
@@ -119,7 +104,7 @@ class DAETrainer:
         """val_fn (deterministic: no noise): (loss, Metrics, mse) -- loss and mse device scalars, the
         Jaccard counts in the Metrics accumulators (api.Metrics.result() -> acc, jacc(2, C), mse)."""
         dae = self.dae
-        score = dae.forward_train(self._h(H), Y_in, noise=0.0)
+        score = dae.forward_train(H if isinstance(H, (list, tuple)) else [H], Y_in, noise=0.0)
         res, _, _ = ops.ctx_loss(score, T, self.losses, self.lmb, grad=False)
         pred = ops.crop_softmax(score, score.shape[2], score.shape[3], off=(0, 0))
         m = Metrics(self.C, score.device)

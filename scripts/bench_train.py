@@ -49,7 +49,7 @@ def one(B, H, W, dt, steps, warmup, hbm_tbs):
     for _ in range(steps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        dae.forward_train(X, Y)
+        dae.forward_train([X], Y)
         e1.record()
         e1.synchronize()
         fwd.append(e0.elapsed_time(e1))
@@ -59,11 +59,11 @@ def one(B, H, W, dt, steps, warmup, hbm_tbs):
     ops.CONV_PROFILE = prof = []
     try:
         n_fwd = None
-        score = dae.forward_train(X, Y, noise=0.1, generator=tr.generator)
+        score = dae.forward_train([X], Y, noise=0.1, generator=tr.generator)
         n_fwd = len(prof)
         res, g, _ = ops.ctx_loss(score, L, tr.losses, tr.lmb)
         dae.backward(g)
-        ops.opt_step(tr.optimizer, dae.flat, dae._gflat, tr.s1, tr.s2, tr.lr, tr.state)
+        ops.opt_step(tr.optimizer, dae.flat, dae.gflat, tr.s1, tr.s2, tr.lr, tr.state)
         torch.cuda.synchronize()
     finally:
         ops.CONV_PROFILE = None

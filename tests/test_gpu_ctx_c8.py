@@ -321,7 +321,7 @@ def test_refusals_launch_nothing(built_lib):
         with pytest.raises(NotImplementedError, match='bf16c8'):
             dae.sqerr_backward(y, y)
         with pytest.raises(NotImplementedError, match='bf16c8'):
-            dae.forward_train(h, y)
+            dae.forward_train([h], y)
         with pytest.raises(NotImplementedError, match='bf16c8'):
             dae.backward(y)
         with pytest.raises(NotImplementedError, match='bf16c8'):

@@ -117,12 +117,24 @@ def _gpu_backward(params, h, y, T, dt, losses=('crossentropy',)):
     from iterative_inference_segm_amd import ops
     from iterative_inference_segm_amd.contextmod import ContextModDAE
     dae = ContextModDAE(params, 11, dtype=dt)
-    score = dae.forward_train(_dev(h, dt), _dev(y, dt))
+    score = dae.forward_train([_dev(h, dt)], _dev(y, dt))
     res, g, _ = ops.ctx_loss(score, _dev(T, dt), losses, 1.0)
     grads = dae.backward(g)
     torch.cuda.synchronize()
     return dae, res, g, {n: (a.cpu().numpy().astype(np.float64), b.cpu().numpy().astype(np.float64))
                          for n, (a, b) in grads.items()}
+
+
+def test_forward_train_takes_the_list_of_h_and_still_the_bare_tensor(built_lib):
+    from iterative_inference_segm_amd.contextmod import ContextModDAE
+    params, h, y, _ = _net_case(1, 40, 36)                  # one image: a bare (1, 3, H, W) tensor has len 1 too
+    dt = torch.float32
+    dae = ContextModDAE(params, 11, dtype=dt)
+    hd, yd = _dev(h, dt), _dev(y, dt)
+    as_list = dae.forward_train([hd], yd).clone()
+    assert torch.equal(dae.forward_train(hd, yd), as_list) and bool(as_list.any())
+    with pytest.raises(ValueError, match='expected 1 h tensor'):
+        dae.forward_train([hd, hd], yd)
 
 
 def _rel_err(got, ref):
@@ -273,6 +285,32 @@ def test_train_step_is_deterministic_and_every_path_sees_the_new_weights(built_l
         Y, iters, _ = engine.refine([hd], yd.clone(), 0.1, 12, graph=True)
         res.append((Y.clone(), iters.clone()))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+
+
+def test_backward_after_a_training_step_runs_on_the_new_adjoint_filters(built_lib):
+    """The data-gradient layers are built by the first `backward` and rewritten by `refresh()` from the same
+    filters: after one train_step, the backward of a second step equals that of a module rebuilt from
+    `state_arrays()`, bit for bit (the `sqerr_backward` half: tests/test_gpu_ctx_grad.py,
+    test_gradient_mode_after_a_training_step_sees_the_new_weights)."""
+    from iterative_inference_segm_amd import ops
+    from iterative_inference_segm_amd.contextmod import ContextModDAE
+    params, h, y, T = _net_case(2, 40, 36)
+    dt = torch.float32
+    hd, yd, Td = _dev(h, dt), _dev(y, dt), _dev(T, dt)
+    tr = _trainer(params, dt, noise=0.1, seed=3, learning_rate=1e-2)
+    tr.train_step(hd, yd, Td)
+    assert tr.dae._adj is not None                           # built by that step, stale until refresh()
+    fresh = ContextModDAE(tr.dae.state_arrays(), 11, dtype=dt)
+    assert torch.equal(fresh.flat, tr.dae.flat)
+    assert not torch.equal(fresh.flat, _dev(R.flatten(params), dt))
+    grads = []
+    for dae in (tr.dae, fresh):
+        score = dae.forward_train([hd], yd)
+        _, g, _ = ops.ctx_loss(score, Td, ('crossentropy',), 1.0)
+        gv = dae.backward(g)
+        assert gv['conv1'][0].data_ptr() == dae.gflat.data_ptr()
+        grads.append(dae.gflat.clone())
+    assert torch.equal(grads[0], grads[1]) and bool(grads[0].any())
 
 
 # ---- 7. training works ----

@@ -242,6 +242,35 @@ def test_whole_backward_f32(built_lib, which):
     assert min(cos.values()) >= 0.999
 
 
+# the bounds of tests/test_gpu_e2e.py::test_true_gradient_mode, x (1 + max|g|)
+@pytest.mark.parametrize('prec,tol', [('f64', 1e-10), ('f32', 2e-4)])
+def test_backward_and_backward_y_are_one_walk_that_keeps_no_state(built_lib, prec, tol):
+    """On a trainable DAE (gradient layers off the Winograd form; the small model: pad 3, so the first layer's data
+    gradient is the crop at offset 2): backward, backward_y, backward again leave the same gradient buffer, and
+    backward_y is dE/dy of E = sum (r - y)^2 through the DAE (oracle/dae_grad.py)."""
+    from oracle import dae_grad as G
+    from iterative_inference_segm_amd import ops
+    dt = DT[prec]
+    params, hs, y = _model_case('small')[:3]
+    dae = _std_dae('small', params, dt)
+    yd = _dev(y, dt)
+    score = dae.forward_train([_dev(h, dt) for h in hs], yd)
+    g = ops.sqerr_softmax_bwd(score, yd, off=(0, 0))
+    dae.backward(g)
+    first = dae.gflat.clone()
+    g_thr = dae.backward_y(g, yd.shape)
+    dae.backward(g)
+    assert torch.equal(dae.gflat, first) and bool(first.any())
+    r = ops.crop_softmax(score, y.shape[2], y.shape[3], off=(0, 0))
+    torch.cuda.synchronize()
+    got = g_thr.cpu().numpy().astype(np.float64) - 2.0 * (r.cpu().numpy().astype(np.float64) - y)
+    g_ref, r_ref = G.dae_sqerr_grad(params, hs, y, **MODELS['small'][3])
+    err, scale = np.abs(got - g_ref).max(), 1 + np.abs(g_ref).max()
+    print('trainable standard DAE backward_y %s: max|g - ref| = %.3g (bound %.3g)' % (prec, err, tol * scale))
+    assert tuple(g_thr.shape) == y.shape and np.abs(g_ref).max() > 0
+    assert err <= tol * scale
+
+
 # ---- 4. training end to end (the second model) ----
 def _trainer(dt, noise=0.1, seed=1, **kw):
     from iterative_inference_segm_amd.train import DAETrainer
