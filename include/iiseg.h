@@ -142,6 +142,21 @@ int iiseg_conv_f32(void* stream, const iiseg_conv_desc* d, const float* x1, cons
  * dilated 3x3 layers, models/contextmod_dae.py:74-105) -- a scheduling fact, for profiles. */
 int iiseg_conv_small_supported(const iiseg_conv_desc* d);
 int iiseg_conv_pool_supported(const iiseg_conv_desc* d);
+
+/* Which of the direct kernels iiseg_conv_f32 runs a (planned) request on, and with which tiling: the
+ * answer of the very dispatch the launch goes through (csrc/conv_igemm.hip), for a plain call -- no fused
+ * pool, mask bytes or input BatchNorm -- with or without a skip-add and a bias.  Returns one of
+ * IISEG_CONV_KERNEL_* and fills tiles[4] = {BM, BN, pixel tiles, channel tiles}: output channels x
+ * pixels of one workgroup's tile, and the grid as pixel tiles x channel tiles.  A descriptor that
+ * iiseg_conv_f32 would refuse gives its negative iiseg_status.  Host only: no launch, no allocation,
+ * no stream work.  The answer follows the IISEG_CONV_* switches of the process and
+ * iiseg_conv_halo_seam. */
+#define IISEG_CONV_KERNEL_SMALL 1  /* conv_small_f32_kernel: vector ALU, 16 rows x 64 columns        */
+#define IISEG_CONV_KERNEL_HALO 2   /* conv_halo_f32_kernel: 3x3, TH rows x 32 columns (BN = TH * 32) */
+#define IISEG_CONV_KERNEL_HALO16 3 /* conv_halo16_f32_kernel: 3x3, at most 16 output channels        */
+#define IISEG_CONV_KERNEL_TAPS 4   /* conv_taps_f32_kernel: 1x1, 3x3, transposed 3x3 / 4x4           */
+#define IISEG_CONV_KERNEL_IGEMM 5  /* conv_igemm_f32_kernel: any filter, table-driven gather         */
+int iiseg_conv_direct_kernel(const iiseg_conv_desc* d, int has_add, int has_bias, int32_t* tiles);
 int iiseg_conv_pool_f32(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
                         const float* pre, const float* pooled, const float* wp, const int32_t* ktab,
                         const float* bias, const float* add, float* out, float* pool_out);

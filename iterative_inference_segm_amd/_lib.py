@@ -97,6 +97,7 @@ SIGNATURES = {
     'iiseg_conv_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 9),
     'iiseg_conv_small_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_pool_supported': (C.c_int, [C.POINTER(ConvDesc)]),
+    'iiseg_conv_direct_kernel': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     'iiseg_conv_pool_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 10),
     'iiseg_conv_halo_seam': (C.c_int, [C.c_int]),
     'iiseg_conv_halo_seam_launches': (_i64, []),

@@ -57,6 +57,19 @@ struct ConvParams {
     long long in_bstride;
 };
 
+// The kernel a launcher takes for a request and its tiling (include/iiseg.h, iiseg_conv_direct_kernel).
+// Every launcher of the direct kernels takes a `ConvRoute*`: when it is set, the launcher fills it in
+// at the point where it would launch, and launches nothing -- the query and the launch share one decision.
+struct ConvRoute {
+    int family;              // IISEG_CONV_KERNEL_*
+    int bm, bn;              // output channels x pixels of a workgroup's tile
+    int n_ptiles, n_mtiles;  // grid = n_ptiles * n_mtiles
+};
+inline int conv_route_set(ConvRoute* r, int family, int bm, int bn, int n_ptiles, int n_mtiles) {
+    r->family = family; r->bm = bm; r->bn = bn; r->n_ptiles = n_ptiles; r->n_mtiles = n_mtiles;
+    return 0;
+}
+
 // Tile order: the XCD that gets block b is b % 8 (round-robin dispatch, speed only), so give
 // each XCD a contiguous run of tiles and, inside a run, walk groups of 8 pixel-tiles x all
 // channel-tiles so that co-resident blocks of one XCD share both X rows and W rows in its L2.

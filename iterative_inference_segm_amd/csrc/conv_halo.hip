@@ -537,13 +537,14 @@ bool halo_seam_applies(const ConvParams& p) {
 }
 
 template <int BM, int TH, int WM, int WN>
-int launch_halo(hipStream_t s, const ConvParams& cp, bool unpool) {
+int launch_halo(hipStream_t s, const ConvParams& cp, bool unpool, ConvRoute* route) {
     ConvParams p = cp;
     const int tiles_y = (p.OH + TH - 1) / TH;
     p.n_mtiles = p.Mpad / BM;
     if (halo_seam_applies(p)) {
         const int tiles_x = (p.B * p.OW + 31) / 32;       // of a row band of all B images
         p.n_ptiles = tiles_y * tiles_x;
+        if (route) return conv_route_set(route, IISEG_CONV_KERNEL_HALO, BM, TH * 32, p.n_ptiles, p.n_mtiles);
         const int grid = p.n_ptiles * p.n_mtiles;
         if (unpool && p.mask_in)
             IISEG_LAUNCH((conv_halo_f32_kernel<BM, TH, WM, WN, true, true, true>), dim3(grid), dim3(256),
@@ -560,6 +561,7 @@ int launch_halo(hipStream_t s, const ConvParams& cp, bool unpool) {
     }
     const int tiles_x = (p.OW + 31) / 32;
     p.n_ptiles = p.B * tiles_y * tiles_x;
+    if (route) return conv_route_set(route, IISEG_CONV_KERNEL_HALO, BM, TH * 32, p.n_ptiles, p.n_mtiles);
     const int grid = p.n_ptiles * p.n_mtiles;
     if (unpool && p.mask_in)
         IISEG_LAUNCH((conv_halo_f32_kernel<BM, TH, WM, WN, true, true>), dim3(grid), dim3(256),
@@ -844,12 +846,13 @@ __global__ __launch_bounds__(256, 2) void conv_halo16_f32_kernel(const ConvParam
     }
 }
 
-int launch_halo16(hipStream_t s, const ConvParams& cp, bool unpool) {
+int launch_halo16(hipStream_t s, const ConvParams& cp, bool unpool, ConvRoute* route) {
     ConvParams p = cp;
     constexpr int TH = 8;
     const int tiles_y = (p.OH + TH - 1) / TH, tiles_x = (p.OW + 31) / 32;
     p.n_ptiles = p.B * tiles_y * tiles_x;
     p.n_mtiles = (p.Cout + 15) / 16;
+    if (route) return conv_route_set(route, IISEG_CONV_KERNEL_HALO16, 16, TH * 32, p.n_ptiles, p.n_mtiles);
     const dim3 grid(p.n_ptiles * p.n_mtiles), block(256);
 #define H16(U, D) IISEG_LAUNCH((conv_halo16_f32_kernel<TH, U, D>), grid, block, 0, s, p, tiles_y, tiles_x)
     if (p.bn_mean) {
@@ -898,12 +901,12 @@ extern "C" int iiseg_conv_halo_seam(int on) {
 
 extern "C" int64_t iiseg_conv_halo_seam_launches(void) { return (int64_t)g_seam_launches.load(); }
 
-int iiseg_launch_conv_halo(hipStream_t s, const ConvParams& p, int bm, bool unpool) {
+int iiseg_launch_conv_halo(hipStream_t s, const ConvParams& p, int bm, bool unpool, ConvRoute* route) {
     static const int h16 = getenv("IISEG_CONV_HALO16") ? atoi(getenv("IISEG_CONV_HALO16")) : 1;
-    if (h16 && p.Cout <= 16) return launch_halo16(s, p, unpool);
+    if (h16 && p.Cout <= 16) return launch_halo16(s, p, unpool, route);
     switch (bm) {
-        case 128: return launch_halo<128, 4, 2, 2>(s, p, unpool);
-        case 64: return launch_halo<64, 8, 1, 4>(s, p, unpool);
-        default: return launch_halo<32, 8, 1, 4>(s, p, unpool);
+        case 128: return launch_halo<128, 4, 2, 2>(s, p, unpool, route);
+        case 64: return launch_halo<64, 8, 1, 4>(s, p, unpool, route);
+        default: return launch_halo<32, 8, 1, 4>(s, p, unpool, route);
     }
 }

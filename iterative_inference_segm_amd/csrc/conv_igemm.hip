@@ -23,13 +23,14 @@ using namespace iiseg;
 
 // conv_taps.hip
 int iiseg_taps_cpt(int KH, int KW);
-int iiseg_launch_conv_taps(hipStream_t s, const ConvParams& p, int KH, int KW, int bm, bool unpool);
+int iiseg_launch_conv_taps(hipStream_t s, const ConvParams& p, int KH, int KW, int bm, bool unpool,
+                           ConvRoute* route);
 // conv_halo.hip: halo-tile direct 3x3 kernel
 bool iiseg_conv_halo_ok(const ConvParams& p, int KH, int KW);
-int iiseg_launch_conv_halo(hipStream_t s, const ConvParams& p, int bm, bool unpool);
+int iiseg_launch_conv_halo(hipStream_t s, const ConvParams& p, int bm, bool unpool, ConvRoute* route);
 // conv_small.hip: layers between at most 16 channels on either side, on the vector ALU
 bool iiseg_conv_small_ok(const ConvParams& p, int KH, int KW);
-int iiseg_launch_conv_small(hipStream_t s, const ConvParams& p, int KH);
+int iiseg_launch_conv_small(hipStream_t s, const ConvParams& p, int KH, ConvRoute* route);
 
 namespace {
 
@@ -397,10 +398,11 @@ extern "C" int iiseg_conv_pack_f32(void* stream, const iiseg_conv_desc* d, const
 }
 
 template <int BM, int BN, int WM, int WN>
-static int launch_conv(hipStream_t s, const ConvParams& cp, bool unpool) {
+static int launch_conv(hipStream_t s, const ConvParams& cp, bool unpool, ConvRoute* route) {
     ConvParams p = cp;
     p.n_ptiles = (p.P + BN - 1) / BN;
     p.n_mtiles = p.Mpad / BM;
+    if (route) return conv_route_set(route, IISEG_CONV_KERNEL_IGEMM, BM, BN, p.n_ptiles, p.n_mtiles);
     const int grid = p.n_ptiles * p.n_mtiles;
     static const int dyn = getenv("IISEG_DEBUG_DYNLDS") ? atoi(getenv("IISEG_DEBUG_DYNLDS")) : 0;
     static const int nog = getenv("IISEG_DEBUG_NOGATHER") ? 1 : 0;
@@ -452,6 +454,8 @@ static int conv_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
                     const float* bias, const float* add, float* out, float* pool_out,
                     const BnIn* bn, const unsigned char* mask_in = nullptr,
                     unsigned char* mask_out = nullptr);
+static void conv_geometry(const iiseg_conv_desc* d, ConvParams& p);
+static int conv_dispatch(hipStream_t s, const iiseg_conv_desc* d, const ConvParams& p, ConvRoute* route);
 
 extern "C" int iiseg_conv_mask_supported(const iiseg_conv_desc* d) {
     if (!d || check_desc(d)) return 0;
@@ -518,13 +522,6 @@ static int conv_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
     p.x1 = x1; p.x2 = x2; p.pre = pre; p.pooled = pooled; p.wp = wp;
     p.ktab = reinterpret_cast<const int4*>(ktab);
     p.bias = bias; p.add = add; p.out = out;
-    p.B = d->B; p.C1 = d->C1; p.C2 = d->C2; p.H = d->H; p.W = d->W;
-    p.h2 = d->H / 2; p.w2 = d->W / 2;
-    p.Cout = d->Cout; p.OH = d->OH; p.OW = d->OW; p.oy0 = d->oy0; p.ox0 = d->ox0;
-    p.AH = d->AH; p.AW = d->AW; p.ay0 = d->ay0; p.ax0 = d->ax0;
-    p.Kpad = d->Kpad; p.Mpad = d->Mpad;
-    p.pad = d->pad; p.dil = d->dil;
-    p.debug_nogather = 0;
     p.pool = pool_out;
     p.mask_in = mask_in; p.mask_out = mask_out;
     p.bn_beta = bn ? bn->beta : nullptr;
@@ -532,6 +529,19 @@ static int conv_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
     p.bn_mean = bn ? bn->mean : nullptr;
     p.bn_inv_std = bn ? bn->inv_std : nullptr;
     p.in_bstride = bn ? bn->bstride : 0;
+    conv_geometry(d, p);
+    return conv_dispatch((hipStream_t)stream, d, p, nullptr);
+}
+
+// The launch parameters that come from the descriptor alone (the operands are the caller's).
+static void conv_geometry(const iiseg_conv_desc* d, ConvParams& p) {
+    p.B = d->B; p.C1 = d->C1; p.C2 = d->C2; p.H = d->H; p.W = d->W;
+    p.h2 = d->H / 2; p.w2 = d->W / 2;
+    p.Cout = d->Cout; p.OH = d->OH; p.OW = d->OW; p.oy0 = d->oy0; p.ox0 = d->ox0;
+    p.AH = d->AH; p.AW = d->AW; p.ay0 = d->ay0; p.ax0 = d->ax0;
+    p.Kpad = d->Kpad; p.Mpad = d->Mpad;
+    p.pad = d->pad; p.dil = d->dil;
+    p.debug_nogather = 0;
     p.pool_H = (d->H + 2 * d->pad - d->dil * (d->KH - 1)) / 2;
     p.pool_W = (d->W + 2 * d->pad - d->dil * (d->KW - 1)) / 2;
     p.out_ctot = d->out_ctot ? d->out_ctot : d->Cout;
@@ -544,8 +554,17 @@ static int conv_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
     p.P = d->B * d->OH * d->OW;
     p.n_ptiles = p.n_mtiles = 0;
     p.relu = (d->flags & IISEG_CONV_RELU) ? 1 : 0;
+}
 
-    hipStream_t s = (hipStream_t)stream;
+// THE choice among the direct kernels, for a validated request with its parameters `p` filled in.  The order
+// below is the precedence.  With `route` set, the launcher that is reached reports its kernel and tiling
+// there and launches nothing (iiseg_conv_direct_kernel).
+static int conv_dispatch(hipStream_t s, const iiseg_conv_desc* d, const ConvParams& p, ConvRoute* route) {
+    const bool unpool = (d->flags & IISEG_CONV_UNPOOL) != 0;
+    const float* const add = p.add;
+    const float* const pool_out = p.pool;
+    const bool bn = p.bn_mean != nullptr;
+    const unsigned char *const mask_in = p.mask_in, *const mask_out = p.mask_out;
     // IISEG_CONV_HALO: 0 = never, 1 = 3x3 layers with Cout < 256 (default), 2 = every 3x3 layer
     static const int halo = getenv("IISEG_CONV_HALO") ? atoi(getenv("IISEG_CONV_HALO")) : 1;
     const bool use_halo = halo && (halo > 1 || d->Cout < 256) && iiseg_conv_halo_ok(p, d->KH, d->KW);
@@ -554,13 +573,34 @@ static int conv_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
     if ((mask_in || mask_out) && !use_halo) return IISEG_ERR_UNSUPPORTED;
     // tiny layers (context module: 11 -> 11, dilated): HBM-bound, half of an MFMA tile would be padding
     if (!unpool && !bn && !pool_out && iiseg_conv_small_ok(p, d->KH, d->KW))
-        return iiseg_launch_conv_small(s, p, d->KH);
-    if (use_halo) return iiseg_launch_conv_halo(s, p, pick_bm(d->Cout), unpool);
+        return iiseg_launch_conv_small(s, p, d->KH, route);
+    if (use_halo) return iiseg_launch_conv_halo(s, p, pick_bm(d->Cout), unpool, route);
     if (iiseg_taps_cpt(d->KH, d->KW) > 0)
-        return iiseg_launch_conv_taps(s, p, d->KH, d->KW, pick_bm(d->Cout), unpool);
+        return iiseg_launch_conv_taps(s, p, d->KH, d->KW, pick_bm(d->Cout), unpool, route);
     switch (pick_bm(d->Cout)) {
-        case 128: return launch_conv<128, 128, 2, 2>(s, p, unpool);
-        case 64: return launch_conv<64, 256, 1, 4>(s, p, unpool);
-        default: return launch_conv<32, 256, 1, 4>(s, p, unpool);
+        case 128: return launch_conv<128, 128, 2, 2>(s, p, unpool, route);
+        case 64: return launch_conv<64, 256, 1, 4>(s, p, unpool, route);
+        default: return launch_conv<32, 256, 1, 4>(s, p, unpool, route);
     }
+}
+
+extern "C" int iiseg_conv_direct_kernel(const iiseg_conv_desc* d, int has_add, int has_bias, int32_t* tiles) {
+    int st = check_desc(d);
+    if (st) return st;
+    if (!tiles) return IISEG_ERR_NULL;
+    if ((d->flags & IISEG_CONV_UNPOOL) && d->C2 != 0) return IISEG_ERR_UNSUPPORTED;
+    if (has_add && (d->AH < d->ay0 + d->OH || d->AW < d->ax0 + d->OW || d->ay0 < 0 || d->ax0 < 0))
+        return IISEG_ERR_SHAPE;
+    ConvParams p = {};
+    // operands count only by their presence here: nothing is read through them, nothing is launched
+    const float* const given = reinterpret_cast<const float*>(16);
+    p.out = const_cast<float*>(given);
+    p.add = has_add ? given : nullptr;
+    p.bias = has_bias ? given : nullptr;
+    conv_geometry(d, p);
+    ConvRoute r = {};
+    st = conv_dispatch(nullptr, d, p, &r);
+    if (st) return st;
+    tiles[0] = r.bm; tiles[1] = r.bn; tiles[2] = r.n_ptiles; tiles[3] = r.n_mtiles;
+    return r.family;
 }

@@ -162,8 +162,9 @@ __global__ __launch_bounds__(256) void conv_small_f32_kernel(const ConvParams p,
 }
 
 template <int T>
-int launch_small(hipStream_t s, const ConvParams& p) {
+int launch_small(hipStream_t s, const ConvParams& p, ConvRoute* route) {
     const int tiles_y = (p.OH + 15) / 16, tiles_x = (p.OW + 63) / 64;
+    if (route) return conv_route_set(route, IISEG_CONV_KERNEL_SMALL, 16, 16 * 64, p.B * tiles_y * tiles_x, 1);
     const dim3 grid(p.B * tiles_y * tiles_x), block(256);
     const int cop = (p.Cout + 3) / 4 * 4;
     switch (cop) {
@@ -382,8 +383,8 @@ bool iiseg_conv_small_ok(const ConvParams& p, int KH, int KW) {
     return true;
 }
 
-int iiseg_launch_conv_small(hipStream_t s, const ConvParams& p, int KH) {
-    return KH == 3 ? launch_small<9>(s, p) : launch_small<1>(s, p);
+int iiseg_launch_conv_small(hipStream_t s, const ConvParams& p, int KH, ConvRoute* route) {
+    return KH == 3 ? launch_small<9>(s, p, route) : launch_small<1>(s, p, route);
 }
 
 extern "C" int iiseg_ctx_tail_partials(int32_t H, int32_t W) {

@@ -301,10 +301,11 @@ __global__ __launch_bounds__(WM * WN * 64, (UNPOOL || BN > 128) ? 2 : 4) void co
 }
 
 template <int BM, int BN, int WM, int WN, int KH, int KW, int CPT>
-int launch_taps(hipStream_t s, const ConvParams& cp, bool unpool) {
+int launch_taps(hipStream_t s, const ConvParams& cp, bool unpool, ConvRoute* route) {
     ConvParams p = cp;
     p.n_ptiles = (p.P + BN - 1) / BN;
     p.n_mtiles = p.Mpad / BM;
+    if (route) return conv_route_set(route, IISEG_CONV_KERNEL_TAPS, BM, BN, p.n_ptiles, p.n_mtiles);
     const int grid = p.n_ptiles * p.n_mtiles;
     static const int dma = getenv("IISEG_CONV_DMA") ? atoi(getenv("IISEG_CONV_DMA")) : 1;
     if (unpool)
@@ -329,28 +330,29 @@ int iiseg_taps_cpt(int KH, int KW) {
     return 0;
 }
 
-int iiseg_launch_conv_taps(hipStream_t s, const ConvParams& p, int KH, int KW, int bm, bool unpool) {
+int iiseg_launch_conv_taps(hipStream_t s, const ConvParams& p, int KH, int KW, int bm, bool unpool,
+                           ConvRoute* route) {
     if (KH == 3 && KW == 3) {
         if (!unpool && p.Mpad % 256 == 0 && p.Cout >= 256)
-            return launch_taps<256, 128, 4, 2, 3, 3, 2>(s, p, unpool);
+            return launch_taps<256, 128, 4, 2, 3, 3, 2>(s, p, unpool, route);
         switch (bm) {
-            case 128: return launch_taps<128, 128, 2, 2, 3, 3, 2>(s, p, unpool);
-            case 64: return launch_taps<64, 256, 1, 4, 3, 3, 2>(s, p, unpool);
-            default: return launch_taps<32, 256, 1, 4, 3, 3, 2>(s, p, unpool);
+            case 128: return launch_taps<128, 128, 2, 2, 3, 3, 2>(s, p, unpool, route);
+            case 64: return launch_taps<64, 256, 1, 4, 3, 3, 2>(s, p, unpool, route);
+            default: return launch_taps<32, 256, 1, 4, 3, 3, 2>(s, p, unpool, route);
         }
     }
     if (KH == 1 && KW == 1) {
         switch (bm) {
-            case 128: return launch_taps<128, 128, 2, 2, 1, 1, 16>(s, p, unpool);
-            case 64: return launch_taps<64, 256, 1, 4, 1, 1, 16>(s, p, unpool);
-            default: return launch_taps<32, 256, 1, 4, 1, 1, 16>(s, p, unpool);
+            case 128: return launch_taps<128, 128, 2, 2, 1, 1, 16>(s, p, unpool, route);
+            case 64: return launch_taps<64, 256, 1, 4, 1, 1, 16>(s, p, unpool, route);
+            default: return launch_taps<32, 256, 1, 4, 1, 1, 16>(s, p, unpool, route);
         }
     }
     if (KH == 4 && KW == 4) {
         switch (bm) {
-            case 128: return launch_taps<128, 128, 2, 2, 4, 4, 2>(s, p, unpool);
-            case 64: return launch_taps<64, 128, 2, 2, 4, 4, 2>(s, p, unpool);
-            default: return launch_taps<32, 128, 1, 4, 4, 4, 2>(s, p, unpool);
+            case 128: return launch_taps<128, 128, 2, 2, 4, 4, 2>(s, p, unpool, route);
+            case 64: return launch_taps<64, 128, 2, 2, 4, 4, 2>(s, p, unpool, route);
+            default: return launch_taps<32, 128, 1, 4, 4, 4, 2>(s, p, unpool, route);
         }
     }
     return IISEG_ERR_UNSUPPORTED;

@@ -36,15 +36,19 @@ def conv_tol(ref, K):
     return 2e-6 * np.sqrt(K) * (1.0 + np.abs(ref).max())
 
 
+# Where each case runs with the default switches (test_host_conv_dispatch.py records it, OPS_CONV_CASES in
+# conv_fallback_cases.py): mostly the kernels that were put in front of the first two since these cases
+# were written.  conv_igemm_f32_kernel, conv_taps_f32_kernel and the split-K GEMM with S > 1 have their own
+# shapes in test_gpu_conv_fallbacks.py.
 CONV_CASES = [
-    # B, Cin, H, W, Cout, k, pad, dil, relu   (covers BM=32/64/128 variants, ragged tiles)
-    (2, 3, 17, 19, 11, 3, 1, 1, False),
-    (1, 11, 20, 20, 64, 3, 5, 1, True),     # big pad, BM=64
-    (3, 40, 13, 9, 130, 3, 1, 1, True),     # BM=128, 2 m-tiles, ragged Cout
-    (2, 16, 9, 9, 200, 7, 0, 1, True),      # 7x7 valid (fc6-like)
-    (2, 70, 7, 7, 33, 1, 0, 1, True),       # 1x1, BM=64
-    (1, 11, 40, 36, 11, 3, 0, 4, False),    # dilated, valid (contextmod-like)
-    (1, 5, 300, 7, 12, 3, 1, 1, False),     # many pixel tiles, tall image
+    # B, Cin, H, W, Cout, k, pad, dil, relu
+    (2, 3, 17, 19, 11, 3, 1, 1, False),     # 16-row halo kernel
+    (1, 11, 20, 20, 64, 3, 5, 1, True),     # big pad; halo kernel, BM=64
+    (3, 40, 13, 9, 130, 3, 1, 1, True),     # halo kernel, BM=128, 2 m-tiles, ragged Cout
+    (2, 16, 9, 9, 200, 7, 0, 1, True),      # 7x7 valid (fc6-like): im2col + GEMM, S = 1
+    (2, 70, 7, 7, 33, 1, 0, 1, True),       # 1x1 on the static-tap kernel, BM=64
+    (1, 11, 40, 36, 11, 3, 0, 4, False),    # dilated, valid (contextmod-like): conv_small on the vector ALU
+    (1, 5, 300, 7, 12, 3, 1, 1, False),     # many pixel tiles, tall image; 16-row halo kernel
 ]
 
 
