@@ -79,15 +79,20 @@ __global__ __launch_bounds__(256) void refine_update_kernel(const T* __restrict_
     store_column<CMAX, T>(ry, act ? t.po : T_OOB, PB, C, yv);
     const T nrm = t.inb ? sqrt_t(ss) : (T)0;  // np.linalg.norm(grad, axis=1), :275
     // bf16 C8 copy of the updated map for the next DAE forward (mma='bf16c8': saves the
-    // nchw_to_c8 pass per step); chunk j = channels 8 j .. 8 j + 7, zeros beyond C
+    // nchw_to_c8 pass per step); chunk j = channels 8 j .. 8 j + 7, zeros beyond C -- in every one of the
+    // C8n <= 4 chunks the host admits, also those past the CMAX channels of this instantiation
     if (y8 && t.inb) {
         const int pix = blockIdx.x * 256 + threadIdx.x;
 #pragma unroll
-        for (int j = 0; j < CMAX / 8; ++j)
+        for (int j = 0; j < 4; ++j)
             if (j < C8n) {
                 float f[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = 8 * j + e < C ? (float)yv[8 * j + e] : 0.f;
+                for (int e = 0; e < 8; ++e) {
+                    constexpr int none = CMAX - 1;     // (any index inside yv: the value is not used)
+                    const int c = 8 * j + e;
+                    f[e] = (c < CMAX && c < C) ? (float)yv[c < CMAX ? c : none] : 0.f;
+                }
                 y8[((size_t)b * C8n + j) * HW + pix] =
                     make_uint4(pack_bf16_t(f[0], f[1]), pack_bf16_t(f[2], f[3]), pack_bf16_t(f[4], f[5]),
                                pack_bf16_t(f[6], f[7]));
