@@ -11,9 +11,12 @@
 namespace {
 
 // stats, stage 1: block (chunk, channel) reduces its slice of the B*HW elements of one channel to
-// (sum, sum of squares) in fp64; stage 2: one thread per channel adds the NCHUNK partials in a
-// fixed order (deterministic, no atomics) and writes mean / inv_std.  (A single workgroup per
+// (sum, sum of squares) of x - K in fp64; stage 2: one thread per channel adds the NCHUNK partials
+// in a fixed order (deterministic, no atomics) and writes mean / inv_std.  (A single workgroup per
 // channel left 240 of the 256 CUs idle for the 16-channel tensors of FC-DenseNet.)
+// K is the channel's pivot, its first element of image 0: the one-pass variance ss / n - (s / n)^2
+// cancels (mean - K)^2 against the spread, not mean^2 -- with K = 0 a channel of mean 100 and std
+// 0.01 lost eight of float64's sixteen digits, and the float64 path is held to 1e-12.
 constexpr int BN_NCHUNK = 64;
 
 template <typename T>
@@ -24,10 +27,11 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
     const size_t n = (size_t)B * HW;
     const size_t per = (n + BN_NCHUNK - 1) / BN_NCHUNK;
     const size_t lo = (size_t)chunk * per, hi = lo + per < n ? lo + per : n;
+    const double pivot = (double)x[(size_t)c * HW];
     double s = 0.0, ss = 0.0;
     for (size_t i = lo + threadIdx.x; i < hi; i += 256) {
         const size_t b = i / HW, r = i - b * HW;
-        const double v = (double)x[b * bstride + (size_t)c * HW + r];
+        const double v = (double)x[b * bstride + (size_t)c * HW + r] - pivot;
         s += v;
         ss += v * v;
     }
@@ -45,8 +49,9 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
 }
 
 template <typename T>
-__global__ void bn_stats_finalize_kernel(const double* __restrict__ partial, int C, double n,
-                                         double eps, T* __restrict__ mean, T* __restrict__ inv_std) {
+__global__ void bn_stats_finalize_kernel(const double* __restrict__ partial, const T* __restrict__ x,
+                                         int HW, int C, double n, double eps, T* __restrict__ mean,
+                                         T* __restrict__ inv_std) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double s = 0.0, ss = 0.0;
@@ -54,10 +59,10 @@ __global__ void bn_stats_finalize_kernel(const double* __restrict__ partial, int
         s += partial[((size_t)c * BN_NCHUNK + k) * 2 + 0];
         ss += partial[((size_t)c * BN_NCHUNK + k) * 2 + 1];
     }
-    const double m = s / n;
+    const double m = s / n;                    // mean of x - pivot
     double var = ss / n - m * m;
     if (var < 0.0) var = 0.0;
-    mean[c] = (T)m;
+    mean[c] = (T)((double)x[(size_t)c * HW] + m);
     inv_std[c] = (T)(1.0 / sqrt(var + eps));
 }
 
@@ -124,7 +129,7 @@ int bn_stats(void* stream, const T* x, int64_t bstride, int32_t B, int32_t C, in
     IISEG_LAUNCH(bn_stats_kernel<T>, dim3(BN_NCHUNK, C), dim3(256), 0, (hipStream_t)stream, x,
                        bstride, B, HW, workspace);
     IISEG_LAUNCH(bn_stats_finalize_kernel<T>, dim3((C + 63) / 64), dim3(64), 0,
-                       (hipStream_t)stream, workspace, C, (double)B * HW, eps, mean, inv_std);
+                       (hipStream_t)stream, workspace, x, HW, C, (double)B * HW, eps, mean, inv_std);
     return iiseg_check_launch();
 }
 

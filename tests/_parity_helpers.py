@@ -1,5 +1,8 @@
 """Shared pieces of the full-size GPU parity tests (fp32 HIP path vs the float64 oracle where the
 DePool2D equality masks make strict free-running parity a float64-only property)."""
+import contextlib
+from unittest import mock
+
 import numpy as np
 import torch
 
@@ -116,3 +119,76 @@ def assert_within_reference_sensitivity(ii32, ii64, o32, o64, steps, step=0.1, f
         assert s_got[1] <= 2.0 * max(s_ref[1], 1e-7) and s_got[0] >= s_ref[0] - 0.05, (label, n, s_ref, s_got)
         out.append((n, s_ref, s_got))
     return out
+
+
+# ---- placement of the edge tests (test_gpu_tail_edges.py, test_gpu_bn_pool_deconv_edges.py) -------------------
+GUARD = 4096
+SENTINEL = -9          # no result is -9: maps lie in [-4, 4], counts, norms and iteration counts are >= 0
+_INT_VIEW = {torch.float32: torch.int32, torch.float64: torch.int64, torch.bfloat16: torch.int16,
+             torch.int32: torch.int32, torch.int64: torch.int64, torch.uint8: torch.uint8}
+
+
+def _sentinel(dtype):
+    # (a mask byte is at most 15: the sentinel's low byte, 247, serves the uint8 tensors)
+    return SENTINEL & 0xFF if dtype == torch.uint8 else SENTINEL
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and \
+        torch.equal(a.contiguous().view(_INT_VIEW[a.dtype]), b.contiguous().view(_INT_VIEW[b.dtype]))
+
+
+class Placed:
+    """Hands out device tensors that are views into the middle of sentinel-filled flat allocations, keeps copies
+    of the read-only inputs, and checks both afterwards."""
+
+    def __init__(self):
+        self.flats, self.inputs, self.blank = [], [], []
+
+    def out(self, shape, dtype, init=None):
+        n = int(np.prod(shape))
+        flat = torch.full((n + 2 * GUARD,), _sentinel(dtype), dtype=dtype, device='cuda')
+        view = flat[GUARD:GUARD + n].view(tuple(shape))
+        if init is not None:
+            view.copy_(init if isinstance(init, torch.Tensor) else torch.from_numpy(np.array(init)))
+        self.flats.append((flat, n))
+        if init is None:
+            self.blank.append(flat)
+        return view
+
+    def inp(self, a, dtype=torch.float32):
+        t = a.cuda() if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a)).to(dtype).cuda()
+        self.inputs.append((t, t.clone()))
+        return t
+
+    def state(self, ops, B, H, W, active=None, iters=None, last_norm=None, npartial=None):
+        """A RefineState whose four tensors are placed between sentinels."""
+        st = ops.RefineState(B, H, W, 'cuda')
+        st.active = self.out((B,), torch.int32,
+                             np.ones(B, np.int32) if active is None else np.asarray(active, np.int32))
+        st.iters = self.out((B,), torch.int32,
+                            np.zeros(B, np.int32) if iters is None else np.asarray(iters, np.int32))
+        st.last_norm = self.out((B,), torch.float64,
+                                np.zeros(B) if last_norm is None else np.asarray(last_norm, np.float64))
+        st.partial = self.out((B * (st.nblk if npartial is None else npartial),), torch.float64)
+        return st
+
+    @contextlib.contextmanager
+    def allocations(self):
+        """Inside: torch.empty_like hands out placed tensors -- the wrappers that allocate their own result
+        (sqerr_softmax_bwd, depool_bwd, pool_relu_bwd, add_noise) do it with that call."""
+        with mock.patch.object(torch, 'empty_like', lambda t, **kw: self.out(t.shape, t.dtype)):
+            yield
+
+    def check(self):
+        torch.cuda.synchronize()
+        for flat, n in self.flats:
+            assert bool((flat[:GUARD] == _sentinel(flat.dtype)).all()), 'wrote in front of a tensor'
+            assert bool((flat[GUARD + n:] == _sentinel(flat.dtype)).all()), 'wrote behind a tensor'
+        for t, kept in self.inputs:
+            assert same_bits(t, kept), 'a read-only input changed'
+
+    def nothing_written(self):
+        """Every tensor handed out without initial contents still holds nothing but sentinels."""
+        torch.cuda.synchronize()
+        return all(bool((flat == _sentinel(flat.dtype)).all()) for flat in self.blank)

@@ -26,28 +26,22 @@ lane -- excepted); `tvoid >= bt` in confusion_kernel
 (every confusion case with more than one pixel); `norm <= eps` in refine_finalize_kernel (the finalize test at every
 nblk); only the first 64 partials added there (nblk 65 and 200); `pv >= 0` in pool_relu_bwd_kernel and a dropped
 fourth term in depool_bwd_kernel (every case of the kernel, the 2 x 2 'tie' map of pool_relu_bwd excepted)."""
-import contextlib
 import functools
-from unittest import mock
 
 import numpy as np
 import pytest
 import torch
 
 import tail_ref as R
+from _parity_helpers import GUARD, SENTINEL, Placed, same_bits
 from oracle import nn as onn
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096
-SENTINEL = -9          # no result is -9: maps lie in [-4, 4], counts, norms and iteration counts are >= 0
 
 DTYPES = {'f32': torch.float32, 'f64': torch.float64}
 MAP_TOL = {'f32': 2e-6, 'f64': 1e-14}
 BWD_TOL = {'f32': 5e-6, 'f64': 1e-14}
 NORM_TOL = {'f32': 1e-6, 'f64': 1e-12}
-_INT_VIEW = {torch.float32: torch.int32, torch.float64: torch.int64, torch.bfloat16: torch.int16,
-             torch.int32: torch.int32, torch.int64: torch.int64}
 
 
 @pytest.fixture(scope='module')
@@ -64,67 +58,6 @@ def dev(a, dtype=torch.float32):
 def host(t):
     torch.cuda.synchronize()
     return t.cpu().numpy()
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and \
-        torch.equal(a.contiguous().view(_INT_VIEW[a.dtype]), b.contiguous().view(_INT_VIEW[b.dtype]))
-
-
-class Placed:
-    """Hands out device tensors that are views into the middle of sentinel-filled flat allocations, keeps copies
-    of the read-only inputs, and checks both afterwards."""
-
-    def __init__(self):
-        self.flats, self.inputs, self.blank = [], [], []
-
-    def out(self, shape, dtype, init=None):
-        n = int(np.prod(shape))
-        flat = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device='cuda')
-        view = flat[GUARD:GUARD + n].view(tuple(shape))
-        if init is not None:
-            view.copy_(init if isinstance(init, torch.Tensor) else torch.from_numpy(np.array(init)))
-        self.flats.append((flat, n))
-        if init is None:
-            self.blank.append(flat)
-        return view
-
-    def inp(self, a, dtype=torch.float32):
-        t = a.cuda() if isinstance(a, torch.Tensor) else dev(a, dtype)
-        self.inputs.append((t, t.clone()))
-        return t
-
-    def state(self, ops, B, H, W, active=None, iters=None, last_norm=None, npartial=None):
-        """A RefineState whose four tensors are placed between sentinels."""
-        st = ops.RefineState(B, H, W, 'cuda')
-        st.active = self.out((B,), torch.int32,
-                             np.ones(B, np.int32) if active is None else np.asarray(active, np.int32))
-        st.iters = self.out((B,), torch.int32,
-                            np.zeros(B, np.int32) if iters is None else np.asarray(iters, np.int32))
-        st.last_norm = self.out((B,), torch.float64,
-                                np.zeros(B) if last_norm is None else np.asarray(last_norm, np.float64))
-        st.partial = self.out((B * (st.nblk if npartial is None else npartial),), torch.float64)
-        return st
-
-    @contextlib.contextmanager
-    def allocations(self):
-        """Inside: torch.empty_like hands out placed tensors -- the wrappers that allocate their own result
-        (sqerr_softmax_bwd, depool_bwd, pool_relu_bwd, add_noise) do it with that call."""
-        with mock.patch.object(torch, 'empty_like', lambda t, **kw: self.out(t.shape, t.dtype)):
-            yield
-
-    def check(self):
-        torch.cuda.synchronize()
-        for flat, n in self.flats:
-            assert bool((flat[:GUARD] == SENTINEL).all()), 'wrote in front of a tensor'
-            assert bool((flat[GUARD + n:] == SENTINEL).all()), 'wrote behind a tensor'
-        for t, kept in self.inputs:
-            assert same_bits(t, kept), 'a read-only input changed'
-
-    def nothing_written(self):
-        """Every tensor handed out without initial contents still holds nothing but sentinels."""
-        torch.cuda.synchronize()
-        return all(bool((flat == SENTINEL).all()) for flat in self.blank)
 
 
 # ---- shared tables of the column kernels (groups A and B) ------------------------------------------------------
