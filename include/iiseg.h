@@ -397,6 +397,26 @@ int iiseg_conv_c8_slice(void* stream, const iiseg_conv_desc* d, const void* x1, 
  * and convolve the result as a plain layer (LDS-DMA staging) instead of selecting through registers per tile. */
 int iiseg_unpool_c8(void* stream, const void* up, const uint8_t* mask, void* out, int BC8, int H, int W,
                     int y0, int x0, int wh, int ww);
+/* The two element-wise adjoints of the standard DAE's backward walk on C8 tensors (true-gradient refinement on
+ * the 16-bit leg; csrc/c8_grad.hip).  B images of C8n chunks (C8n even: whole 16-channel
+ * groups), pooled planes (h2, w2), a pooled-coordinate window (y0, x0, wh, ww) outside which `out` is not written.
+ *   iiseg_depool_bwd_c8   adjoint of DePool2D: out[q] = sum over k = 0..3 with bit k of the mask byte set of
+ *                         gu[2 qy + (k >> 1)][2 qx + (k & 1)], summed in fp32 from 0 in that order and rounded once
+ *                         to bf16 (RNE).  gu (B, C8n, PH, PW, 8) bf16 with PH >= 2 h2, PW >= 2 w2 (the unpaired
+ *                         last row / column of an odd map is never read); mask (B, C8n, h2, w2, 8) bytes; out
+ *                         (B, C8n, h2, w2, 8) bf16.  gate (NULL, or out's shape, bf16): the result of a channel is
+ *                         +0 where gate <= 0 (-0 included) -- iiseg_relu_gate_c8 in the same launch.
+ *   iiseg_relu_gate_c8    out = g where pooled > 0, else +0 (relu'(0) = 0); g, pooled, out (B, C8n, h2, w2, 8)
+ *                         bf16; out may be g.
+ * Max-pool + ReLU backward on C8 is the gate followed by DePool2D of the gated map under the level's own mask
+ * bytes (IISEG_CONV_UNPOOL staging of iiseg_conv_c8, or iiseg_unpool_c8).  Before any launch: NULL operands
+ * IISEG_ERR_NULL; non-positive sizes, odd C8n, a window outside the planes, PH < 2 h2 or PW < 2 w2
+ * IISEG_ERR_SHAPE; tensors not 16-byte (mask: 8-byte) aligned IISEG_ERR_ALIGN; out aliasing gu / gate
+ * (depool_bwd) or pooled (relu_gate) IISEG_ERR_UNSUPPORTED. */
+int iiseg_depool_bwd_c8(void* stream, const void* gu, const uint8_t* mask, const void* gate, void* out, int B,
+                        int C8n, int PH, int PW, int h2, int w2, int y0, int x0, int wh, int ww);
+int iiseg_relu_gate_c8(void* stream, const void* g, const void* pooled, void* out, int B, int C8n, int h2, int w2,
+                       int y0, int x0, int wh, int ww);
 /* The same layer for AT MOST 16 OUTPUT CHANNELS (csrc/conv_c8_m16.hip: v_mfma_f32_16x16x32_bf16, M = 16
  * channels, 16-pixel blocks, 256-pixel th x tw tiles, three workgroups per CU): the DAE's class-score
  * layer (models/fcn_up.py:83-86) and FC-DenseNet's growth-rate-16 dense-block layers

@@ -140,6 +140,8 @@ SIGNATURES = {
     'iiseg_conv_c8': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 6 + [_i32, _vp, _i32, _vp, _vp]),
     'iiseg_conv_c8_slice': (C.c_int, [_vp, C.POINTER(ConvDesc), _vp, _i32] + [_vp] * 5 + [_i32, _vp, _i32, _vp, _vp]),
     'iiseg_unpool_c8': (C.c_int, [_vp] * 4 + [C.c_int] * 7),
+    'iiseg_depool_bwd_c8': (C.c_int, [_vp] * 5 + [C.c_int] * 10),
+    'iiseg_relu_gate_c8': (C.c_int, [_vp] * 4 + [C.c_int] * 8),
     'iiseg_conv_c8_m16_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_c8_m16': (C.c_int, [_vp, C.POINTER(ConvDesc), _vp, _i32] + [_vp] * 6 + [_i32]),
     'iiseg_conv_c8_m16_workspace_bytes': (_i64, [C.POINTER(ConvDesc)]),

@@ -367,6 +367,8 @@ class IterativeInference:
                     # (context module: the softmax backward, the last layer's adjoint and a mask are one launch)
                     g_through = self.dae.sqerr_backward(score, y)
                 else:
+                    # (a C8 standard DAE walks on bf16 C8 maps in there, fp32 NCHW in and out; grad_update does not
+                    # feed the session's y8 -- `c8_feed` -- so the next `scores` converts y itself)
                     g_through = self.dae.backward_y(ops.sqerr_softmax_bwd(score, y, off=(0, 0)), y.shape)
                 ops.grad_update(score, g_through, y, st, step, off=(0, 0))
             elif mode == 'residual':

@@ -1,7 +1,10 @@
-// Status strings / version of the C ABI (include/iiseg.h); launch profiling state.
+// Status strings / version of the C ABI (include/iiseg.h); launch profiling state; the argument checks of the
+// C8 adjoint entries.
+#include <stdint.h>
 #include <mutex>
 #include <vector>
 #include "common.h"
+#include "c8_common.h"
 
 namespace {
 std::mutex g_prof_mu;
@@ -62,6 +65,40 @@ extern "C" const char* iiseg_strerror(int status) {
 
 extern "C" const char* iiseg_last_hip_error(void) {
     return hipGetErrorString((hipError_t)iiseg_hip_error_slot());
+}
+
+// ---- the element-wise adjoints of the standard DAE's C8 backward walk (kernels: c8_grad.hip) ----
+namespace {
+// a pooled-coordinate window of C8 planes: B images of C8n chunks (whole 16-channel groups: C8n even)
+int c8_window_status(int B, int C8n, int h2, int w2, int y0, int x0, int wh, int ww) {
+    if (B <= 0 || C8n <= 0 || (C8n & 1) || h2 <= 0 || w2 <= 0 || wh <= 0 || ww <= 0 || y0 < 0 || x0 < 0 ||
+        y0 > h2 - wh || x0 > w2 - ww)
+        return IISEG_ERR_SHAPE;
+    return IISEG_OK;
+}
+}  // namespace
+
+extern "C" int iiseg_depool_bwd_c8(void* stream, const void* gu, const uint8_t* mask, const void* gate, void* out,
+                                   int B, int C8n, int PH, int PW, int h2, int w2, int y0, int x0, int wh, int ww) {
+    if (!gu || !mask || !out) return IISEG_ERR_NULL;
+    const int st = c8_window_status(B, C8n, h2, w2, y0, x0, wh, ww);
+    if (st) return st;
+    if (PH < 2 * (int64_t)h2 || PW < 2 * (int64_t)w2) return IISEG_ERR_SHAPE;
+    if (((uintptr_t)gu & 15) || ((uintptr_t)gate & 15) || ((uintptr_t)out & 15) || ((uintptr_t)mask & 7))
+        return IISEG_ERR_ALIGN;
+    if (out == gu || out == gate) return IISEG_ERR_UNSUPPORTED;      // not in place: four reads per element
+    return iiseg::depool_bwd_c8_launch(stream, gu, mask, gate, out, (int64_t)B * C8n, PH, PW, h2, w2, y0, x0, wh,
+                                       ww);
+}
+
+extern "C" int iiseg_relu_gate_c8(void* stream, const void* g, const void* pooled, void* out, int B, int C8n,
+                                  int h2, int w2, int y0, int x0, int wh, int ww) {
+    if (!g || !pooled || !out) return IISEG_ERR_NULL;
+    const int st = c8_window_status(B, C8n, h2, w2, y0, x0, wh, ww);
+    if (st) return st;
+    if (((uintptr_t)g & 15) || ((uintptr_t)pooled & 15) || ((uintptr_t)out & 15)) return IISEG_ERR_ALIGN;
+    if (out == pooled) return IISEG_ERR_UNSUPPORTED;                 // (out == g is fine: element-wise)
+    return iiseg::relu_gate_c8_launch(stream, g, pooled, out, (int64_t)B * C8n, h2, w2, y0, x0, wh, ww);
 }
 
 extern "C" int iiseg_abi_version(void) { return 34; }

@@ -42,5 +42,11 @@ inline void rect_shape(int OH, int OW, int cap, int pcap, bool even, int* th_out
     *th_out = bth; *tw_out = btw; *tiles_out = best;
 }
 
+// The launches behind iiseg_depool_bwd_c8 / iiseg_relu_gate_c8 (c8_grad.hip); the entry points (abi.hip) have
+// checked every argument.  BC8 = B * chunks.
+int depool_bwd_c8_launch(void* stream, const void* gu, const uint8_t* mask, const void* gate, void* out,
+                         int64_t BC8, int PH, int PW, int h2, int w2, int y0, int x0, int wh, int ww);
+int relu_gate_c8_launch(void* stream, const void* g, const void* pooled, void* out, int64_t BC8, int h2, int w2,
+                        int y0, int x0, int wh, int ww);
 
 }  // namespace iiseg

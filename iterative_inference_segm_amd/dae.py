@@ -51,6 +51,122 @@ def param_order(concat_h=('pool4',), conv_before_pool=1, additional_pool=2,
 C8_UNPOOL_MIN_CIN = int(os.environ.get('IISEG_C8_UNPOOL_MIN_CIN', '1024'))
 
 
+def _embed(g, hw, off):
+    """Adjoint of a crop: a zeroed map of planes `hw` with `g` at offset `off` (NCHW or C8: dims 2, 3 are the
+    planes in both)."""
+    out = torch.zeros(tuple(g.shape[:2]) + tuple(hw) + tuple(g.shape[4:]), dtype=g.dtype, device=g.device)
+    out[:, :, off[0]:off[0] + g.shape[2], off[1]:off[1] + g.shape[3]].copy_(g)
+    return out
+
+
+class _NCHWAdjoint:
+    """What `StandardDAE._adjoint_walk` does at a level on fp32 / float64 NCHW maps: the flipped-filter convs,
+    ops.depool_bwd / ops.pool_relu_bwd under the forward's (pre, pooled) tensors and, with `gv`, ops.conv_wgrad on
+    the g_z the chain forms and the layer input that `forward_train` saved (DePool2D's output is materialised for
+    the up_conv layers, a concat layer is two calls into one dW, h first)."""
+
+    def __init__(self, dae, override, gv):
+        self.dae, self.bwd = dae, dae._bwd_convs()
+        _, self.pre, self.pool = dae._saved
+        if any(t.device.type == 'meta' for t in self.pre.values()):
+            raise RuntimeError('backward_y needs the pre-pool maps of the forward pass: set '
+                               'dae.keep_pre = True before calling scores()')
+        self.override, self.gv = override, gv
+        if gv is not None:
+            self.h_list, _, self.fused = dae._tsaved
+            self.feeds = regions.concat_feeds(dae.concat_h, dae.total, dae.n_pool)
+
+    def enter(self, g_score):
+        return g_score
+
+    def pre_hw(self, p):
+        return self.pre[p].shape[2], self.pre[p].shape[3]
+
+    def pool_hw(self, p):
+        return self.pool[p].shape[2], self.pool[p].shape[3]
+
+    def decoder(self, p, g_c):
+        """g_c (the gradient w.r.t. up_conv_p's output) -> the gradient w.r.t. the level's pooled-size input."""
+        mpre, mpool = self.override[p] if self.override and p in self.override else (self.pre[p], self.pool[p])
+        if self.gv is not None:
+            t_in = self.pool[self.dae.total] if p == self.dae.total else self.fused['fused_up%d' % (p + 1)]
+            ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *self.gv['up_conv%d' % p], pad=1)
+        return ops.depool_bwd(self.bwd['up_conv%d' % p](g_c), mpre, mpool)
+
+    def encoder(self, p, gp, acc, window, want_data):
+        """gp (the gradient w.r.t. pool_p) through max-pool + ReLU and conv_p: + acc (the skip's share, summed in
+        place); `window` of the result; nothing is formed without `want_data` (the weight gradients only)."""
+        g_z = ops.pool_relu_bwd(gp, self.pre[p], self.pool[p])
+        name = 'conv%d_1' % p
+        if self.gv is not None:
+            fwd, (dW, db) = self.dae.enc[name], self.gv[name]
+            ch = 0
+            if (p - 1) in self.feeds:                    # h first (P13), then the features
+                h = self.h_list[self.feeds[p - 1]]
+                ch = h.shape[1]
+                ops.conv_wgrad(h, g_z, dW, None, pad=fwd.pad, ci0=0)
+            ops.conv_wgrad(self.pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch)
+        if not want_data:
+            return None
+        conv = self.bwd[name]
+        if acc is not None:
+            return conv(g_z, add=acc, out=acc)
+        return conv(g_z) if window is None else conv(g_z, window=window)
+
+
+class _C8Adjoint:
+    """The same two steps on bf16 C8 maps (mma='bf16c8'), from what the C8 forward wrote anyway: per level the
+    pooled map and the DePool2D mask bytes (`StandardDAE._saved_c8`).  Every map between two launches is bf16
+    (rounded once, at its store, from an fp32 sum); gates and mask selects are exact.
+      decoder level : flipped-filter conv, ops.depool_bwd_c8 -- at the deepest level with the ReLU gate of the
+                      encoder stage that follows in the same launch;
+      encoder level : ops.relu_gate_c8 at pooled resolution (relu'(0) = 0; every position equal to the window
+                      maximum receives the gradient: the mask bytes), then the flipped-filter conv whose input
+                      staging IS DePool2D of the gated map under the level's own bytes -- or, from
+                      C8_UNPOOL_MIN_CIN input channels on, ops.unpool_c8 and a plain conv: the choice the decoder
+                      forward makes.  The skip's share enters as the conv's `add` (one fp32 sum, one rounding),
+                      into a buffer of its own; the first layer writes fp32 NCHW."""
+
+    def __init__(self, dae):
+        if dae._saved_c8 is None:
+            raise RuntimeError("backward_y needs the pooled maps and mask bytes of the forward pass: set "
+                               "dae.keep_pre = True before calling scores() (mma='bf16c8')")
+        self.dae, self.bwd = dae, dae._bwd_convs()
+        self.pool8, self.masks, self.hw = dae._saved_c8
+
+    def enter(self, g_score):
+        return ops.nchw_to_c8(g_score)
+
+    def pre_hw(self, p):
+        return self.hw[p]
+
+    def pool_hw(self, p):
+        return self.pool8[p].shape[2], self.pool8[p].shape[3]
+
+    def decoder(self, p, g_c):
+        g_u = self.bwd['up_conv%d' % p](g_c)
+        return ops.depool_bwd_c8(g_u, self.masks[p], gate=self.pool8[p] if p == self.dae.total else None)
+
+    def encoder(self, p, gp, acc, window, want_data):
+        if not want_data:
+            return None
+        if p != self.dae.total:                          # (the deepest level arrives gated: `decoder`)
+            gp = ops.relu_gate_c8(gp, self.pool8[p], out=gp)
+        conv = self.bwd['conv%d_1' % p]
+        kw = {}
+        if acc is not None:
+            kw['add'] = acc
+        if window is not None:
+            kw['window'] = window
+        if p == 1:
+            kw['out_format'] = 'nchw'
+        ph, pw = self.hw[p]
+        if 0 < C8_UNPOOL_MIN_CIN <= conv.Cin and conv.Cout > 16:
+            u = torch.zeros(tuple(gp.shape[:2]) + (ph, pw, 8), dtype=torch.bfloat16, device=gp.device)
+            return conv(ops.unpool_c8(gp, self.masks[p], u), **kw)
+        return conv(gp, mask_in=self.masks[p], unpool_hw=(ph, pw), **kw)
+
+
 class StandardDAE:
     """Callable with (h_1..h_k, y) like the compiled pred_dae_fn (iterative_inference.py:189-190)."""
 
@@ -110,7 +226,7 @@ class StandardDAE:
         self.random_source = None     # callable(kind, level, name, shape) -> tensor, or None: torch RNG
         self._seed, self._gen = int(seed), None
         self.dtype = dtype
-        self._bwd, self._saved = None, None
+        self._bwd, self._saved, self._saved_c8 = None, None, None
         self.unpool_type = unpool_type
         self.concat_h, self.padding, self.skip = concat_h, padding, skip
         self.conv_before_pool = conv_before_pool
@@ -523,8 +639,10 @@ class StandardDAE:
                             in the epilogue (fcn_up.py:64-113); the last one writes fp32 NCHW scores.
         y arrives fp32 NCHW and is converted once per call; the h half of the conv behind a concat
         point is a cached fp32 C8 addend (loop-invariant, `hsplit`)."""
+        # (keep_pre on 'bf16c8': nothing more is stored -- the pooled maps and mask bytes every level writes anyway
+        # are what `backward_y` walks on, `_saved_c8` below; the hi / lo pair mode has no backward walk)
         if self.conv_before_pool != 1 or self.bn or self.unpool_type == 'standard' or \
-                self.trace is not None or self.keep_pre or \
+                self.trace is not None or (self.keep_pre and self.x3) or \
                 (self.emulate_noise and (self.noise > 0 or self.dropout > 0)):
             raise NotImplementedError("mma='bf16c8' runs the plain trackind / inverse DAE "
                                       "(conv_before_pool=1, bn=0, no trace / gradient mode / noise "
@@ -639,7 +757,21 @@ class StandardDAE:
             if self.conv_log is not None:
                 self.conv_log.append((name, conv.flops(B, ph, pw), conv.flops(B, nh, nw)))
         self._saved = None
+        # what backward_y needs of this call: {level: pooled C8 map}, {level: mask bytes} (with a session: the
+        # session's buffers, valid until its next `scores`) and the pre-pool sizes
+        self._saved_c8 = (pool8, masks, {step.level + 1: step.out_hw for step in plan.enc}) if self.keep_pre \
+            else None
         return t
+
+    def saved_c8(self):
+        """{'pool%d': bf16 C8 map, 'mask%d': DePool2D mask bytes (B, C/8, h, w, 8)} per level, as the latest
+        `scores` call of a C8 module with `keep_pre` left them (the tensors themselves, not copies); for tests."""
+        if self._saved_c8 is None:
+            raise RuntimeError("no C8 maps kept: mma='bf16c8' and dae.keep_pre = True before scores()")
+        pool8, masks, _ = self._saved_c8
+        out = {'pool%d' % k: v for k, v in pool8.items()}
+        out.update({'mask%d' % k: v for k, v in masks.items()})
+        return out
 
     # ---- true-gradient mode (SURVEY 8f rank 4; not in the reference, F1) -----------------------
     def _flipped_filters(self):
@@ -663,7 +795,10 @@ class StandardDAE:
             if self.conv_before_pool != 1 or self.bn or self.unpool_type == 'standard':
                 raise NotImplementedError('gradient mode: conv_before_pool=1, bn=0, unpool_type in '
                                           '{trackind, inverse}')
-            bwd = {name: ops.Conv(Wt.contiguous(), None, pad=1, relu=False, device=Wt.device, dtype=self.dtype)
+            # (a C8 module's layers are built for C8 input explicitly -- mma='bf16c8', whatever ops.DEFAULT_MMA says:
+            # the flipped weights are rounded to bf16 when they are packed; no bias)
+            kw = dict(mma='bf16c8') if self.c8 else {}
+            bwd = {name: ops.Conv(Wt.contiguous(), None, pad=1, relu=False, device=Wt.device, dtype=self.dtype, **kw)
                    for name, Wt in self._flipped_filters()}
             if self.trainable:
                 for conv in bwd.values():
@@ -674,72 +809,40 @@ class StandardDAE:
     def _adjoint_walk(self, g_score, y_shape, override=None, gv=None, first_layer=True):
         """The adjoint of the latest `scores()` call, level by level (oracle/dae_grad.py), on full maps (the
         decoder / encoder windows of the forward are not exploited here): `backward_y` and `backward` are its two
-        callers.  override: the forward's {level: (pre, pooled)} DePool2D mask tensors.  gv: {name: (dW, db)} to
-        take the weight gradients into (ops.conv_wgrad on the g_z the chain forms and the layer input that
-        `forward_train` saved; DePool2D's output is materialised for the up_conv layers, a concat layer is two
-        calls into one dW, h first).  first_layer: form (and return) the first layer's data gradient."""
-        bwd = self._bwd_convs()
-        _, pre, pool = self._saved
-        if any(t.device.type == 'meta' for t in pre.values()):
-            raise RuntimeError('backward_y needs the pre-pool maps of the forward pass: set '
-                               'dae.keep_pre = True before calling scores()')
-        if gv is not None:
-            h_list, _, fused = self._tsaved
-            feeds = regions.concat_feeds(self.concat_h, self.total, self.n_pool)
-        B = g_score.shape[0]
-        dev, dt = g_score.device, g_score.dtype
+        callers.  The level structure, the crop / skip geometry and the order of the sums are written here, once;
+        what a level does to its maps is the layout's business: `_NCHWAdjoint` (fp32 / float64 NCHW maps, the
+        forward's pre-pool and pooled maps as masks, optionally the weight gradients) or `_C8Adjoint` (bf16 C8
+        maps, the forward's pooled maps and mask bytes).  override: the forward's {level: (pre, pooled)} DePool2D
+        mask tensors.  gv: {name: (dW, db)} to take the weight gradients into.  first_layer: form (and return) the
+        first layer's data gradient."""
+        lv = _C8Adjoint(self) if self.c8 else _NCHWAdjoint(self, override, gv)
         g_pool = {}
-        g_f = g_score
+        g_f = lv.enter(g_score)
         for p in range(1, self.total + 1):               # decoder, output to input
-            mpre, mpool = override[p] if override and p in override else (pre[p], pool[p])
-            ph, pw = pre[p].shape[2], pre[p].shape[3]
-            other_hw = (pool[p - 1].shape[2], pool[p - 1].shape[3]) if p > 1 else \
-                (y_shape[2], y_shape[3])
+            ph, pw = lv.pre_hw(p)
+            other_hw = lv.pool_hw(p - 1) if p > 1 else (y_shape[2], y_shape[3])
             oh, ow = min(ph, other_hw[0]), min(pw, other_hw[1])
-            cy, cx = center(ph, oh), center(pw, ow)
-            g_c = torch.zeros((B, g_f.shape[1], ph, pw), dtype=dt, device=dev)
-            g_c[:, :, cy:cy + oh, cx:cx + ow].copy_(g_f)           # adjoint of the center crop
-            if self.skip and p > 1:                                 # adjoint of the skip sum
-                gp = torch.zeros_like(pool[p - 1])
-                oy, ox = center(other_hw[0], oh), center(other_hw[1], ow)
-                gp[:, :, oy:oy + oh, ox:ox + ow].copy_(g_f)
-                g_pool[p - 1] = gp
-            if gv is not None:
-                t_in = pool[self.total] if p == self.total else fused['fused_up%d' % (p + 1)]
-                ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *gv['up_conv%d' % p], pad=1)
-            g_u = bwd['up_conv%d' % p](g_c)
-            g_f = ops.depool_bwd(g_u, mpre, mpool)
+            g_c = _embed(g_f, (ph, pw), (center(ph, oh), center(pw, ow)))          # adjoint of the center crop
+            if self.skip and p > 1:                                                 # adjoint of the skip sum
+                g_pool[p - 1] = _embed(g_f, other_hw, (center(other_hw[0], oh), center(other_hw[1], ow)))
+            g_f = lv.decoder(p, g_c)
         g_pool[self.total] = g_f
         g_in = None
         for p in range(self.total, 0, -1):               # encoder, deep to shallow
-            gp = g_pool.get(p)
-            if gp is None:
-                gp = torch.zeros_like(pool[p])
-            g_z = ops.pool_relu_bwd(gp, pre[p], pool[p])
-            name = 'conv%d_1' % p
-            conv, fwd = bwd[name], self.enc[name]
-            if gv is not None:
-                dW, db = gv[name]
-                ch = 0
-                if (p - 1) in feeds:                     # h first (P13), then the features
-                    h = h_list[feeds[p - 1]]
-                    ch = h.shape[1]
-                    ops.conv_wgrad(h, g_z, dW, None, pad=fwd.pad, ci0=0)
-                ops.conv_wgrad(pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch)
+            pad = self.enc['conv%d_1' % p].pad
             if p > 1:
-                acc = g_pool.get(p - 1)
-                g_pool[p - 1] = conv(g_z) if acc is None else conv(g_z, add=acc, out=acc)
-            elif first_layer:
-                if fwd.pad != 1:      # pad-100 first layer: crop at offset pad - 1
-                    g_in = conv(g_z, window=(fwd.pad - 1, fwd.pad - 1, y_shape[2], y_shape[3]))
-                else:
-                    g_in = conv(g_z)
+                g_pool[p - 1] = lv.encoder(p, g_pool[p], g_pool.get(p - 1), None, True)
+            else:                 # pad-100 first layer: the window at offset pad - 1 of the 'same' result
+                g_in = lv.encoder(p, g_pool[p], None, None if pad == 1 else
+                                  (pad - 1, pad - 1, y_shape[2], y_shape[3]), first_layer)
         return g_in
 
     def backward_y(self, g_score, y_shape):
         """dE/dy THROUGH the DAE for an upstream gradient g_score w.r.t. the (cropped) score map
-        of the latest `scores()` call (`_adjoint_walk` under the mask override of that call)."""
-        return self._adjoint_walk(g_score, y_shape, override=self._saved[0])
+        of the latest `scores()` call (`_adjoint_walk` under the mask override of that call).  fp32 NCHW in and
+        out on every leg; a C8 module (mma='bf16c8') walks on bf16 C8 gradient maps in between: g_score is rounded
+        to bf16 on its way in, every map between two layers is, the first layer's data gradient leaves as fp32."""
+        return self._adjoint_walk(g_score, y_shape, override=None if self.c8 else self._saved[0])
 
     # ---- training (DESIGN.md section 12; reference train_dae.py with dae kind 'standard') ----------
     def parameters(self):

@@ -1533,6 +1533,57 @@ def unpool_c8(up, mask, out, window=None):
     return out
 
 
+def _c8_pooled_out(like, out, window, what):
+    """`out` of a windowed element-wise C8 launch: a bf16 C8 tensor of `like`'s shape.  None: a new one, zeros when
+    a window leaves part of it unwritten."""
+    if out is None:
+        return torch.empty(like, dtype=torch.bfloat16, device=what.device) if window is None else \
+            torch.zeros(like, dtype=torch.bfloat16, device=what.device)
+    if not is_c8(out) or tuple(out.shape) != tuple(like) or not out.is_contiguous():
+        raise RuntimeError('C8 output target %s for %s' % (tuple(out.shape), tuple(like)))
+    return out
+
+
+def depool_bwd_c8(gu, mask, out=None, window=None, gate=None):
+    """Adjoint of DePool2D on C8 tensors (include/iiseg.h iiseg_depool_bwd_c8): gu (B, C8, PH, PW, 8) bf16, the
+    gradient w.r.t. the unpooled map, summed over the positions each mask byte selects into `out` (B, C8, h2, w2, 8)
+    -- `mask`'s shape, PH >= 2 h2, PW >= 2 w2 -- on the pooled-coordinate `window` (y0, x0, h, w) (default: all; the
+    rest of a given `out` is left as it is).  `gate` (out's shape): zero where gate <= 0, `relu_gate_c8` in the
+    same launch."""
+    if not (is_c8(gu) and is_c8_mask(mask)) or tuple(gu.shape[:2]) != tuple(mask.shape[:2]) or \
+            not (gu.is_contiguous() and mask.is_contiguous()) or \
+            (gate is not None and (not is_c8(gate) or tuple(gate.shape) != tuple(mask.shape) or
+                                   not gate.is_contiguous())):
+        raise RuntimeError('depool_bwd_c8: gu %s mask %s gate %s' % (tuple(gu.shape), tuple(mask.shape),
+                                                                     None if gate is None else tuple(gate.shape)))
+    B, C8n, PH, PW, _ = gu.shape
+    h2, w2 = mask.shape[2], mask.shape[3]
+    out = _c8_pooled_out(mask.shape, out, window, gu)
+    y0, x0, wh, ww = window if window is not None else (0, 0, h2, w2)
+    if CONV_PROFILE is not None:
+        _add_bytes('depool_bwd_c8_kernel', B * C8n * wh * ww * (4 * 16 + 8 + 16 + (16 if gate is not None else 0)))
+    _launch('depool_bwd_c8_kernel', 0.0, _lib.load().iiseg_depool_bwd_c8, _c8ptr(gu), C.c_void_p(mask.data_ptr()),
+            _c8ptr(gate), _c8ptr(out), B, C8n, PH, PW, h2, w2, int(y0), int(x0), int(wh), int(ww))
+    return out
+
+
+def relu_gate_c8(g, pooled, out=None, window=None):
+    """out = g where pooled > 0, else +0, on C8 tensors of one shape (include/iiseg.h iiseg_relu_gate_c8): the ReLU
+    half of max-pool + ReLU backward, at pooled resolution (the pool half is DePool2D of the result under the
+    level's mask bytes).  `window` as in `depool_bwd_c8`; `out` may be `g`."""
+    if not (is_c8(g) and is_c8(pooled)) or tuple(g.shape) != tuple(pooled.shape) or \
+            not (g.is_contiguous() and pooled.is_contiguous()):
+        raise RuntimeError('relu_gate_c8: g %s pooled %s' % (tuple(g.shape), tuple(pooled.shape)))
+    B, C8n, h2, w2, _ = g.shape
+    out = _c8_pooled_out(g.shape, out, window, g)
+    y0, x0, wh, ww = window if window is not None else (0, 0, h2, w2)
+    if CONV_PROFILE is not None:
+        _add_bytes('relu_gate_c8_kernel', B * C8n * wh * ww * 48)
+    _launch('relu_gate_c8_kernel', 0.0, _lib.load().iiseg_relu_gate_c8, _c8ptr(g), _c8ptr(pooled), _c8ptr(out),
+            B, C8n, h2, w2, int(y0), int(x0), int(wh), int(ww))
+    return out
+
+
 def pool_mask_c8(pre, pooled, mask, origin, full_hw, window, x3=False):
     """2x2 max-pool (+ DePool2D mask bytes, `mask` may be None) of the pooled-coordinate `window`
     (y0, x0, h, w) from the stored piece `pre` (C8 bf16, or C8 fp32: the unrounded conv results)
