@@ -251,6 +251,19 @@ int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
  *                                    bytes): 0 per-tile, 1 LDS-staged, 2 streaming; < 0 an IISEG_ERR_* */
 int iiseg_conv_wino_input_wide(int on);
 int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes);
+/* The products M of the separate-GEMM forms (iiseg_conv_wino_f32 without IISEG_WINO_FUSED, the GEMM form of
+ * iiseg_conv_wino_bf16, the split-K iiseg_conv_gemm_f32 / iiseg_conv_gemm_bf16) lie in the workspace as
+ * M[slice][Mpad / 4][Tpad][4], four consecutive output channels of one tile together: the GEMM writes and
+ * the output kernels read them in 16-byte pieces.  The size of the workspace is the same, and so is every
+ * result, bit for bit.  (A slice of 2 GiB or more keeps M[slice][Mpad][Tpad].)
+ *   iiseg_conv_wino_m_quad(on)   on = 0 / 1: M[slice][Mpad][Tpad] with 4-byte pieces / the quad layout, for
+ *                                the launches that follow (the default is the environment's
+ *                                IISEG_WINO_M_QUAD, 1 when unset); on < 0 only asks.  Returns the setting in
+ *                                force.  For A/B timing and tests.  The setting is process-wide and must NOT
+ *                                change between the separately launched stages of one layer
+ *                                (IISEG_WINO_GEMM, then IISEG_WINO_OUTPUT): the second would read a layout
+ *                                the first did not write. */
+int iiseg_conv_wino_m_quad(int on);
 /* The Winograd call with the 2x2 max-pool and the DePool2D mask bytes (as iiseg_conv_mask_f32):
  *   pool_out   (may be NULL) the FULL pooled tensor (B, Cout, fullH/2, fullW/2); the pooled
  *              positions of the window are written in place by the output transform (or the fused

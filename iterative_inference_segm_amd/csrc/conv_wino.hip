@@ -64,7 +64,11 @@ struct WinoParams {
     float* pool;
     uint8_t* mask_out;
     int pool_H, pool_W;
+    int mq;                  // M is M[xi][Mpad / 4][Tpad][4] (m_quad below), else M[xi][Mpad][Tpad]
 };
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // max of a 2x2 window in the order of maxpool2x2 (pool_unpool.hip): same value, same sign of zero
 __device__ __forceinline__ float pool4(float v00, float v01, float v10, float v11) {
@@ -700,8 +704,29 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoPa
 #undef WINO_STAGE
 #undef WINO_WAIT_ONE_STAGE_IN_FLIGHT
 
-    // M[xi][co][t]: rows of the C/D layout are channels, columns (lane & 31) are tiles
+    // rows of the C/D layout are channels, columns (lane & 31) are tiles
     float* Mx = p.M + (size_t)xi * p.Mpad * p.Tpad;
+    if (p.mq) {
+        // M[xi][co / 4][t][4]: a lane's registers r & 3 = 0..3 are four consecutive channels of one
+        // tile, one 16-byte store; the lane's byte offset is formed once, the quad row (i, r >> 2)
+        // and the column block j are wave-uniform and ride on the scalar offset
+        const __amdgpu_buffer_rsrc_t mr = mk_rsrc(Mx, p.Mpad * p.Tpad * 4);
+        const unsigned qrow = 16u * (unsigned)p.Tpad;   // bytes of one channel quad over all tiles
+        const unsigned lo = (unsigned)((m0 + wm * WTM) / 4 + lh) * qrow + 16u * (unsigned)(t0 + wn * WTN + l31);
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2],
+                                     acc[i][j][4 * q + 3]};
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), mr, (int)lo,
+                                                           (int)((unsigned)(i * 8 + 2 * q) * qrow + 512u * j), 0);
+                }
+        return;
+    }
+    // M[xi][co][t]
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int t = t0 + wn * WTN + j * 32 + l31;
@@ -944,7 +969,12 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wino_fused_kernel(const Wi
 }
 
 // ---- 3. output transform + epilogue ------------------------------------------------------------
+// QUAD: M is M[xi][Mpad / 4][Tpad][4] -- the thread's four channels of one xi are one 16-byte load
+// (a quad that straddles Cout is read whole: rows up to Mpad exist) -- and a tile row with both
+// columns inside the window is one 8-byte store.  Same arithmetic, same bits as the other form.
 constexpr int OCH = 4;
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte access, 4-byte aligned
+template <bool QUAD>
 __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
@@ -961,13 +991,30 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
     // All loads of the thread's OCH channels first (M, skip-add; channel index clamped instead of
     // branching), then the stores: `out` may alias `M` / `add` as far as the compiler knows, so
     // loads placed after a store could not be moved up and every channel would be a round trip.
-    float mv[OCH][16], av[OCH][4];
+    float mv[OCH][16], av[OCH][4], bv[OCH];
+    if constexpr (QUAD) {
+        static_assert(OCH == 4, "one channel quad per thread");
+        // a buffer descriptor per slice (a slice fits 32-bit byte offsets: m_quad) and ONE byte offset
+        // per thread, the same in all 16
+        const unsigned mo = 16u * ((unsigned)blockIdx.y * (unsigned)p.Tpad + (unsigned)t);
+#pragma unroll
+        for (int x = 0; x < 16; ++x) {
+            const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                mk_rsrc(p.M + (size_t)x * xis, p.Mpad * p.Tpad * 4), (int)mo, 0, 0));
+#pragma unroll
+            for (int cc = 0; cc < OCH; ++cc) mv[cc][x] = q[cc];
+        }
+    }
 #pragma unroll
     for (int cc = 0; cc < OCH; ++cc) {
         const int co = min(co0 + cc, p.Cout - 1);
-        const float* m = p.M + (size_t)co * p.Tpad + t;
+        if constexpr (QUAD) {
+            bv[cc] = p.bias ? p.bias[co] : 0.f;
+        } else {
+            const float* m = p.M + (size_t)co * p.Tpad + t;
 #pragma unroll
-        for (int x = 0; x < 16; ++x) mv[cc][x] = m[(size_t)x * xis];
+            for (int x = 0; x < 16; ++x) mv[cc][x] = m[(size_t)x * xis];
+        }
         if (p.add) {
             const float* ad = p.add + ((size_t)b * p.Cout + co) * APL;
 #pragma unroll
@@ -977,10 +1024,18 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
                     const bool ok = okr[i] && okc[j];
                     const ptrdiff_t idx = (ptrdiff_t)(p.ay0 + wy + i) * p.AW + p.ax0 + wx + j;
                     const float a = ad[ok ? idx : 0];
-                    av[cc][i * 2 + j] = ok ? a : 0.f;
+                    // (QUAD: a value outside the window is neither stored nor pooled -- a pooled tile
+                    // lies inside it whole, wino_pool_ok -- and selecting here would wait for this
+                    // channel's loads before the next channel's are issued)
+                    av[cc][i * 2 + j] = QUAD || ok ? a : 0.f;
                 }
         }
     }
+    // QUAD: the first channel's address once per thread, the others one plane further each
+    float* const ob = QUAD && p.out ? p.out + ((size_t)b * p.out_ctot + p.out_c0 + co0) * OPL +
+                                          (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx
+                                    : nullptr;
+    const bool pair = okc[0] && okc[1];
 #pragma unroll
     for (int cc = 0; cc < OCH; ++cc) {
         const int co = co0 + cc;
@@ -992,10 +1047,17 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
             s2[0][j] = m0 + m1 + m2;
             s2[1][j] = m1 - m2 - m3;
         }
-        const float bias = p.bias ? p.bias[co] : 0.f;
-        float* o = p.out ? p.out + ((size_t)b * p.out_ctot + p.out_c0 + co) * OPL +
-                               (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx
-                         : nullptr;
+        float bias;
+        float* o;
+        if constexpr (QUAD) {
+            bias = bv[cc];
+            o = ob ? ob + cc * OPL : nullptr;
+        } else {
+            bias = p.bias ? p.bias[co] : 0.f;
+            o = p.out ? p.out + ((size_t)b * p.out_ctot + p.out_c0 + co) * OPL +
+                            (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx
+                      : nullptr;
+        }
         float vt[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // (A^T m) A
@@ -1006,7 +1068,19 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
                 if (p.add) v += av[cc][i * 2 + j];
                 if (p.relu) v = fmaxf(v, 0.f);
                 vt[i][j] = v;
-                if (o && okr[i] && okc[j]) o[(ptrdiff_t)i * p.out_W + j] = v;
+                if constexpr (!QUAD)
+                    if (o && okr[i] && okc[j]) o[(ptrdiff_t)i * p.out_W + j] = v;
+            }
+            if constexpr (QUAD) {
+                if (o && okr[i]) {
+                    float* orow = o + (ptrdiff_t)i * p.out_W;
+                    if (pair) {
+                        *reinterpret_cast<f32x2u*>(orow) = f32x2u{vt[i][0], vt[i][1]};
+                    } else {   // a tile cut by the window's edge
+                        if (okc[0]) orow[0] = vt[i][0];
+                        if (okc[1]) orow[1] = vt[i][1];
+                    }
+                }
             }
         }
         // even anchor: the tile is one pooling window; a tile cut by the window's end is the map's
@@ -1065,6 +1139,26 @@ int input_wide_setting() {
         g_input_wide.store(v);
     }
     return v;
+}
+
+// IISEG_WINO_M_QUAD (default 1; iiseg_conv_wino_m_quad): 0 = the products stay M[slice][Mpad][Tpad] with
+// one-dword stores and loads on both sides (same bits: A/B timing, tests)
+std::atomic<int> g_m_quad{-1};
+
+int m_quad_setting() {
+    int v = g_m_quad.load();
+    if (v < 0) {
+        v = getenv("IISEG_WINO_M_QUAD") ? (atoi(getenv("IISEG_WINO_M_QUAD")) != 0) : 1;
+        g_m_quad.store(v);
+    }
+    return v;
+}
+
+// The layout of a GEMM's products, for its producer and its consumer alike: channel quads,
+// M[slice][Mpad / 4][Tpad][4], when the setting allows and one slice fits the 32-bit byte offsets of
+// the producers' buffer descriptor (Mpad is a multiple of 64 everywhere: quads are whole).
+int m_quad(int Mpad, int Tpad) {
+    return m_quad_setting() && Mpad % 4 == 0 && (int64_t)Mpad * Tpad * 4 < (int64_t)1 << 31 ? 1 : 0;
 }
 
 // every workgroup's staged rows fit its LDS buffer (exact: the same iw_chunk the kernel runs)
@@ -1167,8 +1261,9 @@ void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
 
 }  // namespace
 
-// Output transform + epilogue for products M[16][Mpad][Tpad] that another GEMM kernel wrote (the
-// bf16-operand path of conv_wino_bf16.hip): same kernel, tile geometry recomputed from `d`.
+// Output transform + epilogue for the 16 slices of products that another GEMM kernel wrote in the layout
+// m_quad(Mpad, Tpad) gives (the bf16-operand path of conv_wino_bf16.hip): same kernel, tile geometry
+// recomputed from `d`.
 int iiseg_wino_output_launch(hipStream_t s, const iiseg_conv_desc* d, const float* M, int Mpad,
                              int Tpad, const float* bias, const float* add, float* out) {
     WinoParams p = {};
@@ -1190,10 +1285,15 @@ int iiseg_wino_output_launch(hipStream_t s, const iiseg_conv_desc* d, const floa
     p.out_W = d->out_H > 0 ? d->out_W : d->OW;
     p.out_y0 = d->out_H > 0 ? d->out_y0 : 0;
     p.out_x0 = d->out_H > 0 ? d->out_x0 : 0;
-    IISEG_LAUNCH(wino_output_kernel, dim3((p.T + 255) / 256, (d->Cout + OCH - 1) / OCH),
-                       dim3(256), 0, s, p);
+    p.mq = m_quad(Mpad, Tpad);
+    const dim3 og((p.T + 255) / 256, (d->Cout + OCH - 1) / OCH);
+    if (p.mq) IISEG_LAUNCH(wino_output_kernel<true>, og, dim3(256), 0, s, p);
+    else IISEG_LAUNCH(wino_output_kernel<false>, og, dim3(256), 0, s, p);
     return iiseg_check_launch();
 }
+
+// the layout launch_gemm_bf16 (conv_wino_bf16.hip) writes for the two consumers in this file
+int iiseg_wino_m_quad_layout(int Mpad, int Tpad) { return m_quad(Mpad, Tpad); }
 
 extern "C" int iiseg_conv_wino_supported(const iiseg_conv_desc* d) {
     WinoGeom g;
@@ -1203,6 +1303,11 @@ extern "C" int iiseg_conv_wino_supported(const iiseg_conv_desc* d) {
 extern "C" int iiseg_conv_wino_input_wide(int on) {
     if (on >= 0) g_input_wide.store(on > 1 ? 2 : on);
     return input_wide_setting();
+}
+
+extern "C" int iiseg_conv_wino_m_quad(int on) {
+    if (on >= 0) g_m_quad.store(on ? 1 : 0);
+    return m_quad_setting();
 }
 
 extern "C" int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes) {
@@ -1312,6 +1417,7 @@ static int wino_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
         return IISEG_ERR_SHAPE;
     p.n_ttiles = g.Tpad / 128;
     p.n_mtiles = g.Mpad / g.bm;
+    p.mq = m_quad(g.Mpad, g.Tpad);
     hipStream_t s = (hipStream_t)stream;
     const int tb = (g.T + 255) / 256;
     if (stages & IISEG_WINO_FUSED) {
@@ -1367,8 +1473,11 @@ static int wino_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
         if (bm == 256) {
             // few, long 256x128 workgroups quantise badly over 256 CUs: fall back to 128x128
             // tiles (about 6 % less MFMA-efficient) when that fills the last round better
+            // IISEG_WINO_GEMM_KEEP256=1: never fall back (A/B of this rule with two batches in flight,
+            // where the other engine's kernels fill a launch's last round; same k order, same bits)
+            static const int keep256 = getenv("IISEG_WINO_GEMM_KEEP256") ? atoi(getenv("IISEG_WINO_GEMM_KEEP256")) : 0;
             const int w256 = grid, w128 = 2 * grid;
-            if (0.5 * 1.06 * ((w128 + 255) / 256) < (double)((w256 + 255) / 256)) bm = 128;
+            if (!keep256 && 0.5 * 1.06 * ((w128 + 255) / 256) < (double)((w256 + 255) / 256)) bm = 128;
         }
         const int grid2 = bm ? 16 * p.n_ttiles * (g.Mpad / bm) : 0;
         if (bm) p.n_mtiles = g.Mpad / bm;
@@ -1392,9 +1501,11 @@ static int wino_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
         else
             IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 2>), dim3(grid2), dim3(256), 0, s, p);
     }
-    if (stages & IISEG_WINO_OUTPUT)
-        IISEG_LAUNCH(wino_output_kernel, dim3(tb, (d->Cout + OCH - 1) / OCH), dim3(256), 0, s,
-                           p);
+    if (stages & IISEG_WINO_OUTPUT) {
+        const dim3 og(tb, (d->Cout + OCH - 1) / OCH);
+        if (p.mq) IISEG_LAUNCH(wino_output_kernel<true>, og, dim3(256), 0, s, p);
+        else IISEG_LAUNCH(wino_output_kernel<false>, og, dim3(256), 0, s, p);
+    }
     return iiseg_check_launch();
 }
 
@@ -1452,6 +1563,9 @@ __global__ __launch_bounds__(256) void gemm_im2col_kernel(const float* __restric
     }
 }
 
+// QUAD: M[s][Mpad / 4][Tpad][4], a thread sums one channel quad (a quad that straddles Cout is read
+// whole: rows up to Mpad exist); each channel's sum runs over the slices in the same fixed order
+template <bool QUAD>
 __global__ __launch_bounds__(256) void gemm_output_kernel(const float* __restrict__ M,
                                                           const float* __restrict__ bias,
                                                           float* __restrict__ out, int Cout, int OHW,
@@ -1460,6 +1574,23 @@ __global__ __launch_bounds__(256) void gemm_output_kernel(const float* __restric
     if (t >= T) return;
     const int b = t / OHW, px = t - b * OHW;
     const size_t ss = (size_t)Mpad * Tpad;
+    if constexpr (QUAD) {
+        for (int q = blockIdx.y; 4 * q < Cout; q += gridDim.y) {
+            const float* m = M + ((size_t)q * Tpad + t) * 4;
+            f32x4 v = *reinterpret_cast<const f32x4*>(m);
+            for (int s = 1; s < S; ++s) v += *reinterpret_cast<const f32x4*>(m + (size_t)s * ss);
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+                const int co = 4 * q + cc;
+                if (co >= Cout) break;
+                float w = v[cc];
+                if (bias) w += bias[co];
+                if (relu) w = fmaxf(w, 0.f);
+                out[((size_t)b * Cout + co) * OHW + px] = w;
+            }
+        }
+        return;
+    }
     for (int co = blockIdx.y; co < Cout; co += gridDim.y) {
         const float* m = M + (size_t)co * Tpad + t;
         float v = m[0];
@@ -1511,14 +1642,25 @@ int gemm_conv_geom(const iiseg_conv_desc* d, GemmConvGeom& g) {
     return IISEG_OK;
 }
 
+void launch_gemm_output(hipStream_t s, const float* M, const float* bias, float* out, int Cout, int OHW,
+                        int T, int Tpad, int Mpad, int S, int relu) {
+    const int tb = (T + 255) / 256;
+    if (m_quad(Mpad, Tpad)) {
+        const int nq = (Cout + 3) / 4;
+        IISEG_LAUNCH(gemm_output_kernel<true>, dim3(tb, nq < 1024 ? nq : 1024), dim3(256), 0, s, M, bias,
+                           out, Cout, OHW, T, Tpad, Mpad, S, relu);
+    } else {
+        IISEG_LAUNCH(gemm_output_kernel<false>, dim3(tb, Cout < 1024 ? Cout : 1024), dim3(256), 0, s, M,
+                           bias, out, Cout, OHW, T, Tpad, Mpad, S, relu);
+    }
+}
+
 }  // namespace
 
-// bias + ReLU + NCHW store of a GEMM result M[Mpad][Tpad] (S = 1) for the bf16 GEMM path
+// bias + ReLU + NCHW store of a GEMM result (S = 1; the layout m_quad gives) for the bf16 GEMM path
 int iiseg_gemm_output_launch(hipStream_t s, const float* M, const float* bias, float* out, int Cout,
                              int OHW, int T, int Tpad, int Mpad, int relu) {
-    const int cy = Cout < 1024 ? Cout : 1024;
-    IISEG_LAUNCH(gemm_output_kernel, dim3((T + 255) / 256, cy), dim3(256), 0, s, M, bias, out,
-                       Cout, OHW, T, Tpad, Mpad, 1, relu);
+    launch_gemm_output(s, M, bias, out, Cout, OHW, T, Tpad, Mpad, 1, relu);
     return iiseg_check_launch();
 }
 
@@ -1559,6 +1701,7 @@ extern "C" int iiseg_conv_gemm_f32(void* stream, const iiseg_conv_desc* d, const
     p.T = g.T;
     p.n_ttiles = g.Tpad / 128;
     p.n_mtiles = g.Mpad / g.bm;
+    p.mq = m_quad(g.Mpad, g.Tpad);
     const int grid = g.S * p.n_ttiles * p.n_mtiles;
     if (stages & IISEG_WINO_GEMM) {
         if (g.bm == 256)
@@ -1566,9 +1709,8 @@ extern "C" int iiseg_conv_gemm_f32(void* stream, const iiseg_conv_desc* d, const
         else
             IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 2>), dim3(grid), dim3(256), 0, s, p);
     }
-    const int cy = d->Cout < 1024 ? d->Cout : 1024;
     if (stages & IISEG_WINO_OUTPUT)
-        IISEG_LAUNCH(gemm_output_kernel, dim3(tb, cy), dim3(256), 0, s, M, bias, out, d->Cout,
-                           OH * OW, g.T, g.Tpad, g.Mpad, g.S, (d->flags & IISEG_CONV_RELU) ? 1 : 0);
+        launch_gemm_output(s, M, bias, out, d->Cout, OH * OW, g.T, g.Tpad, g.Mpad, g.S,
+                           (d->flags & IISEG_CONV_RELU) ? 1 : 0);
     return iiseg_check_launch();
 }

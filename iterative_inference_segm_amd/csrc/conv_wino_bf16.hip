@@ -29,6 +29,8 @@
 
 using namespace iiseg;
 
+int iiseg_wino_m_quad_layout(int Mpad, int Tpad);   // conv_wino.hip: the layout its output kernels read
+
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -56,7 +58,11 @@ struct WinoBfParams {
     int out_ctot, out_c0, out_H, out_W, out_y0, out_x0;
     int n_ttiles, n_mtiles;
     int debug;               // timing experiments only (IISEG_BF16_DEBUG): 1 no A DMA, 2 no B DMA, 4 no MFMA
+    int mq;                  // the GEMM kernel's M is M[xi][Mpad / 4][Tpad][4] (set by launch_gemm_bf16)
 };
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RSRC_W3 = 0x00027000;
 
@@ -762,8 +768,29 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_bf16_kernel(const W
     }
 #undef WBG_STAGE
 
-    // M[xi][co][t]: rows of the C/D layout are channels, columns (lane & 31) are tiles
+    // rows of the C/D layout are channels, columns (lane & 31) are tiles
     float* Mx = M + (size_t)xi * p.Mpad * p.Tpad;
+    if (p.mq) {
+        // M[xi][co / 4][t][4]: a lane's registers r & 3 = 0..3 are four consecutive channels of one
+        // tile, one 16-byte store; the lane's byte offset is formed once, the quad row (i, r >> 2)
+        // and the column block j are wave-uniform and ride on the scalar offset
+        const __amdgpu_buffer_rsrc_t mr = mk_rsrc(Mx, p.Mpad * p.Tpad * 4);
+        const unsigned qrow = 16u * (unsigned)p.Tpad;   // bytes of one channel quad over all tiles
+        const unsigned lo = (unsigned)((m0 + wm * WTM) / 4 + lh) * qrow + 16u * (unsigned)(t0 + wn * WTN + l31);
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 v = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2],
+                                     acc[i][j][4 * q + 3]};
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), mr, (int)lo,
+                                                           (int)((unsigned)(i * 8 + 2 * q) * qrow + 512u * j), 0);
+                }
+        return;
+    }
+    // M[xi][co][t]
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int t = t0 + wn * WTN + j * 32 + l31;
@@ -779,6 +806,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_bf16_kernel(const W
 
 // launches the GEMM kernel for n_xi points: 256 x 128 blocks when Mpad allows, else 128 x 128
 void launch_gemm_bf16(hipStream_t s, WinoBfParams p, float* M, int n_xi) {
+    p.mq = iiseg_wino_m_quad_layout(p.Mpad, p.Tpad);
     static const int big = getenv("IISEG_BF16_GEMM_256") ? atoi(getenv("IISEG_BF16_GEMM_256")) : 1;
     if (big && p.Mpad % 256 == 0 && p.Tpad % 256 == 0 &&
         n_xi * (p.Mpad / 256) * (p.Tpad / 256) >= 200) {

@@ -141,6 +141,15 @@ def wino_input_wide(on=None, force=False):
     return bool(_lib.load().iiseg_conv_wino_input_wide(-1 if on is None else (2 if on and force else int(bool(on)))))
 
 
+# So is the layout of the GEMM products M in the workspace: IISEG_WINO_M_QUAD=0, or `wino_m_quad(False)`.
+def wino_m_quad(on=None):
+    """The products M of the separate-GEMM layers (fp32 / bf16 Winograd GEMM, split-K GEMM) for the launches
+    that follow: True = channel quads, 16-byte stores and loads (the default, IISEG_WINO_M_QUAD), False =
+    M[slice][Mpad][Tpad] in 4-byte pieces; None only asks.  Returns the setting in force.  Same bits (A/B
+    timing, tests).  Process-wide: not to be changed between the separately launched stages of one layer."""
+    return bool(_lib.load().iiseg_conv_wino_m_quad(-1 if on is None else int(bool(on))))
+
+
 class workspace_tag:
     """Context manager: launches inside use the scratch buffers of `tag` (an engine's id)."""
 
