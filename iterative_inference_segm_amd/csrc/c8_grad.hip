@@ -10,15 +10,13 @@
 // fixed-order fp32 sum, rounded once (RNE) at its store.  The entry points (abi.hip) check every argument.
 #include <stdint.h>
 #include "common.h"
+#include "conv_common.h"
 #include "c8_common.h"
+
+using iiseg::pack_bf16;
 
 namespace {
 
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ float bf_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 

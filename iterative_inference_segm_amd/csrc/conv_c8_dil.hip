@@ -28,28 +28,16 @@
 #include <stdint.h>
 #include "iiseg.h"
 #include "common.h"
+#include "conv_common.h"
+
+using namespace iiseg;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;   // beyond every descriptor here (one image of a tensor is < 2^31 bytes)
 constexpr int RT = 4;                   // rows per round of a wave
 constexpr int RB = 8;                   // rows per workgroup
 constexpr int CGW = 4;                  // 16-pixel column groups per workgroup (one per wave)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, RSRC_W3);
-}
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 
 // fp32 -> bf16, round to nearest-even (finite input; the layer objects refuse non-finite parameters)
 __host__ __device__ inline uint16_t bf16_rne(float f) {

@@ -42,12 +42,6 @@ using namespace iiseg;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;
 constexpr int NB = 8;              // 16-pixel blocks per wave: 4 waves x 128 pixels = 512-pixel tiles
 constexpr int NPC = 3;             // 256-chunk staging pieces per 8-channel half
@@ -55,14 +49,6 @@ constexpr int HCAP = 640;          // patch chunks per half (whole 64-chunk DMA 
 constexpr int WROWS = 18 * 16;     // weight chunks per k-tile: (tap, half) x 16 channels
 constexpr int WCAP = 320;          // ... rounded up to whole 64-chunk DMA pieces
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, RSRC_W3);
-}
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ float bf_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
@@ -606,7 +592,6 @@ int m16_check(const iiseg_conv_desc* d) {
     if ((int64_t)(d->C1 / 16) * 18 * 32 * 16 >= (1ll << 31)) return IISEG_ERR_UNSUPPORTED;
     return IISEG_OK;
 }
-
 
 // tile shape of a launch and its split-K factor.  The factor depends on the tiles PER IMAGE and the channel
 // count only -- never on the batch -- so an image gets the same association of its channel sum alone and

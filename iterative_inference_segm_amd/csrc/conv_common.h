@@ -8,6 +8,24 @@ namespace iiseg {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte access, 4-byte aligned
+
+// raw buffer descriptor word 3 for gfx9/CDNA: DST_SEL = XYZW, DATA_FORMAT = 32 (raw dword access)
+constexpr int RSRC_W3 = 0x00027000;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);
+}
+
+// two floats -> two bf16 (round to nearest even; a NaN stays a NaN: v_cvt_pk_bf16_f32)
+__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
+    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+    const bf2 v = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, v);
+}
 
 // compile-time unrolled loop: f(ic<I>) for I in [B, E)
 template <int V> struct ic { static constexpr int value = V; };

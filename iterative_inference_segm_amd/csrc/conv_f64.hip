@@ -26,10 +26,8 @@ namespace {
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;
 constexpr int BM = 64, BN = 128;
-
 
 __device__ __forceinline__ double buf_ld64(const double* base, int bytes, unsigned voff, unsigned soff) {
     __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);

@@ -35,17 +35,8 @@ using namespace iiseg;
 
 namespace {
 
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const float* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc_b(const void* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);
-}
 __device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
 }
@@ -203,7 +194,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
             static_for<0, NQ>([&](auto I) __attribute__((always_inline)) {                         \
                 constexpr int i = decltype(I)::value;                                              \
                 const unsigned vo2 = qc[i] < crem ? qv[i] : OOB;                                   \
-                xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc_b(basem, nq >> 2),             \
+                xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc(basem, nq >> 2),               \
                                                             vo2 == OOB ? OOB : vo2 >> 2,           \
                                                             (unsigned)(c0 * hw2)));                \
                 xu[i] = buf_ld(mk_rsrc(baseu, nq), vo2, (unsigned)(c0 * hw2) * 4u);                \
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
                 const bool cok = cl[i] < crem;                                                     \
                 const unsigned vo = cok ? voff[i] : OOB, vo2 = cok ? voff2[i] : OOB;               \
                 if constexpr (MASKIN) {                                                            \
-                    xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc_b(basem, nq >> 2),         \
+                    xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc(basem, nq >> 2),           \
                                                                 vo2 == OOB ? OOB : vo2 >> 2,       \
                                                                 (unsigned)(c0 * hw2)));            \
                 } else {                                                                           \
@@ -365,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo_f32_kernel(const ConvParams 
         mk_rsrc(p.add ? p.add + (size_t)b * p.Cout * APL : nullptr, p.add ? nimg * p.Cout * APL * 4 : 0);
     const __amdgpu_buffer_rsrc_t r_pool =
         mk_rsrc(pooling ? p.pool + (size_t)b * p.Cout * PPL : nullptr, pooling ? nimg * p.Cout * PPL * 4 : 0);
-    const __amdgpu_buffer_rsrc_t r_mask = mk_rsrc_b(
+    const __amdgpu_buffer_rsrc_t r_mask = mk_rsrc(
         p.mask_out ? p.mask_out + (size_t)b * p.Cout * PPL : nullptr, p.mask_out ? nimg * p.Cout * PPL : 0);
     const bool relu1 = p.relu && !p.add, relu2 = p.relu && p.add;   // (with a skip-add the ReLU comes
                                                                     //  after the sum)
@@ -685,7 +676,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo16_f32_kernel(const ConvParam
             static_for<0, NQ>([&](auto I) __attribute__((always_inline)) {                         \
                 constexpr int i = decltype(I)::value;                                              \
                 const unsigned vo2 = qc[i] < crem ? qv[i] : OOB;                                   \
-                xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc_b(basem, nq >> 2),             \
+                xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc(basem, nq >> 2),               \
                                                             vo2 == OOB ? OOB : vo2 >> 2,           \
                                                             (unsigned)(c0 * hw2)));                \
                 xu[i] = buf_ld(mk_rsrc(baseu, nq), vo2, (unsigned)(c0 * hw2) * 4u);                \
@@ -697,7 +688,7 @@ __global__ __launch_bounds__(256, 2) void conv_halo16_f32_kernel(const ConvParam
                 const bool cok = cl[i] < crem;                                                     \
                 const unsigned vo = cok ? voff[i] : OOB, vo2 = cok ? voff2[i] : OOB;               \
                 if constexpr (MASKIN) {                                                            \
-                    xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc_b(basem, nq >> 2),         \
+                    xq[i] = __builtin_bit_cast(float, buf_ld_u8(mk_rsrc(basem, nq >> 2),           \
                                                                 vo2 == OOB ? OOB : vo2 >> 2,       \
                                                                 (unsigned)(c0 * hw2)));            \
                 } else {                                                                           \

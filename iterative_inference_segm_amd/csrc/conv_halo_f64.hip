@@ -35,7 +35,6 @@ namespace {
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;
 
 __device__ __forceinline__ double ld64(const double* base, int bytes, unsigned voff, unsigned soff) {

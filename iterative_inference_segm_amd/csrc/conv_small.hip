@@ -26,9 +26,7 @@ using namespace iiseg;
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;
 
 // T taps (1 or 9); COP: output channels padded to a multiple of 4 (<= 16).  Tile = 16 rows x 64 columns: thread

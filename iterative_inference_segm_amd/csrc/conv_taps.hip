@@ -29,13 +29,7 @@ using namespace iiseg;
 
 namespace {
 
-// raw buffer descriptor word 3 for gfx9/CDNA: DST_SEL = XYZW, DATA_FORMAT = 32 (raw dword access)
-constexpr int RSRC_W3 = 0x00027000;
 constexpr unsigned OOB = 0x80000000u;  // voffset that fails every range check (buffers < 2 GiB)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const float* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);
-}
 
 __device__ __forceinline__ float buf_ld(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));

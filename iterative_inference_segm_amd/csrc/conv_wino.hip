@@ -31,6 +31,7 @@
 #include "iiseg.h"
 #include "common.h"
 #include "conv_common.h"
+#include "wino_common.h"
 
 using namespace iiseg;
 
@@ -67,9 +68,6 @@ struct WinoParams {
     int mq;                  // M is M[xi][Mpad / 4][Tpad][4] (m_quad below), else M[xi][Mpad][Tpad]
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // max of a 2x2 window in the order of maxpool2x2 (pool_unpool.hip): same value, same sign of zero
 __device__ __forceinline__ float pool4(float v00, float v01, float v10, float v11) {
     const float a = v00 > v01 ? v00 : v01;
@@ -88,12 +86,6 @@ __device__ __forceinline__ void pool_store(const WinoParams& p, int b, int co, i
                                    (v10 == m ? 4u : 0u) | (v11 == m ? 8u : 0u));
 }
 
-constexpr int RSRC_W3 = 0x00027000;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const float* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);
-}
-
 // ---- 0. weights: U[xi][c][co] = (G g G^T)[xi], g = w[co][c] (cross-correlation, P1) -----------
 __global__ void wino_weight_kernel(const float* __restrict__ w, int64_t so, int64_t sc,
                                    float* __restrict__ U, int Cin, int Cout, int Kc, int Mpad) {
@@ -107,21 +99,13 @@ __global__ void wino_weight_kernel(const float* __restrict__ w, int64_t so, int6
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = 0; b < 3; ++b) g[a][b] = real ? (double)w[co * so + c * sc + a * 3 + b] : 0.0;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {  // G g
-            t[0][b] = g[0][b];
-            t[1][b] = 0.5 * (g[0][b] + g[1][b] + g[2][b]);
-            t[2][b] = 0.5 * (g[0][b] - g[1][b] + g[2][b]);
-            t[3][b] = g[2][b];
-        }
+        wino_Gg(g, t);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {  // (G g) G^T
-            const double u0 = t[a][0], u1 = 0.5 * (t[a][0] + t[a][1] + t[a][2]),
-                         u2 = 0.5 * (t[a][0] - t[a][1] + t[a][2]), u3 = t[a][2];
-            U[(int64_t)(a * 4 + 0) * n + i] = (float)u0;
-            U[(int64_t)(a * 4 + 1) * n + i] = (float)u1;
-            U[(int64_t)(a * 4 + 2) * n + i] = (float)u2;
-            U[(int64_t)(a * 4 + 3) * n + i] = (float)u3;
+            double u[4];
+            wino_tGt(t[a], u);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) U[(int64_t)(a * 4 + b) * n + i] = (float)u[b];
         }
     }
 }
@@ -139,11 +123,8 @@ template <bool UNPOOL, int PY, int PX, bool MB = false>
 __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
-    const int ntt = p.nty * p.ntx;
-    const int b = t / ntt;
-    const int r = t - b * ntt;
-    const int tyl = r / p.ntx, txl = r - tyl * p.ntx;
-    const int iy0 = p.ty0 + 2 * tyl - p.pad, ix0 = p.tx0 + 2 * txl - p.pad;
+    const WinoTile tile(p, t);
+    const int b = tile.b, iy0 = tile.y - p.pad, ix0 = tile.x - p.pad;
     int rowoff[4];
     bool rok[4], cok[4];
 #pragma unroll
@@ -238,22 +219,11 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
                     d[i][j] = (rok[i] && cok[j]) ? pv[cc][i][j] : 0.f;
                 }
             }
-        float e[4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {  // B^T d
-            e[0][j] = d[0][j] - d[2][j];
-            e[1][j] = d[1][j] + d[2][j];
-            e[2][j] = d[2][j] - d[1][j];
-            e[3][j] = d[1][j] - d[3][j];
-        }
+        float vv[16];
+        wino_BtdB(d, vv);
         float* v = p.V + (size_t)c * p.Tpad + t;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {  // (B^T d) B
-            v[(size_t)(i * 4 + 0) * xis] = e[i][0] - e[i][2];
-            v[(size_t)(i * 4 + 1) * xis] = e[i][1] + e[i][2];
-            v[(size_t)(i * 4 + 2) * xis] = e[i][2] - e[i][1];
-            v[(size_t)(i * 4 + 3) * xis] = e[i][1] - e[i][3];
-        }
+        for (int x = 0; x < 16; ++x) v[(size_t)x * xis] = vv[x];
     }
 }
 
@@ -361,20 +331,14 @@ __global__ __launch_bounds__(NT) void wino_input_lds_kernel(const WinoParams p, 
                 d[i][0] = lo.x; d[i][1] = lo.y; d[i][2] = hi.x; d[i][3] = hi.y;
             }
             float e[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {  // B^T d
-                e[0][j] = d[0][j] - d[2][j];
-                e[1][j] = d[1][j] + d[2][j];
-                e[2][j] = d[2][j] - d[1][j];
-                e[3][j] = d[1][j] - d[3][j];
-            }
+            wino_Btd(d, e);
             float* vo = p.V + (size_t)c * p.Tpad + t;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {  // (B^T d) B
-                vo[(size_t)(i * 4 + 0) * xis] = e[i][0] - e[i][2];
-                vo[(size_t)(i * 4 + 1) * xis] = e[i][1] + e[i][2];
-                vo[(size_t)(i * 4 + 2) * xis] = e[i][2] - e[i][1];
-                vo[(size_t)(i * 4 + 3) * xis] = e[i][1] - e[i][3];
+                float r[4];
+                wino_eB(e[i], r);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) vo[(size_t)(i * 4 + j) * xis] = r[j];
             }
         }
     }
@@ -531,6 +495,8 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
                 const float2 blo = *reinterpret_cast<const float2*>(Lb);
                 const float2 bhi = *reinterpret_cast<const float2*>(Lb + 2);
                 const float da[4] = {alo.x, alo.y, ahi.x, ahi.y}, db[4] = {blo.x, blo.y, bhi.x, bhi.y};
+                // (row i of wino_Btd, written out: the helper takes all four rows of d, and this kernel is
+                // built around holding two of them; then wino_eB's expressions on four tiles side by side)
                 float e[4];
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) e[jj] = i == 1 ? da[jj] + db[jj] : da[jj] - db[jj];   // B^T d
@@ -874,7 +840,6 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wino_fused_kernel(const Wi
     // pixels of a row go out as ONE 8-byte store (lanes are consecutive tiles: 256 contiguous bytes
     // per 32 lanes) wherever both columns are inside the window; the channel offsets are formed once
     // per (i, r) from 32-bit products.
-    typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
     const int ntt = p.nty * p.ntx;
     const size_t OPL = (size_t)p.out_H * p.out_W, APL = (size_t)p.AH * p.AW;
     // The tile's BM bias values go through LDS (free after the last k-tile's barrier): read from global per
@@ -973,16 +938,12 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void wino_fused_kernel(const Wi
 // (a quad that straddles Cout is read whole: rows up to Mpad exist) -- and a tile row with both
 // columns inside the window is one 8-byte store.  Same arithmetic, same bits as the other form.
 constexpr int OCH = 4;
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte access, 4-byte aligned
 template <bool QUAD>
 __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
-    const int ntt = p.nty * p.ntx;
-    const int b = t / ntt;
-    const int r = t - b * ntt;
-    const int tyl = r / p.ntx, txl = r - tyl * p.ntx;
-    const int wy = p.ty0 + 2 * tyl - p.oy0, wx = p.tx0 + 2 * txl - p.ox0;  // window coords
+    const WinoTile tile(p, t);
+    const int b = tile.b, wy = tile.y - p.oy0, wx = tile.x - p.ox0;  // window coords
     const bool okr[2] = {(unsigned)wy < (unsigned)p.OH, (unsigned)(wy + 1) < (unsigned)p.OH};
     const bool okc[2] = {(unsigned)wx < (unsigned)p.OW, (unsigned)(wx + 1) < (unsigned)p.OW};
     const size_t xis = (size_t)p.Mpad * p.Tpad;
@@ -1041,12 +1002,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
         const int co = co0 + cc;
         if (co >= p.Cout) break;
         float s2[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {  // A^T m
-            const float m0 = mv[cc][j], m1 = mv[cc][4 + j], m2 = mv[cc][8 + j], m3 = mv[cc][12 + j];
-            s2[0][j] = m0 + m1 + m2;
-            s2[1][j] = m1 - m2 - m3;
-        }
+        wino_Atm(mv[cc], s2);
         float bias;
         float* o;
         if constexpr (QUAD) {
@@ -1061,7 +1017,8 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
         float vt[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // (A^T m) A
-            float y[2] = {s2[i][0] + s2[i][1] + s2[i][2], s2[i][1] - s2[i][2] - s2[i][3]};
+            float y[2];
+            wino_sA(s2[i], y);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 float v = y[j] + bias;
@@ -1090,35 +1047,20 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
     }
 }
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // geometry shared by the sizing queries and the launcher
 struct WinoGeom {
     int Kc, Mpad, bm, ty0, tx0, nty, ntx, T, Tpad;
 };
 
 int wino_geom(const iiseg_conv_desc* d, WinoGeom& g) {
-    if (!d) return IISEG_ERR_NULL;
-    if (d->KH != 3 || d->KW != 3 || d->dil != 1 || (d->flags & IISEG_CONV_TRANSPOSED2))
-        return IISEG_ERR_UNSUPPORTED;
-    if ((d->flags & IISEG_CONV_UNPOOL) && d->C2 != 0) return IISEG_ERR_UNSUPPORTED;
-    if (d->B <= 0 || d->C1 <= 0 || d->C2 < 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0 ||
-        d->pad < 0 || d->OH <= 0 || d->OW <= 0 || d->oy0 < 0 || d->ox0 < 0)
-        return IISEG_ERR_SHAPE;
-    const int fullH = d->H + 2 * d->pad - 2, fullW = d->W + 2 * d->pad - 2;
-    if (d->oy0 + d->OH > fullH || d->ox0 + d->OW > fullW) return IISEG_ERR_SHAPE;
-    if ((d->C1 + d->C2) % 16) return IISEG_ERR_UNSUPPORTED;
+    WinoTiles w;
+    const int st = wino_tiles(d, w, 16);
+    if (st) return st;
     g.Kc = d->C1 + d->C2;
     g.bm = d->Cout > 128 ? 256 : (d->Cout > 64 ? 128 : 64);
     g.Mpad = round_up(d->Cout, g.bm);
-    // tiles cover output rows r, r+1 with r = tile_y0 (mod 2): the first one is the last such row
-    // at or before the window origin
-    if ((d->tile_y0 | d->tile_x0) & ~1) return IISEG_ERR_SHAPE;
-    g.ty0 = d->oy0 - ((d->oy0 - d->tile_y0) & 1);
-    g.tx0 = d->ox0 - ((d->ox0 - d->tile_x0) & 1);
-    g.nty = (d->oy0 + d->OH - g.ty0 + 1) >> 1;
-    g.ntx = (d->ox0 + d->OW - g.tx0 + 1) >> 1;
-    const int64_t T = (int64_t)d->B * g.nty * g.ntx;
+    g.ty0 = w.ty0; g.tx0 = w.tx0; g.nty = w.nty; g.ntx = w.ntx;
+    const int64_t T = w.T;
     const int64_t Tpad = (T + 127) / 128 * 128;
     // buffer descriptors address one xi-slice of U / V with 32-bit byte offsets
     if (Tpad * g.Kc * 4 >= (int64_t)1 << 31 || (int64_t)g.Kc * g.Mpad * 4 >= (int64_t)1 << 31)
@@ -1271,20 +1213,15 @@ int iiseg_wino_output_launch(hipStream_t s, const iiseg_conv_desc* d, const floa
     p.bias = bias; p.add = add; p.out = out;
     p.B = d->B; p.Cout = d->Cout; p.pad = d->pad;
     p.oy0 = d->oy0; p.ox0 = d->ox0; p.OH = d->OH; p.OW = d->OW;
-    p.ty0 = d->oy0 - ((d->oy0 - d->tile_y0) & 1);
-    p.tx0 = d->ox0 - ((d->ox0 - d->tile_x0) & 1);
-    p.nty = (d->oy0 + d->OH - p.ty0 + 1) >> 1;
-    p.ntx = (d->ox0 + d->OW - p.tx0 + 1) >> 1;
-    p.T = d->B * p.nty * p.ntx;
+    WinoTiles w;
+    const int st = wino_tiles(d, w, 1);
+    if (st) return st;
+    p.ty0 = w.ty0; p.tx0 = w.tx0; p.nty = w.nty; p.ntx = w.ntx;
+    p.T = (int)w.T;
     p.Tpad = Tpad; p.Mpad = Mpad;
     p.AH = d->AH; p.AW = d->AW; p.ay0 = d->ay0; p.ax0 = d->ax0;
     p.relu = (d->flags & IISEG_CONV_RELU) ? 1 : 0;
-    p.out_ctot = d->out_ctot > 0 ? d->out_ctot : d->Cout;
-    p.out_c0 = d->out_ctot > 0 ? d->out_c0 : 0;
-    p.out_H = d->out_H > 0 ? d->out_H : d->OH;
-    p.out_W = d->out_H > 0 ? d->out_W : d->OW;
-    p.out_y0 = d->out_H > 0 ? d->out_y0 : 0;
-    p.out_x0 = d->out_H > 0 ? d->out_x0 : 0;
+    if (wino_out_place(d, p)) return IISEG_ERR_SHAPE;
     p.mq = m_quad(Mpad, Tpad);
     const dim3 og((p.T + 255) / 256, (d->Cout + OCH - 1) / OCH);
     if (p.mq) IISEG_LAUNCH(wino_output_kernel<true>, og, dim3(256), 0, s, p);
@@ -1406,15 +1343,7 @@ static int wino_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
     if (add && (d->ay0 < 0 || d->ax0 < 0 || d->ay0 + d->OH > d->AH || d->ax0 + d->OW > d->AW))
         return IISEG_ERR_SHAPE;
     p.relu = (d->flags & IISEG_CONV_RELU) ? 1 : 0;
-    p.out_ctot = d->out_ctot > 0 ? d->out_ctot : d->Cout;
-    p.out_c0 = d->out_ctot > 0 ? d->out_c0 : 0;
-    if (p.out_c0 < 0 || p.out_c0 + d->Cout > p.out_ctot) return IISEG_ERR_SHAPE;
-    p.out_H = d->out_H > 0 ? d->out_H : d->OH;
-    p.out_W = d->out_H > 0 ? d->out_W : d->OW;
-    p.out_y0 = d->out_H > 0 ? d->out_y0 : 0;
-    p.out_x0 = d->out_H > 0 ? d->out_x0 : 0;
-    if (p.out_y0 < 0 || p.out_x0 < 0 || p.out_y0 + d->OH > p.out_H || p.out_x0 + d->OW > p.out_W)
-        return IISEG_ERR_SHAPE;
+    if (wino_out_place(d, p)) return IISEG_ERR_SHAPE;
     p.n_ttiles = g.Tpad / 128;
     p.n_mtiles = g.Mpad / g.bm;
     p.mq = m_quad(g.Mpad, g.Tpad);

@@ -26,15 +26,13 @@
 #include "iiseg.h"
 #include "common.h"
 #include "conv_common.h"
+#include "wino_common.h"
 
 using namespace iiseg;
 
 int iiseg_wino_m_quad_layout(int Mpad, int Tpad);   // conv_wino.hip: the layout its output kernels read
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte store, 4-byte aligned
 
 struct WinoBfParams {
     const float* x1;
@@ -61,22 +59,6 @@ struct WinoBfParams {
     int mq;                  // the GEMM kernel's M is M[xi][Mpad / 4][Tpad][4] (set by launch_gemm_bf16)
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int RSRC_W3 = 0x00027000;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, int bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, RSRC_W3);
-}
-
-// two floats -> two bf16 (round to nearest even; a NaN stays a NaN: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
-
 // ---- 0. weights: U16[xi][c/8][co][c%8] = bf16((G g G^T)[xi]), g = w[co][c] (cross-correlation) ----
 __global__ void wino_weight_bf16_kernel(const float* __restrict__ w, int64_t so, int64_t sc,
                                         __bf16* __restrict__ U, int Cin, int Cout, int Kc, int Mpad) {
@@ -90,18 +72,12 @@ __global__ void wino_weight_bf16_kernel(const float* __restrict__ w, int64_t so,
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = 0; b < 3; ++b) g[a][b] = real ? (double)w[co * so + c * sc + a * 3 + b] : 0.0;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {  // G g
-            t[0][b] = g[0][b];
-            t[1][b] = 0.5 * (g[0][b] + g[1][b] + g[2][b]);
-            t[2][b] = 0.5 * (g[0][b] - g[1][b] + g[2][b]);
-            t[3][b] = g[2][b];
-        }
+        wino_Gg(g, t);
         const int64_t chunk = ((int64_t)(c >> 3) * Mpad + co) * 8 + (c & 7);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {  // (G g) G^T
-            const double u[4] = {t[a][0], 0.5 * (t[a][0] + t[a][1] + t[a][2]),
-                                 0.5 * (t[a][0] - t[a][1] + t[a][2]), t[a][2]};
+            double u[4];
+            wino_tGt(t[a], u);
 #pragma unroll
             for (int b = 0; b < 4; ++b) U[(int64_t)(a * 4 + b) * n + chunk] = (__bf16)(float)u[b];
         }
@@ -118,11 +94,8 @@ template <bool UNPOOL, int PY, int PX>
 __global__ __launch_bounds__(256) void wino_input_bf16_kernel(const WinoBfParams p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
-    const int ntt = p.nty * p.ntx;
-    const int b = t / ntt;
-    const int r = t - b * ntt;
-    const int tyl = r / p.ntx, txl = r - tyl * p.ntx;
-    const int iy0 = p.ty0 + 2 * tyl - p.pad, ix0 = p.tx0 + 2 * txl - p.pad;
+    const WinoTile tile(p, t);
+    const int b = tile.b, iy0 = tile.y - p.pad, ix0 = tile.x - p.pad;
     int rowoff[4];
     bool rok[4], cok[4];
 #pragma unroll
@@ -206,21 +179,7 @@ __global__ __launch_bounds__(256) void wino_input_bf16_kernel(const WinoBfParams
                             d[i][j] = (creal[cc] && rok[i] && cok[j]) ? pv[cc][i][j] : 0.f;
                         }
                     }
-                float e[4][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {  // B^T d
-                    e[0][j] = d[0][j] - d[2][j];
-                    e[1][j] = d[1][j] + d[2][j];
-                    e[2][j] = d[2][j] - d[1][j];
-                    e[3][j] = d[1][j] - d[3][j];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {  // (B^T d) B
-                    vv[u][i * 4 + 0] = e[i][0] - e[i][2];
-                    vv[u][i * 4 + 1] = e[i][1] + e[i][2];
-                    vv[u][i * 4 + 2] = e[i][2] - e[i][1];
-                    vv[u][i * 4 + 3] = e[i][1] - e[i][3];
-                }
+                wino_BtdB(d, vv[u]);
             }
 #pragma unroll
             for (int xi = 0; xi < 16; ++xi) res[xi][half * 2 + pr] = pack_bf16(vv[0][xi], vv[1][xi]);
@@ -327,21 +286,7 @@ __global__ __launch_bounds__(NT) void wino_input_lds_bf16_kernel(const WinoBfPar
                 const float2 hi = *reinterpret_cast<const float2*>(L + lbase + i * NC + 2);
                 d[i][0] = lo.x; d[i][1] = lo.y; d[i][2] = hi.x; d[i][3] = hi.y;
             }
-            float e[4][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {  // B^T d
-                e[0][j] = d[0][j] - d[2][j];
-                e[1][j] = d[1][j] + d[2][j];
-                e[2][j] = d[2][j] - d[1][j];
-                e[3][j] = d[1][j] - d[3][j];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {  // (B^T d) B
-                vv[i * 4 + 0] = e[i][0] - e[i][2];
-                vv[i * 4 + 1] = e[i][1] + e[i][2];
-                vv[i * 4 + 2] = e[i][2] - e[i][1];
-                vv[i * 4 + 3] = e[i][1] - e[i][3];
-            }
+            wino_BtdB(d, vv);
         } else {
 #pragma unroll
             for (int x = 0; x < 16; ++x) vv[x] = 0.f;
@@ -841,8 +786,6 @@ void launch_gemm_bf16(hipStream_t s, WinoBfParams p, float* M, int n_xi) {
     }
 }
 
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 constexpr int WBF_BK = 64;   // k-tile of the GEMM kernel: channels are padded to it
 
 // grid of a persistent launch: every tile if they all fit one residency round, else one round
@@ -865,24 +808,14 @@ int split_min_kc() {
 }
 
 int wino_bf16_geom(const iiseg_conv_desc* d, WinoBfGeom& g) {
-    if (!d) return IISEG_ERR_NULL;
-    if (d->KH != 3 || d->KW != 3 || d->dil != 1 || (d->flags & IISEG_CONV_TRANSPOSED2))
-        return IISEG_ERR_UNSUPPORTED;
-    if ((d->flags & IISEG_CONV_UNPOOL) && d->C2 != 0) return IISEG_ERR_UNSUPPORTED;
-    if (d->B <= 0 || d->C1 <= 0 || d->C2 < 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0 ||
-        d->pad < 0 || d->OH <= 0 || d->OW <= 0 || d->oy0 < 0 || d->ox0 < 0)
-        return IISEG_ERR_SHAPE;
-    const int fullH = d->H + 2 * d->pad - 2, fullW = d->W + 2 * d->pad - 2;
-    if (d->oy0 + d->OH > fullH || d->ox0 + d->OW > fullW) return IISEG_ERR_SHAPE;
+    WinoTiles w;
+    const int st = wino_tiles(d, w, 1);   // any channel count: padded to the k-tile with zero channels
+    if (st) return st;
     g.Kc = round_up(d->C1 + d->C2, WBF_BK);
     g.bm = d->Cout > 64 ? 128 : 64;
     g.Mpad = round_up(d->Cout, g.bm);
-    if ((d->tile_y0 | d->tile_x0) & ~1) return IISEG_ERR_SHAPE;
-    g.ty0 = d->oy0 - ((d->oy0 - d->tile_y0) & 1);
-    g.tx0 = d->ox0 - ((d->ox0 - d->tile_x0) & 1);
-    g.nty = (d->oy0 + d->OH - g.ty0 + 1) >> 1;
-    g.ntx = (d->ox0 + d->OW - g.tx0 + 1) >> 1;
-    const int64_t T = (int64_t)d->B * g.nty * g.ntx;
+    g.ty0 = w.ty0; g.tx0 = w.tx0; g.nty = w.nty; g.ntx = w.ntx;
+    const int64_t T = w.T;
     const bool split = g.Kc >= split_min_kc() && g.Mpad % 128 == 0;
     // (the separate GEMM kernel may use 256-tile blocks)
     const int64_t Tpad = split ? (T + 255) / 256 * 256 : (T + 127) / 128 * 128;
@@ -964,15 +897,7 @@ extern "C" int iiseg_conv_wino_bf16(void* stream, const iiseg_conv_desc* d, cons
     p.relu = (d->flags & IISEG_CONV_RELU) ? 1 : 0;
     static const int dbg = getenv("IISEG_BF16_DEBUG") ? atoi(getenv("IISEG_BF16_DEBUG")) : 0;
     p.debug = dbg;
-    p.out_ctot = d->out_ctot > 0 ? d->out_ctot : d->Cout;
-    p.out_c0 = d->out_ctot > 0 ? d->out_c0 : 0;
-    if (p.out_c0 < 0 || p.out_c0 + d->Cout > p.out_ctot) return IISEG_ERR_SHAPE;
-    p.out_H = d->out_H > 0 ? d->out_H : d->OH;
-    p.out_W = d->out_H > 0 ? d->out_W : d->OW;
-    p.out_y0 = d->out_H > 0 ? d->out_y0 : 0;
-    p.out_x0 = d->out_H > 0 ? d->out_x0 : 0;
-    if (p.out_y0 < 0 || p.out_x0 < 0 || p.out_y0 + d->OH > p.out_H || p.out_x0 + d->OW > p.out_W)
-        return IISEG_ERR_SHAPE;
+    if (wino_out_place(d, p)) return IISEG_ERR_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     if (stages & IISEG_WINO_INPUT) launch_wino_input_bf16(s, p, unpool);
     if ((stages & IISEG_WINO_GEMM) && !g.fused) {

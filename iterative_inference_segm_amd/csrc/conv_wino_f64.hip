@@ -23,6 +23,7 @@
 #include "iiseg.h"
 #include "common.h"
 #include "conv_common.h"
+#include "wino_common.h"
 
 using namespace iiseg;
 
@@ -61,26 +62,15 @@ __global__ void wino64_weight_kernel(const double* __restrict__ w, int64_t so, i
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i / Mpad), co = (int)(i % Mpad);
-        double g[3][3], t[4][3];
+        double g[3][3], u[16];
         const bool real = c < Cin && co < Cout;
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = 0; b < 3; ++b) g[a][b] = real ? w[co * so + c * sc + a * 3 + b] : 0.0;
+        wino_GgGt(g, u);
 #pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            t[0][b] = g[0][b];
-            t[1][b] = 0.5 * (g[0][b] + g[1][b] + g[2][b]);
-            t[2][b] = 0.5 * (g[0][b] - g[1][b] + g[2][b]);
-            t[3][b] = g[2][b];
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            U[(int64_t)(a * 4 + 0) * n + i] = t[a][0];
-            U[(int64_t)(a * 4 + 1) * n + i] = 0.5 * (t[a][0] + t[a][1] + t[a][2]);
-            U[(int64_t)(a * 4 + 2) * n + i] = 0.5 * (t[a][0] - t[a][1] + t[a][2]);
-            U[(int64_t)(a * 4 + 3) * n + i] = t[a][2];
-        }
+        for (int x = 0; x < 16; ++x) U[(int64_t)x * n + i] = u[x];
     }
 }
 
@@ -93,11 +83,8 @@ template <bool UNPOOL>
 __global__ __launch_bounds__(256) void wino64_input_kernel(const Wino64Params p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
-    const int ntt = p.nty * p.ntx;
-    const int b = t / ntt;
-    const int r = t - b * ntt;
-    const int tyl = r / p.ntx, txl = r - tyl * p.ntx;
-    const int iy0 = p.ty0 + 2 * tyl - p.pad, ix0 = p.tx0 + 2 * txl - p.pad;
+    const WinoTile tile(p, t);
+    const int b = tile.b, iy0 = tile.y - p.pad, ix0 = tile.x - p.pad;
     int rowoff[4];
     bool rok[4], cok[4];
 #pragma unroll
@@ -164,20 +151,14 @@ __global__ __launch_bounds__(256) void wino64_input_kernel(const Wino64Params p)
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) d[i][j] = (UNPOOL || (rok[i] && cok[j])) ? pv[cc][i][j] : 0.0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {  // B^T d
-            e[0][j] = d[0][j] - d[2][j];
-            e[1][j] = d[1][j] + d[2][j];
-            e[2][j] = d[2][j] - d[1][j];
-            e[3][j] = d[1][j] - d[3][j];
-        }
+        wino_Btd(d, e);
         double* v = p.V + (size_t)c * p.Tpad + t;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {  // (B^T d) B
-            v[(size_t)(i * 4 + 0) * xis] = e[i][0] - e[i][2];
-            v[(size_t)(i * 4 + 1) * xis] = e[i][1] + e[i][2];
-            v[(size_t)(i * 4 + 2) * xis] = e[i][2] - e[i][1];
-            v[(size_t)(i * 4 + 3) * xis] = e[i][1] - e[i][3];
+            double r[4];
+            wino_eB(e[i], r);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[(size_t)(i * 4 + j) * xis] = r[j];
         }
     }
 }
@@ -270,11 +251,8 @@ constexpr int OCH64 = 2;
 __global__ __launch_bounds__(256) void wino64_output_kernel(const Wino64Params p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
-    const int ntt = p.nty * p.ntx;
-    const int b = t / ntt;
-    const int r = t - b * ntt;
-    const int tyl = r / p.ntx, txl = r - tyl * p.ntx;
-    const int wy = p.ty0 + 2 * tyl - p.oy0, wx = p.tx0 + 2 * txl - p.ox0;  // window coords
+    const WinoTile tile(p, t);
+    const int b = tile.b, wy = tile.y - p.oy0, wx = tile.x - p.ox0;  // window coords
     const bool okr[2] = {(unsigned)wy < (unsigned)p.OH, (unsigned)(wy + 1) < (unsigned)p.OH};
     const bool okc[2] = {(unsigned)wx < (unsigned)p.OW, (unsigned)(wx + 1) < (unsigned)p.OW};
     const size_t xis = (size_t)p.Mpad * p.Tpad;
@@ -305,18 +283,14 @@ __global__ __launch_bounds__(256) void wino64_output_kernel(const Wino64Params p
         const int co = co0 + cc;
         if (co >= p.Cout) break;
         double s2[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {  // A^T m
-            const double m0 = mv[cc][j], m1 = mv[cc][4 + j], m2 = mv[cc][8 + j], m3 = mv[cc][12 + j];
-            s2[0][j] = m0 + m1 + m2;
-            s2[1][j] = m1 - m2 - m3;
-        }
+        wino_Atm(mv[cc], s2);
         const double bias = p.bias ? p.bias[co] : 0.0;
         double* o = p.out + ((size_t)b * p.out_ctot + p.out_c0 + co) * OPL +
                     (ptrdiff_t)(p.out_y0 + wy) * p.out_W + p.out_x0 + wx;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // (A^T m) A
-            const double y[2] = {s2[i][0] + s2[i][1] + s2[i][2], s2[i][1] - s2[i][2] - s2[i][3]};
+            double y[2];
+            wino_sA(s2[i], y);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if (okr[i] && okc[j]) {
@@ -338,7 +312,6 @@ __global__ __launch_bounds__(256) void wino64_output_kernel(const Wino64Params p
 // is a scalar offset of the buffer instruction, and V / M are addressed as wave-uniform base + thread index.
 // Same arithmetic in the same order: bit-identical to the kernels above.
 constexpr unsigned OOB64 = 0x80000000u;
-constexpr int RSRC64_W3 = 0x00027000;
 __device__ __forceinline__ double bld64(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     typedef int i32x2_ __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(double, (i32x2_)__builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0));
@@ -380,12 +353,12 @@ __global__ __launch_bounds__(256) void wino64_input2_kernel(const Wino64Params p
         }
     // V as one buffer: slice (xi, c) is a scalar offset, the tile a fixed per-thread offset
     const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.V, 0, (int)(8u * (unsigned)(16 * p.Kc * p.Tpad)), RSRC64_W3);
+        (void*)p.V, 0, (int)(8u * (unsigned)(16 * p.Kc * p.Tpad)), RSRC_W3);
     const unsigned tv = tok ? 8u * (unsigned)t : OOB64;
     const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(UNPOOL ? p.pre : p.x1), 0, (int)(8u * (unsigned)(p.B * p.C1 * HW)), RSRC64_W3);
+        (void*)(UNPOOL ? p.pre : p.x1), 0, (int)(8u * (unsigned)(p.B * p.C1 * HW)), RSRC_W3);
     const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.C2 > 0 ? p.x2 : p.x1), 0, (int)(8u * (unsigned)(p.B * (p.C2 > 0 ? p.C2 : p.C1) * HW)), RSRC64_W3);
+        (void*)(p.C2 > 0 ? p.x2 : p.x1), 0, (int)(8u * (unsigned)(p.B * (p.C2 > 0 ? p.C2 : p.C1) * HW)), RSRC_W3);
     // UNPOOL: the 3 x 3 pooling cells the patch touches (pooled / up), byte offsets inside image b's first plane
     const int hw2 = p.h2 * p.w2;
     unsigned qix[UNPOOL ? 3 : 1][UNPOOL ? 3 : 1];
@@ -401,9 +374,9 @@ __global__ __launch_bounds__(256) void wino64_input2_kernel(const Wino64Params p
             }
     }
     const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(UNPOOL ? p.pooled : p.x1), 0, (int)(8u * (unsigned)(p.B * p.C1 * (UNPOOL ? hw2 : HW))), RSRC64_W3);
+        (void*)(UNPOOL ? p.pooled : p.x1), 0, (int)(8u * (unsigned)(p.B * p.C1 * (UNPOOL ? hw2 : HW))), RSRC_W3);
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.x1, 0, (int)(8u * (unsigned)(p.B * p.C1 * (UNPOOL ? hw2 : HW))), RSRC64_W3);
+        (void*)p.x1, 0, (int)(8u * (unsigned)(p.B * p.C1 * (UNPOOL ? hw2 : HW))), RSRC_W3);
     const size_t xis = (size_t)p.Kc * p.Tpad;
     const int c0 = blockIdx.y * ICG64;
     for (int cc = 0; cc < ICG64; cc += 2) {
@@ -458,6 +431,10 @@ __global__ __launch_bounds__(256) void wino64_input2_kernel(const Wino64Params p
         for (int h = 0; h < 2; ++h) {
             const int c = c0 + cc + h;
             if (c >= p.Kc) break;
+            // (wino_Btd / wino_eB of wino_common.h written out, the only copy left: through the helpers hipcc
+            // forms this kernel's 16 scalar store offsets with s_mul instead of adds, 8 % more instructions
+            // in a kernel that is bound by issue; the child-process test of test_gpu_f64.py holds it to
+            // wino64_input_kernel, which uses them, bit for bit)
             double e[4][4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {  // B^T d
@@ -482,11 +459,8 @@ constexpr int OCG64 = 2;      // output channels per thread (loop)
 __global__ __launch_bounds__(256) void wino64_output2_kernel(const Wino64Params p) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
-    const int ntt = p.nty * p.ntx;
-    const int b = t / ntt;
-    const int r = t - b * ntt;
-    const int tyl = r / p.ntx, txl = r - tyl * p.ntx;
-    const int wy = p.ty0 + 2 * tyl - p.oy0, wx = p.tx0 + 2 * txl - p.ox0;  // window coords
+    const WinoTile tile(p, t);
+    const int b = tile.b, wy = tile.y - p.oy0, wx = tile.x - p.ox0;  // window coords
     const int OPL = p.out_H * p.out_W, APL = p.AH * p.AW;
     unsigned ooff[2][2], aoff[2][2];
 #pragma unroll
@@ -501,11 +475,11 @@ __global__ __launch_bounds__(256) void wino64_output2_kernel(const Wino64Params 
                                        : OOB64;
         }
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.out, 0, (int)(8u * (unsigned)(p.B * p.out_ctot * OPL)), RSRC64_W3);
+        (void*)p.out, 0, (int)(8u * (unsigned)(p.B * p.out_ctot * OPL)), RSRC_W3);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.add ? p.add : p.out), 0, p.add ? (int)(8u * (unsigned)(p.B * p.Cout * APL)) : 0, RSRC64_W3);
+        (void*)(p.add ? p.add : p.out), 0, p.add ? (int)(8u * (unsigned)(p.B * p.Cout * APL)) : 0, RSRC_W3);
     const __amdgpu_buffer_rsrc_t rM = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)p.M, 0, (int)(8u * (unsigned)(16 * p.Mpad * p.Tpad)), RSRC64_W3);
+        (void*)p.M, 0, (int)(8u * (unsigned)(16 * p.Mpad * p.Tpad)), RSRC_W3);
     const unsigned tv = 8u * (unsigned)t, sx = 8u * (unsigned)(p.Mpad * p.Tpad);
     const int co0 = blockIdx.y * OCG64;
     for (int cc = 0; cc < OCG64; ++cc) {
@@ -520,16 +494,12 @@ __global__ __launch_bounds__(256) void wino64_output2_kernel(const Wino64Params 
 #pragma unroll
             for (int j = 0; j < 2; ++j) av[i * 2 + j] = bld64(ra, aoff[i][j], 8u * (unsigned)(co * APL));
         double s2[2][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {  // A^T m
-            const double m0 = mv[j], m1 = mv[4 + j], m2 = mv[8 + j], m3 = mv[12 + j];
-            s2[0][j] = m0 + m1 + m2;
-            s2[1][j] = m1 - m2 - m3;
-        }
+        wino_Atm(mv, s2);
         const double bias = p.bias ? p.bias[co] : 0.0;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // (A^T m) A
-            const double y[2] = {s2[i][0] + s2[i][1] + s2[i][2], s2[i][1] - s2[i][2] - s2[i][3]};
+            double y[2];
+            wino_sA(s2[i], y);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 double v = y[j] + bias;
@@ -546,24 +516,13 @@ struct Wino64Geom {
 };
 
 int wino64_geom(const iiseg_conv_desc* d, Wino64Geom& g) {
-    if (!d) return IISEG_ERR_NULL;
-    if (d->KH != 3 || d->KW != 3 || d->dil != 1 || (d->flags & IISEG_CONV_TRANSPOSED2))
-        return IISEG_ERR_UNSUPPORTED;
-    if ((d->flags & IISEG_CONV_UNPOOL) && d->C2 != 0) return IISEG_ERR_UNSUPPORTED;
-    if (d->B <= 0 || d->C1 <= 0 || d->C2 < 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0 ||
-        d->pad < 0 || d->OH <= 0 || d->OW <= 0 || d->oy0 < 0 || d->ox0 < 0)
-        return IISEG_ERR_SHAPE;
-    const int fullH = d->H + 2 * d->pad - 2, fullW = d->W + 2 * d->pad - 2;
-    if (d->oy0 + d->OH > fullH || d->ox0 + d->OW > fullW) return IISEG_ERR_SHAPE;
-    if ((d->C1 + d->C2) % GBK) return IISEG_ERR_UNSUPPORTED;
-    if ((d->tile_y0 | d->tile_x0) & ~1) return IISEG_ERR_SHAPE;
+    WinoTiles w;
+    const int st = wino_tiles(d, w, GBK);
+    if (st) return st;
     g.Kc = d->C1 + d->C2;
-    g.Mpad = (d->Cout + GBM - 1) / GBM * GBM;
-    g.ty0 = d->oy0 - ((d->oy0 - d->tile_y0) & 1);
-    g.tx0 = d->ox0 - ((d->ox0 - d->tile_x0) & 1);
-    g.nty = (d->oy0 + d->OH - g.ty0 + 1) >> 1;
-    g.ntx = (d->ox0 + d->OW - g.tx0 + 1) >> 1;
-    const int64_t T = (int64_t)d->B * g.nty * g.ntx;
+    g.Mpad = round_up(d->Cout, GBM);
+    g.ty0 = w.ty0; g.tx0 = w.tx0; g.nty = w.nty; g.ntx = w.ntx;
+    const int64_t T = w.T;
     const int64_t Tpad = (T + GBN - 1) / GBN * GBN;
     // one xi-slice of U / V is addressed with 32-bit byte offsets
     if (Tpad * g.Kc * 8 >= (int64_t)1 << 31 || (int64_t)g.Kc * g.Mpad * 8 >= (int64_t)1 << 31)
@@ -746,15 +705,7 @@ extern "C" int iiseg_conv_wino_f64(void* stream, const iiseg_conv_desc* d, const
     p.T = g.T; p.Tpad = g.Tpad; p.Kc = g.Kc; p.Mpad = g.Mpad;
     p.AH = d->AH; p.AW = d->AW; p.ay0 = d->ay0; p.ax0 = d->ax0;
     p.relu = (d->flags & IISEG_CONV_RELU) ? 1 : 0;
-    p.out_ctot = d->out_ctot > 0 ? d->out_ctot : d->Cout;
-    p.out_c0 = d->out_ctot > 0 ? d->out_c0 : 0;
-    if (p.out_c0 < 0 || p.out_c0 + d->Cout > p.out_ctot) return IISEG_ERR_SHAPE;
-    p.out_H = d->out_H > 0 ? d->out_H : d->OH;
-    p.out_W = d->out_H > 0 ? d->out_W : d->OW;
-    p.out_y0 = d->out_H > 0 ? d->out_y0 : 0;
-    p.out_x0 = d->out_H > 0 ? d->out_x0 : 0;
-    if (p.out_y0 < 0 || p.out_x0 < 0 || p.out_y0 + d->OH > p.out_H || p.out_x0 + d->OW > p.out_W)
-        return IISEG_ERR_SHAPE;
+    if (wino_out_place(d, p)) return IISEG_ERR_SHAPE;
     p.n_ttiles = g.Tpad / GBN;
     p.n_mtiles = g.Mpad / GBM;
     hipStream_t s = (hipStream_t)stream;

@@ -25,12 +25,8 @@ using namespace iiseg;
 namespace {
 
 constexpr unsigned OOB = 0x80000000u;
-constexpr int RSRC_W3 = 0x00027000;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <typename T>
 struct PhaseParams {

@@ -6,7 +6,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 rev=$1; f=$2; out=$3
 tmp=$(mktemp -d)
 git -C $R show $rev:iterative_inference_segm_amd/csrc/$f > $tmp/$f
-for h in common.h conv_common.h c8_common.h; do git -C $R show $rev:iterative_inference_segm_amd/csrc/$h > $tmp/$h 2>/dev/null || cp $R/iterative_inference_segm_amd/csrc/$h $tmp/$h; done
+# every csrc/*.h of that revision (a header the revision does not have yet is not copied: its source cannot include it)
+for h in $(git -C $R ls-tree --name-only $rev iterative_inference_segm_amd/csrc/ | grep '\.h$'); do git -C $R show $rev:$h > $tmp/$(basename $h); done
 # (per-source flags as in iterative_inference_segm_amd/build.py EXTRA_FLAGS)
 extra=$(python3 -c "import sys; sys.path.insert(0, '$R'); from iterative_inference_segm_amd.build import EXTRA_FLAGS; print(' '.join(EXTRA_FLAGS.get('$f', [])))")
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 $extra -I$R/include -I$tmp -c $tmp/$f -o $tmp/ab.o

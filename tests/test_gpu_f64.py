@@ -466,3 +466,54 @@ def test_float64_path_with_only_the_halo_kernel_switched_off(built_lib):
     r = subprocess.run([sys.executable, '-c', _HALO_OFF_SCRIPT % {'root': root}], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and 'F64_HALO_OFF_OK' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def _w64_transform_digests(ops):
+    """sha256 of the output bytes of two float64 Winograd launches: WINO64_CASES[4] (plain input, window, odd
+    anchor) and the second test_conv_wino_f64_fused_unpool case (DePool2D input, window, anchor (1, 0)), each
+    with the seed its own test uses."""
+    import hashlib
+    assert ops.WINO_F64_MIN_COUT == 64                        # (the default sends Cout < 128 to the halo kernel)
+    digests = []
+    case = WINO64_CASES[4]
+    B, Cin, H, W, Cout, pad, relu, window, anchor = case
+    rng = np.random.default_rng(sum(case[:6]))
+    x, Wt, b = rng.standard_normal((B, Cin, H, W)), rng.standard_normal((Cout, Cin, 3, 3)), \
+        rng.standard_normal(Cout)
+    conv = ops.Conv(Wt, b, pad=pad, relu=relu, dtype=F64)
+    got = host(conv(dev(x), window=window, anchor=anchor))
+    assert conv.wino_f64 and conv._U is not None              # took the Winograd path
+    digests.append(hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest())
+    shape, window, anchor = (1, 144, 16, 12), (3, 2, 9, 8), (1, 0)
+    rng = np.random.default_rng(shape[2] * shape[3] + shape[1])
+    pre = np.maximum(rng.standard_normal(shape), 0)
+    pooled = onn.maxpool2(pre)
+    up = rng.standard_normal(pooled.shape)
+    Wt, b = rng.standard_normal((80, shape[1], 3, 3)), rng.standard_normal(80)
+    conv = ops.Conv(Wt, b, pad=1, relu=True, dtype=F64)
+    got = host(conv(dev(up), pre=dev(pre), pooled=dev(pooled), anchor=anchor, window=window))
+    assert conv.wino_f64 and conv._U is not None
+    digests.append(hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest())
+    return digests
+
+
+def test_conv_wino_f64_transforms_with_64_bit_addressing(ops, monkeypatch):
+    """wino64_input_kernel<false> and wino64_output_kernel run only for tensors above 2 GiB or with
+    IISEG_W64_FAST_TRANSFORMS=0; conv_wino_f64.hip promises "same arithmetic in the same order" as the
+    32-bit-offset forms that every other test takes.  The switch is read once per process: a child process runs
+    the two launches with it, this process with the defaults, and the output bytes must be the same."""
+    import os
+    import subprocess
+    import sys
+    monkeypatch.setattr(ops, 'WINO_F64_MIN_COUT', 64)
+    assert os.environ.get('IISEG_W64_FAST_TRANSFORMS', '1') != '0'
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ('import sys; sys.path[:0] = [%r, %r]\n'
+            'import test_gpu_f64 as t\n'
+            'from iterative_inference_segm_amd import ops\n'
+            'print("W64_DIGESTS", *t._w64_transform_digests(ops))\n' % (os.path.dirname(here), here))
+    env = dict(os.environ, IISEG_W64_FAST_TRANSFORMS='0', IISEG_WINO_F64_MIN_COUT='64')
+    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300)
+    lines = [l for l in r.stdout.splitlines() if l.startswith('W64_DIGESTS')]
+    assert r.returncode == 0 and len(lines) == 1, r.stdout[-2000:] + r.stderr[-4000:]
+    assert lines[0].split()[1:] == _w64_transform_digests(ops)
