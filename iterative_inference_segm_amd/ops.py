@@ -318,19 +318,25 @@ def _add_bytes(kernel, nbytes):
     KERNEL_BYTES[kernel] = KERNEL_BYTES.get(kernel, 0.0) + nbytes
 
 
-# the descriptor and operands of one NCHW launch of a Conv, as its `_run_<form>` methods take them
-_Launch = collections.namedtuple('_Launch', 'd x1 x2 pre pooled add out pool_out mask_in mask_out')
+# the descriptor and operands of one launch of a Conv, as its `_run_<form>` methods take them; a bf16 C8 launch
+# (`_describe_c8`) also has the scalars its kernels take and the 16-channel kernel's bn / stats / fold vectors
+_Launch = collections.namedtuple(
+    '_Launch', 'd x1 x2 pre pooled add out pool_out mask_in mask_out x1_ctot add_kind kind bn stats fold',
+    defaults=(0, 0, 0, None, None, None))
 
 
 class Conv:
     """One convolution layer bound to its weights: packed-weight (+ gather-table) cache per
     input geometry.  Weight layouts: 'oihw' (Lasagne Conv2DLayer W[out,in,kh,kw], P1) or
     'iohw' (DilatedConv2DLayer W[in,out,kh,kw], P11).  A call on NCHW tensors is three steps:
-    `_describe_call` (host only), `_choose` (the kernel FORM, by name; host only), `_run_<form>`."""
+    `_describe_call` (host only), `_choose` (the kernel FORM, by name; host only), `_run_<form>`.  On bf16 C8
+    tensors: `_choose_c8` (first: each of the two kernels has checks of its own), `_describe_c8`, `_run_<form>`."""
 
     # every form `_choose` can name; each has a `_run_<form>`
     FORMS = ('wino_bf16', 'halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32', 'pool_f64', 'pool_f32',
              'gemm_bf16', 'gemm_f32', 'gemm_f64', 'wino_f64', 'direct')
+    # ... and the two `_choose_c8` can name
+    C8_FORMS = ('c8', 'c8_m16')
     # ... those with the 2x2 max-pool in their epilogue, and those that read / write DePool2D mask bytes
     POOL_FORMS = ('halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32', 'pool_f64', 'pool_f32')
     MASK_FORMS = ('halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32')
@@ -422,6 +428,22 @@ class Conv:
         """Nominal 2*Cin*Cout*k*k*OH*OW*B (SURVEY 6.2 convention)."""
         return 2.0 * self.Cin * self.Cout * self.KH * self.KW * OH * OW * B
 
+    def _fill(self, B, C1, C2, H, W, window, add_geom, flags, out_slice=None, place=None, pad=None):
+        """A ConvDesc of this layer filled in, no library call: an NCHW launch's before `_describe` plans it, a
+        bf16 C8 launch's as it stands (never planned).  window = (oy0, ox0, OH, OW); or None: add_geom = (AH,
+        AW, ay0, ax0), out_slice = (out_ctot, out_c0), place = (out_H, out_W, out_y0, out_x0)."""
+        d = ConvDesc()
+        d.B, d.C1, d.C2, d.H, d.W = B, C1, C2, H, W
+        d.Cout, d.KH, d.KW, d.dil, d.pad = self.Cout, self.KH, self.KW, self.dil, self.pad if pad is None else pad
+        d.oy0, d.ox0, d.OH, d.OW = window
+        if add_geom is not None:
+            d.AH, d.AW, d.ay0, d.ax0 = add_geom
+        d.flags = flags
+        if out_slice is not None:
+            d.out_ctot, d.out_c0 = out_slice
+        if place is not None:
+            d.out_H, d.out_W, d.out_y0, d.out_x0 = place
+        return d
 
     def _describe(self, B, C1, C2, H, W, window, add_geom, unpool, out_slice=None, place=None,
                   anchor=(0, 0)):
@@ -434,19 +456,9 @@ class Conv:
         if C1 + C2 != self.Cin:
             raise RuntimeError('conv expects %d input channels, got %d+%d' % (self.Cin, C1, C2))
         fullH, fullW = self.out_hw(H, W)
-        oy0, ox0, OH, OW = window if window is not None else (0, 0, fullH, fullW)
-        d = ConvDesc()
-        d.B, d.C1, d.C2, d.H, d.W = B, C1, C2, H, W
-        d.Cout, d.KH, d.KW, d.pad, d.dil = self.Cout, self.KH, self.KW, self.pad, self.dil
-        d.oy0, d.ox0, d.OH, d.OW = oy0, ox0, OH, OW
-        if add_geom is not None:
-            d.AH, d.AW, d.ay0, d.ax0 = add_geom
-        d.flags = (CONV_RELU if self.relu else 0) | (CONV_UNPOOL if unpool else 0) | \
-            (CONV_TRANSPOSED2 if self.transposed else 0)
-        if out_slice is not None:
-            d.out_ctot, d.out_c0 = out_slice
-        if place is not None:
-            d.out_H, d.out_W, d.out_y0, d.out_x0 = place
+        d = self._fill(B, C1, C2, H, W, window if window is not None else (0, 0, fullH, fullW), add_geom,
+                       (CONV_RELU if self.relu else 0) | (CONV_UNPOOL if unpool else 0) |
+                       (CONV_TRANSPOSED2 if self.transposed else 0), out_slice, place)
         d.tile_y0, d.tile_x0 = int(anchor[0]) & 1, int(anchor[1]) & 1
         if self.via_im2col:
             # logical layer: 1x1 over C*KH*KW channels of the im2col'd tensor (OH x OW)
@@ -716,9 +728,11 @@ class Conv:
         (uint8, x1's shape) + `unpool_hw` = (H, W) replace `pre` / `pooled` for the unpooled
         input."""
         if is_c8(x1):
-            return self._call_c8(x1, x2, add, add_off, window, out, place, pool_out, mask_in,
-                                 unpool_hw, mask_out, store_out, out_format, out_c0, in_c, bn, stats, fold,
-                                 zins)
+            form = self._choose_c8(x2, add, pool_out, store_out, out_format, zins, in_c, bn, stats, fold)
+            launch = self._describe_c8(form, x1, x2, add, add_off, window, out, out_c0, place, pool_out, mask_in,
+                                       unpool_hw, mask_out, store_out, out_format, in_c, bn, stats, fold, zins)
+            getattr(self, '_run_' + form)(launch)
+            return launch.out
         if zins or in_c is not None or bn is not None or stats is not None or fold is not None:
             raise RuntimeError('in_c / bn / stats: C8 input only (layers with at most 16 output channels)')
         launch = self._describe_call(x1, x2, pre, pooled, add, add_off, window, out, out_c0, place, anchor,
@@ -1006,14 +1020,11 @@ class Conv:
 
     def _c8_weights(self):
         """The layer's weights packed for the C8 kernels, once per layer, for the REAL channel count (the
-        rows of padding channels are zero); shared by `_call_c8` and `_call_c8_m16`.  A captured graph may
+        rows of padding channels are zero); shared by `_run_c8` and `_run_c8_m16`.  A captured graph may
         point at them: never replaced after first use."""
         if self._W16c8 is None:
             lib = self.lib
-            dp = ConvDesc()
-            dp.B, dp.C1, dp.C2, dp.H, dp.W = 1, self.Cin, 0, 8, 8
-            dp.Cout, dp.KH, dp.KW, dp.pad, dp.dil = self.Cout, 3, 3, 1, 1
-            dp.OH, dp.OW = 8, 8
+            dp = self._fill(1, self.Cin, 0, 8, 8, (0, 0, 8, 8), None, 0, pad=1)      # (any 'same' geometry)
             Wsrc, so, sc = self.W, self.so, self.sc
             if self.x3:
                 # two k-groups of whole 16-channel k-tiles [W_hi | W_lo]; the split values are bf16
@@ -1042,139 +1053,105 @@ class Conv:
                                % (tuple(x1.shape), tuple(mask_in.shape), unpool_hw))
         return int(unpool_hw[0]), int(unpool_hw[1])
 
-    def _call_c8_m16(self, x1, window, out, place, mask_in, unpool_hw, out_format, out_c0, in_c, bn,
-                     stats=None, fold=None):
-        """Layers with at most 16 output channels on bf16 C8 activations (include/iiseg.h,
-        iiseg_conv_c8_m16).  in_c: convolve only the first in_c channels of x1 (a dense block's stack);
-        out + out_c0: write the 16 channels [out_c0, out_c0 + 16) of the wider C8 tensor `out`;
-        bn = (a, b): BatchNorm + ReLU x <- max(a x + b, 0) applied to the input on the way in
-        (`bn_fold`); stats = (mean, inv_std, eps): the batch statistics of the 16 produced channels (bf16 C8
-        output) into entries [out_c0, out_c0 + 16) of the two vectors, out of the conv's epilogue; fold =
-        (beta, gamma, a, b, n) (with stats): the reduction that finishes the statistics also forms the
-        (a, b) pair of the NEXT consumer's BatchNorm over the first n channels.  Returns `out`."""
-        lib = self.lib
-        unpool = mask_in is not None
-        B = x1.shape[0]
-        in_ctot = c8_ctot(x1)            # (x1 may be a channel slice of a wider tensor: the parent's count)
-        C1 = x1.shape[1] * 8 if in_c is None else int(in_c)
-        if C1 % 16 or C1 > x1.shape[1] * 8 or C1 < self.Cin or C1 - self.Cin >= 16:
-            raise RuntimeError('conv of %d input channels on the first %d of %d C8 channels'
-                               % (self.Cin, C1, in_ctot))
-        if unpool:
-            H, W = self._c8_unpool_hw(x1, mask_in, unpool_hw, x1.shape[1],
-                                      C1 == in_ctot and x1.is_contiguous())
-        else:
-            H, W = x1.shape[2], x1.shape[3]
-        fullH, fullW = self.out_hw(H, W)
-        oy0, ox0, OH, OW = window if window is not None else (0, 0, fullH, fullW)
-        fmt = out_format or ('c8' if self.Cout % 8 == 0 else 'nchw')
-        if fmt not in ('c8', 'nchw'):
-            raise RuntimeError('16-channel C8 layer: bf16 C8 or fp32 NCHW output')
-        d = ConvDesc()
-        d.B, d.C1, d.C2, d.H, d.W = B, C1, 0, H, W
-        d.Cout, d.KH, d.KW, d.pad, d.dil = self.Cout, 3, 3, self.pad, 1
-        d.oy0, d.ox0, d.OH, d.OW = oy0, ox0, OH, OW
-        d.flags = (CONV_RELU if self.relu else 0) | (CONV_UNPOOL if unpool else 0)
-        if place is not None:
-            if out is None:
-                raise RuntimeError('placement needs a target')
-            d.out_H, d.out_W, d.out_y0, d.out_x0 = out.shape[2], out.shape[3], int(place[0]), int(place[1])
-        if out is None:
-            if out_c0 is not None:
-                raise RuntimeError('out_c0 needs a target')
-            out = torch.empty((B, self.Cout, OH, OW), dtype=torch.float32, device=x1.device) if fmt == 'nchw' \
-                else torch.empty((B, 2, OH, OW, 8), dtype=torch.bfloat16, device=x1.device)
-        if fmt == 'nchw':
-            ok = out.dim() == 4 and out.dtype == torch.float32 and out.shape[1] == self.Cout and out_c0 is None
-        else:
-            ok = out.dim() == 5 and out.dtype == torch.bfloat16 and out.shape[1] % 2 == 0
-            if ok and (out_c0 is not None or out.shape[1] != 2 or not out.is_contiguous()):
-                c0 = int(out_c0 or 0)
-                ok = c0 % 16 == 0 and c0 + 16 <= out.shape[1] * 8
-                d.out_ctot, d.out_c0 = c8_ctot(out), c0
-        if not ok or out.shape[0] != B or (place is None and tuple(out.shape[2:4]) != (OH, OW)):
-            raise RuntimeError('bad output target %s for a 16-channel C8 layer' % (tuple(out.shape),))
-        if bn is not None:
-            if len(bn) != 2 or any(t.dtype != torch.float32 or t.numel() < C1 for t in bn):
-                raise RuntimeError('bn = (a, b): float32, at least %d entries' % C1)
-        if stats is not None and (fmt != 'c8' or stats[0].dtype != torch.float32 or
-                                  stats[1].dtype != torch.float32 or
-                                  min(stats[0].numel(), stats[1].numel()) < (out_c0 or 0) + 16):
-            raise RuntimeError('stats = (mean, inv_std, eps): float32 vectors covering the produced slice, C8 output')
-        if fold is not None and (stats is None or any(t.dtype != torch.float32 or t.numel() < fold[4]
-                                                      for t in fold[:4])):
-            raise RuntimeError('fold = (beta, gamma, a, b, n) needs stats and float32 vectors of n entries')
-        w16 = self._c8_weights()
-        # split-K launches (small maps, long channel loops) sum their slices through a scratch buffer
-        nws = lib.iiseg_conv_c8_m16_workspace_bytes(C.byref(d))
-        ws = _workspace('m16', nws, x1.device) if nws else None
-        _launch('conv_c8_m16_kernel', self.flops(B, OH, OW), lib.iiseg_conv_c8_m16_ws,
-                C.byref(d), _operand(x1), in_ctot, _operand(mask_in),
-                None if bn is None else _ptr(bn[0]), None if bn is None else _ptr(bn[1]),
-                w16, _ptr(self.b), _operand(out), 3 if fmt == 'nchw' else 1,
-                None if ws is None else C.c_void_p(ws.data_ptr()), int(nws),
-                None if stats is None else _ptr(stats[0]), None if stats is None else _ptr(stats[1]),
-                float(stats[2]) if stats is not None else 0.0,
-                *((_ptr(fold[0]), _ptr(fold[1]), _ptr(fold[2]), _ptr(fold[3]), int(fold[4]))
-                  if fold is not None else (None, None, None, None, 0)))
-        if CONV_PROFILE is not None and CONV_PROFILE_INFO is not None:
-            CONV_PROFILE_INFO.append(dict(
-                Cin=self.Cin, Cout=self.Cout, C1=C1, C2=0, H=H, W=W, OH=OH, OW=OW, B=B,
-                unpool=unpool, pool=False, add=0, kind=3 if fmt == 'nchw' else 1, flat='m16'))
-        return out
-
-    def _call_c8(self, x1, x2, add, add_off, window, out, place, pool_out, mask_in, unpool_hw,
-                 mask_out, store_out, out_format, out_c0=None, in_c=None, bn=None, stats=None, fold=None,
-                 zins=False):
-        """The layer on bf16 C8 activations (include/iiseg.h, iiseg_conv_c8).  x1 / x2 / pool_out:
-        C8 tensors (`is_c8`); add: C8 bf16 or C8 fp32 (float32, same 5-D shape); mask_in / mask_out:
-        uint8 (B, C/8, h, w, 8).  out_format: 'c8' (default), 'c8f32', or 'nchw' (fp32 NCHW, the
-        class-score layer: default when Cout is not a multiple of 8).  x1 and `out` may be channel slices
-        of wider C8 tensors; every other operand is contiguous.  Returns the output tensor (None with
-        store_out=False)."""
-        lib = self.lib
+    def _choose_c8(self, x2, add, pool_out, store_out, out_format, zins, in_c, bn, stats, fold):
+        """Step 1 on C8 input: which of C8_FORMS the call gets, from its facts alone -- 'c8_m16' (layers with
+        at most 16 output channels, csrc/conv_c8_m16.hip) or 'c8' (csrc/conv_c8_bf16.hip); refuses what only
+        the former can do on a launch of the latter."""
         if not self.c8:
             raise RuntimeError("C8 input needs a 3x3 layer built with mma='bf16c8'")
         if C8_M16 and self.Cout <= 16 and not self.x3 and x2 is None and add is None and pool_out is None and \
                 store_out and (out_format or 'c8') in ('c8', 'nchw') and not zins:
-            return self._call_c8_m16(x1, window, out, place, mask_in, unpool_hw, out_format, out_c0, in_c, bn,
-                                     stats, fold)
+            return 'c8_m16'
         if stats is not None or fold is not None:
             raise RuntimeError('stats: layers with at most 16 output channels')
         if in_c is not None or bn is not None:
             raise RuntimeError('in_c / bn on C8 input: layers with at most 16 output channels')
-        for name, t in (('x2', x2), ('add', add), ('pool_out', pool_out), ('mask_out', mask_out)):
-            if t is not None and not t.is_contiguous():
-                raise RuntimeError('C8 launch: %s must be contiguous' % name)
-        unpool = mask_in is not None
-        x3 = self.x3
-        pair = 2 if x3 else 1                     # chunk planes of a kind-1 tensor per channel chunk
-        if x1.shape[1] % pair or (x3 and x2 is not None):
-            raise RuntimeError('bf16x3 layer: hi / lo pair input, no channel concat')
-        B, CC1 = x1.shape[0], x1.shape[1] // pair
-        if unpool:
-            H, W = self._c8_unpool_hw(x1, mask_in, unpool_hw, CC1, x2 is None)
-        elif zins:
-            # the logical input is x1 zero-inserted (include/iiseg.h IISEG_CONV_ZINS): TransitionUp
-            if x3 or x2 is not None or self.pad != 0:
-                raise RuntimeError('zero-inserted input: plain single-source valid layers')
-            H, W = 2 * x1.shape[2] + 3, 2 * x1.shape[3] + 3
+        return 'c8'
+
+    def _c8_target(self, x1, OH, OW, fmt, out, out_c0, placed, store, m16):
+        """Where a C8 launch writes: `out` in the format `fmt` ('c8' | 'c8f32' | 'nchw'), allocated here if the
+        call gave none and the map is stored; an (OH, OW) map unless `placed`; whole, or with `out_c0` the
+        chunk planes [out_c0 / 8, ...) of a wider C8 tensor.  Returns (out, (out_ctot, out_c0) or None).  m16,
+        the 16-channel kernel's own rules: out_c0 needs a tensor to point into, any C8 tensor but a contiguous
+        two-chunk one (a wider one, a two-chunk channel slice) is the slice at 0, one message for all."""
+        B, c8 = x1.shape[0], fmt == 'c8'
+        chunks = c8_chunks(self.Cout) * (2 if self.x3 and c8 else 1)
+        dtype = torch.bfloat16 if c8 else torch.float32
+        if out is None and store:
+            if m16 and out_c0 is not None:
+                raise RuntimeError('out_c0 needs a target')
+            out = torch.empty((B, self.Cout, OH, OW) if fmt == 'nchw' else (B, chunks, OH, OW, 8), dtype=dtype,
+                              device=x1.device)
+        elif out is None and out_c0 is None:
+            return None, None               # (only the pool is kept)
+        c0 = out_c0
+        if m16 and c0 is None and c8 and is_c8(out) and (out.shape[1] != 2 or not out.is_contiguous()):
+            c0 = 0
+        if c0 is None:
+            ok = out.dtype == dtype and ((out.dim() == 4 and out.shape[1] == self.Cout) if fmt == 'nchw' else
+                                         (out.dim() == 5 and out.shape[1] == chunks))
         else:
-            H, W = x1.shape[2], x1.shape[3]
-        # x1 as a channel slice of a wider C8 tensor (a dense block's stack): the parent's channel count
-        x1_ctot = 0 if x1.is_contiguous() else c8_ctot(x1)
-        if x1_ctot and (x3 or unpool):
-            raise RuntimeError('channel-slice input: plain bf16 launches only')
-        CC2 = 0
-        if x2 is not None:
-            if not is_c8(x2) or x2.shape[0] != B or tuple(x2.shape[2:4]) != (H, W):
-                raise RuntimeError('concat shapes %s vs %s' % (tuple(x1.shape), tuple(x2.shape)))
-            CC2 = x2.shape[1]
-            if CC1 * 8 + CC2 * 8 != self.Cin:
-                raise RuntimeError('C8 concat needs unpadded sources')
-        if (CC1 + CC2) * 8 < self.Cin or (CC1 % 2) or (CC2 % 2):
-            raise RuntimeError('conv expects %d input channels in whole 16-channel groups, got '
-                               '%d + %d chunks' % (self.Cin, CC1, CC2))
+            ok = c8 and not self.x3 and is_c8(out) and c0 % 16 == 0 and c0 + chunks * 8 <= out.shape[1] * 8 and \
+                not (m16 and out.shape[1] % 2)
+        if not ok or out.shape[0] != B or not (placed or tuple(out.shape[2:4]) == (OH, OW)):
+            shape = None if out is None else tuple(out.shape)
+            raise RuntimeError('bad output target %s for a 16-channel C8 layer' % (shape,) if m16 else
+                               'bad C8 output target %s' % (shape,) if c0 is None else
+                               'bad C8 output slice %s @%s' % (shape, out_c0))
+        return out, None if c0 is None else (c8_ctot(out), int(c0))
+
+    def _describe_c8(self, form, x1, x2, add, add_off, window, out, out_c0, place, pool_out, mask_in, unpool_hw,
+                     mask_out, store_out, out_format, in_c, bn, stats, fold, zins):
+        """Step 2 on C8 input: `__call__`'s arguments checked for the kernel `form`, the launch described, `out`
+        settled (shapes, dtypes and strides only).  x1 / x2 / pool_out: C8 tensors (`is_c8`); add: C8 bf16 or
+        C8 fp32 (float32, same 5-D shape); mask_in / mask_out: uint8 (B, C/8, h, w, 8).  out_format: 'c8'
+        (default), 'c8f32', or 'nchw' (fp32 NCHW, the class-score layer: default when Cout is not a multiple
+        of 8).  x1 and `out` may be channel slices of wider C8 tensors; every other operand is contiguous.
+        'c8_m16' only -- in_c: convolve only the first in_c channels of x1 (a dense block's stack); bn = (a, b):
+        BatchNorm + ReLU x <- max(a x + b, 0) applied to the input on the way in (`bn_fold`); stats = (mean,
+        inv_std, eps): the batch statistics of the 16 produced channels (bf16 C8 output) into entries [out_c0,
+        out_c0 + 16) of the two vectors, out of the conv's epilogue; fold = (beta, gamma, a, b, n) (with stats):
+        the reduction that finishes them also forms the (a, b) pair of the NEXT consumer's BatchNorm over the
+        first n channels."""
+        m16, x3, unpool = form == 'c8_m16', self.x3, mask_in is not None
+        pair = 2 if x3 else 1                     # chunk planes of a kind-1 tensor per channel chunk
+        B, H, W = x1.shape[0], x1.shape[2], x1.shape[3]
+        C2, add_kind, add_geom = 0, 0, None
+        if m16:
+            x1_ctot = c8_ctot(x1)        # (x1 may be a channel slice of a wider tensor: the parent's count)
+            C1, ok = c8_first_channels(x1, in_c, self.Cin)
+            if not ok:
+                raise RuntimeError('conv of %d input channels on the first %d of %d C8 channels'
+                                   % (self.Cin, C1, x1_ctot))
+            if unpool:
+                H, W = self._c8_unpool_hw(x1, mask_in, unpool_hw, x1.shape[1], C1 == x1_ctot and x1.is_contiguous())
+        else:
+            for name, t in (('x2', x2), ('add', add), ('pool_out', pool_out), ('mask_out', mask_out)):
+                if t is not None and not t.is_contiguous():
+                    raise RuntimeError('C8 launch: %s must be contiguous' % name)
+            if x1.shape[1] % pair or (x3 and x2 is not None):
+                raise RuntimeError('bf16x3 layer: hi / lo pair input, no channel concat')
+            C1 = x1.shape[1] // pair * 8
+            if unpool:
+                H, W = self._c8_unpool_hw(x1, mask_in, unpool_hw, C1 // 8, x2 is None)
+            elif zins:
+                # the logical input is x1 zero-inserted (include/iiseg.h IISEG_CONV_ZINS): TransitionUp
+                if x3 or x2 is not None or self.pad != 0:
+                    raise RuntimeError('zero-inserted input: plain single-source valid layers')
+                H, W = 2 * H + 3, 2 * W + 3
+            # x1 as a channel slice of a wider C8 tensor (a dense block's stack): the parent's channel count
+            x1_ctot = 0 if x1.is_contiguous() else c8_ctot(x1)
+            if x1_ctot and (x3 or unpool):
+                raise RuntimeError('channel-slice input: plain bf16 launches only')
+            if x2 is not None:
+                if not is_c8(x2) or x2.shape[0] != B or tuple(x2.shape[2:4]) != (H, W):
+                    raise RuntimeError('concat shapes %s vs %s' % (tuple(x1.shape), tuple(x2.shape)))
+                C2 = x2.shape[1] * 8
+                if C1 + C2 != self.Cin:
+                    raise RuntimeError('C8 concat needs unpadded sources')
+            if C1 + C2 < self.Cin or C1 % 16 or C2 % 16:
+                raise RuntimeError('conv expects %d input channels in whole 16-channel groups, got '
+                                   '%d + %d chunks' % (self.Cin, C1 // 8, C2 // 8))
         fullH, fullW = self.out_hw(H, W)
         oy0, ox0, OH, OW = window if window is not None else (0, 0, fullH, fullW)
         if not store_out and pool_out is not None:
@@ -1182,73 +1159,86 @@ class Conv:
             # ignore_border) feeds nothing -- do not compute it
             OH, OW = max(OH & ~1, 2 if OH > 1 else 1), max(OW & ~1, 2 if OW > 1 else 1)
         fmt = out_format or ('c8' if self.Cout % 8 == 0 else 'nchw')
+        if m16 and fmt not in ('c8', 'nchw'):
+            raise RuntimeError('16-channel C8 layer: bf16 C8 or fp32 NCHW output')
         kind = {'c8': 1, 'c8f32': 2, 'nchw': 3}[fmt]
-        d = ConvDesc()
-        d.B, d.C1, d.C2, d.H, d.W = B, CC1 * 8, CC2 * 8, H, W
-        d.Cout, d.KH, d.KW, d.pad, d.dil = self.Cout, 3, 3, self.pad, 1
-        d.oy0, d.ox0, d.OH, d.OW = oy0, ox0, OH, OW
-        d.flags = (CONV_RELU if self.relu else 0) | (CONV_UNPOOL if unpool else 0) | \
-            (CONV_X3 if x3 else 0) | (CONV_ZINS if zins else 0)
-        add_kind = 0
         if add is not None:
             add_kind = 1 if is_c8(add) else 2
             if add.dim() != 5 or add.shape[0] != B or \
                     add.shape[1] != c8_chunks(self.Cout) * (pair if add_kind == 1 else 1) or \
                     add.dtype not in (torch.bfloat16, torch.float32):
                 raise RuntimeError('add tensor shape %s' % (tuple(add.shape),))
-            d.AH, d.AW, d.ay0, d.ax0 = add.shape[2], add.shape[3], add_off[0], add_off[1]
-        oc8 = (self.Cout + 15) // 16 * 2
+            add_geom = (add.shape[2], add.shape[3], add_off[0], add_off[1])
         if place is not None:
             if out is None:
                 raise RuntimeError('placement needs a target')
-            d.out_H, d.out_W, d.out_y0, d.out_x0 = out.shape[2], out.shape[3], int(place[0]), int(place[1])
+            place = (out.shape[2], out.shape[3], int(place[0]), int(place[1]))
         if not store_out:
             if pool_out is None:
                 raise RuntimeError('store_out=False needs pool_out')
-            out, kind = None, 0
-        elif out is None:
-            if fmt == 'nchw':
-                out = torch.empty((B, self.Cout, OH, OW), dtype=torch.float32, device=x1.device)
-            else:
-                out = torch.empty((B, oc8 * (pair if fmt == 'c8' else 1), OH, OW, 8), device=x1.device,
-                                  dtype=torch.bfloat16 if fmt == 'c8' else torch.float32)
-        if out_c0 is not None:
-            # the Cout channels written as chunk planes [out_c0 / 8, ...) of a wider C8 tensor
-            if out is None or fmt != 'c8' or x3 or not is_c8(out) or out_c0 % 16 or \
-                    out_c0 + oc8 * 8 > out.shape[1] * 8 or out.shape[0] != B or \
-                    (place is None and tuple(out.shape[2:4]) != (OH, OW)):
-                raise RuntimeError('bad C8 output slice %s @%s' % (None if out is None else tuple(out.shape), out_c0))
-            d.out_ctot, d.out_c0 = c8_ctot(out), int(out_c0)
-        elif out is not None:
-            ok = (out.dim() == 4 and out.dtype == torch.float32 and out.shape[1] == self.Cout) \
-                if fmt == 'nchw' else \
-                (out.dim() == 5 and out.shape[1] == oc8 * (pair if fmt == 'c8' else 1) and
-                 out.dtype == (torch.bfloat16 if fmt == 'c8' else torch.float32))
-            if not ok or out.shape[0] != B or (place is None and tuple(out.shape[2:4]) != (OH, OW)):
-                raise RuntimeError('bad C8 output target %s' % (tuple(out.shape),))
+            out, kind = None, 0            # (placement geometry taken above; nothing is written)
+        out, out_slice = self._c8_target(x1, OH, OW, fmt, out, out_c0, place is not None, store_out, m16)
+        if bn is not None and (len(bn) != 2 or any(t.dtype != torch.float32 or t.numel() < C1 for t in bn)):
+            raise RuntimeError('bn = (a, b): float32, at least %d entries' % C1)
+        if stats is not None and (fmt != 'c8' or any(t.dtype != torch.float32 for t in stats[:2]) or
+                                  min(stats[0].numel(), stats[1].numel()) < (out_c0 or 0) + 16):
+            raise RuntimeError('stats = (mean, inv_std, eps): float32 vectors covering the produced slice, C8 output')
+        if fold is not None and (stats is None or any(t.dtype != torch.float32 or t.numel() < fold[4]
+                                                      for t in fold[:4])):
+            raise RuntimeError('fold = (beta, gamma, a, b, n) needs stats and float32 vectors of n entries')
         if pool_out is not None:
-            if not is_c8(pool_out) or \
-                    tuple(pool_out.shape) != (B, oc8 * pair, fullH // 2, fullW // 2, 8):
+            oc8 = c8_chunks(self.Cout)
+            if not is_c8(pool_out) or tuple(pool_out.shape) != (B, oc8 * pair, fullH // 2, fullW // 2, 8):
                 raise RuntimeError('pool_out shape %s' % (tuple(pool_out.shape),))
             if mask_out is not None and (not is_c8_mask(mask_out) or
                                          tuple(mask_out.shape) != (B, oc8, fullH // 2, fullW // 2, 8)):
                 raise RuntimeError('mask_out: uint8 (B, Cout/8, H/2, W/2, 8)')
-        elif mask_out is not None:
+        elif mask_out is not None and not m16:
             raise RuntimeError('mask_out needs pool_out')
-        if out is not None and is_c8(out) and not out.is_contiguous():
-            c8_ctot(out)                   # (validates the slice layout)
-        w16 = self._c8_weights()
-        # (the pool rides in the conv's epilogue on every pixel tiling: with pool_out the pixels of a
-        # tile are ordered by 2x2 pooling windows)
-        _launch('conv_c8_kernel<x3>' if x3 else 'conv_c8_kernel', self.flops(B, OH, OW), lib.iiseg_conv_c8_slice,
-                C.byref(d), _operand(x1), int(x1_ctot), _operand(x2), _operand(mask_in), w16, _ptr(self.b),
-                _operand(add), add_kind, _operand(out), kind, _operand(pool_out), _operand(mask_out))
+        if not m16 and out is not None and is_c8(out) and not out.is_contiguous():
+            c8_ctot(out)                   # (validates the layout of a slice given without out_c0)
+        flags = (CONV_RELU if self.relu else 0) | (CONV_UNPOOL if unpool else 0) | (CONV_X3 if x3 else 0) | \
+            (CONV_ZINS if zins else 0)
+        d = self._fill(B, C1, C2, H, W, (oy0, ox0, OH, OW), add_geom, flags, out_slice, place)
+        return _Launch(d, x1, x2, None, None, add, out, pool_out, mask_in, mask_out, x1_ctot, add_kind, kind,
+                       bn, stats, fold)
+
+    def _c8_profile_info(self, c, m16=False):
+        """The CONV_PROFILE_INFO record of a C8 launch (`flat`: its pixel tiling)."""
         if CONV_PROFILE is not None and CONV_PROFILE_INFO is not None:
+            d = c.d
             CONV_PROFILE_INFO.append(dict(
-                Cin=self.Cin, Cout=self.Cout, C1=d.C1, C2=d.C2, H=H, W=W, OH=OH, OW=OW, B=B,
-                unpool=unpool, pool=pool_out is not None, add=add_kind, kind=kind,
-                flat=self.c8_tiling(d, pool_out is not None)))
-        return out
+                Cin=self.Cin, Cout=self.Cout, C1=d.C1, C2=d.C2, H=d.H, W=d.W, OH=d.OH, OW=d.OW, B=d.B,
+                unpool=c.mask_in is not None, pool=c.pool_out is not None, add=c.add_kind, kind=c.kind,
+                flat='m16' if m16 else self.c8_tiling(d, c.pool_out is not None)))
+
+    def _run_c8(self, c):
+        """The layer on bf16 C8 activations (include/iiseg.h, iiseg_conv_c8).  (The pool rides in the conv's
+        epilogue on every pixel tiling: with pool_out the pixels of a tile are ordered by 2x2 pooling
+        windows)"""
+        d = c.d
+        w16 = self._c8_weights()
+        _launch('conv_c8_kernel<x3>' if self.x3 else 'conv_c8_kernel', self.flops(d.B, d.OH, d.OW),
+                self.lib.iiseg_conv_c8_slice, C.byref(d), _operand(c.x1), int(c.x1_ctot), _operand(c.x2),
+                _operand(c.mask_in), w16, _ptr(self.b), _operand(c.add), c.add_kind, _operand(c.out), c.kind,
+                _operand(c.pool_out), _operand(c.mask_out))
+        self._c8_profile_info(c)
+
+    def _run_c8_m16(self, c):
+        """Layers with at most 16 output channels on bf16 C8 activations (include/iiseg.h, iiseg_conv_c8_m16)."""
+        d, (bn_a, bn_b) = c.d, c.bn or (None, None)
+        mean, inv_std, eps = c.stats or (None, None, 0.0)
+        beta, gamma, a, b, n = c.fold or (None, None, None, None, 0)
+        w16 = self._c8_weights()
+        # split-K launches (small maps, long channel loops) sum their slices through a scratch buffer
+        nws = self.lib.iiseg_conv_c8_m16_workspace_bytes(C.byref(d))
+        ws = _workspace('m16', nws, c.x1.device) if nws else None
+        _launch('conv_c8_m16_kernel', self.flops(d.B, d.OH, d.OW), self.lib.iiseg_conv_c8_m16_ws,
+                C.byref(d), _operand(c.x1), c.x1_ctot, _operand(c.mask_in), _ptr(bn_a), _ptr(bn_b),
+                w16, _ptr(self.b), _operand(c.out), c.kind,
+                None if ws is None else C.c_void_p(ws.data_ptr()), int(nws),
+                _ptr(mean), _ptr(inv_std), float(eps), _ptr(beta), _ptr(gamma), _ptr(a), _ptr(b), int(n))
+        self._c8_profile_info(c, m16=True)
 
 
 DECONV_PHASE = True      # K = 2 stride layers on the output-phase kernel (csrc/deconv_phase.hip)
@@ -1323,6 +1313,14 @@ def c8_ctot(t):
     if tuple(st[1:]) != (H * W * 8, W * 8, 8, 1) or (B > 1 and (st[0] % (H * W * 8) or st[0] < C8n * H * W * 8)):
         raise RuntimeError('C8 operand: a contiguous tensor or a channel slice of one, got strides %s' % (st,))
     return C8n * 8 if B == 1 else st[0] // (H * W * 8) * 8
+
+
+def c8_first_channels(x8, in_c, Cin):
+    """(n, ok): the first `in_c` channels (None: all of them) of the C8 stack `x8` as the input of a layer
+    with `Cin` input channels -- ok if they are whole 16-channel groups of the stack that cover the layer
+    with less than one group of padding channels."""
+    n = x8.shape[1] * 8 if in_c is None else int(in_c)
+    return n, not (n % 16 or n > x8.shape[1] * 8 or n < Cin or n - Cin >= 16)
 
 
 def _c8ptr(t, dtype=torch.bfloat16):
@@ -1867,8 +1865,8 @@ class Conv1x1C8:
     def __call__(self, x8, in_c=None, bn=None, pool=False, out=None, out_c0=0):
         in_ctot = c8_ctot(x8)            # (a contiguous C8 tensor or a channel slice of one)
         B, C8n, H, W, _ = x8.shape
-        cin = int(in_c) if in_c is not None else C8n * 8
-        if cin % 16 or cin > C8n * 8 or cin < self.Cin or cin - self.Cin >= 16:
+        cin, ok = c8_first_channels(x8, in_c, self.Cin)
+        if not ok:
             raise RuntimeError('Conv1x1C8: %d input channels of %d (layer: %d)' % (cin, C8n * 8, self.Cin))
         wp = self._wp.get(cin)
         if wp is None:
