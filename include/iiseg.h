@@ -1056,6 +1056,71 @@ int iiseg_opt_step_grid_f32(void* stream, int32_t kind, float* p, const float* g
 int iiseg_opt_step_grid_f64(void* stream, int32_t kind, double* p, const double* g, double* s1, double* s2,
                             const double* lr, double* state, int64_t n);
 
+/* ---------------------------------------------------------------------------------------
+ * Training FCN-8 (backward-compatible addition).
+ *
+ * Weight and bias gradient of a 'valid' K x K stride-1 layer, 1 <= K <= 7, any channel counts up to 65535
+ * (csrc/conv_wgrad_kxk.hip; float on v_mfma_f32_32x32x2_f32, double on the vector ALU):
+ *   dW[co][ci0 + ci][ky][kx] = sum_{b,y,x} gz[b,co,y,x] x[b,ci,y + ky,x + kx],   db[co] = sum_{b,y,x} gz[b,co,y,x]
+ *   x  : an (H, W) window of a larger map, read in place: element (b, ci, y, x) at b x_image + ci x_plane +
+ *        (x_y0 + y) x_row + x_x0 + x.  x_row >= x_x0 + W, x_plane >= (x_y0 + H) x_row, x_image >= Cin x_plane.
+ *   gz : (B, Cout, OH, OW) contiguous = dL/dout with the ReLU mask already applied, OH = H - K + 1.
+ *   dW, db, ws, (so, sc), ci0, Cin_tot : as iiseg_conv_wgrad_* with K^2 taps in place of 9; everything of dW
+ *        outside input channels [ci0, ci0 + Cin) is left untouched.  db may be NULL.
+ * A workgroup owns 64 x 64 (double: 32 x 32) channels, one filter row and one slab of the pixel range; with more
+ * than one slab a second launch adds the slabs in slab order.  No atomics: the same inputs give the same bits.
+ *
+ * Backward of iiseg_deconv_* on the same descriptor (csrc/deconv_grad.hip; AH, AW, ay0, ax0 are ignored): g =
+ * dL/d(window) (B, Cout, OH, OW), zero outside the window (the crop's adjoint); any K, stride, channel counts.
+ *   dgrad : gx (B, Cin, H, W) = the transposed convolution's adjoint applied to g.
+ *   wgrad : dW (Cin, Cout, K, K) and db (Cout, or NULL); ws = iiseg_deconv_wgrad_partials(d) * (Cin Cout K^2 + Cout)
+ *           elements, always required; the partials are added in their order in double.
+ *
+ * relu_gate : dst[i] = out[i] > 0 ? g[i] : 0 (dst may be g, not out).
+ * l2_term   : over the `nranges` <= IISEG_L2_MAX_RANGES ascending disjoint index ranges [ranges[2k], ranges[2k+1])
+ *             (a HOST array) of the n-element buffers p and g: g += 2 weight_decay p, *penalty = sum p^2 (double,
+ *             fixed order); partial = iiseg_l2_term_partials(nranges) doubles of scratch.
+ * ------------------------------------------------------------------------------------- */
+#define IISEG_L2_MAX_RANGES 64
+
+typedef struct iiseg_conv_wgrad_kxk_desc {
+    int32_t B, Cin, Cout, H, W, K;        /* H, W: the window of x; 1 <= K <= 7 */
+    int32_t ci0, Cin_tot;
+    int32_t x_y0, x_x0;                   /* the window's origin inside the planes of x */
+    int32_t reserved[2];
+    int64_t x_row, x_plane, x_image;      /* strides of x, in elements */
+    int64_t so, sc;
+} iiseg_conv_wgrad_kxk_desc;
+
+/* host only: IISEG_OK or the status a launch of `d` would return */
+int iiseg_conv_wgrad_kxk_check(const iiseg_conv_wgrad_kxk_desc* d);
+/* host only: number of pixel slabs (>= 1) for elements of elem_bytes (4 or 8), or a negative status */
+int iiseg_conv_wgrad_kxk_slabs(const iiseg_conv_wgrad_kxk_desc* d, int32_t elem_bytes);
+/* host only: elements of `ws` (0 with one slab, else slabs * (Cout Cin K^2 + Cout)), or a negative status */
+int64_t iiseg_conv_wgrad_kxk_workspace_elems(const iiseg_conv_wgrad_kxk_desc* d, int32_t elem_bytes);
+int iiseg_conv_wgrad_kxk_f32(void* stream, const iiseg_conv_wgrad_kxk_desc* d, const float* x, const float* gz,
+                             float* ws, float* dW, float* db);
+int iiseg_conv_wgrad_kxk_f64(void* stream, const iiseg_conv_wgrad_kxk_desc* d, const double* x, const double* gz,
+                             double* ws, double* dW, double* db);
+
+int iiseg_deconv_dgrad_f32(void* stream, const iiseg_deconv_desc* d, const float* g, const float* w, float* gx);
+int iiseg_deconv_dgrad_f64(void* stream, const iiseg_deconv_desc* d, const double* g, const double* w, double* gx);
+/* host only: number of partial sums (>= 1), or a negative status */
+int iiseg_deconv_wgrad_partials(const iiseg_deconv_desc* d);
+int iiseg_deconv_wgrad_f32(void* stream, const iiseg_deconv_desc* d, const float* x, const float* g, float* ws,
+                           float* dW, float* db);
+int iiseg_deconv_wgrad_f64(void* stream, const iiseg_deconv_desc* d, const double* x, const double* g, double* ws,
+                           double* dW, double* db);
+
+int iiseg_relu_gate_f32(void* stream, const float* g, const float* out, float* dst, int64_t n);
+int iiseg_relu_gate_f64(void* stream, const double* g, const double* out, double* dst, int64_t n);
+/* host only: doubles of `partial`, or a negative status */
+int iiseg_l2_term_partials(int32_t nranges);
+int iiseg_l2_term_f32(void* stream, const float* p, float* g, int64_t n, const int64_t* ranges, int32_t nranges,
+                      double weight_decay, double* partial, double* penalty);
+int iiseg_l2_term_f64(void* stream, const double* p, double* g, int64_t n, const int64_t* ranges, int32_t nranges,
+                      double weight_decay, double* partial, double* penalty);
+
 #ifdef __cplusplus
 }
 #endif

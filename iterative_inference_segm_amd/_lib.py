@@ -71,6 +71,15 @@ class ConvWgradDesc(C.Structure):
                [('reserved', C.c_int32 * 3), ('so', C.c_int64), ('sc', C.c_int64)]
 
 
+class ConvWgradKxKDesc(C.Structure):
+    """struct iiseg_conv_wgrad_kxk_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'ci0', 'Cin_tot', 'x_y0', 'x_x0')] + \
+               [('reserved', C.c_int32 * 2)] + \
+               [(n, C.c_int64) for n in ('x_row', 'x_plane', 'x_image', 'so', 'sc')]
+
+
+L2_MAX_RANGES = 64
+
 C8DIL_OUT_NCHW = 0x100
 
 
@@ -267,6 +276,22 @@ SIGNATURES = {
     'iiseg_conv_wgrad_f64': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
     'iiseg_opt_step_grid_f32': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
     'iiseg_opt_step_grid_f64': (C.c_int, [_vp, _i32] + [_vp] * 6 + [_i64]),
+    # training FCN-8
+    'iiseg_conv_wgrad_kxk_check': (C.c_int, [C.POINTER(ConvWgradKxKDesc)]),
+    'iiseg_conv_wgrad_kxk_slabs': (C.c_int, [C.POINTER(ConvWgradKxKDesc), _i32]),
+    'iiseg_conv_wgrad_kxk_workspace_elems': (_i64, [C.POINTER(ConvWgradKxKDesc), _i32]),
+    'iiseg_conv_wgrad_kxk_f32': (C.c_int, [_vp, C.POINTER(ConvWgradKxKDesc)] + [_vp] * 5),
+    'iiseg_conv_wgrad_kxk_f64': (C.c_int, [_vp, C.POINTER(ConvWgradKxKDesc)] + [_vp] * 5),
+    'iiseg_deconv_dgrad_f32': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 3),
+    'iiseg_deconv_dgrad_f64': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 3),
+    'iiseg_deconv_wgrad_partials': (C.c_int, [C.POINTER(DeconvDesc)]),
+    'iiseg_deconv_wgrad_f32': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 5),
+    'iiseg_deconv_wgrad_f64': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 5),
+    'iiseg_relu_gate_f32': (C.c_int, [_vp] * 4 + [_i64]),
+    'iiseg_relu_gate_f64': (C.c_int, [_vp] * 4 + [_i64]),
+    'iiseg_l2_term_partials': (C.c_int, [_i32]),
+    'iiseg_l2_term_f32': (C.c_int, [_vp] * 3 + [_i64, C.POINTER(_i64), _i32, _f64, _vp, _vp]),
+    'iiseg_l2_term_f64': (C.c_int, [_vp] * 3 + [_i64, C.POINTER(_i64), _i32, _f64, _vp, _vp]),
 }
 
 _lib = None

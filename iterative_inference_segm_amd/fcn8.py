@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .params import ParamStore
 from .regions import center, conv_region, pool_region
 from .weights import load_param_list
 
@@ -29,10 +30,31 @@ _UID = itertools.count(1)   # identity of a net in the provenance tags (never re
 
 class FCN8:
     def __init__(self, params, n_classes, layer=('probs_dimshuffle',), pad=100, temperature=1.0,
-                 device='cuda', dtype=torch.float32, mma=None):
+                 device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; 'bf16c8' = additionally bf16 C8
-        activations between the 3x3 layers, the h maps handed out stay fp32 NCHW; ops.Conv)."""
+        activations between the 3x3 layers, the h maps handed out stay fp32 NCHW; ops.Conv).
+        trainable=True (float32 with mma='f32', or float64; temperature 1): the parameters live in ONE flat
+        buffer in PARAM_ORDER (W then b per layer), every layer holds views of it and runs on the direct / halo /
+        tap kernels only, so that `refresh()` can pack them again in place after an optimizer step; every map is
+        computed whole (no border fold, no session).  `dropout`: p of the DropoutLayers behind fc6 and fc7 in
+        `forward_train`."""
+        self.trainable = bool(trainable)
+        self.dropout = float(dropout)
+        self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
+        if trainable:
+            # refused here, before any device work
+            if dtype not in (torch.float32, torch.float64) or \
+                    (dtype == torch.float32 and (mma or ops.DEFAULT_MMA) != 'f32'):
+                raise NotImplementedError("training FCN-8: float32 (mma='f32') or float64; the 16-bit legs "
+                                          '(mma=%r) are not trained' % (mma or ops.DEFAULT_MMA,))
+            if float(temperature) != 1.0:
+                raise NotImplementedError('training FCN-8: temperature must be 1 (it divides upsample.W and '
+                                          'upsample.b, which are parameters here)')
+            if not 0.0 <= self.dropout < 1.0:
+                raise ValueError('dropout must be in [0, 1)')
+            self._params = ParamStore(params, PARAM_ORDER, dtype, device)
+            self.flat, params = self._params.flat, self._params.views
         if mma is None:
             # IISEG_MMA=bf16x3 means "the DAE loop on hi / lo pairs"; this net takes the pair form
             # only when asked by name (tests/test_gpu_x3.py: the FCN-8 in fp32 keeps the mode's parity)
@@ -62,13 +84,21 @@ class FCN8:
         self.score2 = ops.Deconv(p['score2'][0], p['score2'][1], 2, device=device, dtype=dtype)    # :90-91
         self.score4 = ops.Deconv(p['score4'][0], p['score4'][1], 2, device=device, dtype=dtype)    # :100-101
         Wu, bu = p['upsample']
-        # temperature divides upsample.W and upsample.b (:194-198)
-        self.upsample = ops.Deconv(np.asarray(Wu) / temperature, np.asarray(bu) / temperature, 8,
-                                   device=device, dtype=dtype)                                      # :109-110
+        if trainable:
+            self.upsample = ops.Deconv(Wu, bu, 8, device=device, dtype=dtype)
+        else:
+            # temperature divides upsample.W and upsample.b (:194-198)
+            self.upsample = ops.Deconv(np.asarray(Wu) / temperature, np.asarray(bu) / temperature, 8,
+                                       device=device, dtype=dtype)                                  # :109-110
         self.conv_log = None  # optional list collecting (name, flops) per conv launch
         # fold the weights-only pad-100 border of the encoder maps once per input geometry
-        self.fold_border = os.environ.get('IISEG_FCN_BORDER_FOLD', '1') != '0'
+        self.fold_border = os.environ.get('IISEG_FCN_BORDER_FOLD', '1') != '0' and not trainable
         self._border = {}
+        if trainable:
+            for layer_ in list(self.convs.values()) + [self.score2, self.score4, self.upsample]:
+                assert self._params.holds(layer_.W) and self._params.holds(layer_.b)      # views, not copies
+            for conv in self.convs.values():
+                conv.wino = conv.wino_f64 = False     # no weight transform to keep in step (Conv.refresh)
         self._uid = next(_UID)
         self.last_provenance = None   # per output of the latest forward: (store id, region) or None
 
@@ -231,6 +261,189 @@ class FCN8:
         side = self._conv(score_name, pool, window=(center(sh, oh), center(sw, ow), oh, ow))
         return deconv(t, add=side, window=(center(dh, oh), center(dw, ow), oh, ow))
 
+    # ---- training (reference train_fcn8.py) ----------------------------------
+    def parameters(self):
+        """{name: (W, b)} in PARAM_ORDER: views of `self.flat`.  After changing them in place call `refresh()`."""
+        self._need_trainable('parameters')
+        return dict(self._params.views)
+
+    def state_arrays(self):
+        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
+        self._need_trainable('state_arrays')
+        return self._params.state_arrays()
+
+    @property
+    def gflat(self):
+        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
+        return self._params.gflat
+
+    def weight_ranges(self):
+        """[(lo, hi)] of the weight arrays (not the biases) inside `flat`: what ops.l2_term walks."""
+        self._need_trainable('weight_ranges')
+        lo = self.flat.data_ptr()
+        out = []
+        for name in PARAM_ORDER:
+            W = self._params.views[name][0]
+            off = (W.data_ptr() - lo) // self.flat.element_size()
+            out.append((off, off + W.numel()))
+        return out
+
+    def _need_trainable(self, what):
+        if not self.trainable:
+            raise RuntimeError('%s needs an FCN8 built with trainable=True' % what)
+
+    def _drop(self, t, keep, generator, deterministic):
+        """DropoutLayer(p, rescale=True) on a copy of t: (dropped map, the 0/1 mask used or None)."""
+        if deterministic or self.dropout == 0.0:
+            return t, None
+        if keep is None:
+            keep = (torch.rand(t.shape, generator=generator, device=t.device, dtype=torch.float32) >=
+                    self.dropout).to(t.dtype)
+        elif tuple(keep.shape) != tuple(t.shape) or keep.dtype != t.dtype:
+            raise RuntimeError('dropout mask %s %s for a map %s %s' % (tuple(keep.shape), keep.dtype,
+                                                                      tuple(t.shape), t.dtype))
+        return ops.dropout_apply(t.clone(), keep, self.dropout), keep
+
+    def _side_sum(self, s, deconv, dname, t, sname, pname):
+        """`_deconv_sum` with what `backward` reads kept: the windows and the side layer's rectified output."""
+        pool = s[pname]
+        dh, dw = deconv.out_hw(t.shape[2], t.shape[3])
+        sh, sw = pool.shape[2], pool.shape[3]
+        oh, ow = min(dh, sh), min(dw, sw)
+        s['win_' + sname] = (center(sh, oh), center(sw, ow), oh, ow)
+        s['win_' + dname] = (center(dh, oh), center(dw, ow), oh, ow)
+        s[sname] = self._conv(sname, pool, window=s['win_' + sname])
+        return deconv(t, add=s[sname], window=s['win_' + dname])
+
+    def forward_train(self, x, keep6=None, keep7=None, generator=None, deterministic=False):
+        """The training-mode forward on whole maps: returns the score map (before the softmax), cropped to the
+        input, and keeps what `backward` reads -- every convolution's input and rectified output, the pooled maps,
+        the centre windows of pool4 / pool3, the inputs of the three transposed convolutions and the two dropout
+        masks.  keep6 / keep7: the caller's 0/1 masks (the maps' shape and dtype) for the DropoutLayers behind fc6
+        and fc7, else drawn from `generator`.  deterministic=True: no dropout (val_fn's forward)."""
+        self._need_trainable('forward_train')
+        s = {'input': x}
+        t = x
+        for bi, names in enumerate(_BLOCKS):
+            for name in names:
+                s['in_' + name] = t
+                t = s[name] = self._conv(name, t)
+            t = s['pool%d' % (bi + 1)] = ops.maxpool2x2(t)
+        s['in_fc6'] = t
+        s['fc6'] = t = self._conv('fc6', t)
+        s['drop6'], s['keep6'] = self._drop(t, keep6, generator, deterministic)
+        s['fc7'] = t = self._conv('fc7', s['drop6'])
+        s['drop7'], s['keep7'] = self._drop(t, keep7, generator, deterministic)
+        s['score_fr'] = t = self._conv('score_fr', s['drop7'])
+        s['fused'] = t = self._side_sum(s, self.score2, 'score2', t, 'score_pool4', 'pool4')
+        s['final'] = t = self._side_sum(s, self.score4, 'score4', t, 'score_pool3', 'pool3')
+        H, W = x.shape[2], x.shape[3]
+        uh, uw = self.upsample.out_hw(t.shape[2], t.shape[3])
+        oh, ow = min(uh, H), min(uw, W)
+        s['win_upsample'] = (center(uh, oh), center(uw, ow), oh, ow)
+        s['score'] = self.upsample(t, window=s['win_upsample'])
+        self._tsaved = s
+        return s['score']
+
+    def saved_maps(self):
+        """What the last `forward_train` kept, under the names of tests/fcn8_train_ref.py; for tests."""
+        return dict(self._tsaved)
+
+    def _flipped_filters(self):
+        """(name, filter) of every layer's backward-data conv (conv1_1 has none): the channel-transposed,
+        spatially flipped filter."""
+        for name in PARAM_ORDER[1:]:
+            if name in self.convs:
+                yield name, self.convs[name].W.transpose(0, 1).flip(2, 3)
+
+    def _bwd_convs(self):
+        """Backward-data of a stride-1 conv = the forward conv of the gradient with the flipped filter: 'same'
+        for the 3x3 pad-1 layers, as it is for the 1x1 layers, and for the 'valid' 7x7 fc6 the 'valid' conv of
+        g_z inside a zero border of 6."""
+        if self._bwd is None:
+            bwd = {name: ops.Conv(Wt.contiguous(), None, pad=1 if Wt.shape[2] == 3 else 0, relu=False,
+                                  device=Wt.device, dtype=self.dtype, mma='f32')
+                   for name, Wt in self._flipped_filters()}
+            for conv in bwd.values():
+                conv.wino = conv.wino_f64 = False
+            self._bwd = bwd
+        return self._bwd
+
+    def backward(self, g_score):
+        """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore = g_score,
+        after `forward_train`.  Last to first: the crop's adjoint and `upsample`, then twice (score_pool3 / score4,
+        score_pool4 / score2) the fan-out of the sum into the side 1x1 layer on the pool's centre window and the
+        transposed convolution, then score_fr, fc7, fc6 (gate, dropout's adjoint, K x K weight gradient, data
+        gradient) and the five blocks (ops.pool_relu_bwd at a block's last convolution, ops.relu_gate at the
+        others, ops.conv_wgrad and the flipped-filter convolution).  pool4 and pool3 receive two gradients: the
+        main path's (conv5_1's / conv4_1's data gradient) comes first, the side branch's is added to it, placed at
+        the centre window's offset.  conv1_1's data gradient is not formed."""
+        self._need_trainable('backward')
+        s = self._tsaved
+        if s is None:
+            raise RuntimeError('backward() needs forward_train() first')
+        gv, bwd = self._params.grad_views(), self._bwd_convs()
+        win = s['win_upsample']
+        ops.deconv_wgrad(s['final'], g_score, *gv['upsample'], stride=8, window=win)
+        g = ops.deconv_dgrad(g_score, self.upsample.W, 8, s['final'].shape[2:], window=win)
+        side = {}
+        for deconv, dname, sname, pname, src in ((self.score4, 'score4', 'score_pool3', 'pool3', 'fused'),
+                                                 (self.score2, 'score2', 'score_pool4', 'pool4', 'score_fr')):
+            gz = ops.relu_gate(g, s[sname])
+            ops.conv_wgrad_kxk(s[pname], gz, *gv[sname], window=s['win_' + sname])
+            side[pname] = (sname, gz)
+            win = s['win_' + dname]
+            ops.deconv_wgrad(s[src], g, *gv[dname], stride=deconv.stride, window=win)
+            g = ops.deconv_dgrad(g, deconv.W, deconv.stride, s[src].shape[2:], window=win)
+        for name, xin, keep in (('score_fr', 'drop7', 'keep7'), ('fc7', 'drop6', 'keep6'), ('fc6', 'in_fc6', None)):
+            gz = ops.relu_gate(g, s[name], dst=g)
+            ops.conv_wgrad_kxk(s[xin], gz, *gv[name])
+            if name == 'fc6':
+                K = self.convs[name].KH
+                gz = _embed(gz, (gz.shape[2] + 2 * (K - 1), gz.shape[3] + 2 * (K - 1)), (K - 1, K - 1))
+            g = bwd[name](gz)
+            if keep is not None and s[keep] is not None:
+                ops.dropout_apply(g, s[keep], self.dropout)             # dropout's adjoint: the forward's mask
+        for bi in range(len(_BLOCKS) - 1, -1, -1):
+            names, pname = _BLOCKS[bi], 'pool%d' % (bi + 1)
+            if pname in side:
+                sname, gz = side[pname]
+                oy, ox = s['win_' + sname][:2]
+                bwd[sname](gz, add=g, add_off=(oy, ox), out=g, place=(oy, ox))   # main first, + the side branch
+            for ni in range(len(names) - 1, -1, -1):
+                name = names[ni]
+                if ni == len(names) - 1:
+                    gz = ops.pool_relu_bwd(g, s[name], s[pname])
+                else:
+                    gz = ops.relu_gate(g, s[name], dst=g)
+                ops.conv_wgrad(s['in_' + name], gz, *gv[name], pad=self.convs[name].pad)
+                if bi or ni:
+                    g = bwd[name](gz)
+        return gv
+
+    def refresh(self):
+        """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into the
+        buffers it already has, and the data-gradient layers take the flipped / transposed filters again.  No
+        host wait."""
+        self._need_trainable('refresh')
+        for conv in self.convs.values():
+            conv.refresh()
+        for deconv in (self.score2, self.score4, self.upsample):
+            deconv.refresh()
+        if self._bwd is not None:
+            for name, Wt in self._flipped_filters():
+                self._bwd[name].W.copy_(Wt)
+            for conv in self._bwd.values():
+                conv.refresh()
+        self._border = {}
+
+
+def _embed(g, hw, off):
+    """Adjoint of a crop: a zeroed map of planes `hw` with `g` at offset `off`."""
+    out = torch.zeros(tuple(g.shape[:2]) + tuple(hw), dtype=g.dtype, device=g.device)
+    out[:, :, off[0]:off[0] + g.shape[2], off[1]:off[1] + g.shape[3]].copy_(g)
+    return out
+
 
 class FCN8DAE:
     """dae kind 'fcn8' (models/fcn8_dae.py:19-171): an FCN-8 on y with h concatenated at
@@ -291,9 +504,10 @@ def buildFCN8(nb_in_channels, input_var=None, path_weights=None, n_classes=21, l
               temperature=1.0, dropout=0.5, params=None, pad=100, device='cuda',
               dtype=torch.float32):
     """Mirror of models/fcn8.py:16-23.  Weights come from `params` (dict name -> (W, b)) or from
-    an `arr_%d` .npz at `path_weights` in get_all_param_values order (:178-180).  `input_var`,
-    `trainable`, `dropout` are accepted for signature compatibility (inference only: dropout is
-    the identity, P8).  pascal .mat import (:134-176) is not supported."""
+    an `arr_%d` .npz at `path_weights` in get_all_param_values order (:178-180).  `input_var` is
+    accepted for signature compatibility.  trainable=True builds the module `train.FCN8Trainer` trains
+    (`FCN8(..., trainable=True, dropout=dropout)`); otherwise dropout is the
+    identity (P8).  pascal .mat import (:134-176) is not supported."""
     if pascal:
         raise NotImplementedError('pascal .mat weights are not supported')
     if params is None:
@@ -304,5 +518,8 @@ def buildFCN8(nb_in_channels, input_var=None, path_weights=None, n_classes=21, l
     if w0.shape[1] != nb_in_channels:
         raise ValueError('conv1_1 expects %d input channels, nb_in_channels=%d'
                          % (w0.shape[1], nb_in_channels))
+    if trainable:
+        return FCN8(params, n_classes, layer=layer, pad=pad, temperature=temperature, device=device,
+                    dtype=dtype, mma='f32', trainable=True, dropout=dropout)
     return FCN8(params, n_classes, layer=layer, pad=pad, temperature=temperature, device=device,
                 dtype=dtype)

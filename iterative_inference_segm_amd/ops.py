@@ -1256,10 +1256,19 @@ class Deconv:
             raise RuntimeError('square kernels only')
         self.stride = int(stride)
         self._wp = None             # weights packed for the output-phase kernel (first call)
+        self._wp_desc = None        # the descriptor they were packed for (`refresh`)
         self.last_form = None
 
     def out_hw(self, H, W):
         return (H - 1) * self.stride + self.K, (W - 1) * self.stride + self.K
+
+    def refresh(self):
+        """After `self.W` has been changed IN PLACE (an optimizer step): the output-phase kernel's packed weights
+        are made again in the buffer they already have.  No host wait."""
+        if self._wp is not None:
+            dt = self.dtype
+            check(_fn('deconv_phase_pack', dt)(_stream(), C.byref(self._wp_desc), _ptr(self.W, dt),
+                                               _ptr(self._wp, dt)), 'iiseg_deconv_phase_pack')
 
     def __call__(self, x, add=None, add_off=(0, 0), window=None, out=None):
         dt = self.dtype
@@ -1285,6 +1294,7 @@ class Deconv:
                 self._wp = torch.empty(lib.iiseg_deconv_phase_weight_elems(C.byref(d)), dtype=dt, device=x.device)
                 check(_fn('deconv_phase_pack', dt)(_stream(), C.byref(d), _ptr(self.W, dt), _ptr(self._wp, dt)),
                       'iiseg_deconv_phase_pack')
+                self._wp_desc = d
             check(_fn('deconv_phase', dt)(_stream(), C.byref(d), _ptr(x, dt), _ptr(self._wp, dt),
                                           _ptr(self.b, dt), _ptr(add, dt), _ptr(out, dt)), 'iiseg_deconv_phase')
             self.last_form = 'phase'
@@ -2207,3 +2217,137 @@ def ctx_grad_head(score, y, out6, W7, layout='iohw', want_gs=False):
         _add_bytes(kern, float(y.element_size()) * B * H * W *
                    ((3 if want_gs else 2) * Cc + (2 if out6 is not None else 1) * Cin))
     return (g6, gs) if want_gs else g6
+
+
+# ---- training FCN-8 (csrc/conv_wgrad_kxk.hip, deconv_grad.hip, fcn8_train.hip) ----
+def conv_wgrad_kxk_desc(x, Cout, K, window=None, Cin_tot=None, ci0=0, layout='oihw'):
+    """The iiseg_conv_wgrad_kxk_desc of a 'valid' K x K layer on `window` = (y0, x0, h, w) of the planes of x
+    (B,Cin,H,W; any strides with unit column stride), default the whole map; x may also be a shape (dense)."""
+    if isinstance(x, torch.Tensor):
+        B, Cin, H, W = (int(v) for v in x.shape)
+        si, sp, sr, s1 = (int(v) for v in x.stride())
+        if s1 != 1:
+            raise RuntimeError('conv_wgrad_kxk: x needs unit column stride (strides %s)' % (x.stride(),))
+    else:
+        B, Cin, H, W = (int(v) for v in x)
+        si, sp, sr = Cin * H * W, H * W, W
+    y0, x0, h, w = (0, 0, H, W) if window is None else (int(v) for v in window)
+    if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise RuntimeError('conv_wgrad_kxk: window %s outside the %d x %d map' % ((y0, x0, h, w), H, W))
+    Cin_tot = Cin if Cin_tot is None else int(Cin_tot)
+    d = _lib.ConvWgradKxKDesc()
+    d.B, d.Cin, d.Cout, d.H, d.W, d.K = B, Cin, int(Cout), h, w, int(K)
+    d.ci0, d.Cin_tot, d.x_y0, d.x_x0 = int(ci0), Cin_tot, y0, x0
+    d.x_row, d.x_plane, d.x_image = sr, sp, si
+    d.so, d.sc = layout_strides(Cin_tot, int(Cout), int(K), layout)
+    return d
+
+
+def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw'):
+    """dW[:, ci0:ci0 + Cin] (and db, unless None) of the 'valid' K x K stride-1 layer (1 <= K <= 7) out = conv(x,
+    W) + b, written in place into the layer's own parameter layout, from the `window` = (y0, x0, h, w) of its
+    input's planes x (B,Cin,H,W), read in place, and gz = dL/dout (ReLU mask applied) (B,Cout,h - K + 1,w - K + 1).
+    The other input channels of dW are not touched.  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU."""
+    dt = x.dtype
+    if dW.dim() != 4 or dW.shape[2] != dW.shape[3]:
+        raise RuntimeError('conv_wgrad_kxk: dW %s is not a K x K parameter' % (tuple(dW.shape),))
+    K = int(dW.shape[2])
+    Cout, Cin_tot = (dW.shape[0], dW.shape[1]) if layout == 'oihw' else (dW.shape[1], dW.shape[0])
+    d = conv_wgrad_kxk_desc(x, Cout, K, window, Cin_tot, ci0, layout)
+    OH, OW = d.H - K + 1, d.W - K + 1
+    if tuple(gz.shape) != (d.B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
+        raise RuntimeError('conv_wgrad_kxk: shapes x %s window %s gz %s dW %s' % (
+            tuple(x.shape), window, tuple(gz.shape), tuple(dW.shape)))
+    if not x.is_cuda or x.dtype != dt or gz.dtype != dt or dW.dtype != dt:
+        raise RuntimeError('conv_wgrad_kxk needs device tensors of one dtype')
+    n = _count(_lib.load().iiseg_conv_wgrad_kxk_workspace_elems(C.byref(d), dW.element_size()),
+               'iiseg_conv_wgrad_kxk_workspace_elems')
+    ws = _workspace(_SUFFIX[dt], n, x.device) if n else None
+    kern = 'conv_wgrad_kxk_kernel'
+    _launch(kern, 2.0 * d.Cin * Cout * K * K * d.B * OH * OW, _fn('conv_wgrad_kxk', dt), C.byref(d),
+            C.c_void_p(x.data_ptr()), _ptr(gz, dt), _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))
+    if CONV_PROFILE is not None:
+        # byte model: the window of x and g_z read once, the slabs written and read once
+        _add_bytes(kern, float(dW.element_size()) * (d.B * d.Cin * d.H * d.W + gz.numel() + 2 * n))
+
+
+def deconv_desc(x_shape, Cout, K, stride, window=None):
+    """The iiseg_deconv_desc of a transposed convolution on x (B,Cin,H,W); window = (oy0, ox0, OH, OW) of its
+    full output, default all of it."""
+    B, Cin, H, W = (int(v) for v in x_shape)
+    d = _lib.DeconvDesc()
+    d.B, d.Cin, d.H, d.W, d.Cout, d.K, d.stride = B, Cin, H, W, int(Cout), int(K), int(stride)
+    full = ((H - 1) * int(stride) + int(K), (W - 1) * int(stride) + int(K))
+    d.oy0, d.ox0, d.OH, d.OW = (0, 0) + full if window is None else tuple(int(v) for v in window)
+    return d
+
+
+def deconv_dgrad(g, W, stride, x_hw, window=None):
+    """g_x (B,Cin,H,W) of the transposed convolution ops.Deconv(W[in,out,k,k], stride) on an input of x_hw = (H,
+    W), from g = dL/d(`window` of its full output) (B,Cout,OH,OW); outside the window the gradient is zero."""
+    dt = g.dtype
+    Cin, Cout, K = int(W.shape[0]), int(W.shape[1]), int(W.shape[2])
+    d = deconv_desc((g.shape[0], Cin, x_hw[0], x_hw[1]), Cout, K, stride, window)
+    if tuple(g.shape) != (d.B, Cout, d.OH, d.OW) or W.shape[2] != W.shape[3]:
+        raise RuntimeError('deconv_dgrad: g %s W %s window %s' % (tuple(g.shape), tuple(W.shape), window))
+    gx = torch.empty((d.B, Cin, d.H, d.W), dtype=dt, device=g.device)
+    kern = 'deconv_dgrad_kernel'
+    _launch(kern, 2.0 * Cin * Cout * (K // int(stride)) ** 2 * g.shape[0] * d.OH * d.OW, _fn('deconv_dgrad', dt),
+            C.byref(d), _ptr(g, dt), _ptr(W, dt), _ptr(gx, dt))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, float(g.element_size()) * (g.numel() + gx.numel()))
+    return gx
+
+
+def deconv_wgrad(x, g, dW, db, stride, window=None):
+    """dW (Cin,Cout,K,K) and db (Cout, or None) of the transposed convolution on x (B,Cin,H,W), written in place,
+    from g = dL/d(`window` of its full output)."""
+    dt = x.dtype
+    Cin, Cout, K = int(dW.shape[0]), int(dW.shape[1]), int(dW.shape[2])
+    d = deconv_desc(tuple(x.shape), Cout, K, stride, window)
+    if x.shape[1] != Cin or tuple(g.shape) != (d.B, Cout, d.OH, d.OW) or dW.shape[2] != dW.shape[3] or \
+            (db is not None and db.numel() != Cout):
+        raise RuntimeError('deconv_wgrad: x %s g %s dW %s window %s' % (tuple(x.shape), tuple(g.shape),
+                                                                       tuple(dW.shape), window))
+    nslab = _count(_lib.load().iiseg_deconv_wgrad_partials(C.byref(d)), 'iiseg_deconv_wgrad_partials')
+    ws = _workspace(_SUFFIX[dt], nslab * (dW.numel() + Cout), x.device)
+    kern = 'deconv_wgrad_kernel'
+    _launch(kern, 2.0 * Cin * Cout * (K // int(stride)) ** 2 * x.shape[0] * d.OH * d.OW, _fn('deconv_wgrad', dt),
+            C.byref(d), _ptr(x, dt), _ptr(g, dt), _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, float(g.element_size()) * (g.numel() + x.numel() + 2 * ws.numel()))
+
+
+def relu_gate(g, out, dst=None):
+    """g * [out > 0] (relu'(0) = 0) for maps of one shape; into `dst` (default a new tensor; may be g itself)."""
+    dt = g.dtype
+    if g.shape != out.shape or (dst is not None and dst.shape != g.shape):
+        raise RuntimeError('relu_gate: g %s out %s' % (tuple(g.shape), tuple(out.shape)))
+    if dst is None:
+        dst = torch.empty_like(g)
+    kern = 'relu_gate_kernel'
+    _launch(kern, 0.0, _fn('relu_gate', dt), _ptr(g, dt), _ptr(out, dt), _ptr(dst, dt), g.numel())
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, float(g.element_size()) * 3 * g.numel())
+    return dst
+
+
+def l2_term(flat, gflat, ranges, weight_decay, penalty=None):
+    """lasagne's regularize_network_params(l2) over the weight ranges [(lo, hi), ...] (ascending, disjoint) of the
+    flat parameter buffer: gflat += 2 weight_decay flat there, and penalty (one double on the device, returned) =
+    sum flat^2 in a fixed order.  Elements outside the ranges (the biases) are not touched."""
+    dt = flat.dtype
+    if flat.numel() != gflat.numel():
+        raise RuntimeError('l2_term: buffers of different sizes')
+    nr = len(ranges)
+    npart = _count(_lib.load().iiseg_l2_term_partials(nr), 'iiseg_l2_term_partials')
+    table = (C.c_int64 * (2 * nr))(*[int(v) for r in ranges for v in r])
+    partial = _workspace('bn', npart, flat.device)
+    if penalty is None:
+        penalty = torch.empty(1, dtype=torch.float64, device=flat.device)
+    kern = 'l2_term_kernel'
+    _launch(kern, 0.0, _fn('l2_term', dt), _ptr(flat, dt), _ptr(gflat, dt), flat.numel(), table, nr,
+            float(weight_decay), _ptr(partial, torch.float64), _ptr(penalty, torch.float64))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, float(flat.element_size()) * 3 * sum(hi - lo for lo, hi in ranges))
+    return penalty

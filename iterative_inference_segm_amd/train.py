@@ -6,7 +6,8 @@ train_dae.py:334-338,
 
 for dae kind 'contextmod'  and kind 'standard' with h at a pool point (section 12).
 Forward and data gradient run on the inference layers (ops.Conv), the loss and the optimizer step on
-csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_wgrad.hip (standard DAE).
+csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_wgrad.hip (standard DAE); and
+the two of train_fcn8.py:116-137 for FCN-8 itself (FCN8Trainer).
 Everything is enqueued on the current stream; nothing here waits for the device.
 """
 import torch
@@ -110,3 +111,55 @@ class DAETrainer:
         m = Metrics(self.C, score.device)
         ops.confusion_accumulate(pred, T, m.cm, m.sums)
         return res[0], m, res[2]
+
+
+class FCN8Trainer:
+    """The two compiled functions of the reference's train_fcn8.py:116-137 for an FCN8 built with trainable=True
+    (DESIGN.md section 14): train_fn = masked cross-entropy + weight_decay * sum W^2 under adam, val_fn = loss and
+    Jaccard counts on the deterministic forward.  The net is trained in place."""
+
+    def __init__(self, net, n_classes, void_labels=(11,), learning_rate=1e-4, weight_decay=0.0, seed=None):
+        if not getattr(net, 'trainable', False):
+            raise NotImplementedError('training an FCN8 needs one built with trainable=True')
+        if list(void_labels) not in ([n_classes], []):
+            raise NotImplementedError('void_labels must be [n_classes] (the last target channel) or empty')
+        if not float(weight_decay) >= 0.0:
+            raise ValueError('weight_decay must be >= 0')
+        self.net, self.C, self.weight_decay = net, int(n_classes), float(weight_decay)
+        dev, dt = net.flat.device, net.flat.dtype
+        self.lr = torch.full((1,), float(learning_rate), dtype=dt, device=dev)     # read by the kernel
+        self.s1 = torch.zeros_like(net.flat)
+        self.s2 = torch.zeros_like(net.flat)
+        self.state = torch.tensor([0.0, 1.0, 1.0], dtype=dt, device=dev)
+        self.ranges = net.weight_ranges()
+        self.generator = None
+        if seed is not None:
+            self.generator = torch.Generator(device=dev)
+            self.generator.manual_seed(int(seed))
+
+    def set_learning_rate(self, lr):
+        self.lr.fill_(float(lr))
+
+    def train_step(self, X, T, keep6=None, keep7=None):
+        """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64).  keep6 / keep7:
+        the caller's dropout masks (tests), else drawn from the trainer's generator."""
+        net = self.net
+        score = net.forward_train(X, keep6, keep7, generator=self.generator)
+        res, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=True)
+        net.backward(g)
+        loss = res[0]
+        if self.weight_decay > 0:
+            loss = loss + self.weight_decay * ops.l2_term(net.flat, net.gflat, self.ranges, self.weight_decay)[0]
+        ops.opt_step('adam', net.flat, net.gflat, self.s1, self.s2, self.lr, self.state, grid=True)
+        net.refresh()
+        return loss
+
+    def val_step(self, X, T):
+        """val_fn (deterministic: no dropout): (loss, Metrics) -- the loss a device scalar, accuracy and the
+        Jaccard counts in the Metrics accumulators (api.Metrics.result() -> acc, jacc(2, C), mse)."""
+        score = self.net.forward_train(X, deterministic=True)
+        res, _, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=False)
+        pred = ops.crop_softmax(score, score.shape[2], score.shape[3], off=(0, 0))
+        m = Metrics(self.C, score.device)
+        ops.confusion_accumulate(pred, T, m.cm, m.sums)
+        return res[0], m

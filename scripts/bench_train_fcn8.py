@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""One training step of FCN-8 (the real architecture, 11 classes, pad 100, default synthetic weights) at batch 10,
+224x224: one JSON line.
+
+    python scripts/bench_train_fcn8.py [--batch 10] [--size 224x224] [--reps 15] [--dtypes float32]
+
+Per precision: step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, L2 term, adam,
+refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch profile, per
+layer the weight-gradient launches' ms (kernel + finalize) next to the forward launch's ms of that same layer in
+that same step, their ratio, and the weight gradient's fraction of `--peak_tflops` (157.3: the fp32 matrix-pipe
+peak) on the nominal 2 Cin Cout K^2 OH OW B; and for the element-wise kernels (relu_gate, l2_term) their GB/s on
+algorithmic bytes against `--stream_gbs` (6600).  The transposed convolutions' forward launches are not recorded
+by the launch profile: theirs are timed between two HIP events on the step's own maps, next to their weight- and
+data-gradient launches.  --width_div / --fc_channels shrink the net.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from iterative_inference_segm_amd import ops, synthetic as S              # noqa: E402
+from iterative_inference_segm_amd.fcn8 import FCN8, PARAM_ORDER           # noqa: E402
+from iterative_inference_segm_amd.train import FCN8Trainer                # noqa: E402
+
+DECONVS = ('upsample', 'score4', 'score2')
+KXK = ('score_pool3', 'score_pool4', 'score_fr', 'fc7', 'fc6')
+
+
+def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay):
+    params = S.make_fcn8_params(3, 11, seed=1234, width_div=width_div, fc_channels=fc_channels)
+    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True)
+    tr = FCN8Trainer(net, 11, [11], learning_rate=1e-4, weight_decay=weight_decay, seed=1)
+    X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
+    T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
+    for _ in range(3):
+        tr.train_step(X, T)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tr.train_step(X, T)
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    step = float(np.median(ms))
+    # one profiled step: every launch of the library between two marks, in launch order
+    prof = []
+    ops.KERNEL_BYTES.clear()
+    ops.profile_begin()
+    ops.CONV_PROFILE = prof
+    try:
+        score = net.forward_train(X, generator=tr.generator)
+        n_fwd = len(prof)
+        _, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0)
+        net.backward(g)
+        if weight_decay > 0:
+            ops.l2_term(net.flat, net.gflat, tr.ranges, weight_decay)
+        torch.cuda.synchronize()
+    finally:
+        ops.CONV_PROFILE = None
+        ops.profile_end()
+    convs = [n for n in PARAM_ORDER if n in net.convs]
+    # forward_train's order: the thirteen block layers, fc6, fc7, score_fr, score_pool4, score_pool3
+    fwd_order = convs[:16] + ['score_pool4', 'score_pool3']
+    fwd = [(k, f, a.elapsed_time(b)) for k, f, a, b in prof[:n_fwd] if f > 0]
+    if len(fwd) != len(fwd_order):
+        raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fwd],))
+    fwd_ms = dict(zip(fwd_order, [t for _, _, t in fwd]))
+    fwd_kernel = dict(zip(fwd_order, [k for k, _, _ in fwd]))
+    back = prof[n_fwd:]
+    by = lambda kern: [(f, a.elapsed_time(b)) for k, f, a, b in back if k == kern]
+    # backward's order of the weight gradients
+    blocks = [n for n in reversed(convs[:13])]
+    wg = dict(zip(DECONVS, by('deconv_wgrad_kernel')))
+    wg.update(zip(KXK, by('conv_wgrad_kxk_kernel')))
+    wg.update(zip(blocks, by('conv_wgrad_kernel')))
+    if sorted(wg) != sorted(PARAM_ORDER):
+        raise RuntimeError('expected one weight-gradient call per layer, got %d' % len(wg))
+    # the transposed convolutions' forward launches do not pass the launch profile: five back-to-back launches
+    # of each between two HIP events, on the maps the profiled step kept
+    sv = net.saved_maps()
+
+    def timed(fn, n=5):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+    fwd_ms['upsample'] = timed(lambda: net.upsample(sv['final'], window=sv['win_upsample']))
+    fwd_ms['score4'] = timed(lambda: net.score4(sv['fused'], add=sv['score_pool3'], window=sv['win_score4']))
+    fwd_ms['score2'] = timed(lambda: net.score2(sv['score_fr'], add=sv['score_pool4'], window=sv['win_score2']))
+    for n in DECONVS:
+        fwd_kernel[n] = 'deconv (%s form; HIP events)' % getattr(net, n).last_form
+    dgrad_ms = dict(zip(DECONVS, [t for _, t in by('deconv_dgrad_kernel')]))
+    out = []
+    for n in PARAM_ORDER:
+        f, t = wg[n]
+        row = {'layer': n, 'shape': list(params[n][0].shape), 'wgrad_ms': round(t, 4),
+               'wgrad_fraction_of_peak': round(f / (t * 1e-3) / (peak * 1e12), 4)}
+        if n in fwd_ms:
+            row.update(forward_kernel=fwd_kernel[n], forward_ms=round(fwd_ms[n], 4),
+                       wgrad_over_forward=round(t / fwd_ms[n], 3))
+        if n in dgrad_ms:
+            row.update(dgrad_ms=round(dgrad_ms[n], 4), dgrad_over_forward=round(dgrad_ms[n] / fwd_ms[n], 3))
+        out.append(row)
+    elem = []
+    for kern in ('relu_gate_kernel', 'l2_term_kernel', 'deconv_dgrad_kernel'):
+        t = sum(t for _, t in by(kern))
+        if t > 0:
+            gbs = ops.KERNEL_BYTES.get(kern, 0.0) / (t * 1e-3) / 1e9
+            elem.append({'kernel': kern, 'launches': len(by(kern)), 'ms': round(t, 4), 'gb_per_s': round(gbs, 1),
+                         'fraction_of_stream': round(gbs / stream, 4)})
+    all_ms = float(sum(a.elapsed_time(b) for _, _, a, b in prof))
+    tw = sum(r['wgrad_ms'] for r in out)
+    twc = sum(r['wgrad_ms'] for r in out if r['layer'] in net.convs)
+    tf = sum(r['forward_ms'] for r in out if r['layer'] in net.convs)
+    return {'dtype': str(dt).replace('torch.', ''), 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+            'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 1),
+            'parameters': int(net.flat.numel()), 'weights': 'default synthetic (synthetic.make_fcn8_params)',
+            'profiled_launch_ms': round(all_ms, 3), 'wgrad_ms_total': round(tw, 3),
+            'forward_conv_ms_total': round(tf, 3), 'step_over_forward_convs': round(step / tf, 3),
+            'wgrad_over_forward': round(twc / tf, 3), 'layers': out, 'elementwise': elem}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=10)
+    ap.add_argument('--size', default='224x224')
+    ap.add_argument('--reps', type=int, default=15)
+    ap.add_argument('--dtypes', nargs='+', default=['float32'])
+    ap.add_argument('--peak_tflops', type=float, default=157.3)
+    ap.add_argument('--stream_gbs', type=float, default=6600.0)
+    ap.add_argument('--width_div', type=int, default=1)
+    ap.add_argument('--fc_channels', type=int, default=4096)
+    ap.add_argument('--weight_decay', type=float, default=1e-4)
+    a = ap.parse_args()
+    H, W = (int(v) for v in a.size.split('x'))
+    rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.width_div,
+                a.fc_channels, a.weight_decay) for name in a.dtypes]
+    print(json.dumps({'bench': 'train_fcn8', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
+                      'stream_gbs': a.stream_gbs, 'reps': a.reps, 'results': rows}))
+
+
+if __name__ == '__main__':
+    main()
