@@ -1121,6 +1121,25 @@ int iiseg_l2_term_f32(void* stream, const float* p, float* g, int64_t n, const i
 int iiseg_l2_term_f64(void* stream, const double* p, double* g, int64_t n, const int64_t* ranges, int32_t nranges,
                       double weight_decay, double* partial, double* penalty);
 
+/* ---------------------------------------------------------------------------------------
+ * Weight gradients on the 16-bit matrix pipe (wgrad='bf16'; backward-compatible addition).
+ *
+ * iiseg_conv_wgrad_f32's sums for the same descriptor and the same fp32 tensors (csrc/conv_wgrad_bf16.hip), with
+ * every x and gz element rounded once to bf16 (to nearest, ties to even) as it is staged and the products formed
+ * by v_mfma_f32_32x32x16_bf16 with fp32 accumulators:
+ *   dW[co][ci0 + ci][ky][kx] = sum_{b,y,x} bf16(gz[b,co,y,x]) bf16(xpad[b,ci,y + ky,x + kx])
+ *   db[co]                   = sum_{b,y,x} gz[b,co,y,x]                        (the unrounded values)
+ * The same contract otherwise: slabs of its own plan (iiseg_conv_wgrad_bf16_slabs), a finalize launch that adds
+ * them in slab order in double, no atomics, the same inputs give the same bits.
+ *   ws : iiseg_conv_wgrad_bf16_workspace_elems(d) floats of scratch (0: may be NULL).
+ * ------------------------------------------------------------------------------------- */
+/* host only: number of pixel slabs (>= 1), or a negative status */
+int iiseg_conv_wgrad_bf16_slabs(const iiseg_conv_wgrad_desc* d);
+/* host only: floats of `ws` (0 with one slab, else slabs * (Cout Cin 9 + Cout)), or a negative status */
+int64_t iiseg_conv_wgrad_bf16_workspace_elems(const iiseg_conv_wgrad_desc* d);
+int iiseg_conv_wgrad_bf16(void* stream, const iiseg_conv_wgrad_desc* d, const float* x, const float* gz, float* ws,
+                          float* dW, float* db);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,6 +292,10 @@ SIGNATURES = {
     'iiseg_l2_term_partials': (C.c_int, [_i32]),
     'iiseg_l2_term_f32': (C.c_int, [_vp] * 3 + [_i64, C.POINTER(_i64), _i32, _f64, _vp, _vp]),
     'iiseg_l2_term_f64': (C.c_int, [_vp] * 3 + [_i64, C.POINTER(_i64), _i32, _f64, _vp, _vp]),
+    # weight gradients on the 16-bit matrix pipe (wgrad='bf16')
+    'iiseg_conv_wgrad_bf16_slabs': (C.c_int, [C.POINTER(ConvWgradDesc)]),
+    'iiseg_conv_wgrad_bf16_workspace_elems': (_i64, [C.POINTER(ConvWgradDesc)]),
+    'iiseg_conv_wgrad_bf16': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
 }
 
 _lib = None

@@ -90,7 +90,8 @@ class _NCHWAdjoint:
         mpre, mpool = self.override[p] if self.override and p in self.override else (self.pre[p], self.pool[p])
         if self.gv is not None:
             t_in = self.pool[self.dae.total] if p == self.dae.total else self.fused['fused_up%d' % (p + 1)]
-            ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *self.gv['up_conv%d' % p], pad=1)
+            ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *self.gv['up_conv%d' % p], pad=1,
+                           mma=self.dae.wgrad)
         return ops.depool_bwd(self.bwd['up_conv%d' % p](g_c), mpre, mpool)
 
     def encoder(self, p, gp, acc, window, want_data):
@@ -104,8 +105,8 @@ class _NCHWAdjoint:
             if (p - 1) in self.feeds:                    # h first (P13), then the features
                 h = self.h_list[self.feeds[p - 1]]
                 ch = h.shape[1]
-                ops.conv_wgrad(h, g_z, dW, None, pad=fwd.pad, ci0=0)
-            ops.conv_wgrad(self.pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch)
+                ops.conv_wgrad(h, g_z, dW, None, pad=fwd.pad, ci0=0, mma=self.dae.wgrad)
+            ops.conv_wgrad(self.pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch, mma=self.dae.wgrad)
         if not want_data:
             return None
         conv = self.bwd[name]
@@ -175,15 +176,24 @@ class StandardDAE:
     def __init__(self, params, n_classes, concat_h=('pool4',), padding=100, n_filters=64,
                  conv_before_pool=1, additional_pool=2, skip=True, unpool_type='trackind', bn=0,
                  device='cuda', dtype=torch.float32, pad_multi_concat=False, noise=0.0,
-                 dropout=0.0, emulate_noise=False, seed=0, mma=None, trainable=False):
+                 dropout=0.0, emulate_noise=False, seed=0, mma=None, trainable=False, wgrad='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; ops.Conv).
         trainable=True: the parameters live in ONE flat buffer in `param_order` (W then b per layer), every
         layer holds views of it and runs on the direct / halo kernels only, so that `refresh()` can pack
-        them again in place after an optimizer step."""
+        them again in place after an optimizer step.
+        wgrad: operand precision of `backward`'s 3x3 weight gradients ('f32' default; 'bf16' = operands rounded
+        to bf16 for v_mfma_f32_32x32x16_bf16, fp32 accumulation -- float32 trainable modules only; the forward,
+        the data gradients, the parameters and db stay float32: DESIGN.md section 15)."""
         concat_h = list(concat_h)
         mma = mma or ops.DEFAULT_MMA
         self.trainable = bool(trainable)
+        if wgrad not in ops.WGRAD_MODES:
+            raise ValueError("wgrad=%r is not one of %s" % (wgrad, ops.WGRAD_MODES))
+        if wgrad == 'bf16' and not (trainable and dtype == torch.float32):
+            raise NotImplementedError("wgrad='bf16': the 16-bit weight gradient of a trainable float32 module "
+                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
+        self.wgrad = wgrad
         self.flat, self._params, self._tsaved = None, None, None
         if trainable:
             if conv_before_pool != 1 or bn or dropout > 0 or unpool_type not in ('trackind', 'inverse'):

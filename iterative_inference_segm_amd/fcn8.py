@@ -30,7 +30,7 @@ _UID = itertools.count(1)   # identity of a net in the provenance tags (never re
 
 class FCN8:
     def __init__(self, params, n_classes, layer=('probs_dimshuffle',), pad=100, temperature=1.0,
-                 device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5):
+                 device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5, wgrad='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; 'bf16c8' = additionally bf16 C8
         activations between the 3x3 layers, the h maps handed out stay fp32 NCHW; ops.Conv).
@@ -38,9 +38,19 @@ class FCN8:
         buffer in PARAM_ORDER (W then b per layer), every layer holds views of it and runs on the direct / halo /
         tap kernels only, so that `refresh()` can pack them again in place after an optimizer step; every map is
         computed whole (no border fold, no session).  `dropout`: p of the DropoutLayers behind fc6 and fc7 in
-        `forward_train`."""
+        `forward_train`.
+        wgrad: operand precision of `backward`'s thirteen 3x3 weight gradients ('f32' default; 'bf16' = operands
+        rounded to bf16 for v_mfma_f32_32x32x16_bf16, fp32 accumulation -- float32 trainable modules only; fc6,
+        fc7, the score and transposed layers, the forward and the data gradients stay float32: DESIGN.md
+        section 15)."""
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
+        if wgrad not in ops.WGRAD_MODES:
+            raise ValueError("wgrad=%r is not one of %s" % (wgrad, ops.WGRAD_MODES))
+        if wgrad == 'bf16' and not (trainable and dtype == torch.float32):
+            raise NotImplementedError("wgrad='bf16': the 16-bit weight gradient of a trainable float32 module "
+                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
+        self.wgrad = wgrad
         self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
         if trainable:
             # refused here, before any device work
@@ -416,7 +426,7 @@ class FCN8:
                     gz = ops.pool_relu_bwd(g, s[name], s[pname])
                 else:
                     gz = ops.relu_gate(g, s[name], dst=g)
-                ops.conv_wgrad(s['in_' + name], gz, *gv[name], pad=self.convs[name].pad)
+                ops.conv_wgrad(s['in_' + name], gz, *gv[name], pad=self.convs[name].pad, mma=self.wgrad)
                 if bi or ni:
                     g = bwd[name](gz)
         return gv

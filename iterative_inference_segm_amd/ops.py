@@ -2111,12 +2111,23 @@ def conv_wgrad_desc(x_shape, Cout, pad, Cin_tot=None, ci0=0, layout='oihw'):
     return d
 
 
-def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw'):
+WGRAD_MODES = ('f32', 'bf16')
+
+
+def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
     """dW[:, ci0:ci0 + Cin] (and db, unless None) of the zero-padded 3x3 layer out = conv(xpad, W) + b, written
     in place into the layer's own parameter layout, from its input x (B,Cin,H,W) and gz = dL/dout (ReLU mask
     applied) (B,Cout,H + 2 pad - 2,W + 2 pad - 2).  The other input channels of dW are not touched (the second
-    source of a concat layer is a second call).  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU."""
+    source of a concat layer is a second call).  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU.
+    mma='bf16' (float32 tensors only; csrc/conv_wgrad_bf16.hip): x and gz are rounded once to bf16 as they are
+    staged and multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulators; db stays the sum of the unrounded
+    gz."""
     dt = x.dtype
+    if mma not in WGRAD_MODES:
+        raise ValueError("conv_wgrad: mma=%r is not one of %s" % (mma, WGRAD_MODES))
+    if mma == 'bf16' and not (dt == gz.dtype == dW.dtype == torch.float32 and (db is None or db.dtype == dt)):
+        raise ValueError("conv_wgrad: mma='bf16' takes float32 tensors only (x %s, gz %s, dW %s)"
+                         % (x.dtype, gz.dtype, dW.dtype))
     if dW.dim() != 4 or tuple(dW.shape[2:]) != (3, 3):
         raise RuntimeError('conv_wgrad: dW %s is not a 3x3 parameter' % (tuple(dW.shape),))
     Cout, Cin_tot = (dW.shape[0], dW.shape[1]) if layout == 'oihw' else (dW.shape[1], dW.shape[0])
@@ -2125,11 +2136,16 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw'):
     if tuple(gz.shape) != (B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
         raise RuntimeError('conv_wgrad: shapes x %s gz %s dW %s' % (tuple(x.shape), tuple(gz.shape), tuple(dW.shape)))
     d = conv_wgrad_desc(tuple(x.shape), Cout, pad, Cin_tot, ci0, layout)
-    n = _count(_lib.load().iiseg_conv_wgrad_workspace_elems(C.byref(d), dW.element_size()),
-               'iiseg_conv_wgrad_workspace_elems')
+    if mma == 'bf16':                                    # a plan, and a profile name, of its own
+        n = _count(_lib.load().iiseg_conv_wgrad_bf16_workspace_elems(C.byref(d)),
+                   'iiseg_conv_wgrad_bf16_workspace_elems')
+        kern, fn = 'conv_wgrad_bf16_kernel', _lib.load().iiseg_conv_wgrad_bf16
+    else:
+        n = _count(_lib.load().iiseg_conv_wgrad_workspace_elems(C.byref(d), dW.element_size()),
+                   'iiseg_conv_wgrad_workspace_elems')
+        kern, fn = 'conv_wgrad_kernel', _fn('conv_wgrad', dt)
     ws = _workspace(_SUFFIX[dt], n, x.device) if n else None
-    kern = 'conv_wgrad_kernel'
-    _launch(kern, 2.0 * Cin * Cout * 9 * B * OH * OW, _fn('conv_wgrad', dt), C.byref(d), _ptr(x, dt), _ptr(gz, dt),
+    _launch(kern, 2.0 * Cin * Cout * 9 * B * OH * OW, fn, C.byref(d), _ptr(x, dt), _ptr(gz, dt),
             _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))
     if CONV_PROFILE is not None:
         # byte model: x and g_z read once, the slabs written and read once

@@ -18,15 +18,28 @@ from .api import Metrics
 SUPPORTED_LOSSES = ('crossentropy', 'squared_error')
 
 
+def check_wgrad(wgrad, dtype):
+    """The weight-gradient mode of a run (host only): 'f32', or 'bf16' with float32."""
+    if wgrad not in ops.WGRAD_MODES:
+        raise ValueError('wgrad must be one of %s (got %r)' % (', '.join(ops.WGRAD_MODES), wgrad))
+    if wgrad == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
+        raise NotImplementedError("wgrad='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
+                                  'be float32 (got %s)' % (dtype,))
+
+
 def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
-                    optimizer='rmsprop', dae_dict=None):
+                    optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32'):
     """Raises NotImplementedError / ValueError with the reason for everything this slice does not train
     (host only: callable before any GPU work).  dae_dict: the standard kind's options (concat_h, bn, dropout,
-    conv_before_pool, unpool_type)."""
+    conv_before_pool, unpool_type).  wgrad, dtype: the weight-gradient mode and the run's precision."""
     if kind not in ('contextmod', 'standard'):
         raise NotImplementedError("training is built for dae kinds 'contextmod' and 'standard' (got %r): the "
                                   'fcn8 kind (strided 4x4 transposed convolutions) has no weight-gradient '
                                   'kernel' % (kind,))
+    check_wgrad(wgrad, dtype)
+    if wgrad == 'bf16' and kind == 'contextmod':
+        raise NotImplementedError("wgrad='bf16' is the zero-padded 3x3 weight gradient of dae kind 'standard' and "
+                                  "of FCN-8: the context module's 11-channel gradient kernels stay float32")
     if kind == 'standard':
         dd = dae_dict or {}
         concat_h = list(dd.get('concat_h', ['input']))

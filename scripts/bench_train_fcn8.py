@@ -3,6 +3,7 @@
 224x224: one JSON line.
 
     python scripts/bench_train_fcn8.py [--batch 10] [--size 224x224] [--reps 15] [--dtypes float32]
+                                       [--wgrad f32 bf16]
 
 Per precision: step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, L2 term, adam,
 refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch profile, per
@@ -12,6 +13,9 @@ peak) on the nominal 2 Cin Cout K^2 OH OW B; and for the element-wise kernels (r
 algorithmic bytes against `--stream_gbs` (6600).  The transposed convolutions' forward launches are not recorded
 by the launch profile: theirs are timed between two HIP events on the step's own maps, next to their weight- and
 data-gradient launches.  --width_div / --fc_channels shrink the net.
+--wgrad: the weight-gradient modes to run, one result row each in the same process (bf16: float32 only; the
+thirteen 3x3 layers of its rows are conv_wgrad_bf16_kernel's launches and take their fraction of
+`--peak_tflops_bf16`, 2500; the other layers stay on the fp32 kernels and the fp32 peak).
 """
 import argparse
 import json
@@ -31,9 +35,10 @@ DECONVS = ('upsample', 'score4', 'score2')
 KXK = ('score_pool3', 'score_pool4', 'score_fr', 'fc7', 'fc6')
 
 
-def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay):
+def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, wgrad='f32',
+        peak_bf16=2500.0):
     params = S.make_fcn8_params(3, 11, seed=1234, width_div=width_div, fc_channels=fc_channels)
-    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True)
+    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad)
     tr = FCN8Trainer(net, 11, [11], learning_rate=1e-4, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
@@ -79,7 +84,7 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay):
     blocks = [n for n in reversed(convs[:13])]
     wg = dict(zip(DECONVS, by('deconv_wgrad_kernel')))
     wg.update(zip(KXK, by('conv_wgrad_kxk_kernel')))
-    wg.update(zip(blocks, by('conv_wgrad_kernel')))
+    wg.update(zip(blocks, by('conv_wgrad_bf16_kernel' if wgrad == 'bf16' else 'conv_wgrad_kernel')))
     if sorted(wg) != sorted(PARAM_ORDER):
         raise RuntimeError('expected one weight-gradient call per layer, got %d' % len(wg))
     # the transposed convolutions' forward launches do not pass the launch profile: five back-to-back launches
@@ -105,7 +110,8 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay):
     for n in PARAM_ORDER:
         f, t = wg[n]
         row = {'layer': n, 'shape': list(params[n][0].shape), 'wgrad_ms': round(t, 4),
-               'wgrad_fraction_of_peak': round(f / (t * 1e-3) / (peak * 1e12), 4)}
+               'wgrad_fraction_of_peak': round(f / (t * 1e-3) /
+                                               ((peak_bf16 if wgrad == 'bf16' and n in blocks else peak) * 1e12), 4)}
         if n in fwd_ms:
             row.update(forward_kernel=fwd_kernel[n], forward_ms=round(fwd_ms[n], 4),
                        wgrad_over_forward=round(t / fwd_ms[n], 3))
@@ -122,11 +128,13 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay):
     all_ms = float(sum(a.elapsed_time(b) for _, _, a, b in prof))
     tw = sum(r['wgrad_ms'] for r in out)
     twc = sum(r['wgrad_ms'] for r in out if r['layer'] in net.convs)
+    t3 = sum(r['wgrad_ms'] for r in out if r['layer'] in blocks)
     tf = sum(r['forward_ms'] for r in out if r['layer'] in net.convs)
-    return {'dtype': str(dt).replace('torch.', ''), 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'batch': B, 'size': '%dx%d' % (H, W),
+            'step_ms': round(step, 3),
             'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 1),
             'parameters': int(net.flat.numel()), 'weights': 'default synthetic (synthetic.make_fcn8_params)',
-            'profiled_launch_ms': round(all_ms, 3), 'wgrad_ms_total': round(tw, 3),
+            'profiled_launch_ms': round(all_ms, 3), 'wgrad_ms_total': round(tw, 3), 'wgrad_3x3_ms_total': round(t3, 3),
             'forward_conv_ms_total': round(tf, 3), 'step_over_forward_convs': round(step / tf, 3),
             'wgrad_over_forward': round(twc / tf, 3), 'layers': out, 'elementwise': elem}
 
@@ -138,6 +146,8 @@ def main():
     ap.add_argument('--reps', type=int, default=15)
     ap.add_argument('--dtypes', nargs='+', default=['float32'])
     ap.add_argument('--peak_tflops', type=float, default=157.3)
+    ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     ap.add_argument('--stream_gbs', type=float, default=6600.0)
     ap.add_argument('--width_div', type=int, default=1)
     ap.add_argument('--fc_channels', type=int, default=4096)
@@ -145,8 +155,10 @@ def main():
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split('x'))
     rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.width_div,
-                a.fc_channels, a.weight_decay) for name in a.dtypes]
+                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16)
+            for name in a.dtypes for mode in a.wgrad if mode == 'f32' or name == 'float32']
     print(json.dumps({'bench': 'train_fcn8', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
+                      'peak_tflops_bf16': a.peak_tflops_bf16,
                       'stream_gbs': a.stream_gbs, 'reps': a.reps, 'results': rows}))
 
 

@@ -3,6 +3,7 @@
 additional_pool=2, pad 100, trackind, skip) at batch 10, 224x224, from_gt, noise 0.1: one JSON line.
 
     python scripts/bench_train_std.py [--batch 10] [--size 224x224] [--reps 15] [--dtypes float32 float64]
+                                      [--wgrad f32 bf16]
 
 Per precision: step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, RMSprop,
 refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch profile, per
@@ -10,6 +11,8 @@ layer the weight-gradient launches' ms (kernel + finalize; both sources of the c
 launch's ms of that same layer in that same step, their ratio, and the weight gradient's fraction of
 `--peak_tflops` (157.3: the fp32 matrix-pipe peak) on the nominal 2 Cin Cout 9 OH OW B.  A trainable StandardDAE
 runs its forward layers on the direct / halo kernels (no Winograd form: DESIGN section 12).
+--wgrad: the weight-gradient modes to run, one result row each in the same process (bf16: float32 only; its rows
+count conv_wgrad_bf16_kernel's launches and take their fraction of `--peak_tflops_bf16`, 2500).
 """
 import argparse
 import json
@@ -26,9 +29,9 @@ from iterative_inference_segm_amd.dae import StandardDAE, param_order     # noqa
 from iterative_inference_segm_amd.train import DAETrainer                 # noqa: E402
 
 
-def one(B, H, W, dt, reps, peak):
+def one(B, H, W, dt, reps, peak, wgrad='f32'):
     params = S.make_dae_params(seed=4321)
-    dae = StandardDAE(params, 11, dtype=dt, mma='f32', trainable=True)
+    dae = StandardDAE(params, 11, dtype=dt, mma='f32', trainable=True, wgrad=wgrad)
     tr = DAETrainer(None, dae, 11, [11], noise=0.1, seed=1)
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
     y = T[:, :11].contiguous()
@@ -69,7 +72,8 @@ def one(B, H, W, dt, reps, peak):
         raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fwd],))
     fwd_ms = dict(zip(order, [t for _, _, t in fwd]))
     fwd_kernel = dict(zip(order, [k for k, _, _ in fwd]))
-    wg = [(f, a.elapsed_time(b)) for k, f, a, b in prof[n_fwd:] if k == 'conv_wgrad_kernel']
+    kern = 'conv_wgrad_bf16_kernel' if wgrad == 'bf16' else 'conv_wgrad_kernel'
+    wg = [(f, a.elapsed_time(b)) for k, f, a, b in prof[n_fwd:] if k == kern]
     # backward's order: up_conv1..total, then conv<total>_1..conv1_1, the concat layer (h behind pool4) twice
     names = ['up_conv%d' % p for p in range(1, total + 1)]
     for p in range(total, 0, -1):
@@ -90,7 +94,8 @@ def one(B, H, W, dt, reps, peak):
                     'wgrad_fraction_of_peak': round(r['flops'] / (r['wgrad_ms'] * 1e-3) / (peak * 1e12), 4)})
     all_ms = float(sum(a.elapsed_time(b) for _, _, a, b in prof))
     tw, tf = sum(r['wgrad_ms'] for r in out), sum(r['forward_ms'] for r in out)
-    return {'dtype': str(dt).replace('torch.', ''), 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'wgrad_peak_tflops': peak, 'batch': B,
+            'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
             'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 1),
             'parameters': int(dae.flat.numel()), 'profiled_launch_ms': round(all_ms, 3),
             'wgrad_ms_total': round(tw, 3), 'forward_conv_ms_total': round(tf, 3),
@@ -104,10 +109,14 @@ def main():
     ap.add_argument('--reps', type=int, default=15)
     ap.add_argument('--dtypes', nargs='+', default=['float32', 'float64'])
     ap.add_argument('--peak_tflops', type=float, default=157.3)
+    ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split('x'))
-    rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops) for name in a.dtypes]
+    rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops_bf16 if mode == 'bf16' else a.peak_tflops,
+                mode) for name in a.dtypes for mode in a.wgrad if mode == 'f32' or name == 'float32']
     print(json.dumps({'bench': 'train_std', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
+                      'peak_tflops_bf16': a.peak_tflops_bf16,
                       'reps': a.reps, 'results': rows}))
 
 
