@@ -1140,6 +1140,43 @@ int64_t iiseg_conv_wgrad_bf16_workspace_elems(const iiseg_conv_wgrad_desc* d);
 int iiseg_conv_wgrad_bf16(void* stream, const iiseg_conv_wgrad_desc* d, const float* x, const float* gz, float* ws,
                           float* dW, float* db);
 
+/* ---------------------------------------------------------------------------------------
+ * Data gradients on the 16-bit matrix pipe (dgrad='bf16'; backward-compatible addition).
+ *
+ * Data gradient of a zero-padded 3x3 stride-1 layer with pad 1 (csrc/conv_dgrad_bf16.hip), from fp32 tensors:
+ *   gx[b][ci][y][x] = sum_{co,ky,kx} bf16(W[co][ci0 + ci][ky][kx]) bf16(gz[b][co][y + 1 - ky][x + 1 - kx])
+ * with gz zero outside its plane, every operand rounded once (to nearest, ties to even), the products formed by
+ * v_mfma_f32_32x32x16_bf16 and accumulated in fp32 in a fixed order: no atomics, the same inputs give the same bits.
+ *   gz     : (B, Cout, H, W), contiguous: dL/dout with the ReLU mask already applied.
+ *   W      : the layer's fp32 parameter array with Cin_tot >= ci0 + Cin input channels; element (co, ci0 + ci, tap)
+ *            at co * so + (ci0 + ci) * sc + tap, (so, sc) = (Cin_tot 9, 9) for W[out,in,3,3] or (9, Cout 9) for
+ *            W[in,out,3,3].  Read by iiseg_conv_dgrad_bf16_pack only.
+ *   packed : iiseg_conv_dgrad_bf16_pack_elems(d) bf16 elements, 16-byte aligned: the image of the Cin channels that
+ *            iiseg_conv_dgrad_bf16_pack writes ([k-tile][tap][co chunk of 8][ci][8 co], zero past Cout and Cin)
+ *            and iiseg_conv_dgrad_bf16 reads.  Pack again whenever W has changed.
+ *   gx     : (B, Cin, H, W), contiguous.  accumulate = 1: gx += the sums, in place.
+ *   gate   : NULL, or a map of gx's shape: the result (after the accumulation) is gx * [gate > 0], relu'(0) = 0.
+ * NULL d, gz, W, packed or gx IISEG_ERR_NULL; K != 3, pad != 1, non-positive sizes, more than 65535 channels or
+ * images, H W > 2^28, ci0 + Cin > Cin_tot, other strides, accumulate outside {0, 1} IISEG_ERR_SHAPE; packed not
+ * 16-byte aligned IISEG_ERR_ALIGN; gx overlapping gz or packed, packed overlapping W IISEG_ERR_UNSUPPORTED.  All
+ * before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct iiseg_conv_dgrad_desc {
+    int32_t B, Cin, Cout, H, W, K, pad;   /* K must be 3, pad 1 */
+    int32_t ci0, Cin_tot;
+    int32_t accumulate;
+    int32_t reserved[2];
+    int64_t so, sc;
+} iiseg_conv_dgrad_desc;
+
+/* host only: IISEG_OK or the status a launch of `d` would return */
+int iiseg_conv_dgrad_bf16_check(const iiseg_conv_dgrad_desc* d);
+/* host only: bf16 elements of `packed`, or a negative status */
+int64_t iiseg_conv_dgrad_bf16_pack_elems(const iiseg_conv_dgrad_desc* d);
+int iiseg_conv_dgrad_bf16_pack(void* stream, const iiseg_conv_dgrad_desc* d, const float* W, void* packed);
+int iiseg_conv_dgrad_bf16(void* stream, const iiseg_conv_dgrad_desc* d, const float* gz, const void* packed,
+                          const float* gate, float* gx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,12 @@ class ConvWgradDesc(C.Structure):
                [('reserved', C.c_int32 * 3), ('so', C.c_int64), ('sc', C.c_int64)]
 
 
+class ConvDgradDesc(C.Structure):
+    """struct iiseg_conv_dgrad_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'pad', 'ci0', 'Cin_tot', 'accumulate')] + \
+               [('reserved', C.c_int32 * 2), ('so', C.c_int64), ('sc', C.c_int64)]
+
+
 class ConvWgradKxKDesc(C.Structure):
     """struct iiseg_conv_wgrad_kxk_desc"""
     _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'ci0', 'Cin_tot', 'x_y0', 'x_x0')] + \
@@ -296,6 +302,11 @@ SIGNATURES = {
     'iiseg_conv_wgrad_bf16_slabs': (C.c_int, [C.POINTER(ConvWgradDesc)]),
     'iiseg_conv_wgrad_bf16_workspace_elems': (_i64, [C.POINTER(ConvWgradDesc)]),
     'iiseg_conv_wgrad_bf16': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
+    # data gradients on the 16-bit matrix pipe (dgrad='bf16')
+    'iiseg_conv_dgrad_bf16_check': (C.c_int, [C.POINTER(ConvDgradDesc)]),
+    'iiseg_conv_dgrad_bf16_pack_elems': (_i64, [C.POINTER(ConvDgradDesc)]),
+    'iiseg_conv_dgrad_bf16_pack': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 2),
+    'iiseg_conv_dgrad_bf16': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 4),
 }
 
 _lib = None

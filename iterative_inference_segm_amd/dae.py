@@ -66,7 +66,9 @@ class _NCHWAdjoint:
     the up_conv layers, a concat layer is two calls into one dW, h first)."""
 
     def __init__(self, dae, override, gv):
-        self.dae, self.bwd = dae, dae._bwd_convs()
+        # (dgrad='bf16': `backward` forms its data gradients with ops.conv_dgrad, no flipped-filter layers)
+        self.d16 = gv is not None and dae.dgrad == 'bf16'
+        self.dae, self.bwd = dae, None if self.d16 else dae._bwd_convs()
         _, self.pre, self.pool = dae._saved
         if any(t.device.type == 'meta' for t in self.pre.values()):
             raise RuntimeError('backward_y needs the pre-pool maps of the forward pass: set '
@@ -92,7 +94,8 @@ class _NCHWAdjoint:
             t_in = self.pool[self.dae.total] if p == self.dae.total else self.fused['fused_up%d' % (p + 1)]
             ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *self.gv['up_conv%d' % p], pad=1,
                            mma=self.dae.wgrad)
-        return ops.depool_bwd(self.bwd['up_conv%d' % p](g_c), mpre, mpool)
+        g_u = self.dae._dgrad16('up_conv%d' % p, g_c) if self.d16 else self.bwd['up_conv%d' % p](g_c)
+        return ops.depool_bwd(g_u, mpre, mpool)
 
     def encoder(self, p, gp, acc, window, want_data):
         """gp (the gradient w.r.t. pool_p) through max-pool + ReLU and conv_p: + acc (the skip's share, summed in
@@ -109,6 +112,10 @@ class _NCHWAdjoint:
             ops.conv_wgrad(self.pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch, mma=self.dae.wgrad)
         if not want_data:
             return None
+        if self.d16:
+            if window is not None:
+                raise NotImplementedError("dgrad='bf16': the pad-100 first layer's window stays on the fp32 path")
+            return self.dae._dgrad16(name, g_z, acc)
         conv = self.bwd[name]
         if acc is not None:
             return conv(g_z, add=acc, out=acc)
@@ -176,7 +183,8 @@ class StandardDAE:
     def __init__(self, params, n_classes, concat_h=('pool4',), padding=100, n_filters=64,
                  conv_before_pool=1, additional_pool=2, skip=True, unpool_type='trackind', bn=0,
                  device='cuda', dtype=torch.float32, pad_multi_concat=False, noise=0.0,
-                 dropout=0.0, emulate_noise=False, seed=0, mma=None, trainable=False, wgrad='f32'):
+                 dropout=0.0, emulate_noise=False, seed=0, mma=None, trainable=False, wgrad='f32',
+                 dgrad='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; ops.Conv).
         trainable=True: the parameters live in ONE flat buffer in `param_order` (W then b per layer), every
@@ -184,7 +192,11 @@ class StandardDAE:
         them again in place after an optimizer step.
         wgrad: operand precision of `backward`'s 3x3 weight gradients ('f32' default; 'bf16' = operands rounded
         to bf16 for v_mfma_f32_32x32x16_bf16, fp32 accumulation -- float32 trainable modules only; the forward,
-        the data gradients, the parameters and db stay float32: DESIGN.md section 15)."""
+        the data gradients, the parameters and db stay float32: DESIGN.md section 15).
+        dgrad: operand precision of `backward`'s 3x3 data gradients ('f32' default: the fp32 flipped-filter layers;
+        'bf16' = ops.conv_dgrad on the parameters themselves, W and g_z rounded once to bf16, fp32 accumulation --
+        float32 trainable modules only; the forward, `backward_y`, the parameters and the masks stay float32:
+        DESIGN.md section 16)."""
         concat_h = list(concat_h)
         mma = mma or ops.DEFAULT_MMA
         self.trainable = bool(trainable)
@@ -194,6 +206,13 @@ class StandardDAE:
             raise NotImplementedError("wgrad='bf16': the 16-bit weight gradient of a trainable float32 module "
                                       "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
         self.wgrad = wgrad
+        if dgrad not in ops.DGRAD_MODES:
+            raise ValueError("dgrad=%r is not one of %s" % (dgrad, ops.DGRAD_MODES))
+        if dgrad == 'bf16' and not (trainable and dtype == torch.float32):
+            raise NotImplementedError("dgrad='bf16': the 16-bit data gradient of a trainable float32 module "
+                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
+        self.dgrad = dgrad
+        self._dpack, self._dpack_fresh = {}, set()       # dgrad='bf16': {name: bf16 filter image}, those up to date
         self.flat, self._params, self._tsaved = None, None, None
         if trainable:
             if conv_before_pool != 1 or bn or dropout > 0 or unpool_type not in ('trackind', 'inverse'):
@@ -902,10 +921,27 @@ class StandardDAE:
         out.update({k: v for k, v in self._tsaved[2].items() if k.startswith('fused_up')})
         return out
 
+    def _dgrad16(self, name, gz, acc=None):
+        """dgrad='bf16': the data gradient of layer `name` for g_z (+ acc, in place) by ops.conv_dgrad on the
+        layer's own parameter -- after a concat the feature channels only: h is a constant.  The bf16 image of the
+        filter is packed on first use after `refresh()`, into the buffer it already has."""
+        conv = self.enc[name] if name in self.enc else self.dec[name]
+        cin = conv.Cin
+        if name in self.enc:
+            p = int(name[4:].split('_')[0])
+            cin = self.n_classes if p == 1 else self.enc['conv%d_1' % (p - 1)].Cout
+        ci0 = conv.Cin - cin
+        if name not in self._dpack_fresh:
+            self._dpack[name] = ops.conv_dgrad_pack(conv.W, tuple(gz.shape), ci0, cin, conv.layout,
+                                                    out=self._dpack.get(name))
+            self._dpack_fresh.add(name)
+        return ops.conv_dgrad(gz, conv.W, ci0=ci0, cin=cin, layout=conv.layout, out=acc, accumulate=acc is not None,
+                              packed=self._dpack[name])
+
     def backward(self, g_score):
         """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
         g_score, after `forward_train`: `_adjoint_walk` with ops.conv_wgrad at every layer.  The data gradient
-        of the first layer is not formed."""
+        of the first layer is not formed.  dgrad='bf16': the data gradients by ops.conv_dgrad (`_dgrad16`)."""
         self._need_trainable('backward')
         if self._tsaved is None or self._saved is None:
             raise RuntimeError('backward() needs forward_train() first')
@@ -925,6 +961,7 @@ class StandardDAE:
                 self._bwd[name].W.copy_(Wt)
             for conv in self._bwd.values():
                 conv.refresh()
+        self._dpack_fresh.clear()
         self._store = None
         self._scratch_sessions.clear()
 

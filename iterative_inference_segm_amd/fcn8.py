@@ -23,6 +23,7 @@ PARAM_ORDER = ['conv1_1', 'conv1_2', 'conv2_1', 'conv2_2', 'conv3_1', 'conv3_2',
 
 _BLOCKS = [('conv1_1', 'conv1_2'), ('conv2_1', 'conv2_2'), ('conv3_1', 'conv3_2', 'conv3_3'),
            ('conv4_1', 'conv4_2', 'conv4_3'), ('conv5_1', 'conv5_2', 'conv5_3')]
+_NAMES_3X3 = frozenset(n for names in _BLOCKS for n in names)
 
 
 _UID = itertools.count(1)   # identity of a net in the provenance tags (never reused, unlike id())
@@ -30,7 +31,8 @@ _UID = itertools.count(1)   # identity of a net in the provenance tags (never re
 
 class FCN8:
     def __init__(self, params, n_classes, layer=('probs_dimshuffle',), pad=100, temperature=1.0,
-                 device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5, wgrad='f32'):
+                 device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5, wgrad='f32',
+                 dgrad='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; 'bf16c8' = additionally bf16 C8
         activations between the 3x3 layers, the h maps handed out stay fp32 NCHW; ops.Conv).
@@ -42,7 +44,11 @@ class FCN8:
         wgrad: operand precision of `backward`'s thirteen 3x3 weight gradients ('f32' default; 'bf16' = operands
         rounded to bf16 for v_mfma_f32_32x32x16_bf16, fp32 accumulation -- float32 trainable modules only; fc6,
         fc7, the score and transposed layers, the forward and the data gradients stay float32: DESIGN.md
-        section 15)."""
+        section 15).
+        dgrad: operand precision of `backward`'s twelve 3x3 data gradients ('f32' default: the fp32 flipped-filter
+        layers; 'bf16' = ops.conv_dgrad on the parameters themselves, W and g_z rounded once to bf16, fp32
+        accumulation, the ReLU gate that follows inside a block in the same launch -- float32 trainable modules
+        only; fc6, fc7, the score and transposed layers and the forward stay float32: DESIGN.md section 16)."""
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
         if wgrad not in ops.WGRAD_MODES:
@@ -51,6 +57,13 @@ class FCN8:
             raise NotImplementedError("wgrad='bf16': the 16-bit weight gradient of a trainable float32 module "
                                       "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
         self.wgrad = wgrad
+        if dgrad not in ops.DGRAD_MODES:
+            raise ValueError("dgrad=%r is not one of %s" % (dgrad, ops.DGRAD_MODES))
+        if dgrad == 'bf16' and not (trainable and dtype == torch.float32):
+            raise NotImplementedError("dgrad='bf16': the 16-bit data gradient of a trainable float32 module "
+                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
+        self.dgrad = dgrad
+        self._dpack, self._dpack_fresh = {}, set()       # dgrad='bf16': {name: bf16 filter image}, those up to date
         self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
         if trainable:
             # refused here, before any device work
@@ -361,9 +374,9 @@ class FCN8:
 
     def _flipped_filters(self):
         """(name, filter) of every layer's backward-data conv (conv1_1 has none): the channel-transposed,
-        spatially flipped filter."""
+        spatially flipped filter.  dgrad='bf16': of the K x K and 1 x 1 layers only."""
         for name in PARAM_ORDER[1:]:
-            if name in self.convs:
+            if name in self.convs and not (self.dgrad == 'bf16' and name in _NAMES_3X3):
                 yield name, self.convs[name].W.transpose(0, 1).flip(2, 3)
 
     def _bwd_convs(self):
@@ -387,7 +400,8 @@ class FCN8:
         gradient) and the five blocks (ops.pool_relu_bwd at a block's last convolution, ops.relu_gate at the
         others, ops.conv_wgrad and the flipped-filter convolution).  pool4 and pool3 receive two gradients: the
         main path's (conv5_1's / conv4_1's data gradient) comes first, the side branch's is added to it, placed at
-        the centre window's offset.  conv1_1's data gradient is not formed."""
+        the centre window's offset.  conv1_1's data gradient is not formed.  dgrad='bf16': the twelve 3x3 data gradients by
+        ops.conv_dgrad (`_dgrad16`), the ops.relu_gate that follows one inside a block as its `gate`."""
         self._need_trainable('backward')
         s = self._tsaved
         if s is None:
@@ -420,16 +434,35 @@ class FCN8:
                 sname, gz = side[pname]
                 oy, ox = s['win_' + sname][:2]
                 bwd[sname](gz, add=g, add_off=(oy, ox), out=g, place=(oy, ox))   # main first, + the side branch
+            gated = False                                # g already carries this layer's ReLU gate (dgrad='bf16')
             for ni in range(len(names) - 1, -1, -1):
                 name = names[ni]
                 if ni == len(names) - 1:
                     gz = ops.pool_relu_bwd(g, s[name], s[pname])
+                elif gated:
+                    gz = g
                 else:
                     gz = ops.relu_gate(g, s[name], dst=g)
                 ops.conv_wgrad(s['in_' + name], gz, *gv[name], pad=self.convs[name].pad, mma=self.wgrad)
-                if bi or ni:
+                if not (bi or ni):
+                    continue
+                if self.dgrad == 'bf16':                 # with the gate of the block's previous layer, if any
+                    g = self._dgrad16(name, gz, s[names[ni - 1]] if ni else None)
+                    gated = ni > 0
+                else:
                     g = bwd[name](gz)
         return gv
+
+    def _dgrad16(self, name, gz, gate):
+        """dgrad='bf16': the data gradient of the 3x3 layer `name` for g_z by ops.conv_dgrad on the layer's own
+        parameter, times [gate > 0].  The bf16 image of the filter is packed on first use after `refresh()`, into
+        the buffer it already has."""
+        conv = self.convs[name]
+        if name not in self._dpack_fresh:
+            self._dpack[name] = ops.conv_dgrad_pack(conv.W, tuple(gz.shape), 0, conv.Cin, conv.layout,
+                                                    out=self._dpack.get(name))
+            self._dpack_fresh.add(name)
+        return ops.conv_dgrad(gz, conv.W, layout=conv.layout, gate=gate, packed=self._dpack[name])
 
     def refresh(self):
         """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into the
@@ -445,6 +478,7 @@ class FCN8:
                 self._bwd[name].W.copy_(Wt)
             for conv in self._bwd.values():
                 conv.refresh()
+        self._dpack_fresh.clear()
         self._border = {}
 
 

@@ -2152,6 +2152,97 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
         _add_bytes(kern, float(dW.element_size()) * (x.numel() + gz.numel() + 2 * n))
 
 
+# ---- data gradients on the 16-bit matrix pipe (csrc/conv_dgrad_bf16.hip) ----
+DGRAD_MODES = ('f32', 'bf16')
+
+
+def conv_dgrad_desc(gz_shape, Wshape, ci0=0, cin=None, layout='oihw', accumulate=False):
+    """The iiseg_conv_dgrad_desc of the pad-1 3x3 layer with parameter `Wshape` stored as `layout`, for g_z
+    (B,Cout,H,W) and the input channels [ci0, ci0 + cin) (default: all from ci0 on)."""
+    B, Cout, H, W = (int(v) for v in gz_shape)
+    Cin_tot, Co, K, so, sc = _param_strides(Wshape, layout)
+    d = _lib.ConvDgradDesc()
+    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin_tot - int(ci0) if cin is None else int(cin), Cout, H, W, K, 1
+    d.ci0, d.Cin_tot, d.accumulate = int(ci0), Cin_tot, int(bool(accumulate))
+    d.so, d.sc = so, sc
+    return d
+
+
+def _dgrad_args(gz, W, layout, what):
+    """What conv_dgrad and conv_dgrad_pack refuse before the library is called."""
+    for name, t in (('gz', gz), ('W', W)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise ValueError('%s: %s must be a float32 tensor (got %s)'
+                             % (what, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if layout not in ('oihw', 'iohw'):
+        raise ValueError('%s: layout %r' % (what, layout))
+    if W.dim() != 4 or tuple(W.shape[2:]) != (3, 3):
+        raise ValueError('%s: W %s is not a 3x3 parameter' % (what, tuple(W.shape)))
+
+
+def conv_dgrad_pack(W, gz_shape, ci0=0, cin=None, layout='oihw', out=None):
+    """The bf16 image of the input channels [ci0, ci0 + cin) of the fp32 3x3 parameter W (read in place: the flip
+    and the transpose are indices) that conv_dgrad multiplies by; into `out` (a bfloat16 tensor of the size a
+    previous call returned: the address stays) or a new tensor.  One small launch; again whenever W has changed."""
+    _dgrad_args(None, W, layout, 'conv_dgrad_pack')
+    d = conv_dgrad_desc(gz_shape, tuple(W.shape), ci0, cin, layout)
+    n = _count(_lib.load().iiseg_conv_dgrad_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_bf16_pack_elems')
+    if out is None:
+        out = torch.empty(n, dtype=torch.bfloat16, device=W.device)
+    elif out.dtype != torch.bfloat16 or out.numel() != n:
+        raise ValueError('conv_dgrad_pack: out holds %d %s elements, the image %d bfloat16' % (out.numel(), out.dtype, n))
+    kern = 'conv_dgrad_bf16_pack_kernel'
+    _launch(kern, 0.0, _lib.load().iiseg_conv_dgrad_bf16_pack, C.byref(d), _ptr(W), _ptr(out, torch.bfloat16))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, 4.0 * d.Cout * d.Cin * 9 + 2.0 * n)
+    return out
+
+
+def conv_dgrad(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=False, gate=None, packed=None):
+    """The data gradient of the zero-padded 3x3 stride-1 pad-1 layer with fp32 parameter W, on the 16-bit matrix
+    pipe (csrc/conv_dgrad_bf16.hip): gx[b,ci,y,x] = sum_{co,ky,kx} bf16(W[co,ci0+ci,ky,kx]) bf16(gz[b,co,y+1-ky,
+    x+1-kx]), every operand rounded once (nearest, ties to even), fp32 accumulation in a fixed order by
+    v_mfma_f32_32x32x16_bf16.  gz (B,Cout,H,W) = dL/dout with the ReLU mask applied.  ci0, cin: the slice of W's
+    input channels whose gradient is formed (a concat layer's goes to the features only).  out: the destination
+    (B,cin,H,W); accumulate=True adds to what it holds (it must be given).  gate: a map of gx's shape -- the result
+    is gx * [gate > 0], relu'(0) = 0.  packed: what conv_dgrad_pack returned for this W, slice and layout (default:
+    packed here, one more launch).  float32 tensors only."""
+    _dgrad_args(gz, W, layout, 'conv_dgrad')
+    for name, t in (('out', out), ('gate', gate)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise ValueError('conv_dgrad: %s must be a float32 tensor (got %s)'
+                             % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if packed is not None and (not torch.is_tensor(packed) or packed.dtype != torch.bfloat16):
+        raise ValueError('conv_dgrad: packed must be the bfloat16 tensor of conv_dgrad_pack')
+    if accumulate and out is None:
+        raise ValueError('conv_dgrad: accumulate=True needs the map to add to (out=)')
+    if gz.dim() != 4:
+        raise ValueError('conv_dgrad: gz %s is not (B, Cout, H, W)' % (tuple(gz.shape),))
+    d = conv_dgrad_desc(tuple(gz.shape), tuple(W.shape), ci0, cin, layout, accumulate)
+    Cout_w = W.shape[0] if layout == 'oihw' else W.shape[1]
+    if gz.shape[1] != Cout_w or d.Cin < 1 or d.ci0 < 0 or d.ci0 + d.Cin > d.Cin_tot:
+        raise ValueError('conv_dgrad: gz %s, W %s (%s), input channels [%d, %d)'
+                         % (tuple(gz.shape), tuple(W.shape), layout, d.ci0, d.ci0 + d.Cin))
+    shape = (d.B, d.Cin, d.H, d.W)
+    for name, t in (('out', out), ('gate', gate)):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError('conv_dgrad: %s %s, the gradient is %s' % (name, tuple(t.shape), shape))
+    n = _count(_lib.load().iiseg_conv_dgrad_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_bf16_pack_elems')
+    if packed is None:
+        packed = conv_dgrad_pack(W, tuple(gz.shape), ci0, cin, layout)
+    elif packed.numel() != n:
+        raise ValueError('conv_dgrad: packed holds %d elements, the image of this slice %d' % (packed.numel(), n))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=gz.device)
+    kern = 'conv_dgrad_bf16_kernel'
+    _launch(kern, 2.0 * d.Cin * d.Cout * 9 * d.B * d.H * d.W, _lib.load().iiseg_conv_dgrad_bf16, C.byref(d), _ptr(gz),
+            _ptr(packed, torch.bfloat16), _ptr(gate), _ptr(out))
+    if CONV_PROFILE is not None:
+        # byte model: g_z and the image read once, gx written once (read once more when it is added to), the gate read
+        _add_bytes(kern, 4.0 * gz.numel() + 2.0 * n + 4.0 * out.numel() * (1 + int(bool(accumulate)) + (gate is not None)))
+    return out
+
+
 # ---- true-gradient refinement through the context-module DAE (csrc/ctx_grad.hip, DESIGN.md section 10) ----
 def _param_strides(Wshape, layout):
     """(Cin, Cout, K, so, sc) of a layer parameter in its own layout."""

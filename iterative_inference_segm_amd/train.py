@@ -27,11 +27,21 @@ def check_wgrad(wgrad, dtype):
                                   'be float32 (got %s)' % (dtype,))
 
 
+def check_dgrad(dgrad, dtype):
+    """The data-gradient mode of a run (host only): 'f32', or 'bf16' with float32."""
+    if dgrad not in ops.DGRAD_MODES:
+        raise ValueError('dgrad must be one of %s (got %r)' % (', '.join(ops.DGRAD_MODES), dgrad))
+    if dgrad == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
+        raise NotImplementedError("dgrad='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
+                                  'be float32 (got %s)' % (dtype,))
+
+
 def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
-                    optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32'):
+                    optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32', dgrad='f32'):
     """Raises NotImplementedError / ValueError with the reason for everything this slice does not train
     (host only: callable before any GPU work).  dae_dict: the standard kind's options (concat_h, bn, dropout,
-    conv_before_pool, unpool_type).  wgrad, dtype: the weight-gradient mode and the run's precision."""
+    conv_before_pool, unpool_type).  wgrad, dgrad, dtype: the weight- and data-gradient modes and the run's
+    precision."""
     if kind not in ('contextmod', 'standard'):
         raise NotImplementedError("training is built for dae kinds 'contextmod' and 'standard' (got %r): the "
                                   'fcn8 kind (strided 4x4 transposed convolutions) has no weight-gradient '
@@ -40,6 +50,10 @@ def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=Fal
     if wgrad == 'bf16' and kind == 'contextmod':
         raise NotImplementedError("wgrad='bf16' is the zero-padded 3x3 weight gradient of dae kind 'standard' and "
                                   "of FCN-8: the context module's 11-channel gradient kernels stay float32")
+    check_dgrad(dgrad, dtype)
+    if dgrad == 'bf16' and kind == 'contextmod':
+        raise NotImplementedError("dgrad='bf16' is the zero-padded 3x3 data gradient of dae kind 'standard' and "
+                                  "of FCN-8: the context module's masked data-gradient kernels stay float32")
     if kind == 'standard':
         dd = dae_dict or {}
         concat_h = list(dd.get('concat_h', ['input']))

@@ -3,7 +3,7 @@
 224x224: one JSON line.
 
     python scripts/bench_train_fcn8.py [--batch 10] [--size 224x224] [--reps 15] [--dtypes float32]
-                                       [--wgrad f32 bf16]
+                                       [--wgrad f32 bf16] [--dgrad f32 bf16]
 
 Per precision: step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, L2 term, adam,
 refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch profile, per
@@ -16,6 +16,14 @@ data-gradient launches.  --width_div / --fc_channels shrink the net.
 --wgrad: the weight-gradient modes to run, one result row each in the same process (bf16: float32 only; the
 thirteen 3x3 layers of its rows are conv_wgrad_bf16_kernel's launches and take their fraction of
 `--peak_tflops_bf16`, 2500; the other layers stay on the fp32 kernels and the fp32 peak).
+--dgrad: the data-gradient modes to run, one result row per (wgrad, dgrad) pair in the same process; a mode may be
+named twice (`--dgrad f32 f32 bf16`: the spread of two runs next to the difference between the modes).  Every row
+lists, for the twelve 3x3 layers behind conv1_1, the data-gradient launch of its mode -- the fp32 flipped-filter
+layer's, or conv_dgrad_bf16_kernel's (with the ReLU gate that follows inside a block) -- with its fraction of the
+mode's peak; the bf16 rows add the yardstick, the existing ops.Conv(..., mma='bf16') forward kernel on the flipped
+filter of that same layer on a map of g_z's shape, and the filter images' pack launches of the step; every row has
+`refresh_ms`, the cost of refresh() (in the fp32 mode it flips, copies and re-packs those filters too).  DESIGN
+section 16.
 """
 import argparse
 import json
@@ -30,15 +38,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from iterative_inference_segm_amd import ops, synthetic as S              # noqa: E402
 from iterative_inference_segm_amd.fcn8 import FCN8, PARAM_ORDER           # noqa: E402
 from iterative_inference_segm_amd.train import FCN8Trainer                # noqa: E402
+from dgrad_bench import launches, layer_rows, marked, yardstick           # noqa: E402
 
 DECONVS = ('upsample', 'score4', 'score2')
 KXK = ('score_pool3', 'score_pool4', 'score_fr', 'fc7', 'fc6')
 
 
 def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, wgrad='f32',
-        peak_bf16=2500.0):
+        peak_bf16=2500.0, dgrad='f32', yard=None):
     params = S.make_fcn8_params(3, 11, seed=1234, width_div=width_div, fc_channels=fc_channels)
-    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad)
+    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad)
     tr = FCN8Trainer(net, 11, [11], learning_rate=1e-4, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
@@ -54,6 +63,13 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
     step = float(np.median(ms))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        net.refresh()
+    e1.record()
+    torch.cuda.synchronize()
+    refresh_ms = e0.elapsed_time(e1) / 5
     # one profiled step: every launch of the library between two marks, in launch order
     prof = []
     ops.KERNEL_BYTES.clear()
@@ -63,7 +79,8 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         score = net.forward_train(X, generator=tr.generator)
         n_fwd = len(prof)
         _, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0)
-        net.backward(g)
+        with marked(net._bwd, prof) as log:
+            net.backward(g)
         if weight_decay > 0:
             ops.l2_term(net.flat, net.gflat, tr.ranges, weight_decay)
         torch.cuda.synchronize()
@@ -118,6 +135,16 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         if n in dgrad_ms:
             row.update(dgrad_ms=round(dgrad_ms[n], 4), dgrad_over_forward=round(dgrad_ms[n] / fwd_ms[n], 3))
         out.append(row)
+    # the twelve 3x3 data gradients, in backward's order (conv1_1's is not formed)
+    dnames = blocks[:-1]
+    if dgrad == 'bf16':
+        dg = [(a.elapsed_time(b), f, k) for k, f, a, b in back if k == 'conv_dgrad_bf16_kernel']
+    else:
+        dg = [launches(prof, i, j) for n, i, j in log if n in dnames]
+        assert [n for n, _, _ in log if n in dnames] == dnames, log
+    if len(dg) != len(dnames):
+        raise RuntimeError('expected %d data-gradient launches, got %d' % (len(dnames), len(dg)))
+    pack_ms = sum(a.elapsed_time(b) for k, _, a, b in back if k == 'conv_dgrad_bf16_pack_kernel')
     elem = []
     for kern in ('relu_gate_kernel', 'l2_term_kernel', 'deconv_dgrad_kernel'):
         t = sum(t for _, t in by(kern))
@@ -130,7 +157,16 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     twc = sum(r['wgrad_ms'] for r in out if r['layer'] in net.convs)
     t3 = sum(r['wgrad_ms'] for r in out if r['layer'] in blocks)
     tf = sum(r['forward_ms'] for r in out if r['layer'] in net.convs)
-    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'batch': B, 'size': '%dx%d' % (H, W),
+    # (the yardstick runs a launch profile of its own: after every figure of the step's has been read)
+    if dgrad == 'bf16' and yard is not None and not yard:
+        yard.update(yardstick(((n, net.convs[n].W.transpose(0, 1).flip(2, 3)) for n in dnames),
+                              {n: tuple(sv[n].shape) for n in dnames}, dt))
+    dlayers = layer_rows(dnames, {n: (t, k) for n, (t, _, k) in zip(dnames, dg)},
+                         {n: f for n, (_, f, _) in zip(dnames, dg)}, peak_bf16 if dgrad == 'bf16' else peak,
+                         yard if dgrad == 'bf16' else None)
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad,
+            'dgrad_3x3_ms_total': round(sum(r['dgrad_ms'] for r in dlayers), 3), 'dgrad_pack_ms': round(pack_ms, 4),
+            'refresh_ms': round(refresh_ms, 4), 'dgrad_layers': dlayers, 'batch': B, 'size': '%dx%d' % (H, W),
             'step_ms': round(step, 3),
             'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 1),
             'parameters': int(net.flat.numel()), 'weights': 'default synthetic (synthetic.make_fcn8_params)',
@@ -147,6 +183,7 @@ def main():
     ap.add_argument('--dtypes', nargs='+', default=['float32'])
     ap.add_argument('--peak_tflops', type=float, default=157.3)
     ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--dgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     ap.add_argument('--stream_gbs', type=float, default=6600.0)
     ap.add_argument('--width_div', type=int, default=1)
@@ -154,9 +191,11 @@ def main():
     ap.add_argument('--weight_decay', type=float, default=1e-4)
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split('x'))
+    yard = {}
     rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.width_div,
-                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16)
-            for name in a.dtypes for mode in a.wgrad if mode == 'f32' or name == 'float32']
+                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16, dmode, yard)
+            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad
+            if (mode == 'f32' and dmode == 'f32') or name == 'float32']
     print(json.dumps({'bench': 'train_fcn8', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
                       'peak_tflops_bf16': a.peak_tflops_bf16,
                       'stream_gbs': a.stream_gbs, 'reps': a.reps, 'results': rows}))

@@ -18,6 +18,8 @@ All arithmetic runs in the HIP kernels of libiiseg_hip.so.
 matrix pipe from operands rounded once to bf16; the forward, the data gradients, the parameters, the optimizer
 state and the checkpoints stay float32, so the experiment folder keeps its name (config.txt records the mode).
 With `--dtype float64` or kind 'contextmod' it is refused before any GPU work.
+`--dgrad bf16` (the same conditions and refusals) forms the 3x3 data gradients of the backward
+pass on the 16-bit matrix pipe from the parameters and g_z rounded once to bf16; config.txt records it as well.
 """
 import argparse
 import json
@@ -48,10 +50,12 @@ def _json_dict(s):
     return json.loads(s) if isinstance(s, str) else s
 
 
-def check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad='f32', dtype='float32'):
+def check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad='f32', dtype='float32',
+                    dgrad='f32'):
     """Everything this build does not train, refused with the reason (host only)."""
     from iterative_inference_segm_amd.train import check_supported as chk
-    chk(dae_dict['kind'], training_loss, ae_h, full_im_ft, optimizer, dae_dict=dae_dict, wgrad=wgrad, dtype=dtype)
+    chk(dae_dict['kind'], training_loss, ae_h, full_im_ft, optimizer, dae_dict=dae_dict, wgrad=wgrad, dtype=dtype,
+        dgrad=dgrad)
     if dae_dict['kind'] == 'contextmod' and list(dae_dict['concat_h']) != ['input']:
         raise NotImplementedError("the context module concatenates the image: concat_h must be ['input']")
 
@@ -95,18 +99,19 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
           max_patience=100, optimizer='rmsprop', training_loss=['squared_error'], batch_size=[10, 1, 1],
           ae_h=False, dae_dict_updates={}, data_augmentation={}, savepath=None, loadpath=None, resume=False,
           train_from_0_255=False, lmb=1, full_im_ft=False, weights_path=None, synthetic=False, n_images=20,
-          image_size=None, seed=0, dtype='float32', wgrad='f32', verbose=True):
+          image_size=None, seed=0, dtype='float32', wgrad='f32', dgrad='f32', verbose=True):
     """Signature of reference train_dae.py:54-60 plus keyword-only extras.  weight_decay only enters the
     experiment name, as in the reference (train_dae.py:91: no regulariser is added to the loss).  wgrad (kind
     'standard': 'f32' | 'bf16', the 3x3 weight gradients' operand precision) is recorded in config.txt and stays
-    out of the experiment name: the checkpoints are float32 either way.  Returns the
+    out of the experiment name: the checkpoints are float32 either way; dgrad (the 3x3 data gradients') likewise.
+    Returns the
     per-epoch lists (err_train, err_valid, jacc_val, mse_val) and the experiment folder."""
     dae_dict = {'kind': 'fcn8', 'dropout': 0.0, 'skip': True, 'unpool_type': 'standard', 'n_filters': 64,
                 'conv_before_pool': 1, 'additional_pool': 0, 'concat_h': ['input'], 'noise': 0.0,
                 'from_gt': True, 'temperature': 1.0, 'path_weights': '', 'layer': 'probs_dimshuffle',
                 'exp_name': '', 'bn': 0}                                                  # :65-79
     dae_dict.update(dae_dict_updates)
-    check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad, dtype)
+    check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad, dtype, dgrad)
     if dataset not in ('camvid', 'polyps912', 'em'):
         raise ValueError('Unknown dataset')
     if segm_net == 'fcn_fcresnet':
@@ -134,7 +139,7 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
                                       training_loss=training_loss, batch_size=batch_size, dae_dict=dae_dict,
                                       data_augmentation=data_augmentation, resume=resume, lmb=lmb,
                                       train_from_0_255=train_from_0_255, seed=seed, dtype=dtype,
-                                      wgrad=wgrad).items()):
+                                      wgrad=wgrad, dgrad=dgrad).items()):
             f.write('{} = {}\n'.format(key, value))
 
     # ---- from here on: the GPU ----
@@ -179,7 +184,7 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
                                        seed=4321 + int(seed), **arch)
         dae = StandardDAE(params, n_classes, padding=100, n_filters=dae_dict['n_filters'],
                           skip=dae_dict['skip'], noise=dae_dict['noise'], dtype=tdt, mma='f32', trainable=True,
-                          wgrad=wgrad, **arch)
+                          wgrad=wgrad, dgrad=dgrad, **arch)
     else:
         order = PARAM_ORDER
         if resume:
@@ -300,6 +305,10 @@ def make_parser():
                         help="kind 'standard', float32: operand precision of the 3x3 weight gradients (bf16: "
                              'v_mfma_f32_32x32x16_bf16 on operands rounded once, fp32 accumulation; everything '
                              'else stays float32).  Recorded in config.txt, not in the experiment name')
+    parser.add_argument('--dgrad', choices=['f32', 'bf16'], default='f32',
+                        help="kind 'standard', float32: operand precision of the backward pass's 3x3 data gradients "
+                             '(bf16: v_mfma_f32_32x32x16_bf16 on the parameters and g_z rounded once, fp32 '
+                             'accumulation).  Recorded in config.txt, not in the experiment name')
     return parser
 
 
@@ -319,7 +328,7 @@ def main(argv=None):
     args, train_dict, dae_dict = parse_args(argv)
     try:
         check_supported(dae_dict, train_dict['training_loss'], args.ae_h, train_dict.get('full_im_ft', False),
-                        train_dict['optimizer'], args.wgrad, args.dtype)
+                        train_dict['optimizer'], args.wgrad, args.dtype, args.dgrad)
     except (NotImplementedError, ValueError) as e:
         print('train_dae.py: ' + str(e), file=sys.stderr)
         return 2
@@ -327,7 +336,7 @@ def main(argv=None):
           data_augmentation=args.data_augmentation, train_from_0_255=args.train_from_0_255, resume=args.resume,
           savepath=args.savepath, loadpath=args.loadpath, weights_path=args.weights_path,
           synthetic=args.synthetic, n_images=args.n_images, image_size=args.image_size, seed=args.seed,
-          dtype=args.dtype, wgrad=args.wgrad, **train_dict)
+          dtype=args.dtype, wgrad=args.wgrad, dgrad=args.dgrad, **train_dict)
     return 0
 
 

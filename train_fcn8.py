@@ -26,6 +26,8 @@ work.  All arithmetic runs in the HIP kernels of libiiseg_hip.so (DESIGN.md sect
 16-bit matrix pipe from operands rounded once to bf16; fc6, fc7, the score and transposed layers, the forward, the
 data gradients, the parameters, adam's state and the checkpoints stay float32, so the experiment folder keeps its
 name (config.txt records the mode).  With `--dtype float64` it is refused like the rest.
+`--dgrad bf16` (the same conditions) forms the twelve 3x3 data gradients of the backward pass on
+the 16-bit matrix pipe from the parameters and g_z rounded once to bf16; config.txt records it as well.
 """
 import argparse
 import json
@@ -73,9 +75,10 @@ def one_hot_void_last(L, n_classes):
 
 
 def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size=(10, 1, 1), num_epochs=1,
-                    max_patience=1, learning_rate=1e-4, weight_decay=0.0, early_stop_class=None, wgrad='f32'):
+                    max_patience=1, learning_rate=1e-4, weight_decay=0.0, early_stop_class=None, wgrad='f32',
+                    dgrad='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
-    from iterative_inference_segm_amd.train import check_wgrad
+    from iterative_inference_segm_amd.train import check_dgrad, check_wgrad
     if savepath is None:
         raise ValueError('A saving directory must be specified')                        # train_fcn8.py:55-56
     if pascal:
@@ -85,6 +88,7 @@ def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size
     if dtype not in ('float32', 'float64'):
         raise NotImplementedError('training FCN-8: float32 or float64; the 16-bit legs are not trained')
     check_wgrad(wgrad, dtype)
+    check_dgrad(dgrad, dtype)
     if not (isinstance(batch_size, (list, tuple)) and len(batch_size) == 3 and all(int(b) >= 1 for b in batch_size)):
         raise ValueError('batch_size must be [train, val, test], each >= 1')
     if int(num_epochs) < 1 or int(max_patience) < 1:
@@ -98,13 +102,14 @@ def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size
 def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_patience=100, data_augmentation={},
           savepath=None, loadpath=None, early_stop_class=None, batch_size=None, resume=False,
           train_from_0_255=False, synthetic=False, n_images=20, image_size=None, seed=0, dtype='float32',
-          width_div=1, fc_channels=4096, max_batches=None, wgrad='f32', verbose=True):
+          width_div=1, fc_channels=4096, max_batches=None, wgrad='f32', dgrad='f32',
+          verbose=True):
     """Signature of reference train_fcn8.py:41-48 plus keyword-only extras.  wgrad ('f32' | 'bf16': the 3x3 weight
     gradients' operand precision) is recorded in config.txt and stays out of the experiment name: the checkpoints
-    are float32 either way.  Returns the per-epoch lists and the experiment folder."""
+    are float32 either way; dgrad (the 3x3 data gradients') likewise.  Returns the per-epoch lists and the experiment folder."""
     bs = list(batch_size) if batch_size is not None else [10, 1, 1]                     # :84-87
     check_supported(dataset, savepath, False, dtype, bs, num_epochs, max_patience, learn_step, weight_decay,
-                    early_stop_class, wgrad)
+                    early_stop_class, wgrad, dgrad)
     exp_name = experiment_name(data_augmentation)
     loadpath = loadpath if loadpath is not None else savepath
     savepath = os.path.join(savepath, dataset, exp_name)
@@ -118,7 +123,7 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
                                       data_augmentation=data_augmentation, early_stop_class=early_stop_class,
                                       batch_size=bs, resume=resume, train_from_0_255=train_from_0_255, seed=seed,
                                       dtype=dtype, width_div=width_div, fc_channels=fc_channels,
-                                      wgrad=wgrad).items()):
+                                      wgrad=wgrad, dgrad=dgrad).items()):
             f.write('{} = {}\n'.format(key, value))
 
     # ---- from here on: the GPU ----
@@ -151,7 +156,7 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
         like = S.make_fcn8_params(nb_in_channels, n_classes, seed=1234, width_div=width_div, fc_channels=fc_channels)
         params = glorot_params({n: (like[n][0].shape, like[n][1].shape[0]) for n in PARAM_ORDER}, 4321 + int(seed))
     net = FCN8(params, n_classes, layer=['probs_dimshuffle'], dtype=tdt, mma='f32', trainable=True,
-               wgrad=wgrad)
+               wgrad=wgrad, dgrad=dgrad)
     trainer = FCN8Trainer(net, n_classes, void_labels, learning_rate=learn_step, weight_decay=weight_decay, seed=seed)
 
     def batch(it):
@@ -261,6 +266,10 @@ def make_parser():
                         help='float32: operand precision of the 3x3 weight gradients (bf16: v_mfma_f32_32x32x16_bf16 '
                              'on operands rounded once, fp32 accumulation; everything else stays float32).  Recorded '
                              'in config.txt, not in the experiment name')
+    parser.add_argument('--dgrad', choices=['f32', 'bf16'], default='f32',
+                        help="float32: operand precision of the backward pass's twelve 3x3 data gradients (bf16: "
+                             'v_mfma_f32_32x32x16_bf16 on the parameters and g_z rounded once, fp32 accumulation).  '
+                             'Recorded in config.txt, not in the experiment name')
     parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
     parser.add_argument('--width_div', type=int, default=1, help='divide the channel counts (small nets for tests)')
     parser.add_argument('--fc_channels', type=int, default=4096)
@@ -278,7 +287,8 @@ def main(argv=None):
     args = parse_args(argv)
     try:
         check_supported(args.dataset, args.savepath, args.pascal, args.dtype, args.batch_size, args.num_epochs,
-                        args.max_patience, args.learning_rate, args.penal_cst, args.early_stop_class, args.wgrad)
+                        args.max_patience, args.learning_rate, args.penal_cst, args.early_stop_class, args.wgrad,
+                        args.dgrad)
     except (NotImplementedError, ValueError, TypeError) as e:
         print('train_fcn8.py: ' + str(e), file=sys.stderr)
         return 2
@@ -287,7 +297,8 @@ def main(argv=None):
           early_stop_class=args.early_stop_class, savepath=args.savepath, loadpath=args.loadpath,
           resume=args.resume, train_from_0_255=args.train_from_0_255, synthetic=args.synthetic,
           n_images=args.n_images, image_size=args.image_size, seed=args.seed, dtype=args.dtype,
-          width_div=args.width_div, fc_channels=args.fc_channels, max_batches=args.max_batches, wgrad=args.wgrad)
+          width_div=args.width_div, fc_channels=args.fc_channels, max_batches=args.max_batches, wgrad=args.wgrad,
+          dgrad=args.dgrad)
     return 0
 
 
