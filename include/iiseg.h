@@ -1177,6 +1177,40 @@ int iiseg_conv_dgrad_bf16_pack(void* stream, const iiseg_conv_dgrad_desc* d, con
 int iiseg_conv_dgrad_bf16(void* stream, const iiseg_conv_dgrad_desc* d, const float* gz, const void* packed,
                           const float* gate, float* gx);
 
+/* ---------------------------------------------------------------------------------------
+ * 'valid' K x K layers on the 16-bit matrix pipe (kxk='bf16'; csrc/conv_kxk_bf16.hip; DESIGN.md section 17;
+ * backward-compatible addition).  1 <= K <= 7, stride 1, fp32 tensors; every operand is rounded once (to nearest,
+ * ties to even) as it is staged, v_mfma_f32_32x32x16_bf16 accumulates in fp32 in a fixed order, the slabs of a split
+ * reduction are added in slab order: no atomics, the same inputs give the same bits.
+ *
+ * Weight gradient, on iiseg_conv_wgrad_kxk_desc with the operands of iiseg_conv_wgrad_kxk_f32:
+ *   dW[co][ci0 + ci][ky][kx] = sum_{b,y,x} bf16(gz[b,co,y,x]) bf16(x[b,ci,y + ky,x + kx]),   db = the fp32 sum of the
+ *   unrounded gz.  ws: iiseg_conv_wgrad_kxk_bf16_workspace_elems(d) floats (0 with one slab).
+ *
+ * Data gradient, on iiseg_conv_dgrad_desc with (H, W) the planes of gz and `pad` ignored:
+ *   gx[b][ci][y][x] = sum_{co,ky,kx} bf16(W[co][ci0 + ci][ky][kx]) bf16(gz[b][co][y - ky][x - kx])
+ *   gz     : (B, Cout, H, W) contiguous, zero outside its plane (no embedded copy is made).
+ *   gx     : (B, Cin, H + K - 1, W + K - 1) contiguous; accumulate, gate as iiseg_conv_dgrad_bf16.
+ *   packed : iiseg_conv_dgrad_kxk_bf16_pack_elems(d) bf16 elements, 16-byte aligned, written by
+ *            iiseg_conv_dgrad_kxk_bf16_pack from the layer's own parameter ([k-tile of 16 co][tap][co chunk of 8][ci,
+ *            padded to 64][8 co], zero past Cout and Cin).  Pack again whenever W has changed.
+ *   ws     : iiseg_conv_dgrad_kxk_bf16_workspace_elems(d) floats (0 with one slab of output channels).
+ * Statuses as the fp32 / 3x3 siblings: NULL pointers IISEG_ERR_NULL, shapes and strides IISEG_ERR_SHAPE, alignment
+ * IISEG_ERR_ALIGN, gx overlapping gz or packed, packed overlapping W IISEG_ERR_UNSUPPORTED; all before any launch.
+ * ------------------------------------------------------------------------------------- */
+int iiseg_conv_wgrad_kxk_bf16_check(const iiseg_conv_wgrad_kxk_desc* d);
+int iiseg_conv_wgrad_kxk_bf16_slabs(const iiseg_conv_wgrad_kxk_desc* d);
+int64_t iiseg_conv_wgrad_kxk_bf16_workspace_elems(const iiseg_conv_wgrad_kxk_desc* d);
+int iiseg_conv_wgrad_kxk_bf16(void* stream, const iiseg_conv_wgrad_kxk_desc* d, const float* x, const float* gz,
+                              float* ws, float* dW, float* db);
+int iiseg_conv_dgrad_kxk_bf16_check(const iiseg_conv_dgrad_desc* d);
+int iiseg_conv_dgrad_kxk_bf16_slabs(const iiseg_conv_dgrad_desc* d);
+int64_t iiseg_conv_dgrad_kxk_bf16_workspace_elems(const iiseg_conv_dgrad_desc* d);
+int64_t iiseg_conv_dgrad_kxk_bf16_pack_elems(const iiseg_conv_dgrad_desc* d);
+int iiseg_conv_dgrad_kxk_bf16_pack(void* stream, const iiseg_conv_dgrad_desc* d, const float* W, void* packed);
+int iiseg_conv_dgrad_kxk_bf16(void* stream, const iiseg_conv_dgrad_desc* d, const float* gz, const void* packed,
+                              const float* gate, float* ws, float* gx);
+
 #ifdef __cplusplus
 }
 #endif

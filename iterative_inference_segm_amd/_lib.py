@@ -307,6 +307,16 @@ SIGNATURES = {
     'iiseg_conv_dgrad_bf16_pack_elems': (_i64, [C.POINTER(ConvDgradDesc)]),
     'iiseg_conv_dgrad_bf16_pack': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 2),
     'iiseg_conv_dgrad_bf16': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 4),
+    'iiseg_conv_wgrad_kxk_bf16_check': (C.c_int, [C.POINTER(ConvWgradKxKDesc)]),
+    'iiseg_conv_wgrad_kxk_bf16_slabs': (C.c_int, [C.POINTER(ConvWgradKxKDesc)]),
+    'iiseg_conv_wgrad_kxk_bf16_workspace_elems': (_i64, [C.POINTER(ConvWgradKxKDesc)]),
+    'iiseg_conv_wgrad_kxk_bf16': (C.c_int, [_vp, C.POINTER(ConvWgradKxKDesc)] + [_vp] * 5),
+    'iiseg_conv_dgrad_kxk_bf16_check': (C.c_int, [C.POINTER(ConvDgradDesc)]),
+    'iiseg_conv_dgrad_kxk_bf16_slabs': (C.c_int, [C.POINTER(ConvDgradDesc)]),
+    'iiseg_conv_dgrad_kxk_bf16_workspace_elems': (_i64, [C.POINTER(ConvDgradDesc)]),
+    'iiseg_conv_dgrad_kxk_bf16_pack_elems': (_i64, [C.POINTER(ConvDgradDesc)]),
+    'iiseg_conv_dgrad_kxk_bf16_pack': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 2),
+    'iiseg_conv_dgrad_kxk_bf16': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 5),
 }
 
 _lib = None

@@ -24,6 +24,7 @@ PARAM_ORDER = ['conv1_1', 'conv1_2', 'conv2_1', 'conv2_2', 'conv3_1', 'conv3_2',
 _BLOCKS = [('conv1_1', 'conv1_2'), ('conv2_1', 'conv2_2'), ('conv3_1', 'conv3_2', 'conv3_3'),
            ('conv4_1', 'conv4_2', 'conv4_3'), ('conv5_1', 'conv5_2', 'conv5_3')]
 _NAMES_3X3 = frozenset(n for names in _BLOCKS for n in names)
+_NAMES_KXK16 = ('fc6', 'fc7')                            # the layers of kxk='bf16'
 
 
 _UID = itertools.count(1)   # identity of a net in the provenance tags (never reused, unlike id())
@@ -32,7 +33,7 @@ _UID = itertools.count(1)   # identity of a net in the provenance tags (never re
 class FCN8:
     def __init__(self, params, n_classes, layer=('probs_dimshuffle',), pad=100, temperature=1.0,
                  device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5, wgrad='f32',
-                 dgrad='f32'):
+                 dgrad='f32', kxk='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; 'bf16c8' = additionally bf16 C8
         activations between the 3x3 layers, the h maps handed out stay fp32 NCHW; ops.Conv).
@@ -48,7 +49,12 @@ class FCN8:
         dgrad: operand precision of `backward`'s twelve 3x3 data gradients ('f32' default: the fp32 flipped-filter
         layers; 'bf16' = ops.conv_dgrad on the parameters themselves, W and g_z rounded once to bf16, fp32
         accumulation, the ReLU gate that follows inside a block in the same launch -- float32 trainable modules
-        only; fc6, fc7, the score and transposed layers and the forward stay float32: DESIGN.md section 16)."""
+        only; fc6, fc7, the score and transposed layers and the forward stay float32: DESIGN.md section 16).
+        kxk: operand precision of `backward`'s weight and data gradients of the two wide 'valid' layers fc6 (7x7)
+        and fc7 (1x1) ('f32' default; 'bf16' = ops.conv_wgrad_kxk(mma='bf16') and ops.conv_dgrad_kxk on the
+        parameters themselves, every operand rounded once to bf16, fp32 accumulation, no flipped fp32 copy of
+        either filter -- float32 trainable modules only; the 11-channel score layers, the transposed layers and
+        the forward stay float32: DESIGN.md section 17).  Independent of wgrad and dgrad."""
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
         if wgrad not in ops.WGRAD_MODES:
@@ -63,7 +69,14 @@ class FCN8:
             raise NotImplementedError("dgrad='bf16': the 16-bit data gradient of a trainable float32 module "
                                       "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
         self.dgrad = dgrad
-        self._dpack, self._dpack_fresh = {}, set()       # dgrad='bf16': {name: bf16 filter image}, those up to date
+        if kxk not in ops.KXK_MODES:
+            raise ValueError("kxk=%r is not one of %s" % (kxk, ops.KXK_MODES))
+        if kxk == 'bf16' and not (trainable and dtype == torch.float32):
+            raise NotImplementedError("kxk='bf16': the 16-bit fc6 / fc7 gradients of a trainable float32 module "
+                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
+        self.kxk = kxk
+        # dgrad='bf16' / kxk='bf16': {name: bf16 filter image}, those up to date
+        self._dpack, self._dpack_fresh = {}, set()
         self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
         if trainable:
             # refused here, before any device work
@@ -374,9 +387,10 @@ class FCN8:
 
     def _flipped_filters(self):
         """(name, filter) of every layer's backward-data conv (conv1_1 has none): the channel-transposed,
-        spatially flipped filter.  dgrad='bf16': of the K x K and 1 x 1 layers only."""
+        spatially flipped filter.  dgrad='bf16': of the K x K and 1 x 1 layers only; kxk='bf16': none of fc6 / fc7."""
         for name in PARAM_ORDER[1:]:
-            if name in self.convs and not (self.dgrad == 'bf16' and name in _NAMES_3X3):
+            if name in self.convs and not (self.dgrad == 'bf16' and name in _NAMES_3X3) and \
+                    not (self.kxk == 'bf16' and name in _NAMES_KXK16):
                 yield name, self.convs[name].W.transpose(0, 1).flip(2, 3)
 
     def _bwd_convs(self):
@@ -401,7 +415,10 @@ class FCN8:
         others, ops.conv_wgrad and the flipped-filter convolution).  pool4 and pool3 receive two gradients: the
         main path's (conv5_1's / conv4_1's data gradient) comes first, the side branch's is added to it, placed at
         the centre window's offset.  conv1_1's data gradient is not formed.  dgrad='bf16': the twelve 3x3 data gradients by
-        ops.conv_dgrad (`_dgrad16`), the ops.relu_gate that follows one inside a block as its `gate`."""
+        ops.conv_dgrad (`_dgrad16`), the ops.relu_gate that follows one inside a block as its `gate`.  kxk='bf16':
+        fc6's and fc7's weight gradients by ops.conv_wgrad_kxk(mma='bf16'), their data gradients by
+        ops.conv_dgrad_kxk on g_z itself (no zero-bordered copy); the dropout adjoint and the ops.relu_gate behind
+        fc7's data gradient stay the launches they are."""
         self._need_trainable('backward')
         s = self._tsaved
         if s is None:
@@ -421,11 +438,15 @@ class FCN8:
             g = ops.deconv_dgrad(g, deconv.W, deconv.stride, s[src].shape[2:], window=win)
         for name, xin, keep in (('score_fr', 'drop7', 'keep7'), ('fc7', 'drop6', 'keep6'), ('fc6', 'in_fc6', None)):
             gz = ops.relu_gate(g, s[name], dst=g)
-            ops.conv_wgrad_kxk(s[xin], gz, *gv[name])
-            if name == 'fc6':
-                K = self.convs[name].KH
-                gz = _embed(gz, (gz.shape[2] + 2 * (K - 1), gz.shape[3] + 2 * (K - 1)), (K - 1, K - 1))
-            g = bwd[name](gz)
+            if self.kxk == 'bf16' and name in _NAMES_KXK16:
+                ops.conv_wgrad_kxk(s[xin], gz, *gv[name], mma='bf16')
+                g = self._dgrad_kxk16(name, gz)
+            else:
+                ops.conv_wgrad_kxk(s[xin], gz, *gv[name])
+                if name == 'fc6':
+                    K = self.convs[name].KH
+                    gz = _embed(gz, (gz.shape[2] + 2 * (K - 1), gz.shape[3] + 2 * (K - 1)), (K - 1, K - 1))
+                g = bwd[name](gz)
             if keep is not None and s[keep] is not None:
                 ops.dropout_apply(g, s[keep], self.dropout)             # dropout's adjoint: the forward's mask
         for bi in range(len(_BLOCKS) - 1, -1, -1):
@@ -463,6 +484,16 @@ class FCN8:
                                                     out=self._dpack.get(name))
             self._dpack_fresh.add(name)
         return ops.conv_dgrad(gz, conv.W, layout=conv.layout, gate=gate, packed=self._dpack[name])
+
+    def _dgrad_kxk16(self, name, gz):
+        """kxk='bf16': the data gradient of the 'valid' layer `name` (fc6, fc7) for g_z by ops.conv_dgrad_kxk on the
+        layer's own parameter; the bf16 image is packed on first use after `refresh()`, into the buffer it has."""
+        conv = self.convs[name]
+        if name not in self._dpack_fresh:
+            self._dpack[name] = ops.conv_dgrad_kxk_pack(conv.W, tuple(gz.shape), 0, conv.Cin, conv.layout,
+                                                        out=self._dpack.get(name))
+            self._dpack_fresh.add(name)
+        return ops.conv_dgrad_kxk(gz, conv.W, layout=conv.layout, packed=self._dpack[name])
 
     def refresh(self):
         """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into the

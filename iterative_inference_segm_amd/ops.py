@@ -2350,12 +2350,40 @@ def conv_wgrad_kxk_desc(x, Cout, K, window=None, Cin_tot=None, ci0=0, layout='oi
     return d
 
 
-def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw'):
+KXK_MODES = ('f32', 'bf16')
+
+
+def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw', mma='f32'):
     """dW[:, ci0:ci0 + Cin] (and db, unless None) of the 'valid' K x K stride-1 layer (1 <= K <= 7) out = conv(x,
     W) + b, written in place into the layer's own parameter layout, from the `window` = (y0, x0, h, w) of its
     input's planes x (B,Cin,H,W), read in place, and gz = dL/dout (ReLU mask applied) (B,Cout,h - K + 1,w - K + 1).
-    The other input channels of dW are not touched.  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU."""
+    The other input channels of dW are not touched.  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU.
+    mma='bf16' (float32 device tensors only; csrc/conv_kxk_bf16.hip): x and gz are rounded
+    once to bf16 as they are staged and multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulators; db stays the
+    sum of the unrounded gz."""
     dt = x.dtype
+    if mma not in KXK_MODES:
+        raise ValueError("conv_wgrad_kxk: mma=%r is not one of %s" % (mma, KXK_MODES))
+    if mma == 'bf16':
+        for name, t in (('x', x), ('gz', gz), ('dW', dW), ('db', db)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+                raise ValueError("conv_wgrad_kxk: mma='bf16' takes float32 tensors only (%s is %s)"
+                                 % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+        if layout not in ('oihw', 'iohw'):
+            raise ValueError('conv_wgrad_kxk: layout %r' % (layout,))
+        if dW.dim() != 4 or dW.shape[2] != dW.shape[3] or not 1 <= dW.shape[2] <= 7:
+            raise ValueError('conv_wgrad_kxk: dW %s is not a K x K parameter, 1 <= K <= 7' % (tuple(dW.shape),))
+        if x.dim() != 4 or gz.dim() != 4:
+            raise ValueError('conv_wgrad_kxk: x %s, gz %s' % (tuple(x.shape), tuple(gz.shape)))
+        h, w = (x.shape[2], x.shape[3]) if window is None else (int(window[2]), int(window[3]))
+        Kk, Co = int(dW.shape[2]), int(dW.shape[0] if layout == 'oihw' else dW.shape[1])
+        Ct = int(dW.shape[1] if layout == 'oihw' else dW.shape[0])
+        if tuple(gz.shape) != (x.shape[0], Co, h - Kk + 1, w - Kk + 1) or h < Kk or w < Kk or \
+                ci0 < 0 or ci0 + x.shape[1] > Ct or (db is not None and db.numel() != Co):
+            raise ValueError('conv_wgrad_kxk: shapes x %s window %s gz %s dW %s (%s) ci0 %d' % (
+                tuple(x.shape), window, tuple(gz.shape), tuple(dW.shape), layout, ci0))
+        if not (x.is_cuda and gz.is_cuda and dW.is_cuda):
+            raise ValueError("conv_wgrad_kxk: mma='bf16' takes device tensors")
     if dW.dim() != 4 or dW.shape[2] != dW.shape[3]:
         raise RuntimeError('conv_wgrad_kxk: dW %s is not a K x K parameter' % (tuple(dW.shape),))
     K = int(dW.shape[2])
@@ -2367,15 +2395,112 @@ def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw'):
             tuple(x.shape), window, tuple(gz.shape), tuple(dW.shape)))
     if not x.is_cuda or x.dtype != dt or gz.dtype != dt or dW.dtype != dt:
         raise RuntimeError('conv_wgrad_kxk needs device tensors of one dtype')
-    n = _count(_lib.load().iiseg_conv_wgrad_kxk_workspace_elems(C.byref(d), dW.element_size()),
-               'iiseg_conv_wgrad_kxk_workspace_elems')
+    if mma == 'bf16':                                    # a plan, and a profile name, of its own
+        n = _count(_lib.load().iiseg_conv_wgrad_kxk_bf16_workspace_elems(C.byref(d)),
+                   'iiseg_conv_wgrad_kxk_bf16_workspace_elems')
+        kern, fn = 'conv_wgrad_kxk_bf16_kernel', _lib.load().iiseg_conv_wgrad_kxk_bf16
+    else:
+        n = _count(_lib.load().iiseg_conv_wgrad_kxk_workspace_elems(C.byref(d), dW.element_size()),
+                   'iiseg_conv_wgrad_kxk_workspace_elems')
+        kern, fn = 'conv_wgrad_kxk_kernel', _fn('conv_wgrad_kxk', dt)
     ws = _workspace(_SUFFIX[dt], n, x.device) if n else None
-    kern = 'conv_wgrad_kxk_kernel'
-    _launch(kern, 2.0 * d.Cin * Cout * K * K * d.B * OH * OW, _fn('conv_wgrad_kxk', dt), C.byref(d),
+    _launch(kern, 2.0 * d.Cin * Cout * K * K * d.B * OH * OW, fn, C.byref(d),
             C.c_void_p(x.data_ptr()), _ptr(gz, dt), _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))
     if CONV_PROFILE is not None:
         # byte model: the window of x and g_z read once, the slabs written and read once
         _add_bytes(kern, float(dW.element_size()) * (d.B * d.Cin * d.H * d.W + gz.numel() + 2 * n))
+
+
+def conv_dgrad_kxk_desc(gz_shape, Wshape, ci0=0, cin=None, layout='oihw', accumulate=False):
+    """The iiseg_conv_dgrad_desc of the 'valid' K x K layer with parameter `Wshape` stored as `layout`, for g_z
+    (B,Cout,OH,OW) and the input channels [ci0, ci0 + cin) (default: all from ci0 on)."""
+    B, Cout, OH, OW = (int(v) for v in gz_shape)
+    Cin_tot, Co, K, so, sc = _param_strides(Wshape, layout)
+    d = _lib.ConvDgradDesc()
+    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin_tot - int(ci0) if cin is None else int(cin), Cout, OH, OW, K, K - 1
+    d.ci0, d.Cin_tot, d.accumulate = int(ci0), Cin_tot, int(bool(accumulate))
+    d.so, d.sc = so, sc
+    return d
+
+
+def _dgrad_kxk_args(gz, W, layout, what):
+    """What conv_dgrad_kxk and conv_dgrad_kxk_pack refuse before the library is called."""
+    for name, t in (('gz', gz), ('W', W)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise ValueError('%s: %s must be a float32 tensor (got %s)'
+                             % (what, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if layout not in ('oihw', 'iohw'):
+        raise ValueError('%s: layout %r' % (what, layout))
+    if W.dim() != 4 or W.shape[2] != W.shape[3] or not 1 <= W.shape[2] <= 7:
+        raise ValueError('%s: W %s is not a K x K parameter, 1 <= K <= 7' % (what, tuple(W.shape)))
+
+
+def conv_dgrad_kxk_pack(W, gz_shape, ci0=0, cin=None, layout='oihw', out=None):
+    """The bf16 image of the input channels [ci0, ci0 + cin) of the fp32 K x K parameter W (read in place: the flip
+    and the transpose are indices) that conv_dgrad_kxk multiplies by; into `out` (a bfloat16 tensor of the size a
+    previous call returned: the address stays) or a new tensor.  One launch; again whenever W has changed."""
+    _dgrad_kxk_args(None, W, layout, 'conv_dgrad_kxk_pack')
+    d = conv_dgrad_kxk_desc(gz_shape, tuple(W.shape), ci0, cin, layout)
+    n = _count(_lib.load().iiseg_conv_dgrad_kxk_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_kxk_bf16_pack_elems')
+    if out is None:
+        out = torch.empty(n, dtype=torch.bfloat16, device=W.device)
+    elif out.dtype != torch.bfloat16 or out.numel() != n:
+        raise ValueError('conv_dgrad_kxk_pack: out holds %d %s elements, the image %d bfloat16'
+                         % (out.numel(), out.dtype, n))
+    kern = 'conv_dgrad_kxk_bf16_pack_kernel'
+    _launch(kern, 0.0, _lib.load().iiseg_conv_dgrad_kxk_bf16_pack, C.byref(d), _ptr(W), _ptr(out, torch.bfloat16))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, 4.0 * d.Cout * d.Cin * d.K * d.K + 2.0 * n)
+    return out
+
+
+def conv_dgrad_kxk(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=False, gate=None, packed=None):
+    """The data gradient of the 'valid' K x K stride-1 layer (1 <= K <= 7) with fp32 parameter W, on the 16-bit
+    matrix pipe (csrc/conv_kxk_bf16.hip): gx[b,ci,y,x] = sum_{co,ky,kx} bf16(W[co,ci0+ci,ky,
+    kx]) bf16(gz[b,co,y-ky,x-kx]), gz (B,Cout,OH,OW) zero outside its plane (no embedded copy), gx (B,cin,OH+K-1,
+    OW+K-1); every operand rounded once (nearest, ties to even), fp32 accumulation in a fixed order by
+    v_mfma_f32_32x32x16_bf16, the slabs of output channels added in slab order.  ci0, cin, out, accumulate, gate:
+    as conv_dgrad.  packed: what conv_dgrad_kxk_pack returned for this W, slice and layout (default: packed here,
+    one more launch).  float32 tensors only."""
+    _dgrad_kxk_args(gz, W, layout, 'conv_dgrad_kxk')
+    for name, t in (('out', out), ('gate', gate)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise ValueError('conv_dgrad_kxk: %s must be a float32 tensor (got %s)'
+                             % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if packed is not None and (not torch.is_tensor(packed) or packed.dtype != torch.bfloat16):
+        raise ValueError('conv_dgrad_kxk: packed must be the bfloat16 tensor of conv_dgrad_kxk_pack')
+    if accumulate and out is None:
+        raise ValueError('conv_dgrad_kxk: accumulate=True needs the map to add to (out=)')
+    if gz.dim() != 4:
+        raise ValueError('conv_dgrad_kxk: gz %s is not (B, Cout, OH, OW)' % (tuple(gz.shape),))
+    d = conv_dgrad_kxk_desc(tuple(gz.shape), tuple(W.shape), ci0, cin, layout, accumulate)
+    Cout_w = W.shape[0] if layout == 'oihw' else W.shape[1]
+    if gz.shape[1] != Cout_w or d.Cin < 1 or d.ci0 < 0 or d.ci0 + d.Cin > d.Cin_tot:
+        raise ValueError('conv_dgrad_kxk: gz %s, W %s (%s), input channels [%d, %d)'
+                         % (tuple(gz.shape), tuple(W.shape), layout, d.ci0, d.ci0 + d.Cin))
+    shape = (d.B, d.Cin, d.H + d.K - 1, d.W + d.K - 1)
+    for name, t in (('out', out), ('gate', gate)):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError('conv_dgrad_kxk: %s %s, the gradient is %s' % (name, tuple(t.shape), shape))
+    lib = _lib.load()
+    n = _count(lib.iiseg_conv_dgrad_kxk_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_kxk_bf16_pack_elems')
+    if packed is None:
+        packed = conv_dgrad_kxk_pack(W, tuple(gz.shape), ci0, cin, layout)
+    elif packed.numel() != n:
+        raise ValueError('conv_dgrad_kxk: packed holds %d elements, the image of this slice %d' % (packed.numel(), n))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=gz.device)
+    nws = _count(lib.iiseg_conv_dgrad_kxk_bf16_workspace_elems(C.byref(d)), 'iiseg_conv_dgrad_kxk_bf16_workspace_elems')
+    ws = _workspace('f32', nws, gz.device) if nws else None
+    kern = 'conv_dgrad_kxk_bf16_kernel'
+    _launch(kern, 2.0 * d.Cin * d.Cout * d.K * d.K * d.B * d.H * d.W, lib.iiseg_conv_dgrad_kxk_bf16, C.byref(d),
+            _ptr(gz), _ptr(packed, torch.bfloat16), _ptr(gate), _ptr(ws), _ptr(out))
+    if CONV_PROFILE is not None:
+        # byte model: g_z and the image read once, the slabs written and read once, gx written once (read once more
+        # when it is added to), the gate read
+        _add_bytes(kern, 4.0 * gz.numel() + 2.0 * n + 8.0 * nws +
+                   4.0 * out.numel() * (1 + int(bool(accumulate)) + (gate is not None)))
+    return out
 
 
 def deconv_desc(x_shape, Cout, K, stride, window=None):

@@ -36,7 +36,16 @@ def check_dgrad(dgrad, dtype):
                                   'be float32 (got %s)' % (dtype,))
 
 
-def check_supported(kind='contextmod', training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
+def check_kxk(kxk, dtype):
+    """The mode of FCN-8's fc6 / fc7 gradients of a run (host only): 'f32', or 'bf16' with float32."""
+    if kxk not in ops.KXK_MODES:
+        raise ValueError('kxk must be one of %s (got %r)' % (', '.join(ops.KXK_MODES), kxk))
+    if kxk == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
+        raise NotImplementedError("kxk='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
+                                  'be float32 (got %s)' % (dtype,))
+
+
+def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
                     optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32', dgrad='f32'):
     """Raises NotImplementedError / ValueError with the reason for everything this slice does not train
     (host only: callable before any GPU work).  dae_dict: the standard kind's options (concat_h, bn, dropout,

@@ -24,6 +24,12 @@ mode's peak; the bf16 rows add the yardstick, the existing ops.Conv(..., mma='bf
 filter of that same layer on a map of g_z's shape, and the filter images' pack launches of the step; every row has
 `refresh_ms`, the cost of refresh() (in the fp32 mode it flips, copies and re-packs those filters too).  DESIGN
 section 16.
+--kxk: the modes of fc6's and fc7's gradients to run (`--kxk f32 f32 bf16`), one row per (wgrad, dgrad, kxk) in the
+same process.  Every row lists under `kxk_layers` the four launches -- fc7's and fc6's weight and data gradient, the
+fp32 K x K kernel and flipped-filter layer or conv_wgrad_kxk_bf16_kernel and conv_dgrad_kxk_bf16_kernel (with its
+finalize) -- each with its fraction of the mode's peak and next to the layer's forward launch, `kxk_pack_ms` (the
+two filter images' pack launches of the step), `refresh_ms` and `max_memory_allocated_mb` (torch.cuda's peak over
+the timed steps).  DESIGN section 17.
 """
 import argparse
 import json
@@ -42,18 +48,20 @@ from dgrad_bench import launches, layer_rows, marked, yardstick           # noqa
 
 DECONVS = ('upsample', 'score4', 'score2')
 KXK = ('score_pool3', 'score_pool4', 'score_fr', 'fc7', 'fc6')
+KXK16 = ('fc7', 'fc6')                                   # the layers of kxk='bf16', in backward's order
 
 
 def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, wgrad='f32',
-        peak_bf16=2500.0, dgrad='f32', yard=None):
+        peak_bf16=2500.0, dgrad='f32', yard=None, kxk='f32'):
     params = S.make_fcn8_params(3, 11, seed=1234, width_div=width_div, fc_channels=fc_channels)
-    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad)
+    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad, kxk=kxk)
     tr = FCN8Trainer(net, 11, [11], learning_rate=1e-4, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
     for _ in range(3):
         tr.train_step(X, T)
     torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
     ms = []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -63,6 +71,7 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         torch.cuda.synchronize()
         ms.append(e0.elapsed_time(e1))
     step = float(np.median(ms))
+    peak_mem = torch.cuda.max_memory_allocated()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(5):
@@ -100,7 +109,11 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     # backward's order of the weight gradients
     blocks = [n for n in reversed(convs[:13])]
     wg = dict(zip(DECONVS, by('deconv_wgrad_kernel')))
-    wg.update(zip(KXK, by('conv_wgrad_kxk_kernel')))
+    if kxk == 'bf16':
+        wg.update(zip(KXK[:3], by('conv_wgrad_kxk_kernel')))
+        wg.update(zip(KXK16, by('conv_wgrad_kxk_bf16_kernel')))
+    else:
+        wg.update(zip(KXK, by('conv_wgrad_kxk_kernel')))
     wg.update(zip(blocks, by('conv_wgrad_bf16_kernel' if wgrad == 'bf16' else 'conv_wgrad_kernel')))
     if sorted(wg) != sorted(PARAM_ORDER):
         raise RuntimeError('expected one weight-gradient call per layer, got %d' % len(wg))
@@ -128,7 +141,8 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         f, t = wg[n]
         row = {'layer': n, 'shape': list(params[n][0].shape), 'wgrad_ms': round(t, 4),
                'wgrad_fraction_of_peak': round(f / (t * 1e-3) /
-                                               ((peak_bf16 if wgrad == 'bf16' and n in blocks else peak) * 1e12), 4)}
+                                               ((peak_bf16 if (wgrad == 'bf16' and n in blocks) or
+                                                 (kxk == 'bf16' and n in KXK16) else peak) * 1e12), 4)}
         if n in fwd_ms:
             row.update(forward_kernel=fwd_kernel[n], forward_ms=round(fwd_ms[n], 4),
                        wgrad_over_forward=round(t / fwd_ms[n], 3))
@@ -145,6 +159,22 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     if len(dg) != len(dnames):
         raise RuntimeError('expected %d data-gradient launches, got %d' % (len(dnames), len(dg)))
     pack_ms = sum(a.elapsed_time(b) for k, _, a, b in back if k == 'conv_dgrad_bf16_pack_kernel')
+    # fc7 and fc6 (backward's order): the four launches of the kxk mode, each next to the layer's forward launch
+    if kxk == 'bf16':
+        kd = [(a.elapsed_time(b), f, k) for k, f, a, b in back if k == 'conv_dgrad_kxk_bf16_kernel']
+    else:
+        kd = [launches(prof, i, j) for n, i, j in log if n in KXK16]
+    if len(kd) != 2:
+        raise RuntimeError('expected the data-gradient launches of fc7 and fc6, got %d' % len(kd))
+    kpeak = peak_bf16 if kxk == 'bf16' else peak
+    kxk_pack_ms = sum(a.elapsed_time(b) for k, _, a, b in back if k == 'conv_dgrad_kxk_bf16_pack_kernel')
+    klayers = []
+    for n, (t, f, kern) in zip(KXK16, kd):
+        fw, tw_ = wg[n]
+        klayers.append({'layer': n, 'forward_ms': round(fwd_ms[n], 4),
+                        'wgrad_ms': round(tw_, 4), 'wgrad_fraction_of_peak': round(fw / (tw_ * 1e-3) / (kpeak * 1e12), 4),
+                        'dgrad_ms': round(t, 4), 'dgrad_kernel': kern,
+                        'dgrad_fraction_of_peak': round(f / (t * 1e-3) / (kpeak * 1e12), 4)})
     elem = []
     for kern in ('relu_gate_kernel', 'l2_term_kernel', 'deconv_dgrad_kernel'):
         t = sum(t for _, t in by(kern))
@@ -164,7 +194,10 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     dlayers = layer_rows(dnames, {n: (t, k) for n, (t, _, k) in zip(dnames, dg)},
                          {n: f for n, (_, f, _) in zip(dnames, dg)}, peak_bf16 if dgrad == 'bf16' else peak,
                          yard if dgrad == 'bf16' else None)
-    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad,
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad, 'kxk': kxk,
+            'kxk_layers': klayers, 'kxk_pack_ms': round(kxk_pack_ms, 4),
+            'kxk_ms_total': round(sum(r['wgrad_ms'] + r['dgrad_ms'] for r in klayers) + kxk_pack_ms, 4),
+            'max_memory_allocated_mb': round(peak_mem / 2.0 ** 20, 1),
             'dgrad_3x3_ms_total': round(sum(r['dgrad_ms'] for r in dlayers), 3), 'dgrad_pack_ms': round(pack_ms, 4),
             'refresh_ms': round(refresh_ms, 4), 'dgrad_layers': dlayers, 'batch': B, 'size': '%dx%d' % (H, W),
             'step_ms': round(step, 3),
@@ -184,6 +217,7 @@ def main():
     ap.add_argument('--peak_tflops', type=float, default=157.3)
     ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--dgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--kxk', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     ap.add_argument('--stream_gbs', type=float, default=6600.0)
     ap.add_argument('--width_div', type=int, default=1)
@@ -193,9 +227,9 @@ def main():
     H, W = (int(v) for v in a.size.split('x'))
     yard = {}
     rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.width_div,
-                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16, dmode, yard)
-            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad
-            if (mode == 'f32' and dmode == 'f32') or name == 'float32']
+                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16, dmode, yard, kmode)
+            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad for kmode in a.kxk
+            if (mode == 'f32' and dmode == 'f32' and kmode == 'f32') or name == 'float32']
     print(json.dumps({'bench': 'train_fcn8', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
                       'peak_tflops_bf16': a.peak_tflops_bf16,
                       'stream_gbs': a.stream_gbs, 'reps': a.reps, 'results': rows}))
