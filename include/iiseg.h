@@ -1211,6 +1211,32 @@ int iiseg_conv_dgrad_kxk_bf16_pack(void* stream, const iiseg_conv_dgrad_desc* d,
 int iiseg_conv_dgrad_kxk_bf16(void* stream, const iiseg_conv_dgrad_desc* d, const float* gz, const void* packed,
                               const float* gate, float* ws, float* gx);
 
+/* ---------------------------------------------------------------------------------------
+ * Forward of a 'valid' K x K stride-1 layer on the 16-bit matrix pipe (fwd='bf16'; csrc/conv_kxk_bf16.hip; DESIGN.md
+ * section 18; backward-compatible addition).  1 <= K <= 7, fp32 tensors:
+ *   z[b][co][y][x] = relu(sum_{ci,ky,kx} bf16(W[co][ci][ky][kx]) bf16(x[b][ci][y + ky][x + kx]) + bias[co])
+ * every operand rounded once (to nearest, ties to even) as it is staged, v_mfma_f32_32x32x16_bf16 accumulating in
+ * fp32 in a fixed order, the slabs of a split reduction added in slab order, the bias added in fp32: no atomics, the
+ * same inputs give the same bits.  No im2col image and no packed copy of W: the parameter is read as it is.
+ *   x    : (B, Cin, H, W) contiguous.      W : (Cout, Cin, K, K) contiguous ('oihw'), the layer's own parameter.
+ *   bias : Cout floats, or NULL.           z : (B, Cout, H - K + 1, W - K + 1) contiguous.    relu: 0 or 1.
+ *   ws   : iiseg_conv_fwd_kxk_bf16_workspace_elems(d) floats (0 with one slab of the reduction).
+ * NULL d, x, W, z (ws with several slabs) IISEG_ERR_NULL; K outside 1..7, H or W below K, non-positive sizes, more
+ * than 65535 channels or images, H W > 2^28, relu outside {0, 1} IISEG_ERR_SHAPE; alignment IISEG_ERR_ALIGN; z
+ * overlapping x or W IISEG_ERR_UNSUPPORTED.  All before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct iiseg_conv_fwd_kxk_desc {
+    int32_t B, Cin, Cout, H, W, K;
+    int32_t relu;
+    int32_t reserved;
+} iiseg_conv_fwd_kxk_desc;
+
+int iiseg_conv_fwd_kxk_bf16_check(const iiseg_conv_fwd_kxk_desc* d);
+int iiseg_conv_fwd_kxk_bf16_slabs(const iiseg_conv_fwd_kxk_desc* d);
+int64_t iiseg_conv_fwd_kxk_bf16_workspace_elems(const iiseg_conv_fwd_kxk_desc* d);
+int iiseg_conv_fwd_kxk_bf16(void* stream, const iiseg_conv_fwd_kxk_desc* d, const float* x, const float* W,
+                            const float* bias, float* ws, float* z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,11 @@ class ConvWgradKxKDesc(C.Structure):
                [(n, C.c_int64) for n in ('x_row', 'x_plane', 'x_image', 'so', 'sc')]
 
 
+class ConvFwdKxKDesc(C.Structure):
+    """struct iiseg_conv_fwd_kxk_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'relu', 'reserved')]
+
+
 L2_MAX_RANGES = 64
 
 C8DIL_OUT_NCHW = 0x100
@@ -317,6 +322,10 @@ SIGNATURES = {
     'iiseg_conv_dgrad_kxk_bf16_pack_elems': (_i64, [C.POINTER(ConvDgradDesc)]),
     'iiseg_conv_dgrad_kxk_bf16_pack': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 2),
     'iiseg_conv_dgrad_kxk_bf16': (C.c_int, [_vp, C.POINTER(ConvDgradDesc)] + [_vp] * 5),
+    'iiseg_conv_fwd_kxk_bf16_check': (C.c_int, [C.POINTER(ConvFwdKxKDesc)]),
+    'iiseg_conv_fwd_kxk_bf16_slabs': (C.c_int, [C.POINTER(ConvFwdKxKDesc)]),
+    'iiseg_conv_fwd_kxk_bf16_workspace_elems': (_i64, [C.POINTER(ConvFwdKxKDesc)]),
+    'iiseg_conv_fwd_kxk_bf16': (C.c_int, [_vp, C.POINTER(ConvFwdKxKDesc)] + [_vp] * 5),
 }
 
 _lib = None

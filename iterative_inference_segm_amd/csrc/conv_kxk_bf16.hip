@@ -5,6 +5,10 @@
 //   db[co]                   = sum_{b,y,x}    g_z[b][co][y][x]                                    (not rounded)
 //   gx[b][ci][y][x]          = sum_{co,ky,kx} bf16(W[co][ci0 + ci][ky][kx]) * bf16(g_z[b][co][y - ky][x - kx])
 //
+// and (fwd='bf16') the layer's forward itself, on the fp32 parameter as it is:
+//
+//   z[b][co][y][x]           = relu(sum_{ci,ky,kx} bf16(W[co][ci][ky][kx]) * bf16(x[b][ci][y + ky][x + kx]) + b[co])
+//
 // g_z (B, Cout, OH, OW) is zero outside its plane; x is an (H, W) = (OH + K - 1, OW + K - 1) window of a larger map
 // and gx is (B, Cin, H, W).  Every operand arrives as fp32 and is rounded once, to nearest even, as it is staged; a
 // product of two bf16 values is exact in fp32, v_mfma_f32_32x32x16_bf16 accumulates in fp32 in a fixed order, and
@@ -32,6 +36,18 @@
 // [co chunk][patch pixel][8 co], per filter row the K taps of the filter image, loaded one row ahead into registers.
 // Wave w owns tile rows 4w .. 4w + 3 as two 32-pixel blocks and both 32-channel blocks.  One slab: the epilogue
 // adds what gx held (accumulate) and applies the gate (gx * [gate > 0]), in that order; more: the finalize does.
+//
+// Forward.  The reduction runs over (tap, 8-channel chunk) UNITS: a k-tile is NCH chunks of eight input channels x
+// all K^2 taps, a k-step two consecutive units (the two k halves of the MFMA; the odd unit past the last multiplies a
+// zero A fragment).  In 'oihw' the (ci, ky, kx) run of an output channel is contiguous, so the k-tile of W is read as
+// 64 runs of 8 NCH K^2 floats straight from the parameter -- no packed image, nothing to refresh -- and turned while
+// it is staged: the thread of (co, unit) gathers the unit's eight channels at stride K^2 and writes one 16-byte word
+// of [co][unit].  A PIXEL TILE is 8 x 8 outputs of one image (K = 1: 64 consecutive pixels of the flat (b, y, x)
+// range), its x patch with the K - 1 halo staged once per k-tile as [chunk][patch pixel][8 ci]: the B operand of a
+// unit is one 16-byte read at the tap's offset.  A workgroup owns, for a slab of k-tiles, 64 output channels x eight
+// pixel tiles (two per wave; K = 1, where nothing is re-used across taps: 128 output channels x four tiles, one per
+// wave): eight accumulators per wave either way.  One slab: the epilogue adds the bias and applies ReLU; more: the
+// slabs go to the workspace and the finalize adds them in slab order, then the bias, then ReLU.
 #include "common.h"
 
 namespace {
@@ -560,6 +576,247 @@ void kd_launch(hipStream_t s, const kd_params& p, const dim3& grid, const float*
     IISEG_LAUNCH((conv_dgrad_kxk_bf16_kernel<K>), grid, dim3(256), 0, s, p, gz, packed, gate, dst);
 }
 
+// ==================================================== forward ====================================================
+constexpr int FT = 8;                                    // output pixel tile edge (K > 1)
+constexpr int FPX = FT * FT;                             // pixels of a tile: two 32-pixel MFMA blocks
+constexpr int F_TARGET_WORKGROUPS = 512;
+constexpr int F_MIN_KT_PER_SLAB = 2;
+
+// A wave owns MB blocks of 32 output channels x TPW pixel tiles (eight accumulators either way): K = 1 stages no
+// halo and re-uses nothing across taps, so its x tile serves 128 output channels; K > 1 gives a W tile 128 pixels.
+constexpr int kf_mb(int K) { return K == 1 ? 4 : 2; }
+constexpr int kf_tpw(int K) { return K == 1 ? 1 : 2; }
+// chunks of eight input channels in a k-tile: K^2 NCH units
+constexpr int kf_nch(int K) { return K == 1 ? 8 : K == 2 ? 4 : K == 3 ? 2 : 1; }
+// units of W staged at a time (K = 7: the 49 taps in two parts, to keep LDS below 64 KiB)
+constexpr int kf_ua(int K) { return K == 7 ? 26 : kf_nch(K) * K * K; }
+
+struct kf_params {
+    int B, Cin, Cout, H, W, OH, OW;
+    int tilesX, tilesY;
+    long long ntile;                                     // pixel tiles
+    unsigned P;                                          // K = 1: pixels in all
+    int nkt, kps, nslab;                                 // k-tiles, k-tiles per slab, slabs
+    int relu;
+    long long N;                                         // elements of z
+};
+
+template <int K>
+__global__ __launch_bounds__(256, 2) void conv_fwd_kxk_bf16_kernel(kf_params p, const float* __restrict__ x,
+                                                                   const float* __restrict__ Wp,
+                                                                   const float* __restrict__ bias,
+                                                                   float* __restrict__ dst) {
+    constexpr int KK = K * K, NCH = kf_nch(K), NU = NCH * KK, UA = kf_ua(K);
+    constexpr int MB = kf_mb(K), TPW = kf_tpw(K), CBF = 32 * MB, FWT = 4 * TPW;
+    constexpr int PW = K > 1 ? FT + K - 1 : FPX, NPIX = K > 1 ? PW * PW : FPX;
+    constexpr int AI = (CBF * UA + 255) / 256;           // (co, unit) items of a thread
+    constexpr int BI = (FWT * NCH * NPIX + 255) / 256;   // (tile, chunk, patch pixel) items of a thread
+    __shared__ __attribute__((aligned(16))) u32x4 As[CBF * UA];           // [co][unit of the part]
+    __shared__ __attribute__((aligned(16))) u32x4 Bs[FWT * NCH * NPIX];   // [tile][chunk][patch pixel]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int co0 = blockIdx.y * CBF, slab = blockIdx.z;
+    const int nco = min(CBF, p.Cout - co0);
+    const size_t HW = (size_t)p.H * p.W, OHW = (size_t)p.OH * p.OW;
+    const int per_img = p.tilesY * p.tilesX;
+
+    // the patch pixels this thread stages: the offset of channel 0 (clamped into the map), the chunk, whether real
+    size_t xo[BI];
+    int xc[BI];
+    bool xin[BI];
+#pragma unroll
+    for (int j = 0; j < BI; ++j) {
+        const int it = min(tid + 256 * j, FWT * NCH * NPIX - 1);
+        const int t = it / (NCH * NPIX), k = it % NPIX;
+        xc[j] = (it / NPIX) % NCH;
+        const long long tile = (long long)blockIdx.x * FWT + t;
+        if constexpr (K > 1) {
+            const long long tt = min(tile, p.ntile - 1);
+            const int b = (int)(tt / per_img), rem = (int)(tt % per_img);
+            const int y = (rem / p.tilesX) * FT + k / PW, xx = (rem % p.tilesX) * FT + k % PW;
+            xin[j] = tile < p.ntile && y < p.H && xx < p.W;
+            xo[j] = (size_t)b * p.Cin * HW + (size_t)min(y, p.H - 1) * p.W + min(xx, p.W - 1);
+        } else {
+            const long long q = tile * FPX + k;
+            xin[j] = q < (long long)p.P;
+            const unsigned qq = xin[j] ? (unsigned)q : 0u;
+            xo[j] = (size_t)(qq / (unsigned)HW) * p.Cin * HW + qq % (unsigned)HW;
+        }
+    }
+
+    // multiplying: wave -> TPW pixel tiles, lane -> (row of A / pixel of the 32-pixel block, k half)
+    const int l31 = lane & 31, half = lane >> 5;
+    const long long tile0 = (long long)blockIdx.x * FWT + wave * TPW;
+    const bool wave_on = tile0 < p.ntile;
+    int pb[2];                                           // the lane's pixel of block n inside the patch
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int pn = n * 32 + l31;
+        pb[n] = K > 1 ? (pn / FT) * PW + pn % FT : pn;
+    }
+    f32x16 acc[MB][2 * TPW];
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int n = 0; n < 2 * TPW; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+
+    const int kt0 = slab * p.kps, kt1 = min(p.nkt, kt0 + p.kps);
+    const long long so = (long long)p.Cin * KK;
+    for (int kt = kt0; kt < kt1; ++kt) {
+        const int cb = kt * NCH * 8;
+#pragma unroll
+        for (int ua = 0; ua < NU; ua += UA) {
+            const int nu = min(UA, NU - ua);                             // units of this part
+            __syncthreads();                                             // the previous part has been read
+            // ---- W: the thread of (co, unit) gathers the unit's eight channels at the tap, rounds, one 16-byte write
+#pragma unroll 2
+            for (int j = 0; j < AI; ++j) {
+                const int it = tid + 256 * j;
+                const int itc = min(it, CBF * UA - 1);
+                const int co = itc / UA, u = min(ua + itc % UA, NU - 1), chunk = u / KK, tap = u % KK;
+                const float* wsrc = Wp + (long long)min(co0 + co, p.Cout - 1) * so + tap;
+                const int c0 = cb + chunk * 8;
+                float v[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = wsrc[(long long)min(c0 + i, p.Cin - 1) * KK];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = co < nco && c0 + i < p.Cin ? v[i] : 0.f;
+                if (it < CBF * UA) As[itc] = pack8(v);
+            }
+            // ---- x, with the k-tile's first part: the patches of the tiles, eight channels of a pixel per word ----
+            if (ua == 0) {
+#pragma unroll
+                for (int j = 0; j < BI; ++j) {
+                    const int c0 = cb + xc[j] * 8;
+                    float v[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] = x[xo[j] + (size_t)min(c0 + i, p.Cin - 1) * HW];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] = xin[j] && c0 + i < p.Cin ? v[i] : 0.f;
+                    if (tid + 256 * j < FWT * NCH * NPIX) Bs[tid + 256 * j] = pack8(v);
+                }
+            }
+            __syncthreads();
+            if (wave_on) {
+                const u32x4* ap = As + l31 * UA;
+                const u32x4* bp = Bs + wave * TPW * NCH * NPIX;
+#pragma unroll 2
+                for (int s = 0; s < (nu + 1) / 2; ++s) {
+                    const int ul = 2 * s + half;
+                    const int ulc = min(ul, nu - 1);                     // the odd unit past the last: A = 0
+                    const int u = ua + ulc, chunk = u / KK, tap = u % KK;
+                    const int off = chunk * NPIX + (tap / K) * PW + tap % K;
+                    bf16x8 a[MB];
+#pragma unroll
+                    for (int m = 0; m < MB; ++m) {
+                        u32x4 w = ap[m * 32 * UA + ulc];
+                        if (ul >= nu) w = u32x4{0u, 0u, 0u, 0u};
+                        a[m] = __builtin_bit_cast(bf16x8, w);
+                    }
+#pragma unroll
+                    for (int n = 0; n < 2 * TPW; ++n) {
+                        const bf16x8 b = __builtin_bit_cast(bf16x8, bp[(n >> 1) * NCH * NPIX + off + pb[n & 1]]);
+#pragma unroll
+                        for (int m = 0; m < MB; ++m)
+                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[m], b, acc[m][n], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- epilogue: z = relu(sum + bias), or this slab of the workspace ----
+    if (!wave_on) return;
+    const bool direct = p.nslab == 1;
+    float* out = direct ? dst : dst + (size_t)slab * p.N;
+#pragma unroll
+    for (int n = 0; n < 2 * TPW; ++n) {
+        const long long tile = tile0 + (n >> 1);
+        if (tile >= p.ntile) continue;
+        const int pn = (n & 1) * 32 + l31;
+        size_t o0;                                                       // the pixel in channel 0 of its image
+        if constexpr (K > 1) {
+            const int b = (int)(tile / per_img), rem = (int)(tile % per_img);
+            const int y = (rem / p.tilesX) * FT + pn / FT, xx = (rem % p.tilesX) * FT + pn % FT;
+            if (y >= p.OH || xx >= p.OW) continue;
+            o0 = (size_t)b * p.Cout * OHW + (size_t)y * p.OW + xx;
+        } else {
+            const long long q = tile * FPX + pn;
+            if (q >= (long long)p.P) continue;
+            o0 = (size_t)((unsigned)q / (unsigned)OHW) * p.Cout * OHW + (unsigned)q % (unsigned)OHW;
+        }
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                if (co >= nco) continue;
+                float v = acc[m][n][r];
+                if (direct) {
+                    if (bias) v += bias[co0 + co];
+                    if (p.relu) v = fmaxf(v, 0.f);
+                }
+                out[o0 + (size_t)(co0 + co) * OHW] = v;
+            }
+    }
+}
+
+// z = relu(the slabs added in slab order, in double, + bias)
+__global__ __launch_bounds__(256) void conv_fwd_kxk_bf16_finalize_kernel(const float* __restrict__ slab, int nslab,
+                                                                         long long N, long long OHW, int Cout,
+                                                                         const float* __restrict__ bias, int relu,
+                                                                         float* __restrict__ z) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= N) return;
+    double v = 0.0;
+    for (int k = 0; k < nslab; ++k) v += (double)slab[(long long)k * N + idx];
+    float f = (float)v;
+    if (bias) f += bias[(idx / OHW) % Cout];
+    if (relu) f = fmaxf(f, 0.f);
+    z[idx] = f;
+}
+
+int kf_plan(const iiseg_conv_fwd_kxk_desc* d, kf_params& p) {
+    if (!d) return IISEG_ERR_NULL;
+    if (d->K < 1 || d->K > KMAX) return IISEG_ERR_SHAPE;
+    if (d->B < 1 || d->B > 65535 || d->Cin < 1 || d->Cin > 65535 || d->Cout < 1 || d->Cout > 65535 || d->H < d->K ||
+        d->W < d->K || (int64_t)d->H * d->W > (int64_t)1 << 28)
+        return IISEG_ERR_SHAPE;
+    if (d->relu != 0 && d->relu != 1) return IISEG_ERR_SHAPE;
+    const int KK = d->K * d->K;
+    if ((int64_t)d->Cout * d->Cin * KK > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    p.B = d->B; p.Cin = d->Cin; p.Cout = d->Cout; p.H = d->H; p.W = d->W;
+    p.OH = d->H - d->K + 1; p.OW = d->W - d->K + 1;
+    if ((int64_t)d->B * d->H * d->W > ((int64_t)1 << 31) - 512) return IISEG_ERR_SHAPE;
+    const int64_t pix = (int64_t)d->B * p.OH * p.OW;
+    p.P = (unsigned)pix;
+    p.tilesY = (p.OH + FT - 1) / FT;
+    p.tilesX = (p.OW + FT - 1) / FT;
+    p.ntile = d->K == 1 ? (pix + FPX - 1) / FPX : (int64_t)d->B * p.tilesY * p.tilesX;
+    const int fwt = 4 * kf_tpw(d->K), cbf = 32 * kf_mb(d->K);
+    const int64_t groups = (p.ntile + fwt - 1) / fwt;
+    if (groups > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    const int64_t coB = (d->Cout + cbf - 1) / cbf;
+    p.nkt = (d->Cin + kf_nch(d->K) * 8 - 1) / (kf_nch(d->K) * 8);
+    const int64_t base = groups * coB;
+    const int64_t target = base >= F_TARGET_WORKGROUPS ? 1 : (F_TARGET_WORKGROUPS + base - 1) / base;
+    int64_t kps = (p.nkt + target - 1) / target;
+    if (kps < F_MIN_KT_PER_SLAB) kps = F_MIN_KT_PER_SLAB;
+    p.kps = (int)kps;
+    p.nslab = (int)((p.nkt + kps - 1) / kps);
+    if (p.nslab > 65535) return IISEG_ERR_SHAPE;                         // grid z
+    p.relu = d->relu;
+    p.N = (long long)d->B * d->Cout * p.OH * p.OW;
+    return IISEG_OK;
+}
+
+template <int K>
+void kf_launch(hipStream_t s, const kf_params& p, const dim3& grid, const float* x, const float* W, const float* bias,
+               float* dst) {
+    IISEG_LAUNCH((conv_fwd_kxk_bf16_kernel<K>), grid, dim3(256), 0, s, p, x, W, bias, dst);
+}
+
 }  // namespace
 
 extern "C" int iiseg_conv_wgrad_kxk_bf16_check(const iiseg_conv_wgrad_kxk_desc* d) {
@@ -659,5 +916,50 @@ extern "C" int iiseg_conv_dgrad_kxk_bf16(void* stream, const iiseg_conv_dgrad_de
     if (p.nslab > 1)
         IISEG_LAUNCH(conv_dgrad_kxk_bf16_finalize_kernel, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, s,
                      (const float*)ws, p.nslab, p.N, p.accumulate, gate, gx);
+    return iiseg_check_launch();
+}
+
+extern "C" int iiseg_conv_fwd_kxk_bf16_check(const iiseg_conv_fwd_kxk_desc* d) {
+    kf_params p;
+    return kf_plan(d, p);
+}
+extern "C" int iiseg_conv_fwd_kxk_bf16_slabs(const iiseg_conv_fwd_kxk_desc* d) {
+    kf_params p;
+    if (int st = kf_plan(d, p)) return st;
+    return p.nslab;
+}
+extern "C" int64_t iiseg_conv_fwd_kxk_bf16_workspace_elems(const iiseg_conv_fwd_kxk_desc* d) {
+    kf_params p;
+    if (int st = kf_plan(d, p)) return st;
+    return p.nslab == 1 ? 0 : (int64_t)p.nslab * p.N;
+}
+extern "C" int iiseg_conv_fwd_kxk_bf16(void* stream, const iiseg_conv_fwd_kxk_desc* d, const float* x, const float* W,
+                                       const float* bias, float* ws, float* z) {
+    kf_params p;
+    if (int st = kf_plan(d, p)) return st;
+    if (!x || !W || !z || (p.nslab > 1 && !ws)) return IISEG_ERR_NULL;
+    if ((uintptr_t)x % 4 || (uintptr_t)W % 4 || (uintptr_t)bias % 4 || (uintptr_t)ws % 4 || (uintptr_t)z % 4)
+        return IISEG_ERR_ALIGN;
+    const int64_t zb = p.N * 4;
+    // z is written while other workgroups still read x and W
+    if (kd_overlap(z, zb, x, (int64_t)d->B * d->Cin * d->H * d->W * 4) ||
+        kd_overlap(z, zb, W, (int64_t)d->Cout * d->Cin * d->K * d->K * 4))
+        return IISEG_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int fwt = 4 * kf_tpw(d->K), cbf = 32 * kf_mb(d->K);
+    const dim3 grid((unsigned)((p.ntile + fwt - 1) / fwt), (unsigned)((p.Cout + cbf - 1) / cbf), (unsigned)p.nslab);
+    float* dst = p.nslab == 1 ? z : ws;
+    switch (d->K) {
+        case 1: kf_launch<1>(s, p, grid, x, W, bias, dst); break;
+        case 2: kf_launch<2>(s, p, grid, x, W, bias, dst); break;
+        case 3: kf_launch<3>(s, p, grid, x, W, bias, dst); break;
+        case 4: kf_launch<4>(s, p, grid, x, W, bias, dst); break;
+        case 5: kf_launch<5>(s, p, grid, x, W, bias, dst); break;
+        case 6: kf_launch<6>(s, p, grid, x, W, bias, dst); break;
+        default: kf_launch<7>(s, p, grid, x, W, bias, dst); break;
+    }
+    if (p.nslab > 1)
+        IISEG_LAUNCH(conv_fwd_kxk_bf16_finalize_kernel, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, s,
+                     (const float*)ws, p.nslab, p.N, (long long)p.OH * p.OW, p.Cout, bias, p.relu, z);
     return iiseg_check_launch();
 }

@@ -25,6 +25,7 @@ _BLOCKS = [('conv1_1', 'conv1_2'), ('conv2_1', 'conv2_2'), ('conv3_1', 'conv3_2'
            ('conv4_1', 'conv4_2', 'conv4_3'), ('conv5_1', 'conv5_2', 'conv5_3')]
 _NAMES_3X3 = frozenset(n for names in _BLOCKS for n in names)
 _NAMES_KXK16 = ('fc6', 'fc7')                            # the layers of kxk='bf16'
+_NAMES_FWD16 = tuple(sorted(_NAMES_3X3)) + _NAMES_KXK16  # the fifteen layers of fwd='bf16'
 
 
 _UID = itertools.count(1)   # identity of a net in the provenance tags (never reused, unlike id())
@@ -33,7 +34,7 @@ _UID = itertools.count(1)   # identity of a net in the provenance tags (never re
 class FCN8:
     def __init__(self, params, n_classes, layer=('probs_dimshuffle',), pad=100, temperature=1.0,
                  device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5, wgrad='f32',
-                 dgrad='f32', kxk='f32'):
+                 dgrad='f32', kxk='f32', fwd='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; 'bf16c8' = additionally bf16 C8
         activations between the 3x3 layers, the h maps handed out stay fp32 NCHW; ops.Conv).
@@ -54,7 +55,14 @@ class FCN8:
         and fc7 (1x1) ('f32' default; 'bf16' = ops.conv_wgrad_kxk(mma='bf16') and ops.conv_dgrad_kxk on the
         parameters themselves, every operand rounded once to bf16, fp32 accumulation, no flipped fp32 copy of
         either filter -- float32 trainable modules only; the 11-channel score layers, the transposed layers and
-        the forward stay float32: DESIGN.md section 17).  Independent of wgrad and dgrad."""
+        the forward stay float32: DESIGN.md section 17).  Independent of wgrad and dgrad.
+        fwd: operand precision of `forward_train`'s thirteen 3x3 layers, fc6 and fc7, with and without
+        deterministic=True ('f32' default; 'bf16' = z = relu(sum bf16(W) bf16(x) + b), every operand rounded once
+        to bf16 as it is staged, fp32 accumulation in a fixed order, the bias added in fp32, the map stored as fp32
+        NCHW: the 3x3 layers on conv_halo_bf16_kernel at every size, fc6 / fc7 by ops.conv_fwd_kxk on the
+        parameters themselves -- float32 trainable modules only; parameters, saved maps, the ReLU / pool / dropout
+        decisions (taken on the fp32 values this forward stores), the score and transposed layers, maxpool2x2 and
+        `backward` stay float32 and the same code: DESIGN.md section 18).  Independent of wgrad, dgrad and kxk."""
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
         if wgrad not in ops.WGRAD_MODES:
@@ -75,6 +83,12 @@ class FCN8:
             raise NotImplementedError("kxk='bf16': the 16-bit fc6 / fc7 gradients of a trainable float32 module "
                                       "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
         self.kxk = kxk
+        if fwd not in ops.FWD_MODES:
+            raise ValueError("fwd=%r is not one of %s" % (fwd, ops.FWD_MODES))
+        if fwd == 'bf16' and not (trainable and dtype == torch.float32):
+            raise NotImplementedError("fwd='bf16': the 16-bit training forward of a trainable float32 module "
+                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
+        self.fwd = fwd
         # dgrad='bf16' / kxk='bf16': {name: bf16 filter image}, those up to date
         self._dpack, self._dpack_fresh = {}, set()
         self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
@@ -105,8 +119,10 @@ class FCN8:
         self.device = device
         self.dtype = dtype
         p = params
+        # (fwd='bf16': the fifteen layers say so themselves; a layer built the old way is what it was)
         c = lambda name, pad_, relu=True: ops.Conv(p[name][0], p[name][1], pad=pad_, relu=relu,
-                                                   device=device, dtype=dtype, mma=mma)
+                                                   device=device, dtype=dtype, mma=mma,
+                                                   fwd16=(fwd == 'bf16' and name in _NAMES_FWD16))
         self.convs = {}
         for bi, names in enumerate(_BLOCKS):
             for ni, name in enumerate(names):

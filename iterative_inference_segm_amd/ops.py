@@ -334,7 +334,7 @@ class Conv:
 
     # every form `_choose` can name; each has a `_run_<form>`
     FORMS = ('wino_bf16', 'halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32', 'pool_f64', 'pool_f32',
-             'gemm_bf16', 'gemm_f32', 'gemm_f64', 'wino_f64', 'direct')
+             'gemm_bf16', 'gemm_f32', 'gemm_f64', 'wino_f64', 'direct', 'kxk_bf16')
     # ... and the two `_choose_c8` can name
     C8_FORMS = ('c8', 'c8_m16')
     # ... those with the 2x2 max-pool in their epilogue, and those that read / write DePool2D mask bytes
@@ -342,10 +342,15 @@ class Conv:
     MASK_FORMS = ('halo_bf16', 'wino_f32', 'mask_f64', 'mask_f32')
 
     def __init__(self, W, b, pad, relu, dil=1, layout='oihw', device='cuda', dtype=torch.float32,
-                 transposed=False, mma=None):
+                 transposed=False, mma=None, fwd16=False):
         """transposed=True: 3x3 stride-2 transposed convolution, crop='valid' (Deconv2DLayer
         W[in,out,3,3] -> layout 'iohw'); output (2H+1, 2W+1).  mma: 'f32' | 'bf16' operand
-        precision on the matrix pipe (float32 tensors only; None: ops.DEFAULT_MMA)."""
+        precision on the matrix pipe (float32 tensors only; None: ops.DEFAULT_MMA).
+        fwd16=True (a trainable module's fwd='bf16'; float32 with mma='f32' only): every
+        launch of a plain 3x3 layer takes the 'halo_bf16' form and every launch of an undilated 'valid' K x K
+        'oihw' layer (1 <= K <= 7, not 3) 'kxk_bf16' (conv_fwd_kxk on the parameter itself), whatever
+        BF16_PICKS or the environment say -- a launch neither kernel takes is an error, never another form -- and
+        `refresh()` packs the 3x3 layer's bf16 image again into the buffer it has."""
         self.lib = _lib.load()
         self.mma = (mma or DEFAULT_MMA) if dtype == torch.float32 else 'f32'
         if self.mma not in ('f32', 'bf16', 'bf16c8', 'bf16x3'):
@@ -409,6 +414,15 @@ class Conv:
         # bf16 mode: every other plain 3x3 layer on the bf16 halo kernel (conv_halo_bf16.hip)
         self.halo_bf16 = self.mma == 'bf16' and self.plain3x3 and not self.wino_bf16
         self.c8 = self.c8 and self.plain3x3
+        self.fwd16 = bool(fwd16)
+        if self.fwd16:
+            kxk = (self.KH == self.KW and 1 <= self.KH <= 7 and self.dil == 1 and self.pad == 0 and
+                   not self.transposed and layout == 'oihw')
+            if dtype != torch.float32 or self.mma != 'f32' or self.c8 or not (self.plain3x3 or kxk):
+                raise NotImplementedError("Conv(fwd16=True): a float32 mma='f32' layer, plain 3x3 or 'valid' K x K "
+                                          "'oihw' with 1 <= K <= 7 (dtype %s, mma %r, filter %dx%d, pad %d, dil %d)"
+                                          % (dtype, self.mma, self.KH, self.KW, self.pad, self.dil))
+        self._W16_desc = None       # fwd16: the descriptor `_W16` was packed for (`refresh`)
         self._U = None
         self._U16 = None
         self._W16 = None
@@ -496,8 +510,9 @@ class Conv:
         """After `self.W` / `self.b` have been changed IN PLACE (an optimizer step): packs every entry of
         `_packs` again into the buffers it already has -- launches that hold their addresses (a captured graph)
         see the new weights.  Layers that already hold a Winograd / 16-bit transform of their weights are
-        refused: those live in tensors a captured graph would keep pointing at.  No host wait."""
-        if any(t is not None for t in (self._U, self._U16, self._W16, self._W16c8)):
+        refused: those live in tensors a captured graph would keep pointing at -- except a fwd16 layer's bf16
+        halo image, which is packed again in place here.  No host wait."""
+        if any(t is not None for t in (self._U, self._U16, None if self.fwd16 else self._W16, self._W16c8)):
             raise NotImplementedError('Conv.refresh: this layer holds transformed weights (Winograd / bf16 forms); '
                                       'only the direct kernels\' packs are refreshed in place')
         so, sc = (self.Cin * self.KH * self.KW, 1) if self.via_im2col else (self.so, self.sc)
@@ -509,6 +524,8 @@ class Conv:
             else:
                 check(self.lib.iiseg_conv_pack_f32(_stream(), C.byref(d), _ptr(self.W), so, sc,
                                                    _ptr(wp), _ptr(ktab, torch.int32)), 'iiseg_conv_pack_f32')
+        if self.fwd16 and self._W16 is not None:
+            self._pack_halo_bf16(self._W16_desc, profiled=True)
 
     def _plan(self, B, C1, C2, H, W, window, add_geom, unpool, out_slice=None, place=None,
               anchor=(0, 0)):
@@ -528,6 +545,15 @@ class Conv:
         if masked and not self.mask_ok(False):
             raise RuntimeError('DePool2D byte masks need a halo-kernel or fp32 Winograd layer '
                                '(Conv.mask_ok)')
+        if self.fwd16:
+            # one kernel and one rounding statement per layer class; nothing else may run the launch
+            if self.plain3x3 and lib.iiseg_conv_halo_bf16_supported(dp):
+                return 'halo_bf16'
+            if not self.plain3x3 and not (masked or pool or add or x2 or unpool) and \
+                    (d.oy0, d.ox0, d.OH, d.OW) == (0, 0) + self.out_hw(d.H, d.W) and not d.out_ctot and not d.out_H:
+                return 'kxk_bf16'
+            raise RuntimeError('Conv(fwd16=True): neither conv_halo_bf16_kernel nor conv_fwd_kxk_bf16_kernel takes '
+                               'this launch (%dx%d filter, window / placement / extras)' % (self.KH, self.KW))
         plain = not masked and not pool
         if plain and self.wino_bf16 and lib.iiseg_conv_wino_bf16_supported(dp):
             if lib.iiseg_conv_halo_bf16_supported(dp):
@@ -919,13 +945,28 @@ class Conv:
         if self._W16 is None:
             self._W16 = torch.empty(lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(d)) // 2,
                                     dtype=torch.bfloat16, device=self.W.device)
-            check(lib.iiseg_conv_halo_bf16_pack(_stream(), C.byref(d), _ptr(self.W), self.so,
-                                                self.sc, _ptr(self._W16, torch.bfloat16)),
-                  'iiseg_conv_halo_bf16_pack')
+            self._W16_desc = d
+            self._pack_halo_bf16(d)
         _launch('conv_halo_bf16_kernel', self.flops(d.B, d.OH, d.OW), lib.iiseg_conv_halo_bf16,
                 C.byref(d), _ptr(c.x1), _ptr(c.x2), _ptr(c.pre), _ptr(c.pooled),
                 _ptr(self._W16, torch.bfloat16), _ptr(self.b), _ptr(c.add), _ptr(c.out), _ptr(c.pool_out),
                 _ptr(c.mask_in, torch.uint8), _ptr(c.mask_out, torch.uint8))
+
+    def _pack_halo_bf16(self, d, profiled=False):
+        """The bf16 image of the 3x3 filter (it depends on the channel counts only) into `_W16`: one launch, no host
+        wait.  profiled: recorded under CONV_PROFILE (the per-step re-pack of `refresh`; first use never is)."""
+        args = (C.byref(d), _ptr(self.W), C.c_int64(self.so), C.c_int64(self.sc), _ptr(self._W16, torch.bfloat16))
+        if not profiled:
+            check(self.lib.iiseg_conv_halo_bf16_pack(_stream(), *args), 'iiseg_conv_halo_bf16_pack')
+            return
+        kern = 'halo_pack_bf16_kernel'
+        _launch(kern, 0.0, self.lib.iiseg_conv_halo_bf16_pack, *args)
+        if CONV_PROFILE is not None:
+            _add_bytes(kern, 4.0 * self.W.numel() + 2.0 * self._W16.numel())
+
+    def _run_kxk_bf16(self, c):
+        """fwd16: the 'valid' K x K layer on the parameter itself (conv_fwd_kxk, csrc/conv_kxk_bf16.hip)."""
+        conv_fwd_kxk(c.x1, self.W, self.b, relu=self.relu, out=c.out)
 
     def _wino_gemm_flops(self, d, K):
         """Multiplies the 16 Winograd GEMMs of a launch actually issue: 16 * 2 * K * Cout * tiles."""
@@ -2500,6 +2541,61 @@ def conv_dgrad_kxk(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=F
         # when it is added to), the gate read
         _add_bytes(kern, 4.0 * gz.numel() + 2.0 * n + 8.0 * nws +
                    4.0 * out.numel() * (1 + int(bool(accumulate)) + (gate is not None)))
+    return out
+
+
+FWD_MODES = ('f32', 'bf16')
+
+
+def conv_fwd_kxk_desc(x_shape, Wshape, relu=True):
+    """The iiseg_conv_fwd_kxk_desc of the 'valid' K x K stride-1 layer with 'oihw' parameter `Wshape` on an x of
+    `x_shape` = (B,Cin,H,W)."""
+    d = _lib.ConvFwdKxKDesc()
+    d.B, d.Cin, d.H, d.W = (int(v) for v in x_shape)
+    d.Cout, d.K, d.relu = int(Wshape[0]), int(Wshape[2]), int(bool(relu))
+    return d
+
+
+def conv_fwd_kxk(x, W, b=None, relu=True, out=None):
+    """The forward of the 'valid' K x K stride-1 layer (1 <= K <= 7) with fp32 'oihw' parameter W (read as it is: no
+    im2col image, no packed copy) and bias b (or None), on the 16-bit matrix pipe (csrc/conv_kxk_bf16.hip, DESIGN.md
+    section 18): z[b,co,y,x] = relu(sum_{ci,ky,kx} bf16(W[co,ci,ky,kx]) bf16(x[b,ci,y+ky,x+kx]) + b[co]), every
+    operand rounded once (nearest, ties to even) as it is staged, fp32 accumulation in a fixed order by
+    v_mfma_f32_32x32x16_bf16, the slabs of a split reduction added in slab order, the bias added in fp32.  Into
+    `out` (B,Cout,H-K+1,W-K+1) or a new tensor.  float32 contiguous device tensors only."""
+    for name, t in (('x', x), ('W', W), ('b', b), ('out', out)):
+        if t is None and name in ('b', 'out'):
+            continue
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError('conv_fwd_kxk: %s must be a float32 tensor (got %s)'
+                             % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if W.dim() != 4 or W.shape[2] != W.shape[3] or not 1 <= W.shape[2] <= 7:
+        raise ValueError('conv_fwd_kxk: W %s is not a K x K parameter, 1 <= K <= 7' % (tuple(W.shape),))
+    K = int(W.shape[2])
+    if x.dim() != 4 or x.shape[1] != W.shape[1] or x.shape[2] < K or x.shape[3] < K or x.shape[0] < 1:
+        raise ValueError("conv_fwd_kxk: x %s, W %s ('oihw')" % (tuple(x.shape), tuple(W.shape)))
+    if b is not None and tuple(b.shape) != (W.shape[0],):
+        raise ValueError('conv_fwd_kxk: b %s for %d output channels' % (tuple(b.shape), W.shape[0]))
+    shape = (x.shape[0], W.shape[0], x.shape[2] - K + 1, x.shape[3] - K + 1)
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError('conv_fwd_kxk: out %s, the map is %s' % (tuple(out.shape), shape))
+    for name, t in (('x', x), ('W', W), ('b', b), ('out', out)):
+        if t is not None and not t.is_cuda:
+            raise ValueError('conv_fwd_kxk: %s must be a device tensor (got %s)' % (name, t.device))
+        if t is not None and not t.is_contiguous():
+            raise ValueError('conv_fwd_kxk: %s must be contiguous' % name)
+    d = conv_fwd_kxk_desc(tuple(x.shape), tuple(W.shape), relu)
+    lib = _lib.load()
+    nws = _count(lib.iiseg_conv_fwd_kxk_bf16_workspace_elems(C.byref(d)), 'iiseg_conv_fwd_kxk_bf16_workspace_elems')
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    ws = _workspace('f32', nws, x.device) if nws else None
+    kern = 'conv_fwd_kxk_bf16_kernel'
+    _launch(kern, 2.0 * d.Cin * d.Cout * K * K * out.shape[0] * out.shape[2] * out.shape[3],
+            lib.iiseg_conv_fwd_kxk_bf16, C.byref(d), _ptr(x), _ptr(W), _ptr(b), _ptr(ws), _ptr(out))
+    if CONV_PROFILE is not None:
+        # byte model: x and the parameter read once, the slabs written and read once, z written once
+        _add_bytes(kern, 4.0 * (x.numel() + W.numel() + 2 * nws + out.numel()))
     return out
 
 

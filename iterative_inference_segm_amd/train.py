@@ -45,6 +45,15 @@ def check_kxk(kxk, dtype):
                                   'be float32 (got %s)' % (dtype,))
 
 
+def check_fwd(fwd, dtype):
+    """The mode of FCN-8's training forward of a run (host only): 'f32', or 'bf16' with float32."""
+    if fwd not in ops.FWD_MODES:
+        raise ValueError('fwd must be one of %s (got %r)' % (', '.join(ops.FWD_MODES), fwd))
+    if fwd == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
+        raise NotImplementedError("fwd='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
+                                  'be float32 (got %s)' % (dtype,))
+
+
 def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
                     optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32', dgrad='f32'):
     """Raises NotImplementedError / ValueError with the reason for everything this slice does not train

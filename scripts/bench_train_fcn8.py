@@ -30,8 +30,18 @@ fp32 K x K kernel and flipped-filter layer or conv_wgrad_kxk_bf16_kernel and con
 finalize) -- each with its fraction of the mode's peak and next to the layer's forward launch, `kxk_pack_ms` (the
 two filter images' pack launches of the step), `refresh_ms` and `max_memory_allocated_mb` (torch.cuda's peak over
 the timed steps).  DESIGN section 17.
+--fwd: the modes of the training forward to run (`--fwd f32 f32 bf16`), one row per (wgrad, dgrad, kxk, fwd) in the
+same process.  Every row lists under `fwd_layers` the forward launch of the thirteen 3x3 layers, fc6 and fc7 in its
+mode -- kernel, ms, fraction of the mode's peak -- and for fc6 / fc7 the yardstick `gemm_bf16_ms`: the existing
+ops.Conv(..., mma='bf16') im2col + GEMM form (iiseg_conv_gemm_bf16) of that same layer on the step's own input map;
+both rows' own layer is timed the yardstick's way too (`warm_ms`: the mean of five back-to-back calls between two
+HIP events, after one warm-up call, operands warm in the last-level cache), so that `warm_ms` and `gemm_bf16_ms`
+compare like for like while `forward_ms` is the single launch inside the profiled step, its operands cold;
+the bf16 rows add the K x K launches' GB/s on their byte model against `--stream_gbs`.  `fwd_pack_ms`: the 3x3
+layers' bf16 images packed again by one refresh() (0 in the fp32 mode).  DESIGN section 18.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -41,7 +51,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from iterative_inference_segm_amd import ops, synthetic as S              # noqa: E402
+from iterative_inference_segm_amd import _lib, ops, synthetic as S        # noqa: E402
 from iterative_inference_segm_amd.fcn8 import FCN8, PARAM_ORDER           # noqa: E402
 from iterative_inference_segm_amd.train import FCN8Trainer                # noqa: E402
 from dgrad_bench import launches, layer_rows, marked, yardstick           # noqa: E402
@@ -49,12 +59,14 @@ from dgrad_bench import launches, layer_rows, marked, yardstick           # noqa
 DECONVS = ('upsample', 'score4', 'score2')
 KXK = ('score_pool3', 'score_pool4', 'score_fr', 'fc7', 'fc6')
 KXK16 = ('fc7', 'fc6')                                   # the layers of kxk='bf16', in backward's order
+FWD_IN = {'fc6': 'in_fc6', 'fc7': 'drop6'}               # the saved input maps of the two K x K layers of fwd='bf16'
 
 
 def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, wgrad='f32',
-        peak_bf16=2500.0, dgrad='f32', yard=None, kxk='f32'):
+        peak_bf16=2500.0, dgrad='f32', yard=None, kxk='f32', fwd='f32', gyard=None):
     params = S.make_fcn8_params(3, 11, seed=1234, width_div=width_div, fc_channels=fc_channels)
-    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad, kxk=kxk)
+    net = FCN8(params, 11, layer=['score'], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad, kxk=kxk,
+               fwd=fwd)
     tr = FCN8Trainer(net, 11, [11], learning_rate=1e-4, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
@@ -79,6 +91,17 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     e1.record()
     torch.cuda.synchronize()
     refresh_ms = e0.elapsed_time(e1) / 5
+    # the bf16 images of the 3x3 layers that one refresh() packs again (fwd='bf16' only)
+    prof = []
+    ops.profile_begin()
+    ops.CONV_PROFILE = prof
+    try:
+        net.refresh()
+        torch.cuda.synchronize()
+    finally:
+        ops.CONV_PROFILE = None
+        ops.profile_end()
+    fwd_pack_ms = sum(a.elapsed_time(b) for k, _, a, b in prof if k == 'halo_pack_bf16_kernel')
     # one profiled step: every launch of the library between two marks, in launch order
     prof = []
     ops.KERNEL_BYTES.clear()
@@ -99,11 +122,11 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     convs = [n for n in PARAM_ORDER if n in net.convs]
     # forward_train's order: the thirteen block layers, fc6, fc7, score_fr, score_pool4, score_pool3
     fwd_order = convs[:16] + ['score_pool4', 'score_pool3']
-    fwd = [(k, f, a.elapsed_time(b)) for k, f, a, b in prof[:n_fwd] if f > 0]
-    if len(fwd) != len(fwd_order):
-        raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fwd],))
-    fwd_ms = dict(zip(fwd_order, [t for _, _, t in fwd]))
-    fwd_kernel = dict(zip(fwd_order, [k for k, _, _ in fwd]))
+    fwl = [(k, f, a.elapsed_time(b)) for k, f, a, b in prof[:n_fwd] if f > 0]
+    if len(fwl) != len(fwd_order):
+        raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fwl],))
+    fwd_ms = dict(zip(fwd_order, [t for _, _, t in fwl]))
+    fwd_kernel = dict(zip(fwd_order, [k for k, _, _ in fwl]))
     back = prof[n_fwd:]
     by = lambda kern: [(f, a.elapsed_time(b)) for k, f, a, b in back if k == kern]
     # backward's order of the weight gradients
@@ -175,6 +198,45 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
                         'wgrad_ms': round(tw_, 4), 'wgrad_fraction_of_peak': round(fw / (tw_ * 1e-3) / (kpeak * 1e12), 4),
                         'dgrad_ms': round(t, 4), 'dgrad_kernel': kern,
                         'dgrad_fraction_of_peak': round(f / (t * 1e-3) / (kpeak * 1e12), 4)})
+    # the fifteen layers of the fwd mode: the forward launch of this row's mode; fc6 / fc7 next to the existing 16-bit
+    # im2col + GEMM form of the same layer on the same input (timed once per process, after the step's figures)
+    fpeak = peak_bf16 if fwd == 'bf16' else peak
+    if gyard is not None and not gyard:
+        for n in FWD_IN:
+            conv = ops.Conv(net.convs[n].W.clone(), net.convs[n].b.clone(), pad=0, relu=True, dtype=dt, mma='bf16')
+            xin = sv[FWD_IN[n]]
+            conv(xin)
+            assert conv._W16 is not None and not conv._packs          # iiseg_conv_gemm_bf16 ran
+            gyard[n] = timed(lambda: conv(xin))
+            del conv
+    # the fp32 split-K GEMM form runs an im2col and an output kernel around its matrix launch: their time too
+    gl = [n for n in fwd_order if fwd_kernel[n] == 'wino_gemm_kernel']
+    around = [[a.elapsed_time(b) for k, _, a, b in prof[:n_fwd] if k == kern]
+              for kern in ('gemm_im2col_kernel', 'gemm_output_kernel')]
+    staged = {}
+    if all(len(v) == len(gl) for v in around):
+        staged = {n: around[0][i] + around[1][i] for i, n in enumerate(gl)}
+    flayers = []
+    for n in convs[:15]:
+        fl = net.convs[n].flops(B, *sv[n].shape[2:])
+        row = {'layer': n, 'forward_kernel': fwd_kernel[n], 'forward_ms': round(fwd_ms[n], 4),
+               'fraction_of_peak': round(fl / (fwd_ms[n] * 1e-3) / (fpeak * 1e12), 4)}
+        if n in staged:
+            row['forward_ms_with_im2col_and_output'] = round(fwd_ms[n] + staged[n], 4)
+        if n in FWD_IN:
+            xw = sv[FWD_IN[n]]
+            row['warm_ms'] = round(timed(lambda: net.convs[n](xw)), 4)
+            if gyard:
+                row['gemm_bf16_ms'] = round(gyard[n], 4)
+            if fwd == 'bf16':
+                xin, Wn = sv[FWD_IN[n]], net.convs[n].W
+                d = ops.conv_fwd_kxk_desc(tuple(xin.shape), tuple(Wn.shape))
+                lib = _lib.load()
+                nws = lib.iiseg_conv_fwd_kxk_bf16_workspace_elems(C.byref(d))
+                nbytes = 4.0 * (xin.numel() + Wn.numel() + 2 * nws + sv[n].numel())
+                row.update(slabs=lib.iiseg_conv_fwd_kxk_bf16_slabs(C.byref(d)), model_mb=round(nbytes / 1e6, 1),
+                           fraction_of_stream=round(nbytes / (fwd_ms[n] * 1e-3) / 1e9 / stream, 4))
+        flayers.append(row)
     elem = []
     for kern in ('relu_gate_kernel', 'l2_term_kernel', 'deconv_dgrad_kernel'):
         t = sum(t for _, t in by(kern))
@@ -194,7 +256,10 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
     dlayers = layer_rows(dnames, {n: (t, k) for n, (t, _, k) in zip(dnames, dg)},
                          {n: f for n, (_, f, _) in zip(dnames, dg)}, peak_bf16 if dgrad == 'bf16' else peak,
                          yard if dgrad == 'bf16' else None)
-    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad, 'kxk': kxk,
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad, 'kxk': kxk, 'fwd': fwd,
+            'fwd_layers': flayers, 'fwd_3x3_ms_total': round(sum(r['forward_ms'] for r in flayers[:13]), 4),
+            'fwd_kxk_ms_total': round(sum(r['forward_ms'] for r in flayers[13:]), 4),
+            'fwd_pack_ms': round(fwd_pack_ms, 4),
             'kxk_layers': klayers, 'kxk_pack_ms': round(kxk_pack_ms, 4),
             'kxk_ms_total': round(sum(r['wgrad_ms'] + r['dgrad_ms'] for r in klayers) + kxk_pack_ms, 4),
             'max_memory_allocated_mb': round(peak_mem / 2.0 ** 20, 1),
@@ -218,6 +283,7 @@ def main():
     ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--dgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--kxk', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--fwd', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     ap.add_argument('--stream_gbs', type=float, default=6600.0)
     ap.add_argument('--width_div', type=int, default=1)
@@ -225,11 +291,12 @@ def main():
     ap.add_argument('--weight_decay', type=float, default=1e-4)
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split('x'))
-    yard = {}
+    yard, gyard = {}, {}
     rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.width_div,
-                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16, dmode, yard, kmode)
-            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad for kmode in a.kxk
-            if (mode == 'f32' and dmode == 'f32' and kmode == 'f32') or name == 'float32']
+                a.fc_channels, a.weight_decay, mode, a.peak_tflops_bf16, dmode, yard, kmode, fmode,
+                gyard if name == 'float32' else None)
+            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad for kmode in a.kxk for fmode in a.fwd
+            if (mode == 'f32' and dmode == 'f32' and kmode == 'f32' and fmode == 'f32') or name == 'float32']
     print(json.dumps({'bench': 'train_fcn8', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
                       'peak_tflops_bf16': a.peak_tflops_bf16,
                       'stream_gbs': a.stream_gbs, 'reps': a.reps, 'results': rows}))

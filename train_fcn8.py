@@ -30,6 +30,9 @@ name (config.txt records the mode).  With `--dtype float64` it is refused like t
 the 16-bit matrix pipe from the parameters and g_z rounded once to bf16; config.txt records it as well.
 `--kxk bf16` (the same conditions) forms the weight and data gradients of fc6 and fc7 on the
 16-bit matrix pipe, likewise; config.txt records it as well.
+`--fwd bf16` (the same conditions) runs the thirteen 3x3 layers, fc6 and fc7 of the training and
+validation forward on the 16-bit matrix pipe, operands rounded once to bf16, fp32 accumulation and fp32 maps;
+config.txt records it as well.
 """
 import argparse
 import json
@@ -78,9 +81,9 @@ def one_hot_void_last(L, n_classes):
 
 def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size=(10, 1, 1), num_epochs=1,
                     max_patience=1, learning_rate=1e-4, weight_decay=0.0, early_stop_class=None, wgrad='f32',
-                    dgrad='f32', kxk='f32'):
+                    dgrad='f32', kxk='f32', fwd='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
-    from iterative_inference_segm_amd.train import check_dgrad, check_kxk, check_wgrad
+    from iterative_inference_segm_amd.train import check_dgrad, check_fwd, check_kxk, check_wgrad
     if savepath is None:
         raise ValueError('A saving directory must be specified')                        # train_fcn8.py:55-56
     if pascal:
@@ -92,6 +95,7 @@ def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size
     check_wgrad(wgrad, dtype)
     check_dgrad(dgrad, dtype)
     check_kxk(kxk, dtype)
+    check_fwd(fwd, dtype)
     if not (isinstance(batch_size, (list, tuple)) and len(batch_size) == 3 and all(int(b) >= 1 for b in batch_size)):
         raise ValueError('batch_size must be [train, val, test], each >= 1')
     if int(num_epochs) < 1 or int(max_patience) < 1:
@@ -105,14 +109,15 @@ def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size
 def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_patience=100, data_augmentation={},
           savepath=None, loadpath=None, early_stop_class=None, batch_size=None, resume=False,
           train_from_0_255=False, synthetic=False, n_images=20, image_size=None, seed=0, dtype='float32',
-          width_div=1, fc_channels=4096, max_batches=None, wgrad='f32', dgrad='f32', kxk='f32',
+          width_div=1, fc_channels=4096, max_batches=None, wgrad='f32', dgrad='f32', kxk='f32', fwd='f32',
           verbose=True):
     """Signature of reference train_fcn8.py:41-48 plus keyword-only extras.  wgrad ('f32' | 'bf16': the 3x3 weight
     gradients' operand precision) is recorded in config.txt and stays out of the experiment name: the checkpoints
-    are float32 either way; dgrad (the 3x3 data gradients') and kxk (fc6's and fc7's gradients) likewise.  Returns the per-epoch lists and the experiment folder."""
+    are float32 either way; dgrad (the 3x3 data gradients'), kxk (fc6's and fc7's gradients) and fwd (the training
+    forward's fifteen wide layers) likewise.  Returns the per-epoch lists and the experiment folder."""
     bs = list(batch_size) if batch_size is not None else [10, 1, 1]                     # :84-87
     check_supported(dataset, savepath, False, dtype, bs, num_epochs, max_patience, learn_step, weight_decay,
-                    early_stop_class, wgrad, dgrad, kxk)
+                    early_stop_class, wgrad, dgrad, kxk, fwd)
     exp_name = experiment_name(data_augmentation)
     loadpath = loadpath if loadpath is not None else savepath
     savepath = os.path.join(savepath, dataset, exp_name)
@@ -126,7 +131,7 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
                                       data_augmentation=data_augmentation, early_stop_class=early_stop_class,
                                       batch_size=bs, resume=resume, train_from_0_255=train_from_0_255, seed=seed,
                                       dtype=dtype, width_div=width_div, fc_channels=fc_channels,
-                                      wgrad=wgrad, dgrad=dgrad, kxk=kxk).items()):
+                                      wgrad=wgrad, dgrad=dgrad, kxk=kxk, fwd=fwd).items()):
             f.write('{} = {}\n'.format(key, value))
 
     # ---- from here on: the GPU ----
@@ -159,7 +164,7 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
         like = S.make_fcn8_params(nb_in_channels, n_classes, seed=1234, width_div=width_div, fc_channels=fc_channels)
         params = glorot_params({n: (like[n][0].shape, like[n][1].shape[0]) for n in PARAM_ORDER}, 4321 + int(seed))
     net = FCN8(params, n_classes, layer=['probs_dimshuffle'], dtype=tdt, mma='f32', trainable=True,
-               wgrad=wgrad, dgrad=dgrad, kxk=kxk)
+               wgrad=wgrad, dgrad=dgrad, kxk=kxk, fwd=fwd)
     trainer = FCN8Trainer(net, n_classes, void_labels, learning_rate=learn_step, weight_decay=weight_decay, seed=seed)
 
     def batch(it):
@@ -277,6 +282,10 @@ def make_parser():
                         help="float32: operand precision of fc6's and fc7's weight and data gradients (bf16: "
                              'v_mfma_f32_32x32x16_bf16 on operands rounded once, fp32 accumulation).  '
                              'Recorded in config.txt, not in the experiment name')
+    parser.add_argument('--fwd', choices=['f32', 'bf16'], default='f32',
+                        help="float32: operand precision of the training and validation forward's 3x3 layers, fc6 "
+                             'and fc7 (bf16: v_mfma_f32_32x32x16_bf16 on operands rounded once, fp32 accumulation, '
+                             'fp32 maps).  Recorded in config.txt, not in the experiment name')
     parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
     parser.add_argument('--width_div', type=int, default=1, help='divide the channel counts (small nets for tests)')
     parser.add_argument('--fc_channels', type=int, default=4096)
@@ -295,7 +304,7 @@ def main(argv=None):
     try:
         check_supported(args.dataset, args.savepath, args.pascal, args.dtype, args.batch_size, args.num_epochs,
                         args.max_patience, args.learning_rate, args.penal_cst, args.early_stop_class, args.wgrad,
-                        args.dgrad, args.kxk)
+                        args.dgrad, args.kxk, args.fwd)
     except (NotImplementedError, ValueError, TypeError) as e:
         print('train_fcn8.py: ' + str(e), file=sys.stderr)
         return 2
@@ -305,7 +314,7 @@ def main(argv=None):
           resume=args.resume, train_from_0_255=args.train_from_0_255, synthetic=args.synthetic,
           n_images=args.n_images, image_size=args.image_size, seed=args.seed, dtype=args.dtype,
           width_div=args.width_div, fc_channels=args.fc_channels, max_batches=args.max_batches, wgrad=args.wgrad,
-          dgrad=args.dgrad, kxk=args.kxk)
+          dgrad=args.dgrad, kxk=args.kxk, fwd=args.fwd)
     return 0
 
 
