@@ -30,7 +30,7 @@
 // 64-channel layers at 422 x 422, two k-tiles per workgroup, ran slower than their fp32 launch).
 // The epilogue writes gx, adds what gx held (accumulate) and applies the gate (gx * [gate > 0], relu'(0) = 0), in
 // that order.
-#include "common.h"
+#include "mma16_common.h"
 
 namespace {
 
@@ -45,10 +45,6 @@ constexpr int WSLICES = 9 * NCHUNK;                      // [tap][chunk] slices 
 constexpr int WN = (WSLICES + 3) / 4;                    // ... a staging wave copies: slices sw, sw + 4, ...
 static_assert(CB == 64 && NCHUNK == 2 && GN % 2 == 0 && KT % 16 == 0, "the staging waves' split of an image");
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct cd_params {
     int B, Cin, Cout, H, W;
     int cin_pad;                   // Cin rounded up to CB
@@ -57,12 +53,6 @@ struct cd_params {
     int ci0, accumulate;
     long long so, sc;
 };
-
-// fp32 -> bf16 (round to nearest even)
-__device__ __forceinline__ unsigned to_bf16(float a) {
-    return __builtin_bit_cast(unsigned short, static_cast<__bf16>(a));
-}
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return to_bf16(lo) | (to_bf16(hi) << 16); }
 
 // The packed filter: element e of [k-tile][tap][chunk][cin_pad][8].
 __global__ __launch_bounds__(256) void conv_dgrad_bf16_pack_kernel(cd_params p, const float* __restrict__ Wp,
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(512, 4) void conv_dgrad_bf16_kernel(cd_params p, co
                 float v[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = gin[j] && c0 + i < p.Cout ? gv[i][j] : 0.f;
-                u32x4 w;
+                u32x4 w;                                                 // (not pack8(v): the call allocates registers differently)
                 w.x = pack2(v[0], v[1]); w.y = pack2(v[2], v[3]); w.z = pack2(v[4], v[5]); w.w = pack2(v[6], v[7]);
                 const int k = lane + 64 * (2 * j + pass0);
                 if (k < NPIX) gs[chunk * NPIX + k] = w;
@@ -223,10 +213,7 @@ int cd_plan(const iiseg_conv_dgrad_desc* d, cd_params& p) {
     if (d->B < 1 || d->B > 65535 || d->Cin < 1 || d->Cin > 65535 || d->Cout < 1 || d->Cout > 65535 || d->H < 1 ||
         d->W < 1 || (int64_t)d->H * d->W > (int64_t)1 << 28)
         return IISEG_ERR_SHAPE;
-    if (d->ci0 < 0 || d->Cin_tot < 1 || d->Cin_tot > 65535 || (int64_t)d->ci0 + d->Cin > d->Cin_tot) return IISEG_ERR_SHAPE;
-    if (!((d->so == (int64_t)d->Cin_tot * 9 && d->sc == 9) || (d->so == 9 && d->sc == (int64_t)d->Cout * 9)))
-        return IISEG_ERR_SHAPE;
-    if ((int64_t)d->Cout * d->Cin_tot * 9 > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    if (!param_layout_ok(d->so, d->sc, d->ci0, d->Cin, d->Cin_tot, d->Cout, 9)) return IISEG_ERR_SHAPE;
     if (d->accumulate != 0 && d->accumulate != 1) return IISEG_ERR_SHAPE;
     p.B = d->B; p.Cin = d->Cin; p.Cout = d->Cout; p.H = d->H; p.W = d->W;
     p.cin_pad = (d->Cin + CB - 1) / CB * CB;
@@ -240,11 +227,6 @@ int cd_plan(const iiseg_conv_dgrad_desc* d, cd_params& p) {
 }
 
 int64_t cd_pack_elems(const cd_params& p) { return (int64_t)p.nkt * 9 * KT * p.cin_pad; }
-
-bool cd_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
-}
 
 }  // namespace
 
@@ -263,7 +245,7 @@ extern "C" int iiseg_conv_dgrad_bf16_pack(void* stream, const iiseg_conv_dgrad_d
     if (!W || !packed) return IISEG_ERR_NULL;
     if ((uintptr_t)W % 4 || (uintptr_t)packed % 16) return IISEG_ERR_ALIGN;
     const int64_t n = cd_pack_elems(p);
-    if (cd_overlap(W, (int64_t)d->Cout * d->Cin_tot * 9 * 4, packed, n * 2)) return IISEG_ERR_UNSUPPORTED;
+    if (ranges_overlap(W, (int64_t)d->Cout * d->Cin_tot * 9 * 4, packed, n * 2)) return IISEG_ERR_UNSUPPORTED;
     IISEG_LAUNCH(conv_dgrad_bf16_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p,
                  W, (unsigned short*)packed, (long long)n);
     return iiseg_check_launch();
@@ -277,7 +259,7 @@ extern "C" int iiseg_conv_dgrad_bf16(void* stream, const iiseg_conv_dgrad_desc* 
     const int64_t plane = (int64_t)d->H * d->W, gzb = (int64_t)d->B * d->Cout * plane * 4,
                   gxb = (int64_t)d->B * d->Cin * plane * 4;
     // gx is written while other workgroups still read g_z and the filter image
-    if (cd_overlap(gx, gxb, gz, gzb) || cd_overlap(gx, gxb, packed, cd_pack_elems(p) * 2)) return IISEG_ERR_UNSUPPORTED;
+    if (ranges_overlap(gx, gxb, gz, gzb) || ranges_overlap(gx, gxb, packed, cd_pack_elems(p) * 2)) return IISEG_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)(p.B * p.tilesY * p.tilesX * (p.cin_pad / CB)));
     IISEG_LAUNCH(conv_dgrad_bf16_kernel, grid, dim3(512), 0, (hipStream_t)stream, p, gz,
                  reinterpret_cast<const u32x4*>(packed), gate, gx);

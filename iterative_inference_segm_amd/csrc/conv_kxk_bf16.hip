@@ -48,27 +48,12 @@
 // pixel tiles (two per wave; K = 1, where nothing is re-used across taps: 128 output channels x four tiles, one per
 // wave): eight accumulators per wave either way.  One slab: the epilogue adds the bias and applies ReLU; more: the
 // slabs go to the workspace and the finalize adds them in slab order, then the bias, then ReLU.
-#include "common.h"
+#include "mma16_common.h"
 
 namespace {
 
 constexpr int CB = 64;                                   // channels of a workgroup (per side)
 constexpr int KMAX = 7;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// fp32 -> bf16 (round to nearest even)
-__device__ __forceinline__ unsigned to_bf16(float a) {
-    return __builtin_bit_cast(unsigned short, static_cast<__bf16>(a));
-}
-__device__ __forceinline__ unsigned pack2(float lo, float hi) { return to_bf16(lo) | (to_bf16(hi) << 16); }
-__device__ __forceinline__ u32x4 pack8(const float* v) {
-    u32x4 w;
-    w.x = pack2(v[0], v[1]); w.y = pack2(v[2], v[3]); w.z = pack2(v[4], v[5]); w.w = pack2(v[6], v[7]);
-    return w;
-}
 
 // ================================================ weight gradient ================================================
 constexpr int GT = 16;                                   // groups of 8 pixel slots per tile: 8 k-steps
@@ -297,10 +282,7 @@ int kw_plan(const iiseg_conv_wgrad_kxk_desc* d, kw_params& p) {
         d->x_image < (int64_t)d->Cin * d->x_plane || d->x_image > (int64_t)1 << 46)
         return IISEG_ERR_SHAPE;
     const int KK = d->K * d->K;
-    if (d->ci0 < 0 || d->Cin_tot < 1 || d->Cin_tot > 65535 || (int64_t)d->ci0 + d->Cin > d->Cin_tot) return IISEG_ERR_SHAPE;
-    if (!((d->so == (int64_t)d->Cin_tot * KK && d->sc == KK) || (d->so == KK && d->sc == (int64_t)d->Cout * KK)))
-        return IISEG_ERR_SHAPE;
-    if ((int64_t)d->Cout * d->Cin_tot * KK > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    if (!param_layout_ok(d->so, d->sc, d->ci0, d->Cin, d->Cin_tot, d->Cout, KK)) return IISEG_ERR_SHAPE;
     const long long ciB = (d->Cin + CB - 1) / CB, coB = (d->Cout + CB - 1) / CB;
     if (ciB * d->K > 65535) return IISEG_ERR_SHAPE;                      // grid z
     p.B = d->B; p.Cin = d->Cin; p.Cout = d->Cout; p.H = d->H; p.W = d->W;
@@ -313,12 +295,9 @@ int kw_plan(const iiseg_conv_wgrad_kxk_desc* d, kw_params& p) {
     p.P = (unsigned)pix;
     p.G = d->K == 1 ? (pix + 7) / 8 : (long long)d->B * p.OH * p.gpr;
     p.T = (p.G + GT - 1) / GT;
-    const long long blocks = coB * ciB * d->K;
-    const long long target = blocks >= W_TARGET_WORKGROUPS ? 1 : (W_TARGET_WORKGROUPS + blocks - 1) / blocks;
-    long long tps = (p.T + target - 1) / target;
-    if (tps < W_MIN_TILES_PER_SLAB) tps = W_MIN_TILES_PER_SLAB;
+    int64_t tps;
+    split_slabs(p.T, coB * ciB * d->K, W_TARGET_WORKGROUPS, W_MIN_TILES_PER_SLAB, &tps, &p.nslab);
     p.tps = (int)tps;
-    p.nslab = (int)((p.T + tps - 1) / tps);
     p.so = d->so; p.sc = d->sc; p.ci0 = d->ci0;
     p.nW = (long long)d->Cout * d->Cin * KK;
     p.S = p.nW + d->Cout;
@@ -534,10 +513,7 @@ int kd_plan(const iiseg_conv_dgrad_desc* d, kd_params& p) {
     const int KK = d->K * d->K;
     const int64_t H = (int64_t)d->H + d->K - 1, W = (int64_t)d->W + d->K - 1;
     if (H * W > (int64_t)1 << 28) return IISEG_ERR_SHAPE;
-    if (d->ci0 < 0 || d->Cin_tot < 1 || d->Cin_tot > 65535 || (int64_t)d->ci0 + d->Cin > d->Cin_tot) return IISEG_ERR_SHAPE;
-    if (!((d->so == (int64_t)d->Cin_tot * KK && d->sc == KK) || (d->so == KK && d->sc == (int64_t)d->Cout * KK)))
-        return IISEG_ERR_SHAPE;
-    if ((int64_t)d->Cout * d->Cin_tot * KK > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    if (!param_layout_ok(d->so, d->sc, d->ci0, d->Cin, d->Cin_tot, d->Cout, KK)) return IISEG_ERR_SHAPE;
     if (d->accumulate != 0 && d->accumulate != 1) return IISEG_ERR_SHAPE;
     p.B = d->B; p.Cin = d->Cin; p.Cout = d->Cout; p.OH = d->H; p.OW = d->W; p.H = (int)H; p.W = (int)W;
     p.cin_pad = (d->Cin + CB - 1) / CB * CB;
@@ -552,11 +528,9 @@ int kd_plan(const iiseg_conv_dgrad_desc* d, kd_params& p) {
     if (base > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
     p.ntile = (int)ntile;
     if (d->K == 1) { p.tilesY = 1; p.tilesX = (int)ntile; }              // one "image" of flat tiles
-    const int64_t target = base >= D_TARGET_WORKGROUPS ? 1 : (D_TARGET_WORKGROUPS + base - 1) / base;
-    int64_t kps = (p.nkt + target - 1) / target;
-    if (kps < D_MIN_KT_PER_SLAB) kps = D_MIN_KT_PER_SLAB;
+    int64_t kps;
+    split_slabs(p.nkt, base, D_TARGET_WORKGROUPS, D_MIN_KT_PER_SLAB, &kps, &p.nslab);
     p.kps = (int)kps;
-    p.nslab = (int)((p.nkt + kps - 1) / kps);
     p.ci0 = d->ci0; p.accumulate = d->accumulate;
     p.so = d->so; p.sc = d->sc;
     p.N = (long long)d->B * d->Cin * H * W;
@@ -564,11 +538,6 @@ int kd_plan(const iiseg_conv_dgrad_desc* d, kd_params& p) {
 }
 
 int64_t kd_pack_elems(const kd_params& p, int K) { return (int64_t)p.nkt * K * K * KT * p.cin_pad; }
-
-bool kd_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
-}
 
 template <int K>
 void kd_launch(hipStream_t s, const kd_params& p, const dim3& grid, const float* gz, const u32x4* packed,
@@ -799,12 +768,9 @@ int kf_plan(const iiseg_conv_fwd_kxk_desc* d, kf_params& p) {
     if (groups > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
     const int64_t coB = (d->Cout + cbf - 1) / cbf;
     p.nkt = (d->Cin + kf_nch(d->K) * 8 - 1) / (kf_nch(d->K) * 8);
-    const int64_t base = groups * coB;
-    const int64_t target = base >= F_TARGET_WORKGROUPS ? 1 : (F_TARGET_WORKGROUPS + base - 1) / base;
-    int64_t kps = (p.nkt + target - 1) / target;
-    if (kps < F_MIN_KT_PER_SLAB) kps = F_MIN_KT_PER_SLAB;
+    int64_t kps;
+    split_slabs(p.nkt, groups * coB, F_TARGET_WORKGROUPS, F_MIN_KT_PER_SLAB, &kps, &p.nslab);
     p.kps = (int)kps;
-    p.nslab = (int)((p.nkt + kps - 1) / kps);
     if (p.nslab > 65535) return IISEG_ERR_SHAPE;                         // grid z
     p.relu = d->relu;
     p.N = (long long)d->B * d->Cout * p.OH * p.OW;
@@ -844,15 +810,7 @@ extern "C" int iiseg_conv_wgrad_kxk_bf16(void* stream, const iiseg_conv_wgrad_kx
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)p.nslab, (unsigned)((p.Cout + CB - 1) / CB), (unsigned)(((p.Cin + CB - 1) / CB) * d->K));
     float* dst = p.nslab == 1 ? dW : ws;
-    switch (d->K) {
-        case 1: kw_launch<1>(s, p, grid, x, gz, dst, db); break;
-        case 2: kw_launch<2>(s, p, grid, x, gz, dst, db); break;
-        case 3: kw_launch<3>(s, p, grid, x, gz, dst, db); break;
-        case 4: kw_launch<4>(s, p, grid, x, gz, dst, db); break;
-        case 5: kw_launch<5>(s, p, grid, x, gz, dst, db); break;
-        case 6: kw_launch<6>(s, p, grid, x, gz, dst, db); break;
-        default: kw_launch<7>(s, p, grid, x, gz, dst, db); break;
-    }
+    dispatch_k(d->K, [&](auto k) { kw_launch<decltype(k)::value>(s, p, grid, x, gz, dst, db); });
     if (p.nslab > 1)
         IISEG_LAUNCH(conv_wgrad_kxk_bf16_finalize_kernel, dim3((unsigned)((p.S + 255) / 256)), dim3(256), 0, s,
                      (const float*)ws, p.nslab, p.S, p.nW, p.Cin, d->K * d->K, p.so, p.sc, p.ci0, dW, db);
@@ -885,7 +843,7 @@ extern "C" int iiseg_conv_dgrad_kxk_bf16_pack(void* stream, const iiseg_conv_dgr
     if ((uintptr_t)W % 4 || (uintptr_t)packed % 16) return IISEG_ERR_ALIGN;
     const int KK = d->K * d->K;
     const int64_t n = kd_pack_elems(p, d->K);
-    if (kd_overlap(W, (int64_t)d->Cout * d->Cin_tot * KK * 4, packed, n * 2)) return IISEG_ERR_UNSUPPORTED;
+    if (ranges_overlap(W, (int64_t)d->Cout * d->Cin_tot * KK * 4, packed, n * 2)) return IISEG_ERR_UNSUPPORTED;
     IISEG_LAUNCH(conv_dgrad_kxk_bf16_pack_kernel, dim3((unsigned)(p.cin_pad / PCB), (unsigned)p.nkt), dim3(256),
                  (size_t)KK * 2 * PCB * 16, (hipStream_t)stream, p, KK, W, reinterpret_cast<u32x4*>(packed));
     return iiseg_check_launch();
@@ -899,20 +857,12 @@ extern "C" int iiseg_conv_dgrad_kxk_bf16(void* stream, const iiseg_conv_dgrad_de
         return IISEG_ERR_ALIGN;
     const int64_t gzb = (int64_t)d->B * d->Cout * d->H * d->W * 4, gxb = p.N * 4;
     // gx is written while other workgroups still read g_z and the filter image
-    if (kd_overlap(gx, gxb, gz, gzb) || kd_overlap(gx, gxb, packed, kd_pack_elems(p, d->K) * 2)) return IISEG_ERR_UNSUPPORTED;
+    if (ranges_overlap(gx, gxb, gz, gzb) || ranges_overlap(gx, gxb, packed, kd_pack_elems(p, d->K) * 2)) return IISEG_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)(p.ntile * (p.cin_pad / CB)), (unsigned)p.nslab);
     const u32x4* pk = reinterpret_cast<const u32x4*>(packed);
     float* dst = p.nslab == 1 ? gx : ws;
-    switch (d->K) {
-        case 1: kd_launch<1>(s, p, grid, gz, pk, gate, dst); break;
-        case 2: kd_launch<2>(s, p, grid, gz, pk, gate, dst); break;
-        case 3: kd_launch<3>(s, p, grid, gz, pk, gate, dst); break;
-        case 4: kd_launch<4>(s, p, grid, gz, pk, gate, dst); break;
-        case 5: kd_launch<5>(s, p, grid, gz, pk, gate, dst); break;
-        case 6: kd_launch<6>(s, p, grid, gz, pk, gate, dst); break;
-        default: kd_launch<7>(s, p, grid, gz, pk, gate, dst); break;
-    }
+    dispatch_k(d->K, [&](auto k) { kd_launch<decltype(k)::value>(s, p, grid, gz, pk, gate, dst); });
     if (p.nslab > 1)
         IISEG_LAUNCH(conv_dgrad_kxk_bf16_finalize_kernel, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, s,
                      (const float*)ws, p.nslab, p.N, p.accumulate, gate, gx);
@@ -942,22 +892,14 @@ extern "C" int iiseg_conv_fwd_kxk_bf16(void* stream, const iiseg_conv_fwd_kxk_de
         return IISEG_ERR_ALIGN;
     const int64_t zb = p.N * 4;
     // z is written while other workgroups still read x and W
-    if (kd_overlap(z, zb, x, (int64_t)d->B * d->Cin * d->H * d->W * 4) ||
-        kd_overlap(z, zb, W, (int64_t)d->Cout * d->Cin * d->K * d->K * 4))
+    if (ranges_overlap(z, zb, x, (int64_t)d->B * d->Cin * d->H * d->W * 4) ||
+        ranges_overlap(z, zb, W, (int64_t)d->Cout * d->Cin * d->K * d->K * 4))
         return IISEG_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const int fwt = 4 * kf_tpw(d->K), cbf = 32 * kf_mb(d->K);
     const dim3 grid((unsigned)((p.ntile + fwt - 1) / fwt), (unsigned)((p.Cout + cbf - 1) / cbf), (unsigned)p.nslab);
     float* dst = p.nslab == 1 ? z : ws;
-    switch (d->K) {
-        case 1: kf_launch<1>(s, p, grid, x, W, bias, dst); break;
-        case 2: kf_launch<2>(s, p, grid, x, W, bias, dst); break;
-        case 3: kf_launch<3>(s, p, grid, x, W, bias, dst); break;
-        case 4: kf_launch<4>(s, p, grid, x, W, bias, dst); break;
-        case 5: kf_launch<5>(s, p, grid, x, W, bias, dst); break;
-        case 6: kf_launch<6>(s, p, grid, x, W, bias, dst); break;
-        default: kf_launch<7>(s, p, grid, x, W, bias, dst); break;
-    }
+    dispatch_k(d->K, [&](auto k) { kf_launch<decltype(k)::value>(s, p, grid, x, W, bias, dst); });
     if (p.nslab > 1)
         IISEG_LAUNCH(conv_fwd_kxk_bf16_finalize_kernel, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, s,
                      (const float*)ws, p.nslab, p.N, (long long)p.OH * p.OW, p.Cout, bias, p.relu, z);

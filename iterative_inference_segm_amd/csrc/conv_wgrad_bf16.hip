@@ -40,16 +40,6 @@ constexpr int XLD = PH * XROW + 4;                       // bf16 per x channel: 
 constexpr int GPIX = TH * TW, XPIX = PH * PW;            // pixels of a channel's tile / patch
 constexpr int GN = GPIX / 64, XN = (XPIX + 63) / 64;     // loads per lane and channel: pixel lane + 64 j
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// fp32 -> bf16 (round to nearest even)
-__device__ __forceinline__ unsigned short to_bf16(float a) {
-    return __builtin_bit_cast(unsigned short, static_cast<__bf16>(a));
-}
-
 __device__ __forceinline__ bf16x8 frag(unsigned a, unsigned b, unsigned c, unsigned d) {
     u32x4 v;
     v.x = a; v.y = b; v.z = c; v.w = d;

@@ -2,7 +2,7 @@
 // bf16 operands): the launch parameters, the plan of pixel tiles and slabs, the border pixels of a wide zero
 // padding and the finalize launch that adds the slabs in slab order.
 #pragma once
-#include "common.h"
+#include "mma16_common.h"
 
 namespace {
 
@@ -61,11 +61,7 @@ inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw,
         return IISEG_ERR_SHAPE;
     const int64_t OH = (int64_t)d->H + 2 * d->pad - 2, OW = (int64_t)d->W + 2 * d->pad - 2;
     if (OH < 1 || OW < 1 || OH * OW > (int64_t)1 << 30) return IISEG_ERR_SHAPE;
-    // the parameter array: Cin_tot input channels, this call's at [ci0, ci0 + Cin); 'oihw' or 'iohw' strides
-    if (d->ci0 < 0 || d->Cin_tot < 1 || d->Cin_tot > 65535 || (int64_t)d->ci0 + d->Cin > d->Cin_tot) return IISEG_ERR_SHAPE;
-    if (!((d->so == (int64_t)d->Cin_tot * 9 && d->sc == 9) || (d->so == 9 && d->sc == (int64_t)d->Cout * 9)))
-        return IISEG_ERR_SHAPE;
-    if ((int64_t)d->Cout * d->Cin_tot * 9 > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    if (!param_layout_ok(d->so, d->sc, d->ci0, d->Cin, d->Cin_tot, d->Cout, 9)) return IISEG_ERR_SHAPE;
     p.B = d->B; p.Cin = d->Cin; p.Cout = d->Cout; p.H = d->H; p.W = d->W; p.pad = d->pad;
     p.OH = (int)OH; p.OW = (int)OW;
     // output pixel y reads input rows y - pad .. y - pad + 2: it meets [0, H) for y in [pad - 2, H + pad)
@@ -77,12 +73,10 @@ inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw,
     p.tilesX = (p.AW + tw - 1) / tw;
     p.T = (long long)d->B * p.tilesY * p.tilesX;
     const long long blocks = (long long)((d->Cout + cb - 1) / cb) * ((d->Cin + cb - 1) / cb);
-    const long long target = blocks >= target_wgs ? 1 : (target_wgs + blocks - 1) / blocks;
-    long long tps = (p.T + target - 1) / target;
-    if (tps < min_tps) tps = min_tps;
+    int64_t tps;
+    split_slabs(p.T, blocks, target_wgs, min_tps, &tps, &p.nslab);
     if (tps > ((long long)1 << 30)) return IISEG_ERR_SHAPE;
     p.tps = (int)tps;
-    p.nslab = (int)((p.T + tps - 1) / tps);
     p.so = d->so; p.sc = d->sc; p.ci0 = d->ci0;
     p.nW = (long long)d->Cout * d->Cin * 9;
     p.S = p.nW + d->Cout;

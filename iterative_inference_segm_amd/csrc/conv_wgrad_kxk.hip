@@ -20,7 +20,7 @@
 // workspace, and a finalize launch adds the slabs in slab order (in double).  db comes from the workgroups of the
 // first input-channel block and filter row: the g_z values summed as they are read as the A operand.  No atomics:
 // every sum has a fixed order, the same inputs give the same bits.
-#include "common.h"
+#include "mma16_common.h"
 
 namespace {
 
@@ -30,8 +30,6 @@ constexpr int TARGET_WORKGROUPS = 512;                   // two per CU
 constexpr int KMAX = 7;
 
 template <typename T> constexpr int chan_block() { return sizeof(T) == 4 ? 64 : 32; }
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ck_params {
     int B, Cin, Cout, H, W, OH, OW;
@@ -235,11 +233,7 @@ int ck_plan(const iiseg_conv_wgrad_kxk_desc* d, ck_params& p) {
         d->x_image < (int64_t)d->Cin * d->x_plane || d->x_image > (int64_t)1 << 46)
         return IISEG_ERR_SHAPE;
     const int KK = d->K * d->K;
-    // the parameter array: Cin_tot input channels, this call's at [ci0, ci0 + Cin); 'oihw' or 'iohw' strides
-    if (d->ci0 < 0 || d->Cin_tot < 1 || d->Cin_tot > 65535 || (int64_t)d->ci0 + d->Cin > d->Cin_tot) return IISEG_ERR_SHAPE;
-    if (!((d->so == (int64_t)d->Cin_tot * KK && d->sc == KK) || (d->so == KK && d->sc == (int64_t)d->Cout * KK)))
-        return IISEG_ERR_SHAPE;
-    if ((int64_t)d->Cout * d->Cin_tot * KK > ((int64_t)1 << 31) - 1) return IISEG_ERR_SHAPE;
+    if (!param_layout_ok(d->so, d->sc, d->ci0, d->Cin, d->Cin_tot, d->Cout, KK)) return IISEG_ERR_SHAPE;
     constexpr int CB = chan_block<T>();
     const long long ciB = (d->Cin + CB - 1) / CB, coB = (d->Cout + CB - 1) / CB;
     if (ciB * d->K > 65535) return IISEG_ERR_SHAPE;                      // grid z
@@ -253,13 +247,10 @@ int ck_plan(const iiseg_conv_wgrad_kxk_desc* d, ck_params& p) {
     p.tilesX = (p.OW + p.tw - 1) / p.tw;
     p.T = (long long)d->B * p.tilesY * p.tilesX;
     if (d->K == 1) p.T = ((long long)d->B * p.OH * p.OW + PIX - 1) / PIX;          // flat pixel tiles
-    const long long blocks = coB * ciB * d->K;
-    const long long target = blocks >= TARGET_WORKGROUPS ? 1 : (TARGET_WORKGROUPS + blocks - 1) / blocks;
-    long long tps = (p.T + target - 1) / target;
-    if (tps < MIN_TILES_PER_SLAB) tps = MIN_TILES_PER_SLAB;
+    int64_t tps;
+    split_slabs(p.T, coB * ciB * d->K, TARGET_WORKGROUPS, MIN_TILES_PER_SLAB, &tps, &p.nslab);
     if (tps > ((long long)1 << 30)) return IISEG_ERR_SHAPE;
     p.tps = (int)tps;
-    p.nslab = (int)((p.T + tps - 1) / tps);
     p.so = d->so; p.sc = d->sc; p.ci0 = d->ci0;
     p.nW = (long long)d->Cout * d->Cin * KK;
     p.S = p.nW + d->Cout;
@@ -288,15 +279,7 @@ int ck_run(void* stream, const iiseg_conv_wgrad_kxk_desc* d, const T* x, const T
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)p.nslab, (unsigned)((p.Cout + CB - 1) / CB), (unsigned)(((p.Cin + CB - 1) / CB) * d->K));
     T* dst = p.nslab == 1 ? dW : ws;
-    switch (d->K) {
-        case 1: ck_launch<T, 1>(s, p, grid, x, gz, dst, db); break;
-        case 2: ck_launch<T, 2>(s, p, grid, x, gz, dst, db); break;
-        case 3: ck_launch<T, 3>(s, p, grid, x, gz, dst, db); break;
-        case 4: ck_launch<T, 4>(s, p, grid, x, gz, dst, db); break;
-        case 5: ck_launch<T, 5>(s, p, grid, x, gz, dst, db); break;
-        case 6: ck_launch<T, 6>(s, p, grid, x, gz, dst, db); break;
-        default: ck_launch<T, 7>(s, p, grid, x, gz, dst, db); break;
-    }
+    dispatch_k(d->K, [&](auto k) { ck_launch<T, decltype(k)::value>(s, p, grid, x, gz, dst, db); });
     if (p.nslab > 1)
         IISEG_LAUNCH(conv_wgrad_kxk_finalize_kernel<T>, dim3((unsigned)((p.S + 255) / 256)), dim3(256), 0, s,
                      (const T*)ws, p.nslab, p.S, p.nW, p.Cin, d->K * d->K, p.so, p.sc, p.ci0, dW, db);

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ops, regions
-from .params import ParamStore
+from .params import PackedImages, ParamStore, check_mode
 from .regions import center
 from .weights import load_param_list
 
@@ -200,19 +200,12 @@ class StandardDAE:
         concat_h = list(concat_h)
         mma = mma or ops.DEFAULT_MMA
         self.trainable = bool(trainable)
-        if wgrad not in ops.WGRAD_MODES:
-            raise ValueError("wgrad=%r is not one of %s" % (wgrad, ops.WGRAD_MODES))
-        if wgrad == 'bf16' and not (trainable and dtype == torch.float32):
-            raise NotImplementedError("wgrad='bf16': the 16-bit weight gradient of a trainable float32 module "
-                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
-        self.wgrad = wgrad
-        if dgrad not in ops.DGRAD_MODES:
-            raise ValueError("dgrad=%r is not one of %s" % (dgrad, ops.DGRAD_MODES))
-        if dgrad == 'bf16' and not (trainable and dtype == torch.float32):
-            raise NotImplementedError("dgrad='bf16': the 16-bit data gradient of a trainable float32 module "
-                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
-        self.dgrad = dgrad
-        self._dpack, self._dpack_fresh = {}, set()       # dgrad='bf16': {name: bf16 filter image}, those up to date
+        for switch, mode in (('wgrad', wgrad), ('dgrad', dgrad)):
+            setattr(self, switch, check_mode(switch, mode, dtype, bool(trainable)))
+        # dgrad='bf16': {name: bf16 filter image}, those up to date (`_dpack`, `_dpack_fresh`: its own dict and set,
+        # by the names the tests read)
+        self._images = PackedImages()
+        self._dpack, self._dpack_fresh = self._images.images, self._images.fresh
         self.flat, self._params, self._tsaved = None, None, None
         if trainable:
             if conv_before_pool != 1 or bn or dropout > 0 or unpool_type not in ('trackind', 'inverse'):
@@ -931,12 +924,10 @@ class StandardDAE:
             p = int(name[4:].split('_')[0])
             cin = self.n_classes if p == 1 else self.enc['conv%d_1' % (p - 1)].Cout
         ci0 = conv.Cin - cin
-        if name not in self._dpack_fresh:
-            self._dpack[name] = ops.conv_dgrad_pack(conv.W, tuple(gz.shape), ci0, cin, conv.layout,
-                                                    out=self._dpack.get(name))
-            self._dpack_fresh.add(name)
+        packed = self._images.image(
+            name, lambda out: ops.conv_dgrad_pack(conv.W, tuple(gz.shape), ci0, cin, conv.layout, out=out))
         return ops.conv_dgrad(gz, conv.W, ci0=ci0, cin=cin, layout=conv.layout, out=acc, accumulate=acc is not None,
-                              packed=self._dpack[name])
+                              packed=packed)
 
     def backward(self, g_score):
         """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
@@ -961,7 +952,7 @@ class StandardDAE:
                 self._bwd[name].W.copy_(Wt)
             for conv in self._bwd.values():
                 conv.refresh()
-        self._dpack_fresh.clear()
+        self._images.invalidate()
         self._store = None
         self._scratch_sessions.clear()
 

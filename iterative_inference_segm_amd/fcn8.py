@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .params import ParamStore
+from .params import PackedImages, ParamStore, check_mode
 from .regions import center, conv_region, pool_region
 from .weights import load_param_list
 
@@ -65,32 +65,12 @@ class FCN8:
         `backward` stay float32 and the same code: DESIGN.md section 18).  Independent of wgrad, dgrad and kxk."""
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
-        if wgrad not in ops.WGRAD_MODES:
-            raise ValueError("wgrad=%r is not one of %s" % (wgrad, ops.WGRAD_MODES))
-        if wgrad == 'bf16' and not (trainable and dtype == torch.float32):
-            raise NotImplementedError("wgrad='bf16': the 16-bit weight gradient of a trainable float32 module "
-                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
-        self.wgrad = wgrad
-        if dgrad not in ops.DGRAD_MODES:
-            raise ValueError("dgrad=%r is not one of %s" % (dgrad, ops.DGRAD_MODES))
-        if dgrad == 'bf16' and not (trainable and dtype == torch.float32):
-            raise NotImplementedError("dgrad='bf16': the 16-bit data gradient of a trainable float32 module "
-                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
-        self.dgrad = dgrad
-        if kxk not in ops.KXK_MODES:
-            raise ValueError("kxk=%r is not one of %s" % (kxk, ops.KXK_MODES))
-        if kxk == 'bf16' and not (trainable and dtype == torch.float32):
-            raise NotImplementedError("kxk='bf16': the 16-bit fc6 / fc7 gradients of a trainable float32 module "
-                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
-        self.kxk = kxk
-        if fwd not in ops.FWD_MODES:
-            raise ValueError("fwd=%r is not one of %s" % (fwd, ops.FWD_MODES))
-        if fwd == 'bf16' and not (trainable and dtype == torch.float32):
-            raise NotImplementedError("fwd='bf16': the 16-bit training forward of a trainable float32 module "
-                                      "(trainable=%r, dtype=%s)" % (bool(trainable), dtype))
-        self.fwd = fwd
-        # dgrad='bf16' / kxk='bf16': {name: bf16 filter image}, those up to date
-        self._dpack, self._dpack_fresh = {}, set()
+        for switch, mode in (('wgrad', wgrad), ('dgrad', dgrad), ('kxk', kxk), ('fwd', fwd)):
+            setattr(self, switch, check_mode(switch, mode, dtype, bool(trainable)))
+        # dgrad='bf16' / kxk='bf16': {name: bf16 filter image}, those up to date (`_dpack`, `_dpack_fresh`: its own
+        # dict and set, by the names the tests read)
+        self._images = PackedImages()
+        self._dpack, self._dpack_fresh = self._images.images, self._images.fresh
         self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
         if trainable:
             # refused here, before any device work
@@ -456,7 +436,7 @@ class FCN8:
             gz = ops.relu_gate(g, s[name], dst=g)
             if self.kxk == 'bf16' and name in _NAMES_KXK16:
                 ops.conv_wgrad_kxk(s[xin], gz, *gv[name], mma='bf16')
-                g = self._dgrad_kxk16(name, gz)
+                g = self._dgrad16(name, gz)
             else:
                 ops.conv_wgrad_kxk(s[xin], gz, *gv[name])
                 if name == 'fc6':
@@ -490,26 +470,15 @@ class FCN8:
                     g = bwd[name](gz)
         return gv
 
-    def _dgrad16(self, name, gz, gate):
-        """dgrad='bf16': the data gradient of the 3x3 layer `name` for g_z by ops.conv_dgrad on the layer's own
-        parameter, times [gate > 0].  The bf16 image of the filter is packed on first use after `refresh()`, into
-        the buffer it already has."""
+    def _dgrad16(self, name, gz, gate=None):
+        """dgrad='bf16' / kxk='bf16': the data gradient of layer `name` for g_z, times [gate > 0], on the layer's own
+        parameter: ops.conv_dgrad for a 3x3 layer, ops.conv_dgrad_kxk for the 'valid' fc6 / fc7.  The bf16 image of
+        the filter is packed on first use after `refresh()`, into the buffer it already has."""
         conv = self.convs[name]
-        if name not in self._dpack_fresh:
-            self._dpack[name] = ops.conv_dgrad_pack(conv.W, tuple(gz.shape), 0, conv.Cin, conv.layout,
-                                                    out=self._dpack.get(name))
-            self._dpack_fresh.add(name)
-        return ops.conv_dgrad(gz, conv.W, layout=conv.layout, gate=gate, packed=self._dpack[name])
-
-    def _dgrad_kxk16(self, name, gz):
-        """kxk='bf16': the data gradient of the 'valid' layer `name` (fc6, fc7) for g_z by ops.conv_dgrad_kxk on the
-        layer's own parameter; the bf16 image is packed on first use after `refresh()`, into the buffer it has."""
-        conv = self.convs[name]
-        if name not in self._dpack_fresh:
-            self._dpack[name] = ops.conv_dgrad_kxk_pack(conv.W, tuple(gz.shape), 0, conv.Cin, conv.layout,
-                                                        out=self._dpack.get(name))
-            self._dpack_fresh.add(name)
-        return ops.conv_dgrad_kxk(gz, conv.W, layout=conv.layout, packed=self._dpack[name])
+        pack, run = (ops.conv_dgrad_kxk_pack, ops.conv_dgrad_kxk) if name in _NAMES_KXK16 else \
+            (ops.conv_dgrad_pack, ops.conv_dgrad)
+        packed = self._images.image(name, lambda out: pack(conv.W, tuple(gz.shape), 0, conv.Cin, conv.layout, out=out))
+        return run(gz, conv.W, layout=conv.layout, gate=gate, packed=packed)
 
     def refresh(self):
         """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into the
@@ -525,7 +494,7 @@ class FCN8:
                 self._bwd[name].W.copy_(Wt)
             for conv in self._bwd.values():
                 conv.refresh()
-        self._dpack_fresh.clear()
+        self._images.invalidate()
         self._border = {}
 
 

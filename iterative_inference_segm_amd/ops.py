@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, DeconvDesc, CONV_RELU, CONV_UNPOOL, CONV_TRANSPOSED2, CONV_X3, CONV_ZINS, check
+from .params import MODES_16BIT
 
 # When set to a list, every conv launch appends (kernel, executed_flops, start_event, end_event):
 # HIP events recorded on the launch stream right around the kernel (bench.py's roofline leg).
@@ -2152,7 +2153,7 @@ def conv_wgrad_desc(x_shape, Cout, pad, Cin_tot=None, ci0=0, layout='oihw'):
     return d
 
 
-WGRAD_MODES = ('f32', 'bf16')
+WGRAD_MODES = DGRAD_MODES = KXK_MODES = FWD_MODES = MODES_16BIT
 
 
 def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
@@ -2193,50 +2194,117 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
         _add_bytes(kern, float(dW.element_size()) * (x.numel() + gz.numel() + 2 * n))
 
 
-# ---- data gradients on the 16-bit matrix pipe (csrc/conv_dgrad_bf16.hip) ----
-DGRAD_MODES = ('f32', 'bf16')
+# ---- data gradients on the 16-bit matrix pipe (csrc/conv_dgrad_bf16.hip, conv_kxk_bf16.hip) ----
+def _need_f32(what, named, required=()):
+    """The `named` (name, argument) pairs of `what` must be float32 tensors; None is a left-out argument unless the
+    name is `required`."""
+    for name, t in named:
+        if (t is not None or name in required) and (not torch.is_tensor(t) or t.dtype != torch.float32):
+            raise ValueError('%s: %s must be a float32 tensor (got %s)'
+                             % (what, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
 
 
-def conv_dgrad_desc(gz_shape, Wshape, ci0=0, cin=None, layout='oihw', accumulate=False):
-    """The iiseg_conv_dgrad_desc of the pad-1 3x3 layer with parameter `Wshape` stored as `layout`, for g_z
-    (B,Cout,H,W) and the input channels [ci0, ci0 + cin) (default: all from ci0 on)."""
+# The two data-gradient kernels, both on iiseg_conv_dgrad_desc.  name: the public function; k_ok, k_what: the K check
+# and its wording; pad(K): the zero padding of the layer's forward as the descriptor names it -- gx is (H + 2 pad -
+# K + 1) square-wise: g_z's own size at pad 1, OH + K - 1 for a 'valid' layer; gz_dims: how g_z is described; stem:
+# the library symbols stem, stem_pack, stem_pack_elems (stem_workspace_elems) and, less 'iiseg_', the profile names
+# stem_kernel and stem_pack_kernel; slabs: the reduction may be split (a workspace, and its term of the byte model).
+_DgradKind = collections.namedtuple('_DgradKind', 'name k_ok k_what pad gz_dims stem slabs')
+_DGRAD_3X3 = _DgradKind('conv_dgrad', lambda W: tuple(W.shape[2:]) == (3, 3), 'a 3x3 parameter', lambda K: 1,
+                        '(B, Cout, H, W)', 'iiseg_conv_dgrad_bf16', False)
+_DGRAD_KXK = _DgradKind('conv_dgrad_kxk', lambda W: W.shape[2] == W.shape[3] and 1 <= W.shape[2] <= 7,
+                        'a K x K parameter, 1 <= K <= 7', lambda K: K - 1, '(B, Cout, OH, OW)',
+                        'iiseg_conv_dgrad_kxk_bf16', True)
+
+
+def _dgrad_desc(kind, gz_shape, Wshape, ci0, cin, layout, accumulate=False):
     B, Cout, H, W = (int(v) for v in gz_shape)
     Cin_tot, Co, K, so, sc = _param_strides(Wshape, layout)
     d = _lib.ConvDgradDesc()
-    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin_tot - int(ci0) if cin is None else int(cin), Cout, H, W, K, 1
+    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin_tot - int(ci0) if cin is None else int(cin), Cout, H, W, K, kind.pad(K)
     d.ci0, d.Cin_tot, d.accumulate = int(ci0), Cin_tot, int(bool(accumulate))
     d.so, d.sc = so, sc
     return d
 
 
-def _dgrad_args(gz, W, layout, what):
-    """What conv_dgrad and conv_dgrad_pack refuse before the library is called."""
-    for name, t in (('gz', gz), ('W', W)):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
-            raise ValueError('%s: %s must be a float32 tensor (got %s)'
-                             % (what, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+def _dgrad_args(kind, gz, W, layout, what):
+    """What the data gradient and its pack refuse before the library is called."""
+    _need_f32(what, (('gz', gz), ('W', W)))
     if layout not in ('oihw', 'iohw'):
         raise ValueError('%s: layout %r' % (what, layout))
-    if W.dim() != 4 or tuple(W.shape[2:]) != (3, 3):
-        raise ValueError('%s: W %s is not a 3x3 parameter' % (what, tuple(W.shape)))
+    if W.dim() != 4 or not kind.k_ok(W):
+        raise ValueError('%s: W %s is not %s' % (what, tuple(W.shape), kind.k_what))
+
+
+def _dgrad_pack(kind, W, gz_shape, ci0, cin, layout, out):
+    what = kind.name + '_pack'
+    _dgrad_args(kind, None, W, layout, what)
+    d = _dgrad_desc(kind, gz_shape, tuple(W.shape), ci0, cin, layout)
+    n = _count(getattr(_lib.load(), kind.stem + '_pack_elems')(C.byref(d)), kind.stem + '_pack_elems')
+    if out is None:
+        out = torch.empty(n, dtype=torch.bfloat16, device=W.device)
+    elif out.dtype != torch.bfloat16 or out.numel() != n:
+        raise ValueError('%s: out holds %d %s elements, the image %d bfloat16' % (what, out.numel(), out.dtype, n))
+    kern = kind.stem[6:] + '_pack_kernel'
+    _launch(kern, 0.0, getattr(_lib.load(), kind.stem + '_pack'), C.byref(d), _ptr(W), _ptr(out, torch.bfloat16))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, 4.0 * d.Cout * d.Cin * d.K * d.K + 2.0 * n)
+    return out
+
+
+def _dgrad_run(kind, gz, W, ci0, cin, layout, out, accumulate, gate, packed):
+    what = kind.name
+    _dgrad_args(kind, gz, W, layout, what)
+    _need_f32(what, (('out', out), ('gate', gate)))
+    if packed is not None and (not torch.is_tensor(packed) or packed.dtype != torch.bfloat16):
+        raise ValueError('%s: packed must be the bfloat16 tensor of %s_pack' % (what, what))
+    if accumulate and out is None:
+        raise ValueError('%s: accumulate=True needs the map to add to (out=)' % what)
+    if gz.dim() != 4:
+        raise ValueError('%s: gz %s is not %s' % (what, tuple(gz.shape), kind.gz_dims))
+    d = _dgrad_desc(kind, tuple(gz.shape), tuple(W.shape), ci0, cin, layout, accumulate)
+    Cout_w = W.shape[0] if layout == 'oihw' else W.shape[1]
+    if gz.shape[1] != Cout_w or d.Cin < 1 or d.ci0 < 0 or d.ci0 + d.Cin > d.Cin_tot:
+        raise ValueError('%s: gz %s, W %s (%s), input channels [%d, %d)'
+                         % (what, tuple(gz.shape), tuple(W.shape), layout, d.ci0, d.ci0 + d.Cin))
+    shape = (d.B, d.Cin, d.H + 2 * d.pad - d.K + 1, d.W + 2 * d.pad - d.K + 1)
+    for name, t in (('out', out), ('gate', gate)):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError('%s: %s %s, the gradient is %s' % (what, name, tuple(t.shape), shape))
+    lib = _lib.load()
+    n = _count(getattr(lib, kind.stem + '_pack_elems')(C.byref(d)), kind.stem + '_pack_elems')
+    if packed is None:
+        packed = _dgrad_pack(kind, W, tuple(gz.shape), ci0, cin, layout, None)
+    elif packed.numel() != n:
+        raise ValueError('%s: packed holds %d elements, the image of this slice %d' % (what, packed.numel(), n))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=gz.device)
+    nws, ws = 0, ()
+    if kind.slabs:
+        nws = _count(getattr(lib, kind.stem + '_workspace_elems')(C.byref(d)), kind.stem + '_workspace_elems')
+        ws = (_ptr(_workspace('f32', nws, gz.device) if nws else None),)
+    kern = kind.stem[6:] + '_kernel'
+    _launch(kern, 2.0 * d.Cin * d.Cout * d.K * d.K * d.B * d.H * d.W, getattr(lib, kind.stem), C.byref(d), _ptr(gz),
+            _ptr(packed, torch.bfloat16), _ptr(gate), *ws, _ptr(out))
+    if CONV_PROFILE is not None:
+        # byte model: g_z and the image read once, the slabs written and read once, gx written once (read once more
+        # when it is added to), the gate read
+        _add_bytes(kern, 4.0 * gz.numel() + 2.0 * n + 8.0 * nws +
+                   4.0 * out.numel() * (1 + int(bool(accumulate)) + (gate is not None)))
+    return out
+
+
+def conv_dgrad_desc(gz_shape, Wshape, ci0=0, cin=None, layout='oihw', accumulate=False):
+    """The iiseg_conv_dgrad_desc of the pad-1 3x3 layer with parameter `Wshape` stored as `layout`, for g_z
+    (B,Cout,H,W) and the input channels [ci0, ci0 + cin) (default: all from ci0 on)."""
+    return _dgrad_desc(_DGRAD_3X3, gz_shape, Wshape, ci0, cin, layout, accumulate)
 
 
 def conv_dgrad_pack(W, gz_shape, ci0=0, cin=None, layout='oihw', out=None):
     """The bf16 image of the input channels [ci0, ci0 + cin) of the fp32 3x3 parameter W (read in place: the flip
     and the transpose are indices) that conv_dgrad multiplies by; into `out` (a bfloat16 tensor of the size a
     previous call returned: the address stays) or a new tensor.  One small launch; again whenever W has changed."""
-    _dgrad_args(None, W, layout, 'conv_dgrad_pack')
-    d = conv_dgrad_desc(gz_shape, tuple(W.shape), ci0, cin, layout)
-    n = _count(_lib.load().iiseg_conv_dgrad_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_bf16_pack_elems')
-    if out is None:
-        out = torch.empty(n, dtype=torch.bfloat16, device=W.device)
-    elif out.dtype != torch.bfloat16 or out.numel() != n:
-        raise ValueError('conv_dgrad_pack: out holds %d %s elements, the image %d bfloat16' % (out.numel(), out.dtype, n))
-    kern = 'conv_dgrad_bf16_pack_kernel'
-    _launch(kern, 0.0, _lib.load().iiseg_conv_dgrad_bf16_pack, C.byref(d), _ptr(W), _ptr(out, torch.bfloat16))
-    if CONV_PROFILE is not None:
-        _add_bytes(kern, 4.0 * d.Cout * d.Cin * 9 + 2.0 * n)
-    return out
+    return _dgrad_pack(_DGRAD_3X3, W, gz_shape, ci0, cin, layout, out)
 
 
 def conv_dgrad(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=False, gate=None, packed=None):
@@ -2248,40 +2316,7 @@ def conv_dgrad(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=False
     (B,cin,H,W); accumulate=True adds to what it holds (it must be given).  gate: a map of gx's shape -- the result
     is gx * [gate > 0], relu'(0) = 0.  packed: what conv_dgrad_pack returned for this W, slice and layout (default:
     packed here, one more launch).  float32 tensors only."""
-    _dgrad_args(gz, W, layout, 'conv_dgrad')
-    for name, t in (('out', out), ('gate', gate)):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
-            raise ValueError('conv_dgrad: %s must be a float32 tensor (got %s)'
-                             % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
-    if packed is not None and (not torch.is_tensor(packed) or packed.dtype != torch.bfloat16):
-        raise ValueError('conv_dgrad: packed must be the bfloat16 tensor of conv_dgrad_pack')
-    if accumulate and out is None:
-        raise ValueError('conv_dgrad: accumulate=True needs the map to add to (out=)')
-    if gz.dim() != 4:
-        raise ValueError('conv_dgrad: gz %s is not (B, Cout, H, W)' % (tuple(gz.shape),))
-    d = conv_dgrad_desc(tuple(gz.shape), tuple(W.shape), ci0, cin, layout, accumulate)
-    Cout_w = W.shape[0] if layout == 'oihw' else W.shape[1]
-    if gz.shape[1] != Cout_w or d.Cin < 1 or d.ci0 < 0 or d.ci0 + d.Cin > d.Cin_tot:
-        raise ValueError('conv_dgrad: gz %s, W %s (%s), input channels [%d, %d)'
-                         % (tuple(gz.shape), tuple(W.shape), layout, d.ci0, d.ci0 + d.Cin))
-    shape = (d.B, d.Cin, d.H, d.W)
-    for name, t in (('out', out), ('gate', gate)):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError('conv_dgrad: %s %s, the gradient is %s' % (name, tuple(t.shape), shape))
-    n = _count(_lib.load().iiseg_conv_dgrad_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_bf16_pack_elems')
-    if packed is None:
-        packed = conv_dgrad_pack(W, tuple(gz.shape), ci0, cin, layout)
-    elif packed.numel() != n:
-        raise ValueError('conv_dgrad: packed holds %d elements, the image of this slice %d' % (packed.numel(), n))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=gz.device)
-    kern = 'conv_dgrad_bf16_kernel'
-    _launch(kern, 2.0 * d.Cin * d.Cout * 9 * d.B * d.H * d.W, _lib.load().iiseg_conv_dgrad_bf16, C.byref(d), _ptr(gz),
-            _ptr(packed, torch.bfloat16), _ptr(gate), _ptr(out))
-    if CONV_PROFILE is not None:
-        # byte model: g_z and the image read once, gx written once (read once more when it is added to), the gate read
-        _add_bytes(kern, 4.0 * gz.numel() + 2.0 * n + 4.0 * out.numel() * (1 + int(bool(accumulate)) + (gate is not None)))
-    return out
+    return _dgrad_run(_DGRAD_3X3, gz, W, ci0, cin, layout, out, accumulate, gate, packed)
 
 
 # ---- true-gradient refinement through the context-module DAE (csrc/ctx_grad.hip, DESIGN.md section 10) ----
@@ -2391,9 +2426,6 @@ def conv_wgrad_kxk_desc(x, Cout, K, window=None, Cin_tot=None, ci0=0, layout='oi
     return d
 
 
-KXK_MODES = ('f32', 'bf16')
-
-
 def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw', mma='f32'):
     """dW[:, ci0:ci0 + Cin] (and db, unless None) of the 'valid' K x K stride-1 layer (1 <= K <= 7) out = conv(x,
     W) + b, written in place into the layer's own parameter layout, from the `window` = (y0, x0, h, w) of its
@@ -2405,38 +2437,29 @@ def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw', mma='f
     dt = x.dtype
     if mma not in KXK_MODES:
         raise ValueError("conv_wgrad_kxk: mma=%r is not one of %s" % (mma, KXK_MODES))
-    if mma == 'bf16':
-        for name, t in (('x', x), ('gz', gz), ('dW', dW), ('db', db)):
-            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
-                raise ValueError("conv_wgrad_kxk: mma='bf16' takes float32 tensors only (%s is %s)"
-                                 % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    # one pass over the arguments: what mma='bf16' refuses is a ValueError, the float modes' refusals RuntimeError
+    bf16 = mma == 'bf16'
+    err = ValueError if bf16 else RuntimeError
+    if bf16:
+        _need_f32("conv_wgrad_kxk: mma='bf16'", (('x', x), ('gz', gz), ('dW', dW), ('db', db)))
         if layout not in ('oihw', 'iohw'):
             raise ValueError('conv_wgrad_kxk: layout %r' % (layout,))
-        if dW.dim() != 4 or dW.shape[2] != dW.shape[3] or not 1 <= dW.shape[2] <= 7:
-            raise ValueError('conv_wgrad_kxk: dW %s is not a K x K parameter, 1 <= K <= 7' % (tuple(dW.shape),))
-        if x.dim() != 4 or gz.dim() != 4:
-            raise ValueError('conv_wgrad_kxk: x %s, gz %s' % (tuple(x.shape), tuple(gz.shape)))
-        h, w = (x.shape[2], x.shape[3]) if window is None else (int(window[2]), int(window[3]))
-        Kk, Co = int(dW.shape[2]), int(dW.shape[0] if layout == 'oihw' else dW.shape[1])
-        Ct = int(dW.shape[1] if layout == 'oihw' else dW.shape[0])
-        if tuple(gz.shape) != (x.shape[0], Co, h - Kk + 1, w - Kk + 1) or h < Kk or w < Kk or \
-                ci0 < 0 or ci0 + x.shape[1] > Ct or (db is not None and db.numel() != Co):
-            raise ValueError('conv_wgrad_kxk: shapes x %s window %s gz %s dW %s (%s) ci0 %d' % (
-                tuple(x.shape), window, tuple(gz.shape), tuple(dW.shape), layout, ci0))
-        if not (x.is_cuda and gz.is_cuda and dW.is_cuda):
-            raise ValueError("conv_wgrad_kxk: mma='bf16' takes device tensors")
-    if dW.dim() != 4 or dW.shape[2] != dW.shape[3]:
-        raise RuntimeError('conv_wgrad_kxk: dW %s is not a K x K parameter' % (tuple(dW.shape),))
+    if dW.dim() != 4 or dW.shape[2] != dW.shape[3] or (bf16 and not 1 <= dW.shape[2] <= 7):
+        raise err('conv_wgrad_kxk: dW %s is not a K x K parameter%s' % (tuple(dW.shape), ', 1 <= K <= 7' * bf16))
+    if bf16 and (x.dim() != 4 or gz.dim() != 4):
+        raise ValueError('conv_wgrad_kxk: x %s, gz %s' % (tuple(x.shape), tuple(gz.shape)))
     K = int(dW.shape[2])
     Cout, Cin_tot = (dW.shape[0], dW.shape[1]) if layout == 'oihw' else (dW.shape[1], dW.shape[0])
-    d = conv_wgrad_kxk_desc(x, Cout, K, window, Cin_tot, ci0, layout)
-    OH, OW = d.H - K + 1, d.W - K + 1
-    if tuple(gz.shape) != (d.B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
-        raise RuntimeError('conv_wgrad_kxk: shapes x %s window %s gz %s dW %s' % (
-            tuple(x.shape), window, tuple(gz.shape), tuple(dW.shape)))
-    if not x.is_cuda or x.dtype != dt or gz.dtype != dt or dW.dtype != dt:
-        raise RuntimeError('conv_wgrad_kxk needs device tensors of one dtype')
-    if mma == 'bf16':                                    # a plan, and a profile name, of its own
+    h, w = (x.shape[2], x.shape[3]) if window is None else (int(window[2]), int(window[3]))
+    OH, OW = h - K + 1, w - K + 1
+    if tuple(gz.shape) != (x.shape[0], Cout, OH, OW) or (db is not None and db.numel() != Cout) or \
+            (bf16 and (h < K or w < K or ci0 < 0 or ci0 + x.shape[1] > Cin_tot)):
+        raise err('conv_wgrad_kxk: shapes x %s window %s gz %s dW %s (%s) ci0 %d' % (
+            tuple(x.shape), window, tuple(gz.shape), tuple(dW.shape), layout, ci0))
+    if not x.is_cuda or gz.dtype != dt or dW.dtype != dt or (bf16 and not (gz.is_cuda and dW.is_cuda)):
+        raise err('conv_wgrad_kxk needs device tensors of one dtype')
+    d = conv_wgrad_kxk_desc(x, Cout, K, window, Cin_tot, ci0, layout)   # (refuses a window outside x)
+    if bf16:                                             # a plan, and a profile name, of its own
         n = _count(_lib.load().iiseg_conv_wgrad_kxk_bf16_workspace_elems(C.byref(d)),
                    'iiseg_conv_wgrad_kxk_bf16_workspace_elems')
         kern, fn = 'conv_wgrad_kxk_bf16_kernel', _lib.load().iiseg_conv_wgrad_kxk_bf16
@@ -2455,44 +2478,14 @@ def conv_wgrad_kxk(x, gz, dW, db=None, window=None, ci0=0, layout='oihw', mma='f
 def conv_dgrad_kxk_desc(gz_shape, Wshape, ci0=0, cin=None, layout='oihw', accumulate=False):
     """The iiseg_conv_dgrad_desc of the 'valid' K x K layer with parameter `Wshape` stored as `layout`, for g_z
     (B,Cout,OH,OW) and the input channels [ci0, ci0 + cin) (default: all from ci0 on)."""
-    B, Cout, OH, OW = (int(v) for v in gz_shape)
-    Cin_tot, Co, K, so, sc = _param_strides(Wshape, layout)
-    d = _lib.ConvDgradDesc()
-    d.B, d.Cin, d.Cout, d.H, d.W, d.K, d.pad = B, Cin_tot - int(ci0) if cin is None else int(cin), Cout, OH, OW, K, K - 1
-    d.ci0, d.Cin_tot, d.accumulate = int(ci0), Cin_tot, int(bool(accumulate))
-    d.so, d.sc = so, sc
-    return d
-
-
-def _dgrad_kxk_args(gz, W, layout, what):
-    """What conv_dgrad_kxk and conv_dgrad_kxk_pack refuse before the library is called."""
-    for name, t in (('gz', gz), ('W', W)):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
-            raise ValueError('%s: %s must be a float32 tensor (got %s)'
-                             % (what, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
-    if layout not in ('oihw', 'iohw'):
-        raise ValueError('%s: layout %r' % (what, layout))
-    if W.dim() != 4 or W.shape[2] != W.shape[3] or not 1 <= W.shape[2] <= 7:
-        raise ValueError('%s: W %s is not a K x K parameter, 1 <= K <= 7' % (what, tuple(W.shape)))
+    return _dgrad_desc(_DGRAD_KXK, gz_shape, Wshape, ci0, cin, layout, accumulate)
 
 
 def conv_dgrad_kxk_pack(W, gz_shape, ci0=0, cin=None, layout='oihw', out=None):
     """The bf16 image of the input channels [ci0, ci0 + cin) of the fp32 K x K parameter W (read in place: the flip
     and the transpose are indices) that conv_dgrad_kxk multiplies by; into `out` (a bfloat16 tensor of the size a
     previous call returned: the address stays) or a new tensor.  One launch; again whenever W has changed."""
-    _dgrad_kxk_args(None, W, layout, 'conv_dgrad_kxk_pack')
-    d = conv_dgrad_kxk_desc(gz_shape, tuple(W.shape), ci0, cin, layout)
-    n = _count(_lib.load().iiseg_conv_dgrad_kxk_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_kxk_bf16_pack_elems')
-    if out is None:
-        out = torch.empty(n, dtype=torch.bfloat16, device=W.device)
-    elif out.dtype != torch.bfloat16 or out.numel() != n:
-        raise ValueError('conv_dgrad_kxk_pack: out holds %d %s elements, the image %d bfloat16'
-                         % (out.numel(), out.dtype, n))
-    kern = 'conv_dgrad_kxk_bf16_pack_kernel'
-    _launch(kern, 0.0, _lib.load().iiseg_conv_dgrad_kxk_bf16_pack, C.byref(d), _ptr(W), _ptr(out, torch.bfloat16))
-    if CONV_PROFILE is not None:
-        _add_bytes(kern, 4.0 * d.Cout * d.Cin * d.K * d.K + 2.0 * n)
-    return out
+    return _dgrad_pack(_DGRAD_KXK, W, gz_shape, ci0, cin, layout, out)
 
 
 def conv_dgrad_kxk(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=False, gate=None, packed=None):
@@ -2503,48 +2496,7 @@ def conv_dgrad_kxk(gz, W, ci0=0, cin=None, layout='oihw', out=None, accumulate=F
     v_mfma_f32_32x32x16_bf16, the slabs of output channels added in slab order.  ci0, cin, out, accumulate, gate:
     as conv_dgrad.  packed: what conv_dgrad_kxk_pack returned for this W, slice and layout (default: packed here,
     one more launch).  float32 tensors only."""
-    _dgrad_kxk_args(gz, W, layout, 'conv_dgrad_kxk')
-    for name, t in (('out', out), ('gate', gate)):
-        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32):
-            raise ValueError('conv_dgrad_kxk: %s must be a float32 tensor (got %s)'
-                             % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
-    if packed is not None and (not torch.is_tensor(packed) or packed.dtype != torch.bfloat16):
-        raise ValueError('conv_dgrad_kxk: packed must be the bfloat16 tensor of conv_dgrad_kxk_pack')
-    if accumulate and out is None:
-        raise ValueError('conv_dgrad_kxk: accumulate=True needs the map to add to (out=)')
-    if gz.dim() != 4:
-        raise ValueError('conv_dgrad_kxk: gz %s is not (B, Cout, OH, OW)' % (tuple(gz.shape),))
-    d = conv_dgrad_kxk_desc(tuple(gz.shape), tuple(W.shape), ci0, cin, layout, accumulate)
-    Cout_w = W.shape[0] if layout == 'oihw' else W.shape[1]
-    if gz.shape[1] != Cout_w or d.Cin < 1 or d.ci0 < 0 or d.ci0 + d.Cin > d.Cin_tot:
-        raise ValueError('conv_dgrad_kxk: gz %s, W %s (%s), input channels [%d, %d)'
-                         % (tuple(gz.shape), tuple(W.shape), layout, d.ci0, d.ci0 + d.Cin))
-    shape = (d.B, d.Cin, d.H + d.K - 1, d.W + d.K - 1)
-    for name, t in (('out', out), ('gate', gate)):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError('conv_dgrad_kxk: %s %s, the gradient is %s' % (name, tuple(t.shape), shape))
-    lib = _lib.load()
-    n = _count(lib.iiseg_conv_dgrad_kxk_bf16_pack_elems(C.byref(d)), 'iiseg_conv_dgrad_kxk_bf16_pack_elems')
-    if packed is None:
-        packed = conv_dgrad_kxk_pack(W, tuple(gz.shape), ci0, cin, layout)
-    elif packed.numel() != n:
-        raise ValueError('conv_dgrad_kxk: packed holds %d elements, the image of this slice %d' % (packed.numel(), n))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=gz.device)
-    nws = _count(lib.iiseg_conv_dgrad_kxk_bf16_workspace_elems(C.byref(d)), 'iiseg_conv_dgrad_kxk_bf16_workspace_elems')
-    ws = _workspace('f32', nws, gz.device) if nws else None
-    kern = 'conv_dgrad_kxk_bf16_kernel'
-    _launch(kern, 2.0 * d.Cin * d.Cout * d.K * d.K * d.B * d.H * d.W, lib.iiseg_conv_dgrad_kxk_bf16, C.byref(d),
-            _ptr(gz), _ptr(packed, torch.bfloat16), _ptr(gate), _ptr(ws), _ptr(out))
-    if CONV_PROFILE is not None:
-        # byte model: g_z and the image read once, the slabs written and read once, gx written once (read once more
-        # when it is added to), the gate read
-        _add_bytes(kern, 4.0 * gz.numel() + 2.0 * n + 8.0 * nws +
-                   4.0 * out.numel() * (1 + int(bool(accumulate)) + (gate is not None)))
-    return out
-
-
-FWD_MODES = ('f32', 'bf16')
+    return _dgrad_run(_DGRAD_KXK, gz, W, ci0, cin, layout, out, accumulate, gate, packed)
 
 
 def conv_fwd_kxk_desc(x_shape, Wshape, relu=True):
@@ -2563,12 +2515,7 @@ def conv_fwd_kxk(x, W, b=None, relu=True, out=None):
     operand rounded once (nearest, ties to even) as it is staged, fp32 accumulation in a fixed order by
     v_mfma_f32_32x32x16_bf16, the slabs of a split reduction added in slab order, the bias added in fp32.  Into
     `out` (B,Cout,H-K+1,W-K+1) or a new tensor.  float32 contiguous device tensors only."""
-    for name, t in (('x', x), ('W', W), ('b', b), ('out', out)):
-        if t is None and name in ('b', 'out'):
-            continue
-        if not torch.is_tensor(t) or t.dtype != torch.float32:
-            raise ValueError('conv_fwd_kxk: %s must be a float32 tensor (got %s)'
-                             % (name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    _need_f32('conv_fwd_kxk', (('x', x), ('W', W), ('b', b), ('out', out)), required=('x', 'W'))
     if W.dim() != 4 or W.shape[2] != W.shape[3] or not 1 <= W.shape[2] <= 7:
         raise ValueError('conv_fwd_kxk: W %s is not a K x K parameter, 1 <= K <= 7' % (tuple(W.shape),))
     K = int(W.shape[2])

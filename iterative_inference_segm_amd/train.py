@@ -14,44 +14,29 @@ import torch
 
 from . import ops
 from .api import Metrics
+from .params import check_mode
 
 SUPPORTED_LOSSES = ('crossentropy', 'squared_error')
 
 
 def check_wgrad(wgrad, dtype):
     """The weight-gradient mode of a run (host only): 'f32', or 'bf16' with float32."""
-    if wgrad not in ops.WGRAD_MODES:
-        raise ValueError('wgrad must be one of %s (got %r)' % (', '.join(ops.WGRAD_MODES), wgrad))
-    if wgrad == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
-        raise NotImplementedError("wgrad='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
-                                  'be float32 (got %s)' % (dtype,))
+    check_mode('wgrad', wgrad, dtype)
 
 
 def check_dgrad(dgrad, dtype):
     """The data-gradient mode of a run (host only): 'f32', or 'bf16' with float32."""
-    if dgrad not in ops.DGRAD_MODES:
-        raise ValueError('dgrad must be one of %s (got %r)' % (', '.join(ops.DGRAD_MODES), dgrad))
-    if dgrad == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
-        raise NotImplementedError("dgrad='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
-                                  'be float32 (got %s)' % (dtype,))
+    check_mode('dgrad', dgrad, dtype)
 
 
 def check_kxk(kxk, dtype):
     """The mode of FCN-8's fc6 / fc7 gradients of a run (host only): 'f32', or 'bf16' with float32."""
-    if kxk not in ops.KXK_MODES:
-        raise ValueError('kxk must be one of %s (got %r)' % (', '.join(ops.KXK_MODES), kxk))
-    if kxk == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
-        raise NotImplementedError("kxk='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
-                                  'be float32 (got %s)' % (dtype,))
+    check_mode('kxk', kxk, dtype)
 
 
 def check_fwd(fwd, dtype):
     """The mode of FCN-8's training forward of a run (host only): 'f32', or 'bf16' with float32."""
-    if fwd not in ops.FWD_MODES:
-        raise ValueError('fwd must be one of %s (got %r)' % (', '.join(ops.FWD_MODES), fwd))
-    if fwd == 'bf16' and str(dtype).replace('torch.', '') != 'float32':
-        raise NotImplementedError("fwd='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
-                                  'be float32 (got %s)' % (dtype,))
+    check_mode('fwd', fwd, dtype)
 
 
 def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
