@@ -335,6 +335,19 @@ int iiseg_conv_halo_bf16(void* stream, const iiseg_conv_desc* d, const float* x1
                          const float* pre, const float* pooled, const void* wp16, const float* bias,
                          const float* add, float* out, float* pool_out, const uint8_t* mask_in,
                          uint8_t* mask_out);
+/* The same kernel as a trainable module's forward launches it (fwd='bf16'; ops.Conv(fwd16=True)): the four
+ * entries above with one refusal lifted -- a two-source layer's first source may have ANY channel count.  The
+ * k-tile that holds channel C1 is then staged from both sources (each channel c from x1 if c < C1, else from x2 at
+ * plane c - C1, else zero); every other launch runs the code it runs through iiseg_conv_halo_bf16.
+ * iiseg_conv_halo_bf16_fwd_check: the status of the host-side checks (IISEG_OK, or why not), no launch. */
+int iiseg_conv_halo_bf16_fwd_check(const iiseg_conv_desc* d);
+int64_t iiseg_conv_halo_bf16_fwd_weight_bytes(const iiseg_conv_desc* d);
+int iiseg_conv_halo_bf16_fwd_pack(void* stream, const iiseg_conv_desc* d, const float* w,
+                                  int64_t stride_o, int64_t stride_c, void* wp16);
+int iiseg_conv_halo_bf16_fwd(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
+                             const float* pre, const float* pooled, const void* wp16, const float* bias,
+                             const float* add, float* out, float* pool_out, const uint8_t* mask_in,
+                             uint8_t* mask_out);
 
 /* float64 Winograd F(2x2,3x3) form of iiseg_conv_f64 for the wide 3x3 layers of the strict-parity
  * path (stride 1, dil 1, (C1+C2) % 16 == 0, no TRANSPOSED2; with IISEG_CONV_UNPOOL x1 = up, pre,

@@ -149,6 +149,10 @@ SIGNATURES = {
     'iiseg_conv_halo_bf16_weight_bytes': (_i64, [C.POINTER(ConvDesc)]),
     'iiseg_conv_halo_bf16_pack': (C.c_int, [_vp, C.POINTER(ConvDesc), _vp, _i64, _i64, _vp]),
     'iiseg_conv_halo_bf16': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 11),
+    'iiseg_conv_halo_bf16_fwd_check': (C.c_int, [C.POINTER(ConvDesc)]),
+    'iiseg_conv_halo_bf16_fwd_weight_bytes': (_i64, [C.POINTER(ConvDesc)]),
+    'iiseg_conv_halo_bf16_fwd_pack': (C.c_int, [_vp, C.POINTER(ConvDesc), _vp, _i64, _i64, _vp]),
+    'iiseg_conv_halo_bf16_fwd': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 11),
     'iiseg_conv_wino_f64_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_wino_f64_weight_elems': (_i64, [C.POINTER(ConvDesc)]),
     'iiseg_conv_wino_f64_workspace_elems': (_i64, [C.POINTER(ConvDesc)]),

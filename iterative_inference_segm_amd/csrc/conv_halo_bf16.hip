@@ -60,8 +60,12 @@ __global__ void halo_pack_bf16_kernel(const float* __restrict__ w, int64_t so, i
 }
 
 // MASKIN (with UNPOOL): DePool2D mask from bytes (ConvParams::mask_in) instead of pre == pooled
-template <int BM, int TH, int WM, int WN, bool UNPOOL, bool MASKIN = false>
-__global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf16_kernel(const ConvParams p, const int tiles_y,
+// STRADDLE (two sources, C1 % 16 != 0; a fwd16 launch only): the k-tile that holds channel C1 takes its channels
+// c < C1 from x1 and the others from x2 at plane c - C1 -- two loads per patch element of THAT k-tile, each with a
+// wave-uniform descriptor (the lanes of the other source get the out-of-range offset: zeros, no memory traffic),
+// OR-ed together when the chunk is packed; every other k-tile is staged as without the flag.
+template <int BM, int TH, int WM, int WN, bool UNPOOL, bool MASKIN = false, bool STRADDLE = false>
+__global__ __launch_bounds__(256, ((UNPOOL && !MASKIN) || STRADDLE) ? 2 : 3) void conv_halo_bf16_kernel(const ConvParams p, const int tiles_y,
                                                                 const int tiles_x) {
     constexpr int TW = 32, PH = TH + 2, PW = TW + 2, PP = PH * PW;
     constexpr int NCHK = 2 * PP;                  // patch chunks per k-tile
@@ -77,6 +81,7 @@ __global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf
     constexpr int WCH = 9 * 2 * BM;               // weight chunks per k-tile
     constexpr int WPT = (WCH + 255) / 256;
     static_assert(WM * WN == 4 && TH % WN == 0 && BM % (WM * 32) == 0, "tile config");
+    static_assert(!(STRADDLE && UNPOOL), "a DePool2D layer has one source");
 
     // ONE LDS array (a second __shared__ object can make hipcc drain the DMA queue early), carved
     // into the weight ring Ws[2][WCH] ([tap][h][BM] chunks), the single patch buffer Ps[NCHK]
@@ -163,6 +168,8 @@ __global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     float xv[NE][8];
+    float xw[STRADDLE ? NE : 1][8];                // STRADDLE: the x2 share of the straddling k-tile
+    const int kt_s = (STRADDLE && C1 % CPT) ? C1 / CPT : -1;   // ... which is this one
     float xq[UNPOOL ? NL : 1][8], xu[UNPOOL ? NL : 1][8];
     const int nkt = p.Kpad;                        // bf16 plan: Kpad holds the number of k-tiles
     static_assert(WCH % 64 == 0, "a wave's DMA piece is whole");
@@ -197,10 +204,20 @@ __global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf
                         xq[i][j] = buf_ld(mk_rsrc(baseq, nq), vo2, so2);                           \
                     xu[i][j] = buf_ld(mk_rsrc(baseu, nq), vo2, so2);                               \
                 }                                                                                  \
+                if constexpr (STRADDLE) {                                                          \
+                    /* (KT == kt_s: s1 holds, the load above took the lanes with c < C1 from x1.)  The     \
+                       plane of x2 goes into the per-lane offset: c0 + j - C1 alone may be negative */     \
+                    if ((KT) == kt_s) {                                                            \
+                        const int c2 = ((hbits >> i) & 1) * 8 + j - crem;                          \
+                        const bool ok2 = c2 >= 0 && c2 < p.C2 && voff[i] != OOB;                   \
+                        xw[i][j] = buf_ld(mk_rsrc(base2, n2),                                      \
+                                          ok2 ? voff[i] + 4u * (unsigned)((c0 + j - C1) * HW) : OOB, 0); \
+                    }                                                                              \
+                }                                                                                  \
             }                                                                                      \
         });                                                                                        \
     }
-#define HBF_STORE_X(BUF)                                                                           \
+#define HBF_STORE_X(BUF, KT)                                                                       \
     if constexpr (MASKIN) {                                                                        \
         _Pragma("unroll") for (int sl = 0; sl < 4; ++sl) {                                         \
             /* bit (row & 1) * 2 + (col & 1) of the window's byte: pre == pooled */                \
@@ -221,6 +238,11 @@ __global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf
                 v[j] = ((__builtin_bit_cast(unsigned, xq[i][j]) >> bsel[i]) & 1u) ? xu[i][j] : 0.f; \
             else if constexpr (UNPOOL) v[j] = (xv[i][j] == xq[i][j]) ? xu[i][j] : 0.f;             \
             else v[j] = xv[i][j];                                                                  \
+            if constexpr (STRADDLE) {              /* one of the two is zero bits */                \
+                if ((KT) == kt_s)                                                                  \
+                    v[j] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[j]) |          \
+                                                     __builtin_bit_cast(unsigned, xw[i][j]));      \
+            }                                                                                      \
         }                                                                                          \
         if (NE * 256 == NCHK || i * 256 + tid < NCHK)                                              \
             Ps[BUF][i * 256 + tid] = make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]),      \
@@ -244,7 +266,7 @@ __global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf
     HBF_LOAD_X(0)
     HBF_LOAD_W(0, 0)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    HBF_STORE_X(0)
+    HBF_STORE_X(0, 0)
     __syncthreads();
 
     const int lrow = wn * RW;   // first output row of this wave inside the tile
@@ -291,7 +313,7 @@ __global__ __launch_bounds__(256, (UNPOOL && !MASKIN) ? 2 : 3) void conv_halo_bf
         if (more) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();                 // every wave has read the patch of k-tile kt
-            HBF_STORE_X(0)
+            HBF_STORE_X(0, kt + 1)
         }
         __syncthreads();
     }
@@ -425,7 +447,10 @@ int launch_halo_bf16(hipStream_t s, const ConvParams& cp, bool unpool) {
     p.n_ptiles = p.B * tiles_y * tiles_x;
     p.n_mtiles = p.Mpad / BM;
     const int grid = p.n_ptiles * p.n_mtiles;
-    if (unpool && p.mask_in)
+    if (p.C2 > 0 && p.C1 % CPT)              // (halo_bf16_check: a fwd16 launch, never with DePool2D)
+        IISEG_LAUNCH((conv_halo_bf16_kernel<BM, TH, WM, WN, false, false, true>), dim3(grid), dim3(256),
+                           0, s, p, tiles_y, tiles_x);
+    else if (unpool && p.mask_in)
         IISEG_LAUNCH((conv_halo_bf16_kernel<BM, TH, WM, WN, true, true>), dim3(grid), dim3(256),
                            0, s, p, tiles_y, tiles_x);
     else if (unpool)
@@ -439,7 +464,8 @@ int launch_halo_bf16(hipStream_t s, const ConvParams& cp, bool unpool) {
 
 int halo_bf16_bm(int Cout) { return Cout > 32 ? 64 : 32; }
 
-int halo_bf16_check(const iiseg_conv_desc* d) {
+// straddle: a k-tile may hold channels of both sources (C1 % 16 != 0; the iiseg_conv_halo_bf16_fwd entries)
+int halo_bf16_check(const iiseg_conv_desc* d, bool straddle = false) {
     if (!d) return IISEG_ERR_NULL;
     if (d->KH != 3 || d->KW != 3 || d->dil != 1 || (d->flags & IISEG_CONV_TRANSPOSED2))
         return IISEG_ERR_UNSUPPORTED;
@@ -449,7 +475,7 @@ int halo_bf16_check(const iiseg_conv_desc* d) {
     const int fullH = d->H + 2 * d->pad - 2, fullW = d->W + 2 * d->pad - 2;
     if (d->oy0 + d->OH > fullH || d->ox0 + d->OW > fullW) return IISEG_ERR_SHAPE;
     if ((d->flags & IISEG_CONV_UNPOOL) && d->C2 != 0) return IISEG_ERR_UNSUPPORTED;
-    if (d->C2 > 0 && d->C1 % CPT) return IISEG_ERR_UNSUPPORTED;  // a k-tile must not straddle sources
+    if (d->C2 > 0 && d->C1 % CPT && !straddle) return IISEG_ERR_UNSUPPORTED;  // a k-tile must not straddle sources
     if (d->out_ctot != 0 && (d->out_c0 < 0 || d->out_c0 + d->Cout > d->out_ctot)) return IISEG_ERR_SHAPE;
     if (d->out_H != 0 && (d->out_y0 < 0 || d->out_x0 < 0 || d->out_y0 + d->OH > d->out_H ||
                           d->out_x0 + d->OW > d->out_W))
@@ -475,16 +501,16 @@ extern "C" int iiseg_conv_halo_bf16_supported(const iiseg_conv_desc* d) {
     return halo_bf16_check(d) == IISEG_OK ? 1 : 0;
 }
 
-extern "C" int64_t iiseg_conv_halo_bf16_weight_bytes(const iiseg_conv_desc* d) {
-    if (halo_bf16_check(d) != IISEG_OK) return 0;
+static int64_t halo_bf16_weight_bytes(const iiseg_conv_desc* d, bool straddle) {
+    if (halo_bf16_check(d, straddle) != IISEG_OK) return 0;
     const int nkt = (d->C1 + d->C2 + CPT - 1) / CPT;
     const int bm = halo_bf16_bm(d->Cout), mpad = (d->Cout + bm - 1) / bm * bm;
     return (int64_t)nkt * 18 * mpad * 16;
 }
 
-extern "C" int iiseg_conv_halo_bf16_pack(void* stream, const iiseg_conv_desc* d, const float* w,
-                                         int64_t stride_o, int64_t stride_c, void* wp16) {
-    const int st = halo_bf16_check(d);
+static int halo_bf16_pack(void* stream, const iiseg_conv_desc* d, const float* w, int64_t stride_o,
+                         int64_t stride_c, void* wp16, bool straddle) {
+    const int st = halo_bf16_check(d, straddle);
     if (st) return st;
     if (!w || !wp16) return IISEG_ERR_NULL;
     if ((uintptr_t)wp16 & 15) return IISEG_ERR_ALIGN;
@@ -497,12 +523,11 @@ extern "C" int iiseg_conv_halo_bf16_pack(void* stream, const iiseg_conv_desc* d,
     return iiseg_check_launch();
 }
 
-extern "C" int iiseg_conv_halo_bf16(void* stream, const iiseg_conv_desc* d, const float* x1,
-                                    const float* x2, const float* pre, const float* pooled,
-                                    const void* wp16, const float* bias, const float* add, float* out,
-                                    float* pool_out, const unsigned char* mask_in,
-                                    unsigned char* mask_out) {
-    const int st = halo_bf16_check(d);
+static int halo_bf16_run(void* stream, const iiseg_conv_desc* d, const float* x1, const float* x2,
+                        const float* pre, const float* pooled, const void* wp16, const float* bias,
+                        const float* add, float* out, float* pool_out, const unsigned char* mask_in,
+                        unsigned char* mask_out, bool straddle) {
+    const int st = halo_bf16_check(d, straddle);
     if (st) return st;
     if (!x1 || !wp16) return IISEG_ERR_NULL;
     if (!out && !(pool_out && mask_out)) return IISEG_ERR_NULL;   // pre-pool map may be skipped
@@ -550,4 +575,42 @@ extern "C" int iiseg_conv_halo_bf16(void* stream, const iiseg_conv_desc* d, cons
     hipStream_t s = (hipStream_t)stream;
     if (bm == 64) return launch_halo_bf16<64, 8, 1, 4>(s, p, unpool);
     return launch_halo_bf16<32, 8, 1, 4>(s, p, unpool);
+}
+
+extern "C" int64_t iiseg_conv_halo_bf16_weight_bytes(const iiseg_conv_desc* d) {
+    return halo_bf16_weight_bytes(d, false);
+}
+
+extern "C" int iiseg_conv_halo_bf16_pack(void* stream, const iiseg_conv_desc* d, const float* w,
+                                         int64_t stride_o, int64_t stride_c, void* wp16) {
+    return halo_bf16_pack(stream, d, w, stride_o, stride_c, wp16, false);
+}
+
+extern "C" int iiseg_conv_halo_bf16(void* stream, const iiseg_conv_desc* d, const float* x1,
+                                    const float* x2, const float* pre, const float* pooled,
+                                    const void* wp16, const float* bias, const float* add, float* out,
+                                    float* pool_out, const unsigned char* mask_in,
+                                    unsigned char* mask_out) {
+    return halo_bf16_run(stream, d, x1, x2, pre, pooled, wp16, bias, add, out, pool_out, mask_in, mask_out, false);
+}
+
+// ---- the entries of a fwd16 layer (ops.Conv(fwd16=True)): the same kernel, the same checks, and a two-source
+// layer whose first source has any channel count (the straddling k-tile of the patch staging)
+extern "C" int iiseg_conv_halo_bf16_fwd_check(const iiseg_conv_desc* d) { return halo_bf16_check(d, true); }
+
+extern "C" int64_t iiseg_conv_halo_bf16_fwd_weight_bytes(const iiseg_conv_desc* d) {
+    return halo_bf16_weight_bytes(d, true);
+}
+
+extern "C" int iiseg_conv_halo_bf16_fwd_pack(void* stream, const iiseg_conv_desc* d, const float* w,
+                                             int64_t stride_o, int64_t stride_c, void* wp16) {
+    return halo_bf16_pack(stream, d, w, stride_o, stride_c, wp16, true);
+}
+
+extern "C" int iiseg_conv_halo_bf16_fwd(void* stream, const iiseg_conv_desc* d, const float* x1,
+                                        const float* x2, const float* pre, const float* pooled,
+                                        const void* wp16, const float* bias, const float* add, float* out,
+                                        float* pool_out, const unsigned char* mask_in,
+                                        unsigned char* mask_out) {
+    return halo_bf16_run(stream, d, x1, x2, pre, pooled, wp16, bias, add, out, pool_out, mask_in, mask_out, true);
 }

@@ -184,7 +184,7 @@ class StandardDAE:
                  conv_before_pool=1, additional_pool=2, skip=True, unpool_type='trackind', bn=0,
                  device='cuda', dtype=torch.float32, pad_multi_concat=False, noise=0.0,
                  dropout=0.0, emulate_noise=False, seed=0, mma=None, trainable=False, wgrad='f32',
-                 dgrad='f32'):
+                 dgrad='f32', fwd='f32'):
         """mma: matrix-pipe operand precision of the float32 path's convolutions ('f32' default,
         'bf16' = 16-bit MFMA operands with fp32 accumulation; ops.Conv).
         trainable=True: the parameters live in ONE flat buffer in `param_order` (W then b per layer), every
@@ -196,11 +196,18 @@ class StandardDAE:
         dgrad: operand precision of `backward`'s 3x3 data gradients ('f32' default: the fp32 flipped-filter layers;
         'bf16' = ops.conv_dgrad on the parameters themselves, W and g_z rounded once to bf16, fp32 accumulation --
         float32 trainable modules only; the forward, `backward_y`, the parameters and the masks stay float32:
-        DESIGN.md section 16)."""
+        DESIGN.md section 16).
+        fwd: operand precision of every forward of the module -- `forward_train`, `scores` with and without a
+        session, `__call__` / `residual` ('f32' default: every bit, launch and buffer as without the keyword; 'bf16'
+        = every encoder and decoder layer an ops.Conv(fwd16=True): z = sum bf16(W) bf16(x) + b (+ the skip addend) on
+        conv_halo_bf16_kernel with the pool, DePool2D, the addend's crop, windows and placement in the launch as
+        before, fp32 accumulation, fp32 NCHW maps -- float32 trainable modules only; the parameters, the saved maps,
+        the pool / ReLU / DePool2D decisions, the loss, `backward`, `backward_y` and the optimizer stay float32:
+        DESIGN.md section 20)."""
         concat_h = list(concat_h)
         mma = mma or ops.DEFAULT_MMA
         self.trainable = bool(trainable)
-        for switch, mode in (('wgrad', wgrad), ('dgrad', dgrad)):
+        for switch, mode in (('wgrad', wgrad), ('dgrad', dgrad), ('fwd', fwd)):
             setattr(self, switch, check_mode(switch, mode, dtype, bool(trainable)))
         # dgrad='bf16': {name: bf16 filter image}, those up to date (`_dpack`, `_dpack_fresh`: its own dict and set,
         # by the names the tests read)
@@ -256,6 +263,8 @@ class StandardDAE:
         self.n_pool, self.total = _n_pool(concat_h, additional_pool)
         self.device = device
         self.enc, self.dec = {}, {}
+        # (fwd='bf16': the layers say so themselves; a layer built the old way is what it was)
+        fwd16 = dict(fwd16=True) if self.fwd == 'bf16' else {}
         for p in range(self.total):
             for i in range(1, conv_before_pool + 1):
                 # pad-100 rule of fcn_down.py:90-94
@@ -266,7 +275,7 @@ class StandardDAE:
                 name = 'conv%d_%d' % (p + 1, i)
                 self.enc[name] = ops.Conv(params[name][0], params[name][1],
                                           pad=padding if first_pad else 1, relu=True,
-                                          device=device, dtype=dtype, mma=mma)        # :102-104
+                                          device=device, dtype=dtype, mma=mma, **fwd16)        # :102-104
                 if bn:   # BatchNormLayer on the rectified conv, stored averages (:112-114)
                     self.enc_bn[name] = tuple(
                         torch.as_tensor(np.asarray(a)).to(dtype).contiguous().to(device)
@@ -310,7 +319,7 @@ class StandardDAE:
                 W = np.asarray(W, np.float64) * sc[:, None, None, None]
                 b = (np.asarray(b, np.float64) - mean) * sc + beta
             self.dec[name] = ops.Conv(W, b, pad=1, relu=False, device=device,
-                                      dtype=dtype, mma=mma)                           # fcn_up.py:83-86
+                                      dtype=dtype, mma=mma, **fwd16)                  # fcn_up.py:83-86
         self.conv_log = None
         # DePool2D fused into the conv's input load (halo kernel: 3 loads per PATCH element;
         # Winograd: applied by the input transform) or materialised first.  None (auto): fused in

@@ -351,7 +351,8 @@ class Conv:
         launch of a plain 3x3 layer takes the 'halo_bf16' form and every launch of an undilated 'valid' K x K
         'oihw' layer (1 <= K <= 7, not 3) 'kxk_bf16' (conv_fwd_kxk on the parameter itself), whatever
         BF16_PICKS or the environment say -- a launch neither kernel takes is an error, never another form -- and
-        `refresh()` packs the 3x3 layer's bf16 image again into the buffer it has."""
+        `refresh()` packs the 3x3 layer's bf16 image again into the buffer it has.  A two-source launch of such a
+        layer may have any C1 (iiseg_conv_halo_bf16_fwd: the k-tile that straddles x1 and x2)."""
         self.lib = _lib.load()
         self.mma = (mma or DEFAULT_MMA) if dtype == torch.float32 else 'f32'
         if self.mma not in ('f32', 'bf16', 'bf16c8', 'bf16x3'):
@@ -548,7 +549,8 @@ class Conv:
                                '(Conv.mask_ok)')
         if self.fwd16:
             # one kernel and one rounding statement per layer class; nothing else may run the launch
-            if self.plain3x3 and lib.iiseg_conv_halo_bf16_supported(dp):
+            # (its own check: a two-source launch may have any C1 -- the straddling k-tile)
+            if self.plain3x3 and lib.iiseg_conv_halo_bf16_fwd_check(dp) == 0:
                 return 'halo_bf16'
             if not self.plain3x3 and not (masked or pool or add or x2 or unpool) and \
                     (d.oy0, d.ox0, d.OH, d.OW) == (0, 0) + self.out_hw(d.H, d.W) and not d.out_ctot and not d.out_H:
@@ -943,12 +945,14 @@ class Conv:
     def _run_halo_bf16(self, c):
         """Direct 3x3 form on the bf16 matrix pipe (include/iiseg.h, iiseg_conv_halo_bf16)."""
         lib, d = self.lib, c.d
+        # (a fwd16 layer goes through the _fwd entries: the same kernel, C1 of a two-source launch free)
+        nbytes, run = (lib.iiseg_conv_halo_bf16_fwd_weight_bytes, lib.iiseg_conv_halo_bf16_fwd) if self.fwd16 else \
+            (lib.iiseg_conv_halo_bf16_weight_bytes, lib.iiseg_conv_halo_bf16)
         if self._W16 is None:
-            self._W16 = torch.empty(lib.iiseg_conv_halo_bf16_weight_bytes(C.byref(d)) // 2,
-                                    dtype=torch.bfloat16, device=self.W.device)
+            self._W16 = torch.empty(nbytes(C.byref(d)) // 2, dtype=torch.bfloat16, device=self.W.device)
             self._W16_desc = d
             self._pack_halo_bf16(d)
-        _launch('conv_halo_bf16_kernel', self.flops(d.B, d.OH, d.OW), lib.iiseg_conv_halo_bf16,
+        _launch('conv_halo_bf16_kernel', self.flops(d.B, d.OH, d.OW), run,
                 C.byref(d), _ptr(c.x1), _ptr(c.x2), _ptr(c.pre), _ptr(c.pooled),
                 _ptr(self._W16, torch.bfloat16), _ptr(self.b), _ptr(c.add), _ptr(c.out), _ptr(c.pool_out),
                 _ptr(c.mask_in, torch.uint8), _ptr(c.mask_out, torch.uint8))
@@ -957,11 +961,12 @@ class Conv:
         """The bf16 image of the 3x3 filter (it depends on the channel counts only) into `_W16`: one launch, no host
         wait.  profiled: recorded under CONV_PROFILE (the per-step re-pack of `refresh`; first use never is)."""
         args = (C.byref(d), _ptr(self.W), C.c_int64(self.so), C.c_int64(self.sc), _ptr(self._W16, torch.bfloat16))
+        pack = self.lib.iiseg_conv_halo_bf16_fwd_pack if self.fwd16 else self.lib.iiseg_conv_halo_bf16_pack
         if not profiled:
-            check(self.lib.iiseg_conv_halo_bf16_pack(_stream(), *args), 'iiseg_conv_halo_bf16_pack')
+            check(pack(_stream(), *args), 'iiseg_conv_halo_bf16_pack')
             return
         kern = 'halo_pack_bf16_kernel'
-        _launch(kern, 0.0, self.lib.iiseg_conv_halo_bf16_pack, *args)
+        _launch(kern, 0.0, pack, *args)
         if CONV_PROFILE is not None:
             _add_bytes(kern, 4.0 * self.W.numel() + 2.0 * self._W16.numel())
 

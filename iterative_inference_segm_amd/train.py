@@ -35,16 +35,17 @@ def check_kxk(kxk, dtype):
 
 
 def check_fwd(fwd, dtype):
-    """The mode of FCN-8's training forward of a run (host only): 'f32', or 'bf16' with float32."""
+    """The mode of the training forward of a run, FCN-8's or the standard DAE's (host only): 'f32', or 'bf16' with
+    float32."""
     check_mode('fwd', fwd, dtype)
 
 
 def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
-                    optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32', dgrad='f32'):
+                    optimizer='rmsprop', dae_dict=None, wgrad='f32', dtype='float32', dgrad='f32', fwd='f32'):
     """Raises NotImplementedError / ValueError with the reason for everything this slice does not train
     (host only: callable before any GPU work).  dae_dict: the standard kind's options (concat_h, bn, dropout,
-    conv_before_pool, unpool_type).  wgrad, dgrad, dtype: the weight- and data-gradient modes and the run's
-    precision."""
+    conv_before_pool, unpool_type).  wgrad, dgrad, fwd, dtype: the weight-gradient, data-gradient and forward modes
+    and the run's precision."""
     if kind not in ('contextmod', 'standard'):
         raise NotImplementedError("training is built for dae kinds 'contextmod' and 'standard' (got %r): the "
                                   'fcn8 kind (strided 4x4 transposed convolutions) has no weight-gradient '
@@ -57,6 +58,11 @@ def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=Fals
     if dgrad == 'bf16' and kind == 'contextmod':
         raise NotImplementedError("dgrad='bf16' is the zero-padded 3x3 data gradient of dae kind 'standard' and "
                                   "of FCN-8: the context module's masked data-gradient kernels stay float32")
+    check_fwd(fwd, dtype)
+    if fwd == 'bf16' and kind == 'contextmod':
+        raise NotImplementedError("fwd='bf16' is the forward of dae kind 'standard' (its 3x3 layers on the 16-bit "
+                                  "matrix pipe) and of FCN-8: the context module's dilated 11-channel layers stay "
+                                  "float32")
     if kind == 'standard':
         dd = dae_dict or {}
         concat_h = list(dd.get('concat_h', ['input']))

@@ -3,7 +3,7 @@
 additional_pool=2, pad 100, trackind, skip) at batch 10, 224x224, from_gt, noise 0.1: one JSON line.
 
     python scripts/bench_train_std.py [--batch 10] [--size 224x224] [--reps 15] [--dtypes float32 float64]
-                                      [--wgrad f32 bf16] [--dgrad f32 bf16]
+                                      [--wgrad f32 bf16] [--dgrad f32 bf16] [--fwd f32 bf16]
 
 Per precision: step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, RMSprop,
 refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch profile, per
@@ -20,6 +20,11 @@ conv_dgrad_bf16_kernel's -- with its fraction of the mode's peak; the bf16 rows 
 ops.Conv(..., mma='bf16') forward kernel on the flipped filter of that same layer on a map of g_z's shape, and the
 filter images' pack launches of the step; every row has `refresh_ms`, the cost of refresh() (in the fp32 mode it
 flips, copies and re-packs the data-gradient filters too).  DESIGN section 16.
+--fwd: the forward modes to run (StandardDAE's `fwd`; bf16: float32 only), one result row per (wgrad, dgrad, fwd)
+triple in the same process; a mode may be named twice (`--fwd f32 f32 bf16`).  Every row lists per layer the forward
+launch of its mode (`forward_kernel`, `forward_ms`: conv_halo_bf16_kernel's in the bf16 rows), `refresh_ms` (the bf16
+rows re-pack the twelve bf16 filter images instead of the fp32 packs) and `peak_mem_mib`, the allocator's peak over
+the row.  DESIGN section 20.
 """
 import argparse
 import json
@@ -37,9 +42,11 @@ from iterative_inference_segm_amd.train import DAETrainer                 # noqa
 from dgrad_bench import launches, layer_rows, marked, yardstick           # noqa: E402
 
 
-def one(B, H, W, dt, reps, peak, wgrad='f32', dgrad='f32', peak_d=157.3, yard=None):
+def one(B, H, W, dt, reps, peak, wgrad='f32', dgrad='f32', peak_d=157.3, yard=None, fwd='f32'):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
     params = S.make_dae_params(seed=4321)
-    dae = StandardDAE(params, 11, dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad)
+    dae = StandardDAE(params, 11, dtype=dt, mma='f32', trainable=True, wgrad=wgrad, dgrad=dgrad, fwd=fwd)
     tr = DAETrainer(None, dae, 11, [11], noise=0.1, seed=1)
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
     y = T[:, :11].contiguous()
@@ -83,11 +90,11 @@ def one(B, H, W, dt, reps, peak, wgrad='f32', dgrad='f32', peak_d=157.3, yard=No
         ops.profile_end()
     order = param_order()
     total = len(order) // 2
-    fwd = [(k, f, a.elapsed_time(b)) for k, f, a, b in prof[:n_fwd] if f > 0]
-    if len(fwd) != len(order):
-        raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fwd],))
-    fwd_ms = dict(zip(order, [t for _, _, t in fwd]))
-    fwd_kernel = dict(zip(order, [k for k, _, _ in fwd]))
+    fl = [(k, f, a.elapsed_time(b)) for k, f, a, b in prof[:n_fwd] if f > 0]
+    if len(fl) != len(order):
+        raise RuntimeError('expected one forward convolution launch per layer, got %s' % ([k for k, _, _ in fl],))
+    fwd_ms = dict(zip(order, [t for _, _, t in fl]))
+    fwd_kernel = dict(zip(order, [k for k, _, _ in fl]))
     kern = 'conv_wgrad_bf16_kernel' if wgrad == 'bf16' else 'conv_wgrad_kernel'
     wg = [(f, a.elapsed_time(b)) for k, f, a, b in prof[n_fwd:] if k == kern]
     # backward's order: up_conv1..total, then conv<total>_1..conv1_1, the concat layer (h behind pool4) twice
@@ -128,7 +135,8 @@ def one(B, H, W, dt, reps, peak, wgrad='f32', dgrad='f32', peak_d=157.3, yard=No
         yard.update(yardstick(dae._flipped_filters(), shapes, dt))
     dlayers = layer_rows(dnames, {n: (t, k) for n, (t, _, k) in zip(dnames, dg)},
                          {n: f for n, (_, f, _) in zip(dnames, dg)}, peak_d, yard if dgrad == 'bf16' else None)
-    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad, 'wgrad_peak_tflops': peak,
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'dgrad': dgrad, 'fwd': fwd,
+            'peak_mem_mib': round(torch.cuda.max_memory_allocated() / 2.0 ** 20, 1), 'wgrad_peak_tflops': peak,
             'dgrad_peak_tflops': peak_d, 'dgrad_ms_total': round(sum(r['dgrad_ms'] for r in dlayers), 3),
             'dgrad_pack_ms': round(pack_ms, 4), 'refresh_ms': round(refresh_ms, 4), 'dgrad_layers': dlayers, 'batch': B,
             'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
@@ -147,14 +155,15 @@ def main():
     ap.add_argument('--peak_tflops', type=float, default=157.3)
     ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--dgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--fwd', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split('x'))
     yard = {}
     rows = [one(a.batch, H, W, getattr(torch, name), a.reps, a.peak_tflops_bf16 if mode == 'bf16' else a.peak_tflops,
-                mode, dmode, a.peak_tflops_bf16 if dmode == 'bf16' else a.peak_tflops, yard)
-            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad
-            if (mode == 'f32' and dmode == 'f32') or name == 'float32']
+                mode, dmode, a.peak_tflops_bf16 if dmode == 'bf16' else a.peak_tflops, yard, fmode)
+            for name in a.dtypes for mode in a.wgrad for dmode in a.dgrad for fmode in a.fwd
+            if (mode == 'f32' and dmode == 'f32' and fmode == 'f32') or name == 'float32']
     print(json.dumps({'bench': 'train_std', 'device': torch.cuda.get_device_name(0), 'peak_tflops': a.peak_tflops,
                       'peak_tflops_bf16': a.peak_tflops_bf16,
                       'reps': a.reps, 'results': rows}))

@@ -20,6 +20,9 @@ state and the checkpoints stay float32, so the experiment folder keeps its name 
 With `--dtype float64` or kind 'contextmod' it is refused before any GPU work.
 `--dgrad bf16` (the same conditions and refusals) forms the 3x3 data gradients of the backward
 pass on the 16-bit matrix pipe from the parameters and g_z rounded once to bf16; config.txt records it as well.
+`-train_dict '{"fwd": "bf16"}'` (the same conditions and refusals) runs every forward of the
+standard DAE -- training, validation -- on the 16-bit matrix pipe from W and the layer inputs rounded once to bf16;
+it has no flag of its own and is no default of the dictionary; config.txt records it as well.
 """
 import argparse
 import json
@@ -51,11 +54,11 @@ def _json_dict(s):
 
 
 def check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad='f32', dtype='float32',
-                    dgrad='f32'):
+                    dgrad='f32', fwd='f32'):
     """Everything this build does not train, refused with the reason (host only)."""
     from iterative_inference_segm_amd.train import check_supported as chk
     chk(dae_dict['kind'], training_loss, ae_h, full_im_ft, optimizer, dae_dict=dae_dict, wgrad=wgrad, dtype=dtype,
-        dgrad=dgrad)
+        dgrad=dgrad, fwd=fwd)
     if dae_dict['kind'] == 'contextmod' and list(dae_dict['concat_h']) != ['input']:
         raise NotImplementedError("the context module concatenates the image: concat_h must be ['input']")
 
@@ -99,11 +102,12 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
           max_patience=100, optimizer='rmsprop', training_loss=['squared_error'], batch_size=[10, 1, 1],
           ae_h=False, dae_dict_updates={}, data_augmentation={}, savepath=None, loadpath=None, resume=False,
           train_from_0_255=False, lmb=1, full_im_ft=False, weights_path=None, synthetic=False, n_images=20,
-          image_size=None, seed=0, dtype='float32', wgrad='f32', dgrad='f32', verbose=True):
+          image_size=None, seed=0, dtype='float32', wgrad='f32', dgrad='f32', fwd='f32', verbose=True):
     """Signature of reference train_dae.py:54-60 plus keyword-only extras.  weight_decay only enters the
     experiment name, as in the reference (train_dae.py:91: no regulariser is added to the loss).  wgrad (kind
     'standard': 'f32' | 'bf16', the 3x3 weight gradients' operand precision) is recorded in config.txt and stays
-    out of the experiment name: the checkpoints are float32 either way; dgrad (the 3x3 data gradients') likewise.
+    out of the experiment name: the checkpoints are float32 either way; dgrad (the 3x3 data gradients') and fwd
+    (every forward of the module: StandardDAE's `fwd`) likewise.
     Returns the
     per-epoch lists (err_train, err_valid, jacc_val, mse_val) and the experiment folder."""
     dae_dict = {'kind': 'fcn8', 'dropout': 0.0, 'skip': True, 'unpool_type': 'standard', 'n_filters': 64,
@@ -111,7 +115,7 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
                 'from_gt': True, 'temperature': 1.0, 'path_weights': '', 'layer': 'probs_dimshuffle',
                 'exp_name': '', 'bn': 0}                                                  # :65-79
     dae_dict.update(dae_dict_updates)
-    check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad, dtype, dgrad)
+    check_supported(dae_dict, training_loss, ae_h, full_im_ft, optimizer, wgrad, dtype, dgrad, fwd)
     if dataset not in ('camvid', 'polyps912', 'em'):
         raise ValueError('Unknown dataset')
     if segm_net == 'fcn_fcresnet':
@@ -139,7 +143,7 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
                                       training_loss=training_loss, batch_size=batch_size, dae_dict=dae_dict,
                                       data_augmentation=data_augmentation, resume=resume, lmb=lmb,
                                       train_from_0_255=train_from_0_255, seed=seed, dtype=dtype,
-                                      wgrad=wgrad, dgrad=dgrad).items()):
+                                      wgrad=wgrad, dgrad=dgrad, fwd=fwd).items()):
             f.write('{} = {}\n'.format(key, value))
 
     # ---- from here on: the GPU ----
@@ -184,7 +188,7 @@ def train(dataset, segm_net, learning_rate=0.005, lr_anneal=1.0, weight_decay=1e
                                        seed=4321 + int(seed), **arch)
         dae = StandardDAE(params, n_classes, padding=100, n_filters=dae_dict['n_filters'],
                           skip=dae_dict['skip'], noise=dae_dict['noise'], dtype=tdt, mma='f32', trainable=True,
-                          wgrad=wgrad, dgrad=dgrad, **arch)
+                          wgrad=wgrad, dgrad=dgrad, fwd=fwd, **arch)
     else:
         order = PARAM_ORDER
         if resume:
@@ -279,7 +283,9 @@ def make_parser():
     parser.add_argument('-train_dict', type=_json_dict, default=dict(TRAIN_DICT),
                         help='Training configuration (JSON; keys given replace the defaults).  weight_decay '
                              'only enters the experiment name, as in the reference: no regulariser is added '
-                             'to the loss')
+                             'to the loss.  "fwd": "bf16" (kind \'standard\', float32; no default of the dictionary '
+                             'and no flag of its own) runs the DAE\'s forward on the 16-bit matrix pipe: recorded in '
+                             'config.txt, not in the experiment name')
     parser.add_argument('-dae_dict', type=_json_dict, default=dict(DAE_DICT),
                         help="DAE kind and parameters (JSON).  Kinds 'contextmod' and 'standard' (h at a pool point) are "
                              "trained here")
@@ -328,7 +334,8 @@ def main(argv=None):
     args, train_dict, dae_dict = parse_args(argv)
     try:
         check_supported(dae_dict, train_dict['training_loss'], args.ae_h, train_dict.get('full_im_ft', False),
-                        train_dict['optimizer'], args.wgrad, args.dtype, args.dgrad)
+                        train_dict['optimizer'], args.wgrad, args.dtype, args.dgrad,
+                        train_dict.get('fwd', 'f32'))
     except (NotImplementedError, ValueError) as e:
         print('train_dae.py: ' + str(e), file=sys.stderr)
         return 2
