@@ -13,7 +13,8 @@ import os
 import torch
 
 from . import ops
-from .params import ParamStore
+from .datagrads import DataGrads, Layer
+from .params import Trainable
 from .weights import load_param_list
 
 # inside a refinement loop the image half of the first layer (3 of its 14 input channels; h is the image and does not
@@ -25,7 +26,7 @@ PARAM_ORDER = ['conv1'] + ['dilconv%d' % i for i in range(1, 8)]   # get_all_par
 DILATIONS = [1, 2, 4, 8, 16, 1]                                     # contextmod_dae.py:78-101
 
 
-class ContextModDAE:
+class ContextModDAE(Trainable):
     kind = 'contextmod'
 
     def __init__(self, params, n_classes, concat_h=('input',), device='cuda',
@@ -44,9 +45,7 @@ class ContextModDAE:
         # ONE flat parameter buffer in PARAM_ORDER (W then b per layer): every ops.Conv below holds VIEWS of it,
         # so an optimizer step on `flat` followed by `refresh()` reaches every path (training, section 9)
         self.device, self.dtype = device, dtype
-        self._params = ParamStore(params, PARAM_ORDER, dtype, device)
-        self.flat, params = self._params.flat, self._params.views
-        self._views = params
+        self._views = params = self._store_params(params, PARAM_ORDER, dtype, device)
         self.conv1 = ops.Conv(params['conv1'][0], params['conv1'][1], pad=1, relu=True,
                               device=device, dtype=dtype)                         # :74-76
         self.dil = []
@@ -67,12 +66,16 @@ class ContextModDAE:
         W, b = params['dilconv1']
         self.dil1_valid = ops.Conv(W, b, pad=0, relu=True, dil=DILATIONS[0], layout='iohw', device=device,
                                    dtype=dtype)
-        for conv in self._shared_convs():
-            assert self._params.holds(conv.W) and self._params.holds(conv.b)              # views, not copies
+        self._hold_views(self._shared_convs())
         self._sessions = {}
         self._conv1_params = (params['conv1'][0], params['conv1'][1], device, dtype)
         self._hsplit = {}           # h channels -> (image-half conv, y-half conv) of the first layer
-        self._adj = None            # training: the data-gradient layers (`_adjoints`)
+        # training: the data-gradient layers of dilconv1..7.  The adjoint of a 'valid' dilated 3x3 layer is the same
+        # layer with the channel-transposed, spatially flipped filter on g_z inside a zero border of 2 d (the
+        # weight-gradient kernel stores g_z there) -- W[in,out,k,k] flipped and READ as W[out,in,k,k] is that filter
+        self.dgrads = DataGrads([(name, Layer(lambda W=params[name][0]: W.flip(2, 3),
+                                              dict(pad=0, dil=d, layout='oihw', dtype=dtype)))
+                                 for name, d in zip(PARAM_ORDER[1:], DILATIONS + [1])])
         self._train = {}            # training: buffers per geometry
         self._saved = None          # training: what `forward_train` kept for `backward`
         self._keep_pre, self._pre = False, None
@@ -338,33 +341,10 @@ class ContextModDAE:
         return nblk
 
     # ---- training (reference train_dae.py with dae kind 'contextmod') ----
-    def parameters(self):
-        """{name: (W, b)} in PARAM_ORDER: views of `self.flat`, the checkpoint's arrays in the checkpoint's
-        layouts.  After changing them in place call `refresh()`."""
-        return dict(self._views)
-
-    def state_arrays(self):
-        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
-        return self._params.state_arrays()
-
     @property
-    def gflat(self):
-        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
-        return self._params.gflat
-
-    def _adjoint_filters(self):
-        """(filter, dilation) of the data-gradient layer of dilconv1..7: the adjoint of a 'valid' dilated 3x3
-        layer is the same layer with the channel-transposed, spatially flipped filter on g_z inside a zero border
-        of 2 d -- W[in,out,k,k] flipped and READ as W[out,in,k,k] is exactly that filter."""
-        for i, d in enumerate(DILATIONS + [1]):
-            yield self._views['dilconv%d' % (i + 1)][0].flip(2, 3), d
-
-    def _adjoints(self):
-        """The data-gradient layers (`_adjoint_filters`), built at first use."""
-        if self._adj is None:
-            self._adj = [ops.Conv(Wf.contiguous(), None, pad=0, relu=False, dil=d, layout='oihw',
-                                  device=self.device, dtype=self.dtype) for Wf, d in self._adjoint_filters()]
-        return self._adj
+    def _adj(self):
+        """The data-gradient layers in layer order (None until a `backward` has built them); for tests."""
+        return None if self.dgrads.layers is None else list(self.dgrads.layers.values())
 
     def refresh(self):
         """The parameters (`self.flat`) have been changed in place: every layer object that holds them -- the
@@ -386,10 +366,7 @@ class ContextModDAE:
         for sess in self._sessions.values():          # the cached image half of a session that is still in use
             if sess['split'] is not None:
                 sess['split'][0](sess['hpad'], out=sess['hb'])
-        if self._adj is not None:
-            for adj, (Wf, _) in zip(self._adj, self._adjoint_filters()):
-                adj.W.copy_(Wf)
-                adj.refresh()
+        self.dgrads.refresh()
 
     def _train_buffers(self, B, ch, Cy, H, W, device):
         key = (B, ch, Cy, H, W)
@@ -448,17 +425,18 @@ class ContextModDAE:
         s = self._saved
         if s is None:
             raise RuntimeError('backward() needs forward_train() first')
-        gv, adj, acts, buf = self._params.grad_views(), self._adjoints(), s['acts'], s['buf']
+        gv, dgrads, acts, buf = self._params.grad_views(), self.dgrads, s['acts'], s['buf']
+        dgrads.prepare()
         H, W = s['hw']
         ops.conv_small_wgrad(acts[6], g_score, None, *gv['dilconv7'], dil=1, layout='iohw')
-        g = adj[6](g_score)
+        g = dgrads('dilconv7', g_score)
         for L in range(6, 0, -1):
             d = DILATIONS[L - 1]
             gz = buf['gz'][L - 1]
             ops.conv_small_wgrad(acts[L - 1], g, acts[L], *gv['dilconv%d' % L], dil=d, layout='iohw', gz=gz,
                                  gz_off=(2 * d, 2 * d))
             # PadLayer(32)'s adjoint is the crop at (32, 32): only that window of dilconv1's data gradient
-            g = adj[L - 1](gz, window=(32, 32, H, W)) if L == 1 else adj[L - 1](gz)
+            g = dgrads('dilconv%d' % L, gz, window=(32, 32, H, W) if L == 1 else None)
         c1 = acts[0][:, :, 32:32 + H, 32:32 + W].contiguous()
         ops.conv_small_wgrad(buf['cat'], g, c1, *gv['conv1'], dil=1, layout='oihw')
         return gv

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import ops, regions
-from .params import PackedImages, ParamStore, check_mode
+from .datagrads import DataGrads, Layer, Views, _embed, flipped
+from .params import Trainable, check_mode
 from .regions import center
 from .weights import load_param_list
 
@@ -51,24 +52,16 @@ def param_order(concat_h=('pool4',), conv_before_pool=1, additional_pool=2,
 C8_UNPOOL_MIN_CIN = int(os.environ.get('IISEG_C8_UNPOOL_MIN_CIN', '1024'))
 
 
-def _embed(g, hw, off):
-    """Adjoint of a crop: a zeroed map of planes `hw` with `g` at offset `off` (NCHW or C8: dims 2, 3 are the
-    planes in both)."""
-    out = torch.zeros(tuple(g.shape[:2]) + tuple(hw) + tuple(g.shape[4:]), dtype=g.dtype, device=g.device)
-    out[:, :, off[0]:off[0] + g.shape[2], off[1]:off[1] + g.shape[3]].copy_(g)
-    return out
-
-
 class _NCHWAdjoint:
-    """What `StandardDAE._adjoint_walk` does at a level on fp32 / float64 NCHW maps: the flipped-filter convs,
-    ops.depool_bwd / ops.pool_relu_bwd under the forward's (pre, pooled) tensors and, with `gv`, ops.conv_wgrad on
-    the g_z the chain forms and the layer input that `forward_train` saved (DePool2D's output is materialised for
-    the up_conv layers, a concat layer is two calls into one dW, h first)."""
+    """What `StandardDAE._adjoint_walk` does at a level on fp32 / float64 NCHW maps: the layers' data gradients
+    (`StandardDAE.dgrads`), ops.depool_bwd / ops.pool_relu_bwd under the forward's (pre, pooled) tensors and, with
+    `gv`, ops.conv_wgrad on the g_z the chain forms and the layer input that `forward_train` saved (DePool2D's
+    output is materialised for the up_conv layers, a concat layer is two calls into one dW, h first)."""
 
     def __init__(self, dae, override, gv):
-        # (dgrad='bf16': `backward` forms its data gradients with ops.conv_dgrad, no flipped-filter layers)
-        self.d16 = gv is not None and dae.dgrad == 'bf16'
-        self.dae, self.bwd = dae, None if self.d16 else dae._bwd_convs()
+        # (without `gv` -- backward_y -- every data gradient takes the fp32 flipped-filter form, whatever `dgrad` says)
+        self.dae, self.flipped = dae, gv is None
+        dae.dgrads.prepare(self.flipped)
         _, self.pre, self.pool = dae._saved
         if any(t.device.type == 'meta' for t in self.pre.values()):
             raise RuntimeError('backward_y needs the pre-pool maps of the forward pass: set '
@@ -94,7 +87,7 @@ class _NCHWAdjoint:
             t_in = self.pool[self.dae.total] if p == self.dae.total else self.fused['fused_up%d' % (p + 1)]
             ops.conv_wgrad(ops.unpool_eqmask(t_in, mpre, mpool), g_c, *self.gv['up_conv%d' % p], pad=1,
                            mma=self.dae.wgrad)
-        g_u = self.dae._dgrad16('up_conv%d' % p, g_c) if self.d16 else self.bwd['up_conv%d' % p](g_c)
+        g_u = self.dae.dgrads('up_conv%d' % p, g_c, flipped=self.flipped)
         return ops.depool_bwd(g_u, mpre, mpool)
 
     def encoder(self, p, gp, acc, window, want_data):
@@ -112,14 +105,7 @@ class _NCHWAdjoint:
             ops.conv_wgrad(self.pool[p - 1], g_z, dW, db, pad=fwd.pad, ci0=ch, mma=self.dae.wgrad)
         if not want_data:
             return None
-        if self.d16:
-            if window is not None:
-                raise NotImplementedError("dgrad='bf16': the pad-100 first layer's window stays on the fp32 path")
-            return self.dae._dgrad16(name, g_z, acc)
-        conv = self.bwd[name]
-        if acc is not None:
-            return conv(g_z, add=acc, out=acc)
-        return conv(g_z) if window is None else conv(g_z, window=window)
+        return self.dae.dgrads(name, g_z, acc=acc, window=window, flipped=self.flipped)
 
 
 class _C8Adjoint:
@@ -152,7 +138,7 @@ class _C8Adjoint:
         return self.pool8[p].shape[2], self.pool8[p].shape[3]
 
     def decoder(self, p, g_c):
-        g_u = self.bwd['up_conv%d' % p](g_c)
+        g_u = self.dae.dgrads('up_conv%d' % p, g_c)
         return ops.depool_bwd_c8(g_u, self.masks[p], gate=self.pool8[p] if p == self.dae.total else None)
 
     def encoder(self, p, gp, acc, window, want_data):
@@ -160,25 +146,25 @@ class _C8Adjoint:
             return None
         if p != self.dae.total:                          # (the deepest level arrives gated: `decoder`)
             gp = ops.relu_gate_c8(gp, self.pool8[p], out=gp)
-        conv = self.bwd['conv%d_1' % p]
-        kw = {}
+        name = 'conv%d_1' % p
+        conv = self.bwd[name]
+        kw = dict(window=window)
         if acc is not None:
             kw['add'] = acc
-        if window is not None:
-            kw['window'] = window
         if p == 1:
             kw['out_format'] = 'nchw'
         ph, pw = self.hw[p]
         if 0 < C8_UNPOOL_MIN_CIN <= conv.Cin and conv.Cout > 16:
             u = torch.zeros(tuple(gp.shape[:2]) + (ph, pw, 8), dtype=torch.bfloat16, device=gp.device)
-            return conv(ops.unpool_c8(gp, self.masks[p], u), **kw)
-        return conv(gp, mask_in=self.masks[p], unpool_hw=(ph, pw), **kw)
+            return self.dae.dgrads(name, ops.unpool_c8(gp, self.masks[p], u), **kw)
+        return self.dae.dgrads(name, gp, mask_in=self.masks[p], unpool_hw=(ph, pw), **kw)
 
 
-class StandardDAE:
+class StandardDAE(Trainable, Views):
     """Callable with (h_1..h_k, y) like the compiled pred_dae_fn (iterative_inference.py:189-190)."""
 
     kind = 'standard'
+    _BUILT = 'a StandardDAE'
 
     def __init__(self, params, n_classes, concat_h=('pool4',), padding=100, n_filters=64,
                  conv_before_pool=1, additional_pool=2, skip=True, unpool_type='trackind', bn=0,
@@ -209,11 +195,7 @@ class StandardDAE:
         self.trainable = bool(trainable)
         for switch, mode in (('wgrad', wgrad), ('dgrad', dgrad), ('fwd', fwd)):
             setattr(self, switch, check_mode(switch, mode, dtype, bool(trainable)))
-        # dgrad='bf16': {name: bf16 filter image}, those up to date (`_dpack`, `_dpack_fresh`: its own dict and set,
-        # by the names the tests read)
-        self._images = PackedImages()
-        self._dpack, self._dpack_fresh = self._images.images, self._images.fresh
-        self.flat, self._params, self._tsaved = None, None, None
+        self._tsaved = None
         if trainable:
             if conv_before_pool != 1 or bn or dropout > 0 or unpool_type not in ('trackind', 'inverse'):
                 raise NotImplementedError('training the standard DAE: conv_before_pool=1, bn=0, dropout=0, '
@@ -225,9 +207,8 @@ class StandardDAE:
                 raise NotImplementedError('training the standard DAE: emulate_noise (DePool2D masks of a hidden '
                                           'noisy re-forward) is not built: the weight gradients take the masks of '
                                           'the training forward itself')
-            self._params = ParamStore(params, param_order(concat_h, conv_before_pool, additional_pool, unpool_type,
-                                                          bn), dtype, device)
-            self.flat, params = self._params.flat, self._params.views
+            params = self._store_params(params, param_order(concat_h, conv_before_pool, additional_pool, unpool_type,
+                                                            bn), dtype, device)
         self.mma = mma
         # bf16 C8 activations between the layers (ops.Conv mma='bf16c8', `_scores_c8`)
         # ('bf16x3': the same plan on hi / lo pairs, the fp32-class mode of that kernel)
@@ -255,7 +236,7 @@ class StandardDAE:
         self.random_source = None     # callable(kind, level, name, shape) -> tensor, or None: torch RNG
         self._seed, self._gen = int(seed), None
         self.dtype = dtype
-        self._bwd, self._saved, self._saved_c8 = None, None, None
+        self._saved, self._saved_c8 = None, None
         self.unpool_type = unpool_type
         self.concat_h, self.padding, self.skip = concat_h, padding, skip
         self.conv_before_pool = conv_before_pool
@@ -341,9 +322,8 @@ class StandardDAE:
         self.use_masks = os.environ.get('IISEG_DEPOOL_MASKS', '1') != '0'
         self.keep_pre = False   # True: the pre-pool maps are needed afterwards (backward_y)
         if trainable:
-            for conv in self.conv_layers().values():
-                assert self._params.holds(conv.W) and self._params.holds(conv.b)          # views, not copies
-                conv.wino = conv.wino_f64 = False     # no weight transform to keep in step (Conv.refresh)
+            self._hold_views(self.conv_layers().values(), plain=True)
+        self.dgrads = DataGrads(self._dgrad_table(), self._refuse_gradient_mode)
 
     def _mask_levels(self, overridden):
         """Levels (1-based) whose DePool2D mask travels as bytes in this call."""
@@ -805,37 +785,32 @@ class StandardDAE:
         return out
 
     # ---- true-gradient mode (SURVEY 8f rank 4; not in the reference, F1) -----------------------
-    def _flipped_filters(self):
-        """(name, filter) of every layer's backward-data conv: the channel-transposed, spatially flipped filter.
-        After a concat only the filters of the non-h channels are kept: h is a constant of the loop."""
-        prev = self.n_classes
+    def _dgrad_table(self):
+        """[(name, how the layer's data gradient is formed)] (datagrads.Layer), encoder then decoder.  Backward-data
+        of a 3x3 stride-1 conv = the forward conv of the gradient with the flipped filter ('same' for pad 1; for the
+        pad-100 first layer the window at offset pad-1 of that 'same' result).  After a concat only the filters of
+        the non-h channels are kept: h is a constant of the loop.  dgrad='bf16': ops.conv_dgrad on the layer's own
+        parameter -- after a concat the feature channels only -- in `backward`; `backward_y` forces the flipped form.
+        (A C8 module's layers are built for C8 input explicitly -- mma='bf16c8', whatever ops.DEFAULT_MMA says: the
+        flipped weights are rounded to bf16 when they are packed; no bias.)"""
+        kw = dict(pad=1, dtype=self.dtype, **(dict(mma='bf16c8') if self.c8 else {}))
+        op = 'conv_dgrad' if self.dgrad == 'bf16' else None
+        table, prev = [], self.n_classes
         for p in range(self.total):
-            name = 'conv%d_1' % (p + 1)
-            W = self.enc[name].W                         # (Cout, ch + prev, 3, 3), on the device
-            yield name, W[:, W.shape[1] - prev:].transpose(0, 1).flip(2, 3)
-            prev = W.shape[0]
+            conv = self.enc['conv%d_1' % (p + 1)]        # W (Cout, ch + prev, 3, 3), on the device
+            table.append(('conv%d_1' % (p + 1), Layer(lambda conv=conv, prev=prev: flipped(conv.W[:, conv.Cin - prev:]),
+                                                      kw, self.trainable, 0, op, conv, conv.Cin - prev, prev)))
+            prev = conv.Cout
         for p in range(self.total, 0, -1):
-            name = 'up_conv%d' % p
-            yield name, self.dec[name].W.transpose(0, 1).flip(2, 3)
+            conv = self.dec.get('up_conv%d' % p)         # (unpool_type='standard' has none: `_refuse_gradient_mode`)
+            table.append(('up_conv%d' % p, Layer(lambda conv=conv: flipped(conv.W), kw, self.trainable, 0, op, conv, 0,
+                                                 conv and conv.Cin)))
+        return table
 
-    def _bwd_convs(self):
-        """Backward-data of a 3x3 stride-1 conv = the forward conv of the gradient with the flipped filter
-        (`_flipped_filters`; 'same' for pad 1; for the pad-100 first layer the window at offset pad-1 of that
-        'same' result)."""
-        if self._bwd is None:
-            if self.conv_before_pool != 1 or self.bn or self.unpool_type == 'standard':
-                raise NotImplementedError('gradient mode: conv_before_pool=1, bn=0, unpool_type in '
-                                          '{trackind, inverse}')
-            # (a C8 module's layers are built for C8 input explicitly -- mma='bf16c8', whatever ops.DEFAULT_MMA says:
-            # the flipped weights are rounded to bf16 when they are packed; no bias)
-            kw = dict(mma='bf16c8') if self.c8 else {}
-            bwd = {name: ops.Conv(Wt.contiguous(), None, pad=1, relu=False, device=Wt.device, dtype=self.dtype, **kw)
-                   for name, Wt in self._flipped_filters()}
-            if self.trainable:
-                for conv in bwd.values():
-                    conv.wino = conv.wino_f64 = False
-            self._bwd = bwd
-        return self._bwd
+    def _refuse_gradient_mode(self):
+        if self.conv_before_pool != 1 or self.bn or self.unpool_type == 'standard':
+            raise NotImplementedError('gradient mode: conv_before_pool=1, bn=0, unpool_type in '
+                                      '{trackind, inverse}')
 
     def _adjoint_walk(self, g_score, y_shape, override=None, gv=None, first_layer=True):
         """The adjoint of the latest `scores()` call, level by level (oracle/dae_grad.py), on full maps (the
@@ -876,24 +851,6 @@ class StandardDAE:
         return self._adjoint_walk(g_score, y_shape, override=None if self.c8 else self._saved[0])
 
     # ---- training (reference train_dae.py with dae kind 'standard') ----------
-    def parameters(self):
-        """{name: (W, b)} in `param_order`: views of `self.flat`.  After changing them in place call
-        `refresh()`."""
-        return dict(self._params.views)
-
-    def state_arrays(self):
-        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
-        return self._params.state_arrays()
-
-    @property
-    def gflat(self):
-        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
-        return self._params.gflat
-
-    def _need_trainable(self, what):
-        if not self.trainable:
-            raise RuntimeError('%s needs a StandardDAE built with trainable=True' % what)
-
     def forward_train(self, h_list, y, noise=0.0, generator=None, eps=None):
         """The training-mode forward: GaussianNoiseLayer on y (y + noise * N(0, 1) formed ONCE, `eps` = the
         caller's standard-normal sample, else drawn from `generator`), then `scores` on full maps with the
@@ -923,25 +880,10 @@ class StandardDAE:
         out.update({k: v for k, v in self._tsaved[2].items() if k.startswith('fused_up')})
         return out
 
-    def _dgrad16(self, name, gz, acc=None):
-        """dgrad='bf16': the data gradient of layer `name` for g_z (+ acc, in place) by ops.conv_dgrad on the
-        layer's own parameter -- after a concat the feature channels only: h is a constant.  The bf16 image of the
-        filter is packed on first use after `refresh()`, into the buffer it already has."""
-        conv = self.enc[name] if name in self.enc else self.dec[name]
-        cin = conv.Cin
-        if name in self.enc:
-            p = int(name[4:].split('_')[0])
-            cin = self.n_classes if p == 1 else self.enc['conv%d_1' % (p - 1)].Cout
-        ci0 = conv.Cin - cin
-        packed = self._images.image(
-            name, lambda out: ops.conv_dgrad_pack(conv.W, tuple(gz.shape), ci0, cin, conv.layout, out=out))
-        return ops.conv_dgrad(gz, conv.W, ci0=ci0, cin=cin, layout=conv.layout, out=acc, accumulate=acc is not None,
-                              packed=packed)
-
     def backward(self, g_score):
         """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore =
         g_score, after `forward_train`: `_adjoint_walk` with ops.conv_wgrad at every layer.  The data gradient
-        of the first layer is not formed.  dgrad='bf16': the data gradients by ops.conv_dgrad (`_dgrad16`)."""
+        of the first layer is not formed.  dgrad='bf16': the data gradients by ops.conv_dgrad (`_dgrad_table`)."""
         self._need_trainable('backward')
         if self._tsaved is None or self._saved is None:
             raise RuntimeError('backward() needs forward_train() first')
@@ -956,12 +898,7 @@ class StandardDAE:
         self._need_trainable('refresh')
         for conv in self.conv_layers().values():
             conv.refresh()
-        if self._bwd is not None:
-            for name, Wt in self._flipped_filters():
-                self._bwd[name].W.copy_(Wt)
-            for conv in self._bwd.values():
-                conv.refresh()
-        self._images.invalidate()
+        self.dgrads.refresh()
         self._store = None
         self._scratch_sessions.clear()
 

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .params import PackedImages, ParamStore, check_mode
+from .datagrads import DataGrads, Layer, Views, flipped
+from .params import Trainable, check_mode
 from .regions import center, conv_region, pool_region
 from .weights import load_param_list
 
@@ -31,7 +32,9 @@ _NAMES_FWD16 = tuple(sorted(_NAMES_3X3)) + _NAMES_KXK16  # the fifteen layers of
 _UID = itertools.count(1)   # identity of a net in the provenance tags (never reused, unlike id())
 
 
-class FCN8:
+class FCN8(Trainable, Views):
+    _BUILT = 'an FCN8'
+
     def __init__(self, params, n_classes, layer=('probs_dimshuffle',), pad=100, temperature=1.0,
                  device='cuda', dtype=torch.float32, mma=None, trainable=False, dropout=0.5, wgrad='f32',
                  dgrad='f32', kxk='f32', fwd='f32'):
@@ -67,11 +70,7 @@ class FCN8:
         self.dropout = float(dropout)
         for switch, mode in (('wgrad', wgrad), ('dgrad', dgrad), ('kxk', kxk), ('fwd', fwd)):
             setattr(self, switch, check_mode(switch, mode, dtype, bool(trainable)))
-        # dgrad='bf16' / kxk='bf16': {name: bf16 filter image}, those up to date (`_dpack`, `_dpack_fresh`: its own
-        # dict and set, by the names the tests read)
-        self._images = PackedImages()
-        self._dpack, self._dpack_fresh = self._images.images, self._images.fresh
-        self.flat, self._params, self._tsaved, self._bwd = None, None, None, None
+        self._tsaved = None
         if trainable:
             # refused here, before any device work
             if dtype not in (torch.float32, torch.float64) or \
@@ -83,8 +82,7 @@ class FCN8:
                                           'upsample.b, which are parameters here)')
             if not 0.0 <= self.dropout < 1.0:
                 raise ValueError('dropout must be in [0, 1)')
-            self._params = ParamStore(params, PARAM_ORDER, dtype, device)
-            self.flat, params = self._params.flat, self._params.views
+            params = self._store_params(params, PARAM_ORDER, dtype, device)
         if mma is None:
             # IISEG_MMA=bf16x3 means "the DAE loop on hi / lo pairs"; this net takes the pair form
             # only when asked by name (tests/test_gpu_x3.py: the FCN-8 in fp32 keeps the mode's parity)
@@ -127,10 +125,11 @@ class FCN8:
         self.fold_border = os.environ.get('IISEG_FCN_BORDER_FOLD', '1') != '0' and not trainable
         self._border = {}
         if trainable:
-            for layer_ in list(self.convs.values()) + [self.score2, self.score4, self.upsample]:
-                assert self._params.holds(layer_.W) and self._params.holds(layer_.b)      # views, not copies
-            for conv in self.convs.values():
-                conv.wino = conv.wino_f64 = False     # no weight transform to keep in step (Conv.refresh)
+            self._hold_views(self.convs.values(), plain=True)
+            self._hold_views([self.score2, self.score4, self.upsample])
+        self.dgrads = DataGrads(self._dgrad_table())
+        # kxk='bf16': the operand precision of fc6's / fc7's weight gradients (the other 'valid' layers' stay fp32)
+        self._wgrad_kxk = {name: kxk if name in _NAMES_KXK16 else 'f32' for name in self.convs}
         self._uid = next(_UID)
         self.last_provenance = None   # per output of the latest forward: (store id, region) or None
 
@@ -294,36 +293,6 @@ class FCN8:
         return deconv(t, add=side, window=(center(dh, oh), center(dw, ow), oh, ow))
 
     # ---- training (reference train_fcn8.py) ----------------------------------
-    def parameters(self):
-        """{name: (W, b)} in PARAM_ORDER: views of `self.flat`.  After changing them in place call `refresh()`."""
-        self._need_trainable('parameters')
-        return dict(self._params.views)
-
-    def state_arrays(self):
-        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
-        self._need_trainable('state_arrays')
-        return self._params.state_arrays()
-
-    @property
-    def gflat(self):
-        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
-        return self._params.gflat
-
-    def weight_ranges(self):
-        """[(lo, hi)] of the weight arrays (not the biases) inside `flat`: what ops.l2_term walks."""
-        self._need_trainable('weight_ranges')
-        lo = self.flat.data_ptr()
-        out = []
-        for name in PARAM_ORDER:
-            W = self._params.views[name][0]
-            off = (W.data_ptr() - lo) // self.flat.element_size()
-            out.append((off, off + W.numel()))
-        return out
-
-    def _need_trainable(self, what):
-        if not self.trainable:
-            raise RuntimeError('%s needs an FCN8 built with trainable=True' % what)
-
     def _drop(self, t, keep, generator, deterministic):
         """DropoutLayer(p, rescale=True) on a copy of t: (dropped map, the 0/1 mask used or None)."""
         if deterministic or self.dropout == 0.0:
@@ -381,26 +350,24 @@ class FCN8:
         """What the last `forward_train` kept, under the names of tests/fcn8_train_ref.py; for tests."""
         return dict(self._tsaved)
 
-    def _flipped_filters(self):
-        """(name, filter) of every layer's backward-data conv (conv1_1 has none): the channel-transposed,
-        spatially flipped filter.  dgrad='bf16': of the K x K and 1 x 1 layers only; kxk='bf16': none of fc6 / fc7."""
+    def _dgrad_table(self):
+        """[(name, how the layer's data gradient is formed)] (datagrads.Layer) of every conv but conv1_1, which has
+        none.  Backward-data of a stride-1 conv = the forward conv of the gradient with the flipped filter: 'same'
+        for the 3x3 pad-1 layers, as it is for the 1x1 layers, and for the 'valid' 7x7 fc6 the 'valid' conv of g_z
+        inside a zero border of 6.  dgrad='bf16': the 3x3 layers by ops.conv_dgrad, kxk='bf16': fc6 / fc7 by
+        ops.conv_dgrad_kxk on g_z itself (no zero-bordered copy), on the layer's own parameter; no fp32 flipped
+        copy of a filter the bf16 form replaces is built."""
+        table = []
         for name in PARAM_ORDER[1:]:
-            if name in self.convs and not (self.dgrad == 'bf16' and name in _NAMES_3X3) and \
-                    not (self.kxk == 'bf16' and name in _NAMES_KXK16):
-                yield name, self.convs[name].W.transpose(0, 1).flip(2, 3)
-
-    def _bwd_convs(self):
-        """Backward-data of a stride-1 conv = the forward conv of the gradient with the flipped filter: 'same'
-        for the 3x3 pad-1 layers, as it is for the 1x1 layers, and for the 'valid' 7x7 fc6 the 'valid' conv of
-        g_z inside a zero border of 6."""
-        if self._bwd is None:
-            bwd = {name: ops.Conv(Wt.contiguous(), None, pad=1 if Wt.shape[2] == 3 else 0, relu=False,
-                                  device=Wt.device, dtype=self.dtype, mma='f32')
-                   for name, Wt in self._flipped_filters()}
-            for conv in bwd.values():
-                conv.wino = conv.wino_f64 = False
-            self._bwd = bwd
-        return self._bwd
+            if name not in self.convs:
+                continue
+            conv = self.convs[name]
+            op = 'conv_dgrad' if self.dgrad == 'bf16' and name in _NAMES_3X3 else \
+                'conv_dgrad_kxk' if self.kxk == 'bf16' and name in _NAMES_KXK16 else None
+            table.append((name, Layer(None if op else (lambda conv=conv: flipped(conv.W)),
+                                      dict(pad=1 if conv.KH == 3 else 0, dtype=self.dtype, mma='f32'), True,
+                                      0 if conv.KH == 3 else conv.KH - 1, op, conv)))
+        return table
 
     def backward(self, g_score):
         """{name: (dW, db)} (views of one flat gradient buffer laid out as `self.flat`) for dL/dscore = g_score,
@@ -410,8 +377,9 @@ class FCN8:
         gradient) and the five blocks (ops.pool_relu_bwd at a block's last convolution, ops.relu_gate at the
         others, ops.conv_wgrad and the flipped-filter convolution).  pool4 and pool3 receive two gradients: the
         main path's (conv5_1's / conv4_1's data gradient) comes first, the side branch's is added to it, placed at
-        the centre window's offset.  conv1_1's data gradient is not formed.  dgrad='bf16': the twelve 3x3 data gradients by
-        ops.conv_dgrad (`_dgrad16`), the ops.relu_gate that follows one inside a block as its `gate`.  kxk='bf16':
+        the centre window's offset.  conv1_1's data gradient is not formed.  Every data gradient is `self.dgrads`'
+        (`_dgrad_table`): with dgrad='bf16' the twelve 3x3 ones by ops.conv_dgrad, the ReLU gate that follows one
+        inside a block in the same launch instead of the ops.relu_gate launch behind the fp32 layer.  kxk='bf16':
         fc6's and fc7's weight gradients by ops.conv_wgrad_kxk(mma='bf16'), their data gradients by
         ops.conv_dgrad_kxk on g_z itself (no zero-bordered copy); the dropout adjoint and the ops.relu_gate behind
         fc7's data gradient stay the launches they are."""
@@ -419,7 +387,8 @@ class FCN8:
         s = self._tsaved
         if s is None:
             raise RuntimeError('backward() needs forward_train() first')
-        gv, bwd = self._params.grad_views(), self._bwd_convs()
+        gv, dgrads = self._params.grad_views(), self.dgrads
+        dgrads.prepare()
         win = s['win_upsample']
         ops.deconv_wgrad(s['final'], g_score, *gv['upsample'], stride=8, window=win)
         g = ops.deconv_dgrad(g_score, self.upsample.W, 8, s['final'].shape[2:], window=win)
@@ -434,15 +403,8 @@ class FCN8:
             g = ops.deconv_dgrad(g, deconv.W, deconv.stride, s[src].shape[2:], window=win)
         for name, xin, keep in (('score_fr', 'drop7', 'keep7'), ('fc7', 'drop6', 'keep6'), ('fc6', 'in_fc6', None)):
             gz = ops.relu_gate(g, s[name], dst=g)
-            if self.kxk == 'bf16' and name in _NAMES_KXK16:
-                ops.conv_wgrad_kxk(s[xin], gz, *gv[name], mma='bf16')
-                g = self._dgrad16(name, gz)
-            else:
-                ops.conv_wgrad_kxk(s[xin], gz, *gv[name])
-                if name == 'fc6':
-                    K = self.convs[name].KH
-                    gz = _embed(gz, (gz.shape[2] + 2 * (K - 1), gz.shape[3] + 2 * (K - 1)), (K - 1, K - 1))
-                g = bwd[name](gz)
+            ops.conv_wgrad_kxk(s[xin], gz, *gv[name], mma=self._wgrad_kxk[name])
+            g = dgrads(name, gz)
             if keep is not None and s[keep] is not None:
                 ops.dropout_apply(g, s[keep], self.dropout)             # dropout's adjoint: the forward's mask
         for bi in range(len(_BLOCKS) - 1, -1, -1):
@@ -450,35 +412,15 @@ class FCN8:
             if pname in side:
                 sname, gz = side[pname]
                 oy, ox = s['win_' + sname][:2]
-                bwd[sname](gz, add=g, add_off=(oy, ox), out=g, place=(oy, ox))   # main first, + the side branch
-            gated = False                                # g already carries this layer's ReLU gate (dgrad='bf16')
+                dgrads(sname, gz, add=g, add_off=(oy, ox), out=g, place=(oy, ox))   # main first, + the side branch
             for ni in range(len(names) - 1, -1, -1):
                 name = names[ni]
-                if ni == len(names) - 1:
-                    gz = ops.pool_relu_bwd(g, s[name], s[pname])
-                elif gated:
-                    gz = g
-                else:
-                    gz = ops.relu_gate(g, s[name], dst=g)
+                # (inside a block g arrives gated: the data gradient behind it took this layer's output as `gate`)
+                gz = ops.pool_relu_bwd(g, s[name], s[pname]) if ni == len(names) - 1 else g
                 ops.conv_wgrad(s['in_' + name], gz, *gv[name], pad=self.convs[name].pad, mma=self.wgrad)
-                if not (bi or ni):
-                    continue
-                if self.dgrad == 'bf16':                 # with the gate of the block's previous layer, if any
-                    g = self._dgrad16(name, gz, s[names[ni - 1]] if ni else None)
-                    gated = ni > 0
-                else:
-                    g = bwd[name](gz)
+                if bi or ni:
+                    g = dgrads(name, gz, gate=s[names[ni - 1]] if ni else None)
         return gv
-
-    def _dgrad16(self, name, gz, gate=None):
-        """dgrad='bf16' / kxk='bf16': the data gradient of layer `name` for g_z, times [gate > 0], on the layer's own
-        parameter: ops.conv_dgrad for a 3x3 layer, ops.conv_dgrad_kxk for the 'valid' fc6 / fc7.  The bf16 image of
-        the filter is packed on first use after `refresh()`, into the buffer it already has."""
-        conv = self.convs[name]
-        pack, run = (ops.conv_dgrad_kxk_pack, ops.conv_dgrad_kxk) if name in _NAMES_KXK16 else \
-            (ops.conv_dgrad_pack, ops.conv_dgrad)
-        packed = self._images.image(name, lambda out: pack(conv.W, tuple(gz.shape), 0, conv.Cin, conv.layout, out=out))
-        return run(gz, conv.W, layout=conv.layout, gate=gate, packed=packed)
 
     def refresh(self):
         """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into the
@@ -489,20 +431,8 @@ class FCN8:
             conv.refresh()
         for deconv in (self.score2, self.score4, self.upsample):
             deconv.refresh()
-        if self._bwd is not None:
-            for name, Wt in self._flipped_filters():
-                self._bwd[name].W.copy_(Wt)
-            for conv in self._bwd.values():
-                conv.refresh()
-        self._images.invalidate()
+        self.dgrads.refresh()
         self._border = {}
-
-
-def _embed(g, hw, off):
-    """Adjoint of a crop: a zeroed map of planes `hw` with `g` at offset `off`."""
-    out = torch.zeros(tuple(g.shape[:2]) + tuple(hw), dtype=g.dtype, device=g.device)
-    out[:, :, off[0]:off[0] + g.shape[2], off[1]:off[1] + g.shape[3]].copy_(g)
-    return out
 
 
 class FCN8DAE:

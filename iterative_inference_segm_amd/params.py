@@ -1,8 +1,8 @@
 """The parameters of a trainable DAE as ONE flat buffer (W then b per layer, in the checkpoint's order and the
 checkpoint's layouts) with views per layer, and its gradient twin: what the optimizer step (ops.opt_step) walks
-and what every layer object of the DAE holds views of (DESIGN.md sections 9 and 12); the 16-bit training switches
-of the trainable modules and the bf16 filter images their data gradients keep.  Plain torch:
-works on host tensors too, needs no library."""
+and what every layer object of the DAE holds views of (DESIGN.md sections 9 and 12); the parameter side every
+trainable net shares (`Trainable`) and the 16-bit training switches of the trainable modules.
+Plain torch: works on host tensors too, needs no library."""
 import torch
 
 # The 16-bit training switches (keyword and attribute of FCN8 / StandardDAE, option of the drivers): what each is
@@ -28,24 +28,6 @@ def check_mode(switch, mode, dtype, trainable=None):
             raise NotImplementedError("%s='bf16': the 16-bit %s of a trainable float32 module (trainable=%r, dtype=%s)"
                                       % (switch, SWITCHES_16BIT[switch], bool(trainable), dtype))
     return mode
-
-
-class PackedImages:
-    """{name: bf16 image of a layer's filter} (ops.conv_dgrad_pack / conv_dgrad_kxk_pack) and the names packed since
-    the parameters last changed: an image is packed on first use after `invalidate()`, into the buffer it has."""
-
-    def __init__(self):
-        self.images, self.fresh = {}, set()
-
-    def image(self, name, pack):
-        """The image of `name`; stale or missing: pack(out) makes it, into `out` (None: a new tensor)."""
-        if name not in self.fresh:
-            self.images[name] = pack(self.images.get(name))
-            self.fresh.add(name)
-        return self.images[name]
-
-    def invalidate(self):
-        self.fresh.clear()
 
 
 class ParamStore:
@@ -89,3 +71,54 @@ class ParamStore:
         """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
         return {n: (W.detach().cpu().float().numpy(), b.detach().cpu().float().numpy())
                 for n, (W, b) in self.views.items()}
+
+
+class Trainable:
+    """The parameter side of a trainable net (ContextModDAE, StandardDAE, FCN8): one ParamStore, its views handed
+    to the layers, and what a trainer and a checkpoint read of it.  A class names itself in `_BUILT` ('a
+    StandardDAE') and says in `trainable` whether this instance was built to be trained."""
+
+    trainable, flat, _params = True, None, None
+
+    def _store_params(self, params, order, dtype, device):
+        """The parameters into ONE flat buffer in `order` (W then b per layer): returns {name: (W, b)}, views of
+        `self.flat`, for the layers to be built on."""
+        self._params = ParamStore(params, order, dtype, device)
+        self.flat = self._params.flat
+        return self._params.views
+
+    def _hold_views(self, layers, plain=False):
+        """Every layer holds views of `flat`, not copies; plain: and runs on the direct / halo / tap kernels only
+        (no weight transform to keep in step, Conv.refresh)."""
+        for layer in layers:
+            assert self._params.holds(layer.W) and self._params.holds(layer.b)
+            if plain:
+                layer.wino = layer.wino_f64 = False
+
+    def _need_trainable(self, what):
+        if not self.trainable:
+            raise RuntimeError('%s needs %s built with trainable=True' % (what, self._BUILT))
+
+    def parameters(self):
+        """{name: (W, b)} in the order of `flat`: views of it, the checkpoint's arrays in the checkpoint's layouts.
+        After changing them in place call `refresh()`."""
+        self._need_trainable('parameters')
+        return dict(self._params.views)
+
+    def state_arrays(self):
+        """{name: (W, b)} as host arrays (float32, what weights.save_param_list writes); waits for the device."""
+        self._need_trainable('state_arrays')
+        return self._params.state_arrays()
+
+    @property
+    def gflat(self):
+        """The flat gradient buffer `backward` writes, laid out as `self.flat` (ParamStore.gflat)."""
+        self._need_trainable('gflat')
+        return self._params.gflat
+
+    def weight_ranges(self):
+        """[(lo, hi)] of the weight arrays (not the biases) inside `flat`: what ops.l2_term walks."""
+        self._need_trainable('weight_ranges')
+        lo, size = self.flat.data_ptr(), self.flat.element_size()
+        return [((W.data_ptr() - lo) // size, (W.data_ptr() - lo) // size + W.numel())
+                for W, _ in self._params.views.values()]

@@ -10,6 +10,8 @@ csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_
 the two of train_fcn8.py:116-137 for FCN-8 itself (FCN8Trainer).
 Everything is enqueued on the current stream; nothing here waits for the device.
 """
+import functools
+
 import torch
 
 from . import ops
@@ -19,25 +21,11 @@ from .params import check_mode
 SUPPORTED_LOSSES = ('crossentropy', 'squared_error')
 
 
-def check_wgrad(wgrad, dtype):
-    """The weight-gradient mode of a run (host only): 'f32', or 'bf16' with float32."""
-    check_mode('wgrad', wgrad, dtype)
-
-
-def check_dgrad(dgrad, dtype):
-    """The data-gradient mode of a run (host only): 'f32', or 'bf16' with float32."""
-    check_mode('dgrad', dgrad, dtype)
-
-
-def check_kxk(kxk, dtype):
-    """The mode of FCN-8's fc6 / fc7 gradients of a run (host only): 'f32', or 'bf16' with float32."""
-    check_mode('kxk', kxk, dtype)
-
-
-def check_fwd(fwd, dtype):
-    """The mode of the training forward of a run, FCN-8's or the standard DAE's (host only): 'f32', or 'bf16' with
-    float32."""
-    check_mode('fwd', fwd, dtype)
+# The mode of a run's 16-bit switch (host only): 'f32', or 'bf16' with float32 -- check_x(mode, dtype).
+check_wgrad = functools.partial(check_mode, 'wgrad')      # the weight gradients
+check_dgrad = functools.partial(check_mode, 'dgrad')      # the data gradients
+check_kxk = functools.partial(check_mode, 'kxk')          # FCN-8's fc6 / fc7 gradients
+check_fwd = functools.partial(check_mode, 'fwd')          # the training forward, FCN-8's or the standard DAE's
 
 
 def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=False, full_im_ft=False,
@@ -93,7 +81,36 @@ def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=Fals
         raise ValueError('Unknown optimizer')                      # train_dae.py:330-331
 
 
-class DAETrainer:
+class _Trainer:
+    """What the trainers share: the optimizer state of a net's flat parameter buffer, the learning rate the
+    kernels read, the generator, and val_fn's softmax + confusion counts."""
+
+    def __init__(self, net, n_classes, void_labels, optimizer, learning_rate, seed):
+        if list(void_labels) not in ([n_classes], []):
+            raise NotImplementedError('void_labels must be [n_classes] (the last target channel) or empty')
+        self.C, self.optimizer = int(n_classes), optimizer
+        dev, dt = net.flat.device, net.flat.dtype
+        self.lr = torch.full((1,), float(learning_rate), dtype=dt, device=dev)     # read by the kernel
+        self.s1 = torch.zeros_like(net.flat)
+        self.s2 = torch.zeros_like(net.flat) if optimizer == 'adam' else None
+        self.state = torch.tensor([0.0, 1.0, 1.0], dtype=dt, device=dev) if optimizer == 'adam' else None
+        self.generator = None
+        if seed is not None:
+            self.generator = torch.Generator(device=dev)
+            self.generator.manual_seed(int(seed))
+
+    def set_learning_rate(self, lr):
+        self.lr.fill_(float(lr))
+
+    def _metrics(self, score, T):
+        """The Metrics of one batch: the softmax of `score`, then its confusion counts against T."""
+        pred = ops.crop_softmax(score, score.shape[2], score.shape[3], off=(0, 0))
+        m = Metrics(self.C, score.device)
+        ops.confusion_accumulate(pred, T, m.cm, m.sums)
+        return m
+
+
+class DAETrainer(_Trainer):
     """fcn: the segmentation net (callable X -> [H..., Y]; may be None when the caller brings H and Y);
     dae: a ContextModDAE, or a StandardDAE built with trainable=True; trained in place."""
 
@@ -104,22 +121,9 @@ class DAETrainer:
             raise NotImplementedError('training a StandardDAE needs one built with trainable=True')
         check_supported(kind, training_loss, optimizer=optimizer, dae_dict={'concat_h': getattr(dae, 'concat_h', ())})
         self.grid = kind == 'standard'     # millions of parameters: the many-workgroup optimizer step, same bits
-        if list(void_labels) not in ([n_classes], []):
-            raise NotImplementedError('void_labels must be [n_classes] (the last target channel) or empty')
-        self.fcn, self.dae, self.C = fcn, dae, int(n_classes)
-        self.optimizer, self.losses, self.lmb, self.noise = optimizer, tuple(training_loss), float(lmb), float(noise)
-        dev, dt = dae.flat.device, dae.flat.dtype
-        self.lr = torch.full((1,), float(learning_rate), dtype=dt, device=dev)     # read by the kernel
-        self.s1 = torch.zeros_like(dae.flat)
-        self.s2 = torch.zeros_like(dae.flat) if optimizer == 'adam' else None
-        self.state = torch.tensor([0.0, 1.0, 1.0], dtype=dt, device=dev) if optimizer == 'adam' else None
-        self.generator = None
-        if seed is not None:
-            self.generator = torch.Generator(device=dev)
-            self.generator.manual_seed(int(seed))
-
-    def set_learning_rate(self, lr):
-        self.lr.fill_(float(lr))
+        super().__init__(dae, n_classes, void_labels, optimizer, learning_rate, seed)
+        self.fcn, self.dae = fcn, dae
+        self.losses, self.lmb, self.noise = tuple(training_loss), float(lmb), float(noise)
 
     def anneal(self, factor):
         """lr <- lr * factor on the device (train_dae.py:424)."""
@@ -143,13 +147,10 @@ class DAETrainer:
         dae = self.dae
         score = dae.forward_train(H if isinstance(H, (list, tuple)) else [H], Y_in, noise=0.0)
         res, _, _ = ops.ctx_loss(score, T, self.losses, self.lmb, grad=False)
-        pred = ops.crop_softmax(score, score.shape[2], score.shape[3], off=(0, 0))
-        m = Metrics(self.C, score.device)
-        ops.confusion_accumulate(pred, T, m.cm, m.sums)
-        return res[0], m, res[2]
+        return res[0], self._metrics(score, T), res[2]
 
 
-class FCN8Trainer:
+class FCN8Trainer(_Trainer):
     """The two compiled functions of the reference's train_fcn8.py:116-137 for an FCN8 built with trainable=True
     (DESIGN.md section 14): train_fn = masked cross-entropy + weight_decay * sum W^2 under adam, val_fn = loss and
     Jaccard counts on the deterministic forward.  The net is trained in place."""
@@ -157,24 +158,10 @@ class FCN8Trainer:
     def __init__(self, net, n_classes, void_labels=(11,), learning_rate=1e-4, weight_decay=0.0, seed=None):
         if not getattr(net, 'trainable', False):
             raise NotImplementedError('training an FCN8 needs one built with trainable=True')
-        if list(void_labels) not in ([n_classes], []):
-            raise NotImplementedError('void_labels must be [n_classes] (the last target channel) or empty')
         if not float(weight_decay) >= 0.0:
             raise ValueError('weight_decay must be >= 0')
-        self.net, self.C, self.weight_decay = net, int(n_classes), float(weight_decay)
-        dev, dt = net.flat.device, net.flat.dtype
-        self.lr = torch.full((1,), float(learning_rate), dtype=dt, device=dev)     # read by the kernel
-        self.s1 = torch.zeros_like(net.flat)
-        self.s2 = torch.zeros_like(net.flat)
-        self.state = torch.tensor([0.0, 1.0, 1.0], dtype=dt, device=dev)
-        self.ranges = net.weight_ranges()
-        self.generator = None
-        if seed is not None:
-            self.generator = torch.Generator(device=dev)
-            self.generator.manual_seed(int(seed))
-
-    def set_learning_rate(self, lr):
-        self.lr.fill_(float(lr))
+        super().__init__(net, n_classes, void_labels, 'adam', learning_rate, seed)
+        self.net, self.weight_decay, self.ranges = net, float(weight_decay), net.weight_ranges()
 
     def train_step(self, X, T, keep6=None, keep7=None):
         """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64).  keep6 / keep7:
@@ -195,7 +182,4 @@ class FCN8Trainer:
         Jaccard counts in the Metrics accumulators (api.Metrics.result() -> acc, jacc(2, C), mse)."""
         score = self.net.forward_train(X, deterministic=True)
         res, _, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=False)
-        pred = ops.crop_softmax(score, score.shape[2], score.shape[3], off=(0, 0))
-        m = Metrics(self.C, score.device)
-        ops.confusion_accumulate(pred, T, m.cm, m.sums)
-        return res[0], m
+        return res[0], self._metrics(score, T)

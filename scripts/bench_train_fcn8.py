@@ -111,7 +111,7 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         score = net.forward_train(X, generator=tr.generator)
         n_fwd = len(prof)
         _, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0)
-        with marked(net._bwd, prof) as log:
+        with marked(net.dgrads.layers, prof) as log:
             net.backward(g)
         if weight_decay > 0:
             ops.l2_term(net.flat, net.gflat, tr.ranges, weight_decay)

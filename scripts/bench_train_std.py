@@ -82,7 +82,7 @@ def one(B, H, W, dt, reps, peak, wgrad='f32', dgrad='f32', peak_d=157.3, yard=No
         score = dae.forward_train(h, y, noise=0.1, generator=tr.generator)
         n_fwd = len(prof)
         _, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0)
-        with marked(dae._bwd if dgrad == 'f32' else None, prof) as log:
+        with marked(dae.dgrads.layers if dgrad == 'f32' else None, prof) as log:
             dae.backward(g)
         torch.cuda.synchronize()
     finally:
