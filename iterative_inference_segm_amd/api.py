@@ -301,8 +301,10 @@ class IterativeInference:
                 "mode='gradient' needs the DAE's backward pass (backward_y), which the DAE kind %r (%s) does "
                 "not have: it is built for the kinds 'standard' and 'contextmod'"
                 % (getattr(self.dae, 'kind', '?'), type(self.dae).__name__))
-        if mode == 'gradient' and getattr(self.dae, 'kind', None) == 'contextmod' and getattr(self.dae, 'c8', False):
-            self.dae._refuse_c8("mode='gradient'")      # (no backward pass on the 16-bit leg: before any launch)
+        if mode == 'gradient' and getattr(self.dae, 'kind', None) == 'contextmod':
+            if getattr(self.dae, 'c8', False):
+                self.dae._refuse_c8("mode='gradient'")  # (no backward pass on the 16-bit leg: before any launch)
+            self.dae._refuse_wide("mode='gradient'")    # (nor with more than 16 channels into conv1)
         H_in = list(H) if isinstance(H, (list, tuple)) else [H]
         want_graph = GRAPH_MODE if graph is None else ('1' if graph else '0')
         if inplace:

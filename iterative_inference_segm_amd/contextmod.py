@@ -24,6 +24,7 @@ CTX_HSPLIT = os.environ.get('IISEG_CTX_HSPLIT', '1') != '0'
 
 PARAM_ORDER = ['conv1'] + ['dilconv%d' % i for i in range(1, 8)]   # get_all_param_values (P14)
 DILATIONS = [1, 2, 4, 8, 16, 1]                                     # contextmod_dae.py:78-101
+GRAD_MAX_CHANNELS = 16      # csrc/ctx_train.hip wgrad_check, csrc/ctx_grad.hip dgrad_check: Cin, Cout <= 16
 
 
 class ContextModDAE(Trainable):
@@ -96,6 +97,17 @@ class ContextModDAE(Trainable):
                                       "backward_y / sqerr_backward, no forward_train / backward): %s needs "
                                       "mma='f32'" % what)
 
+    def _refuse_wide(self, what):
+        """The weight- and data-gradient kernels (ops.conv_small_wgrad / conv_small_dgrad) take at most
+        GRAD_MAX_CHANNELS channels on either side, and conv1's input is [h, y].  Inference has no such limit (a
+        wider conv1 is not on the small-channel kernel, that is all).  Refused HERE, before a launch: conv1 is the LAST layer a backward
+        pass reaches."""
+        if self.conv1.Cin > GRAD_MAX_CHANNELS:
+            raise NotImplementedError(
+                'context module: %s needs classes + h channels <= %d for training and gradient mode (conv1 has '
+                '%d input channels); inference (scores / refine in residual mode) has no such limit'
+                % (what, GRAD_MAX_CHANNELS, self.conv1.Cin))
+
     @property
     def keep_pre(self):
         """True: `scores` keeps the seven rectified layer outputs and the score map of its latest call, which
@@ -106,6 +118,7 @@ class ContextModDAE(Trainable):
     def keep_pre(self, on):
         if on:
             self._refuse_c8('keep_pre (true-gradient mode)')
+            self._refuse_wide('keep_pre (true-gradient mode)')
         self._keep_pre = bool(on)
         if not on:
             self._pre = None
@@ -302,12 +315,14 @@ class ContextModDAE(Trainable):
         map of the latest `scores` call (made with `keep_pre` set).  Eight launches; the ReLU masks are applied
         while the gradient maps are read."""
         self._refuse_c8('backward_y')
+        self._refuse_wide('backward_y')
         return self._chain(g_score.contiguous(), 7, False, y_shape)
 
     def sqerr_backward(self, score, y):
         """`backward_y(ops.sqerr_softmax_bwd(score, y), y.shape)` with the softmax backward, dilconv7's adjoint
         and dilconv6's mask as ONE launch (ops.ctx_grad_head): the same bits, one launch fewer."""
         self._refuse_c8('sqerr_backward')
+        self._refuse_wide('sqerr_backward')
         if self._pre is None:
             raise RuntimeError('sqerr_backward needs the layer outputs of the forward pass: set dae.keep_pre = '
                                'True before calling scores()')
@@ -391,6 +406,7 @@ class ContextModDAE(Trainable):
         which this method took before it took a list, is still accepted.  Returns the score map (B,C,H,W) before
         the softmax."""
         self._refuse_c8('forward_train')
+        self._refuse_wide('forward_train')
         if isinstance(h_list, torch.Tensor):
             h_list = [h_list]
         if len(h_list) != 1:
@@ -422,6 +438,7 @@ class ContextModDAE(Trainable):
         g_score, after `forward_train`.  Per layer, last to first: the weight-gradient kernel (which applies
         the ReLU mask and stores g_z inside its zero border), then the data gradient as a 'valid' layer."""
         self._refuse_c8('backward')
+        self._refuse_wide('backward')
         s = self._saved
         if s is None:
             raise RuntimeError('backward() needs forward_train() first')

@@ -124,6 +124,42 @@ def test_refine_refuses_a_dae_without_backward_before_any_work():
         ii._refine([None], None, 0.05, 2, mode='newton')
 
 
+def test_context_module_refuses_training_and_gradient_mode_past_16_input_channels():
+    """14 classes + an RGB image are 17 channels into conv1, one more than the weight- / data-gradient kernels take
+    (Cin <= 16: the status codes above) -- and conv1 is the LAST layer a backward pass reaches.  Every entry that
+    leads there refuses at its front, naming the limit; 13 classes (16 channels) pass the same point."""
+    import torch
+
+    from iterative_inference_segm_amd import synthetic as S
+    from iterative_inference_segm_amd.api import IterativeInference
+    from iterative_inference_segm_amd.contextmod import GRAD_MAX_CHANNELS, ContextModDAE
+    assert GRAD_MAX_CHANNELS == 16
+    dae = ContextModDAE(S.make_contextmod_params(14, 3, seed=31), 14, device='cpu')
+    assert dae.conv1.Cin == 17
+    h, y = torch.zeros(1, 3, 8, 8), torch.zeros(1, 14, 8, 8)
+    limit = r'classes \+ h channels <= 16 for training and gradient mode'
+    with pytest.raises(NotImplementedError, match=limit):
+        dae.forward_train([h], y)
+    with pytest.raises(NotImplementedError, match=limit):
+        dae.backward(y)
+    with pytest.raises(NotImplementedError, match=limit):
+        dae.keep_pre = True
+    assert dae.keep_pre is False
+    with pytest.raises(NotImplementedError, match=limit):
+        dae.backward_y(y, y.shape)
+    with pytest.raises(NotImplementedError, match=limit):
+        dae.sqerr_backward(y, y)
+    ii = IterativeInference.__new__(IterativeInference)
+    ii.dae = dae
+    with pytest.raises(NotImplementedError, match=limit):
+        ii._refine([h], y, 0.05, 2, mode='gradient')
+    dae.keep_pre = False                                     # (switching it off is always allowed)
+    ok = ContextModDAE(S.make_contextmod_params(13, 3, seed=31), 13, device='cpu')
+    assert ok.conv1.Cin == 16
+    ok.keep_pre = True
+    assert ok.keep_pre is True
+
+
 def test_gradient_product_never_imports_oracle_or_tests():
     for path in (os.path.join(ROOT, 'iterative_inference_segm_amd', 'contextmod.py'),
                  os.path.join(ROOT, 'scripts', 'bench_ctx_grad.py')):

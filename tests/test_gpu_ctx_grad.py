@@ -45,7 +45,21 @@ DG_CASES = [
     (1, 11, None, 11, 37, 150, 3, 16, 'iohw', (32, 32, 37, 118)),     # PadLayer(32)'s adjoint: a window
     (3, 11, None, 11, 84, 82, 3, 1, 'iohw', (32, 32, 50, 40)),
     (1, 16, (2, 13), 16, 37, 150, 3, 4, 'iohw', (5, 3, 30, 131)),     # 16 channels either side, 13 of them asked
+    # off 11 classes: conv_small_dgrad_kernel<T, K, CIP> is compiled for CIP = the channels asked padded to 4, 8, 12,
+    # 16; the cases above reach CIP 12 and 16, and Cout 11 and 16, only
+    (1, 1, None, 1, 2, 3, 3, 1, 'iohw', None),            # K 3, CIP 4: one channel either side
+    (3, 3, None, 2, 17, 65, 3, 2, 'oihw', None),          # K 3, CIP 4, Cout 2: crosses a tile edge both ways
+    (1, 7, (3, 4), 4, 16, 62, 3, 4, 'oihw', None),        # K 3, CIP 4 exactly: conv1 of 4 classes
+    (2, 8, (3, 5), 5, 20, 18, 3, 1, 'oihw', (1, 1, 20, 18)),          # K 3, CIP 8, windowed: conv1 of 5 classes
+    (1, 8, None, 8, 9, 63, 1, 1, 'iohw', None),           # K 1, CIP 8 exactly
+    (1, 16, (3, 13), 13, 33, 70, 3, 1, 'oihw', (1, 1, 33, 70)),       # K 3, CIP 16: conv1 of 13 classes
+    (1, 16, (15, 1), 16, 12, 10, 3, 16, 'iohw', (3, 5, 7, 4)),        # K 3, CIP 4: only the last input channel, a
+    #                                                                   window one thread wide
+    (2, 2, None, 3, 5, 7, 1, 1, 'iohw', None),            # K 1, CIP 4, and
+    (1, 16, None, 13, 5, 66, 1, 1, 'oihw', None),         # K 1, CIP 16: the two instantiations left (K 1, CIP 12: above)
 ]
+# the 2 x 3 map has six mask values: the seed's offset at which they hold a zero, a negative and a positive one
+DG_SEED_OFFSET = {(2, 3): 2}
 
 
 @pytest.mark.parametrize('prec', ['f32', 'f64'])
@@ -53,7 +67,7 @@ DG_CASES = [
 def test_masked_data_gradient_is_exact_on_integers(built_lib, prec, B, Cin, ci, Cout, OH, OW, K, d, layout, window):
     from iterative_inference_segm_amd import ops
     dt = DT[prec]
-    rng = np.random.default_rng(OH * 7 + d + K + Cin + B)
+    rng = np.random.default_rng(OH * 7 + d + K + Cin + B + DG_SEED_OFFSET.get((OH, OW), 0))
     gout = rng.integers(-2, 3, size=(B, Cout, OH, OW)).astype(np.float64)
     out = rng.integers(-2, 3, size=(B, Cout, OH, OW)).astype(np.float64)        # zeros and negatives: masked
     assert (out == 0).any() and (out < 0).any() and (out > 0).any()
@@ -85,17 +99,27 @@ def test_masked_data_gradient_is_exact_on_integers(built_lib, prec, B, Cin, ci, 
 
 
 # ---- 2. head ----
+HEAD_CASES = [  # (C of the score map, Cin of dilconv7 = channels of out6, H, W): a block is 256 pixels of one image
+    (11, 11, 37, 50),      # 1850 pixels: 8 blocks, the last one ragged
+    (2, 16, 1, 1),         # one pixel; C at the lower end, Cin at the upper: the two parameter strides differ
+    (5, 9, 5, 51),         # 255 pixels
+    (16, 3, 16, 16),       # 256 pixels; C at the upper end, Cin < C
+    (13, 13, 1, 257),      # 257 pixels
+]
+
+
 @pytest.mark.parametrize('prec', ['f32', 'f64'])
-def test_head_matches_softmax_backward_bits_and_the_restatement(built_lib, prec):
+@pytest.mark.parametrize('Cc,Cin,H,W', HEAD_CASES)
+def test_head_matches_softmax_backward_bits_and_the_restatement(built_lib, prec, Cc, Cin, H, W):
     from iterative_inference_segm_amd import ops
     dt = DT[prec]
     rng = np.random.default_rng(17)
-    B, Cc, H, W = 3, 11, 37, 50                              # 1850 pixels: 8 blocks, the last one ragged
+    B = 3
     score = rng.standard_normal((B, Cc, H, W)) * 3
     y = rng.random((B, Cc, H, W))
     y /= y.sum(1, keepdims=True)
-    out6 = np.maximum(rng.standard_normal((B, Cc, H, W)), 0.0)           # about half exact zeros
-    W7 = rng.standard_normal((Cc, Cc, 1, 1))
+    out6 = np.maximum(rng.standard_normal((B, Cin, H, W)), 0.0)          # about half exact zeros
+    W7 = rng.standard_normal((Cin, Cc, 1, 1))                            # 'iohw': W[in, out, 1, 1]
     sd, yd, od, Wd = (_dev(a, dt) for a in (score, y, out6, W7))
     g6, gs = ops.ctx_grad_head(sd, yd, od, Wd, layout='iohw', want_gs=True)
     assert torch.equal(gs, ops.sqerr_softmax_bwd(sd, yd, off=(0, 0)))
@@ -104,10 +128,12 @@ def test_head_matches_softmax_backward_bits_and_the_restatement(built_lib, prec)
     to = lambda t: host(t).astype(np.float64)
     g6_ref, gs_ref = G.head(to(sd), to(yd), to(od), to(Wd))
     err = np.abs(to(g6) - g6_ref).max() / np.abs(g6_ref).max()
-    print('head %s: max|g6 - ref| / max|ref| = %.3g' % (prec, err))
-    assert (to(g6)[to(od) <= 0] == 0).all() and np.abs(g6_ref).max() > 1e-2
-    # float64: the issue's bound.  float32: exp and 11-term FMA chains in fp32, each term below max|g_s| max|W|:
-    # 1e-5 of the largest entry is an order above 11 x 2^-24 x that.
+    print('head %s %s: max|g6 - ref| / max|ref| = %.3g' % (prec, (Cc, Cin, H, W), err))
+    assert tuple(g6.shape) == (B, Cin, H, W) and (to(g6)[to(od) <= 0] == 0).all() and np.abs(g6_ref).max() > 0
+    if out6.size >= 1000:                                    # (statistics of the inputs: not of 3 x 16 values)
+        assert 0.4 < (out6 == 0).mean() < 0.6 and np.abs(g6_ref).max() > 1e-2
+    # float64: the issue's bound.  float32: exp and C-term FMA chains in fp32 (C <= 16), each term below max|g_s|
+    # max|W|: 1e-5 of the largest entry is an order above 16 x 2^-24 x that.
     assert err <= (1e-13 if prec == 'f64' else 1e-5)
     # the other parameter layout, and no mask
     Wt = _dev(np.ascontiguousarray(np.transpose(W7, (1, 0, 2, 3))), dt)

@@ -26,6 +26,19 @@ WG_CASES = [  # (B, Cin, Cout, H, W of the OUTPUT, K, dil, layout)
     (3, 14, 11, 84, 82, 3, 8, 'oihw'), (1, 11, 11, 37, 150, 3, 16, 'iohw'), (3, 11, 11, 84, 82, 1, 1, 'iohw'),
     (1, 14, 11, 37, 150, 1, 1, 'oihw'), (1, 11, 11, 288, 288, 3, 1, 'iohw'), (1, 14, 11, 288, 288, 3, 16, 'oihw'),
     (3, 11, 11, 84, 82, 3, 16, 'oihw'), (1, 11, 11, 288, 288, 1, 1, 'oihw'), (1, 14, 16, 37, 150, 3, 2, 'iohw'),
+    # off 11 classes: conv_small_wgrad_kernel<T, K, CP> is compiled for CP = Cout padded to 4, 8, 12, 16; the cases
+    # above reach CP 12 and 16 only.  (Tile: 64 columns x 16 rows in fp32, x 8 rows in float64.)
+    (1, 1, 1, 1, 1, 3, 1, 'oihw'),       # K 3, CP 4: one pixel, one channel either side, three of the four waves idle
+    (3, 3, 2, 17, 65, 3, 2, 'iohw'),     # K 3, CP 4: Cin < 4 waves; a row and a column past the fp32 tile; 12 fp32 slabs
+    #                                      (18 in float64): fewer than / just past the finalize kernel's 16 segments
+    (1, 7, 4, 16, 64, 3, 4, 'oihw'),     # K 3, CP 4 exactly: one fp32 tile, two float64 tiles; conv1 of 4 classes
+    (3, 8, 5, 9, 63, 1, 1, 'iohw'),      # K 1, CP 8
+    (1, 9, 8, 8, 128, 3, 16, 'oihw'),    # K 3, CP 8 exactly
+    (2, 15, 12, 24, 130, 3, 8, 'iohw'),  # K 3, CP 12 exactly
+    (1, 16, 13, 33, 70, 3, 1, 'oihw'),   # K 3, CP 16 with three padding planes, Cin at its maximum: conv1 of 13 classes
+    (1, 16, 16, 5, 3, 1, 1, 'iohw'),     # K 1, CP 16: both sides at the maximum on a tiny map
+    (2, 2, 3, 5, 7, 1, 1, 'oihw'),       # K 1, CP 4 (dilconv7 of a 3-class module): the one instantiation left
+    #                                      (K 1, CP 12: the 11 -> 11 cases above)
 ]
 
 
@@ -69,36 +82,78 @@ def test_weight_gradient_is_exact_on_integers(built_lib, prec, B, Cin, Cout, OH,
 
 
 # ---- 2. loss kernel ----
+LOSS_SHAPES = [  # (B, C, H, W): a block is 256 pixels of one image
+    (3, 11, 37, 50),       # 8 blocks per image, the last one ragged
+    (1, 2, 1, 1),          # one pixel, C at the lower end of its range
+    (2, 5, 5, 51),         # 255 pixels: one short of a block
+    (1, 16, 16, 16),       # 256 pixels: one block exactly, C at the upper end
+    (3, 13, 1, 257),       # one pixel past a block
+    (9, 4, 90, 90),        # 9 x 32 = 288 partials: the strided loop of `columns2` takes a second trip
+]
+
+
+def _loss_case(B, Cc, H, W, void):
+    # (the one-pixel map from a seed of its own: seed 3 puts its two logits 13.8 apart, r = [1 - 1e-6, 1e-6], and the
+    # whole gradient map -- r0 r1 (gr0 - gr1) -- is 2e-6, below the float32 rounding 2^-24 |gr| of the `gr - dot`
+    # it is the difference of: a bound relative to max|g| says nothing on a map whose ONLY pixel is saturated)
+    rng = np.random.default_rng(3 if H * W > 1 else 4)
+    score = rng.standard_normal((B, Cc, H, W)) * 3
+    if void:                                                 # (the one-pixel map cannot hold both kinds of pixel)
+        T = np.zeros((B, Cc + 1, H, W))
+        T[:, Cc] = 1
+    else:
+        # (label and void blobs of 16 x 16 pixels; 4 x 4 on the maps that are no larger than one such blob)
+        T = S.make_labels(B, H, W, n_classes=Cc, void_frac=0.0 if H * W == 1 else 0.2, seed=5,
+                          block=16 if min(H, W) > 16 else 4).astype(np.float64)
+        assert 0 < T[:, Cc].sum() < B * H * W or H * W == 1  # void and labelled pixels
+    if B > 1:
+        T[1] = 0
+        T[1, Cc] = 1                                         # an all-void image in the batch
+    if H >= 4:
+        score[0, :, :4] = -60.0                              # probabilities driven into the clip, both ends
+        score[0, min(3, Cc - 1), :4] = 60.0
+    return score, T
+
+
 @pytest.mark.parametrize('losses,lmb', [(('crossentropy',), 1.0), (('squared_error',), 1.0),
                                         (('crossentropy', 'squared_error'), 0.5)])
-def test_loss_kernel_f64(built_lib, losses, lmb):
+@pytest.mark.parametrize('B,Cc,H,W,void', [s + (False,) for s in LOSS_SHAPES] + [(1, 2, 1, 1, True)])
+def test_loss_kernel_f64(built_lib, losses, lmb, B, Cc, H, W, void):
     from iterative_inference_segm_amd import ops
-    rng = np.random.default_rng(3)
-    B, Cc, H, W = 3, 11, 37, 50
-    score = rng.standard_normal((B, Cc, H, W)) * 3
-    T = S.make_labels(B, H, W, n_classes=Cc, void_frac=0.2, seed=5).astype(np.float64)
-    T[1] = 0
-    T[1, Cc] = 1                                             # an all-void image in the batch
-    score[0, :, :4] = -60.0                                  # probabilities driven into the clip, both ends
-    score[0, 3, :4] = 60.0
+    score, T = _loss_case(B, Cc, H, W, void)
     loss, ce, se, g, (n_ce, n_se) = R.loss_and_grad(score, T, losses, lmb)
-    res, gd, cnt = ops.ctx_loss(_dev(score, torch.float64), _dev(T, torch.float64), losses, lmb)
+    sd, Td = _dev(score, torch.float64), _dev(T, torch.float64)
+    res, gd, cnt = ops.ctx_loss(sd, Td, losses, lmb)
+    # the validation pass's call (no gradient stored): the same loss and counts, bit for bit
+    res_v, g_v, cnt_v = ops.ctx_loss(sd, Td, losses, lmb, grad=False)
     torch.cuda.synchronize()
+    assert g_v is None and torch.equal(res_v, res) and torch.equal(cnt_v, cnt)
     res, cnt, gd = res.cpu().numpy(), cnt.cpu().numpy(), gd.cpu().numpy()
     assert cnt[0] == n_ce and cnt[1] == n_se
-    print('loss kernel f64: |dloss| %.3g  max|dg| / max|g| %.3g' %
-          (abs(res[0] - loss), np.abs(gd - g).max() / np.abs(g).max()))
-    # sums of ~5000 terms in double: 1e-12 relative is three orders above the rounding
-    assert abs(res[0] - loss) <= 1e-12 * abs(loss) and abs(res[1] - ce) <= 1e-12 * ce and abs(res[2] - se) <= 1e-12 * se
-    assert np.abs(gd - g).max() <= 1e-12 * np.abs(g).max()
-    assert not gd[1].any()                                   # the all-void image
+    if void:
+        assert n_ce == 0 and n_se == 0 and loss == 0.0 and not g.any()
+        assert float(res[0]) == 0.0 and not gd.any() and cnt[2] == 0.0 and cnt[3] == 0.0
+    else:
+        # (the bounds below are relative to max|g|: some pixel's softmax is not saturated, so that its gradient
+        # entry, before the division by the pixel count, is of the order of the terms it is the difference of)
+        assert n_ce > 0 and n_se > 0 and np.abs(g).max() * n_ce > 1e-2
+        print('loss kernel f64 %s: |dloss| %.3g  max|dg| / max|g| %.3g' %
+              ((B, Cc, H, W), abs(res[0] - loss), np.abs(gd - g).max() / np.abs(g).max()))
+        # sums of at most ~73000 terms in double: 1e-12 relative is two orders above the rounding
+        assert abs(res[0] - loss) <= 1e-12 * abs(loss) and abs(res[1] - ce) <= 1e-12 * ce and abs(res[2] - se) <= 1e-12 * se
+        assert np.abs(gd - g).max() <= 1e-12 * np.abs(g).max()
+    if B > 1:
+        assert not gd[1].any()                               # the all-void image
     # a batch without a single non-void pixel: zero loss and gradient, no NaN (documented in iiseg.h)
     Tv = np.zeros_like(T)
     Tv[:, Cc] = 1
-    res, gd, cnt = ops.ctx_loss(_dev(score, torch.float64), _dev(Tv, torch.float64), losses, lmb)
+    res, gd, cnt = ops.ctx_loss(sd, _dev(Tv, torch.float64), losses, lmb)
     assert float(res[0]) == 0.0 and not bool(gd.any()) and float(cnt[2]) == 0.0
     # float32 runs and agrees to float32 accuracy
-    res32, g32, _ = ops.ctx_loss(_dev(score, torch.float32), _dev(T, torch.float32), losses, lmb)
+    s32, T32 = _dev(score, torch.float32), _dev(T, torch.float32)
+    res32, g32, cnt32 = ops.ctx_loss(s32, T32, losses, lmb)
+    res32_v, _, cnt32_v = ops.ctx_loss(s32, T32, losses, lmb, grad=False)
+    assert torch.equal(res32_v, res32) and torch.equal(cnt32_v, cnt32)
     assert abs(float(res32[0]) - loss) <= 1e-5 * abs(loss)
     assert np.abs(g32.cpu().numpy() - g).max() <= 1e-5 * np.abs(g).max()
 
@@ -231,6 +286,73 @@ def test_optimizer_steps(built_lib, kind, prec):
         lr_host = npdt(lr.cpu().numpy()[0])
     if kind == 'adam':
         assert std.cpu().numpy().tolist() == [3.0, float(st[1]), float(st[2])]
+
+
+# opt_step_kernel: ONE workgroup of 1024 threads strides over the buffer; opt_step_grid_kernel: blocks of 256 threads,
+# at most 2048 of them, grid-stride beyond 2048 x 256 = 524288 scalars
+OPT_SIZES = [(False, n) for n in (1, 2, 1023, 1024, 1025)] + \
+            [(True, n) for n in (1, 255, 256, 257, 524288, 524289)]
+OPT_BORDER, OPT_SENTINEL = 67, -77.0
+
+
+@pytest.mark.parametrize('kind', ['rmsprop', 'adam'])
+@pytest.mark.parametrize('prec', ['f32', 'f64'])
+@pytest.mark.parametrize('grid,n', OPT_SIZES)
+def test_optimizer_step_at_the_block_edges(built_lib, kind, prec, grid, n):
+    """Both forms against numpy (R.rmsprop_step / R.adam_step) below, at and just past their block sizes, two steps;
+    p, s1 and s2 live inside sentinel buffers whose borders must stay as they are."""
+    from iterative_inference_segm_amd import ops
+    dt, npdt = DT[prec], {'f32': np.float32, 'f64': np.float64}[prec]
+    rng = np.random.default_rng(9 + n)
+    lo, hi = OPT_BORDER, OPT_BORDER + n
+
+    def bordered(inner=None):
+        t = torch.full((n + 2 * OPT_BORDER,), OPT_SENTINEL, dtype=dt, device='cuda')
+        if inner is None:
+            t[lo:hi].zero_()
+        else:
+            t[lo:hi].copy_(_dev(inner, dt))
+        return t
+    p = rng.standard_normal(n).astype(npdt)
+    bufs = {'p': bordered(p), 's1': bordered()}
+    if kind == 'adam':
+        bufs['s2'] = bordered()
+    pd, s1d = bufs['p'][lo:hi], bufs['s1'][lo:hi]
+    s2d = bufs['s2'][lo:hi] if kind == 'adam' else None
+    std = torch.tensor([0.0, 1.0, 1.0], dtype=dt, device='cuda') if kind == 'adam' else None
+    lr = torch.full((1,), 1e-3, dtype=dt, device='cuda')
+    lr_host = npdt(lr.cpu().numpy()[0])
+    a, m, v, st = np.zeros_like(p), np.zeros_like(p), np.zeros_like(p), (0, npdt(1), npdt(1))
+
+    def same(got, ref, what, step):
+        got = got.cpu().numpy()
+        ulp = np.abs(got.astype(np.float64) - ref.astype(np.float64)) / np.spacing(np.abs(ref)).astype(np.float64)
+        if prec == 'f32':                                     # the criteria of test_optimizer_steps
+            assert np.array_equal(got, ref), (what, step, float(ulp.max()))
+        else:
+            assert ulp.max() <= 4, (what, step, float(ulp.max()))
+    for step in range(2):
+        g = (rng.standard_normal(n) * 10.0 ** rng.integers(-6, 1, size=n)).astype(npdt)
+        if n > 2:
+            g[rng.integers(0, n, size=max(1, n // 100))] = 0
+        ops.opt_step(kind, pd, _dev(g, dt), s1d, s2d, lr, std, grid=grid)
+        if kind == 'rmsprop':
+            p, a = R.rmsprop_step(p, g, a, lr_host, npdt)
+            same(s1d, a, 'a', step)
+        else:
+            p, m, v, st = R.adam_step(p, g, m, v, st, lr_host, npdt)
+            same(s1d, m, 'm', step)
+            same(s2d, v, 'v', step)
+        same(pd, p, 'p', step)
+        lr.mul_(0.5)
+        lr_host = npdt(lr.cpu().numpy()[0])
+    for name, t in bufs.items():
+        th = t.cpu().numpy()
+        assert np.all(th[:lo] == OPT_SENTINEL) and np.all(th[hi:] == OPT_SENTINEL), name
+    if kind == 'adam':
+        # the powers as running products, each rounded in the step's own type
+        assert std.cpu().numpy().tolist() == [2.0, float(npdt(0.9) * npdt(0.9)), float(npdt(0.999) * npdt(0.999))]
+        assert (float(st[1]), float(st[2])) == (float(npdt(0.9) * npdt(0.9)), float(npdt(0.999) * npdt(0.999)))
 
 
 # ---- 6. determinism and refresh ----

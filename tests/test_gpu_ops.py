@@ -698,6 +698,14 @@ SMALL_CASES = [  # B, Cin, H, W, Cout, k, pad, dil, relu, window, place
     (1, 3, 19, 19, 5, 3, 0, 4, True, None, False),         # tiny map
     (2, 11, 21, 31, 11, 3, 0, 1, True, None, False),       # ragged last pixel group at the end of the buffer
     (2, 11, 23, 37, 11, 3, 0, 2, False, None, False),
+    # conv_small_f32_kernel<T, COP> is compiled for COP = Cout padded to 4, 8, 12, 16: the cases above reach
+    # <9, 8>, <9, 12>, <9, 16> and <1, 12>
+    (2, 3, 21, 70, 2, 3, 0, 2, True, None, False),         # <9, 4>: Cout 2
+    (1, 7, 18, 66, 4, 3, 0, 1, True, None, False),         # <9, 4> exactly: conv1 of 4 classes
+    (1, 16, 18, 66, 13, 1, 0, 1, False, None, False),      # <1, 16> with three padding channels, Cin at the maximum
+    (1, 1, 5, 5, 1, 3, 0, 1, True, None, False),           # <9, 4>: one channel either side
+    (2, 2, 9, 67, 3, 1, 0, 1, False, None, False),         # <1, 4>, and
+    (1, 6, 17, 65, 8, 1, 0, 1, True, None, False),         # <1, 8>: the two instantiations left
 ]
 
 
