@@ -768,6 +768,40 @@ int iiseg_bn_relu_f64(void* stream, const double* x, int64_t bstride, int32_t B,
                       const double* inv_std, double* out);
 
 /* ---------------------------------------------------------------------------------------
+ * Training FC-DenseNet (csrc/bn_grad.hip).
+ * bn_relu_bwd : backward of t = relu(y), y = gamma xhat + beta, xhat = (x - mean) inv_std with BATCH statistics
+ *   (mean, inv_std those of x over (B,H,W), N = B HW), for one consumer of a stack: x and gstack are the first C
+ *   channels of (B, >=C, H, W) buffers with `bstride` elements between images, g_t = dL/dt is dense (B,C,H,W).
+ *     IISEG_BN_BWD_REDUCE : dbeta[c] = sum g_y, dgamma[c] = sum g_y xhat, g_y = g_t [y > 0] (relu'(0) = 0), y
+ *                           recomputed from x as iiseg_bn_relu_* forms it; double partial sums in a fixed order
+ *                           through `workspace` (iiseg_bn_relu_bwd_workspace_elems(C, HW) doubles: two per channel
+ *                           and chunk of the plane), no atomics
+ *     IISEG_BN_BWD_APPLY  : gstack[b,c] += gamma[c] inv_std[c] (g_y - dbeta[c] / N - xhat dgamma[c] / N), reading
+ *                           dbeta / dgamma
+ *   `stages`: either or both (reduce first).  Nothing but gstack's first C channels, dbeta, dgamma and the workspace
+ *   is written.  16-byte accesses when HW and bstride are multiples of 16 bytes of elements and x, g_t, gstack are
+ *   16-byte aligned; scalar ones otherwise.
+ * maxpool2x2_bwd : gz[y,x] = pre[y,x] == pooled[y/2,x/2] ? gpool[y/2,x/2] : 0 inside (2 (H/2), 2 (W/2)), 0 outside:
+ *   iiseg_pool_relu_bwd_* without the > 0 gate (the pool of a linear map).  pre, gz (BC,H,W); gpool, pooled
+ *   (BC,H/2,W/2).
+ * ------------------------------------------------------------------------------------- */
+#define IISEG_BN_BWD_REDUCE 1
+#define IISEG_BN_BWD_APPLY 2
+int64_t iiseg_bn_relu_bwd_workspace_elems(int32_t C, int32_t HW);
+int iiseg_bn_relu_bwd_f32(void* stream, const float* x, int64_t bstride, const float* g_t, float* gstack,
+                          int32_t B, int32_t C, int32_t HW, const float* beta, const float* gamma,
+                          const float* mean, const float* inv_std, float* dbeta, float* dgamma,
+                          double* workspace, int32_t stages);
+int iiseg_bn_relu_bwd_f64(void* stream, const double* x, int64_t bstride, const double* g_t, double* gstack,
+                          int32_t B, int32_t C, int32_t HW, const double* beta, const double* gamma,
+                          const double* mean, const double* inv_std, double* dbeta, double* dgamma,
+                          double* workspace, int32_t stages);
+int iiseg_maxpool2x2_bwd_f32(void* stream, const float* gpool, const float* pre, const float* pooled,
+                             float* gz, int32_t BC, int32_t H, int32_t W);
+int iiseg_maxpool2x2_bwd_f64(void* stream, const double* gpool, const double* pre, const double* pooled,
+                             double* gz, int32_t BC, int32_t H, int32_t W);
+
+/* ---------------------------------------------------------------------------------------
  * float64 variants (strict-parity mode).  The reference's CPU path computes in float64 (Theano
  * floatX default) and DePool2D compares activations for exact equality, so only
  * float64 arithmetic reproduces its mask decisions at near-tied pooling windows.

@@ -90,6 +90,7 @@ class ConvFwdKxKDesc(C.Structure):
 
 
 L2_MAX_RANGES = 64
+BN_BWD_REDUCE, BN_BWD_APPLY = 1, 2       # iiseg_bn_relu_bwd_*'s stages
 
 C8DIL_OUT_NCHW = 0x100
 
@@ -218,6 +219,11 @@ SIGNATURES = {
     'iiseg_bn_relu_f32': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 5),
     'iiseg_bn_stats_f64': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _f64, _vp, _vp, _vp]),
     'iiseg_bn_relu_f64': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 5),
+    'iiseg_bn_relu_bwd_workspace_elems': (_i64, [_i32, _i32]),
+    'iiseg_bn_relu_bwd_f32': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32] + [_vp] * 7 + [_i32]),
+    'iiseg_bn_relu_bwd_f64': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32] + [_vp] * 7 + [_i32]),
+    'iiseg_maxpool2x2_bwd_f32': (C.c_int, [_vp] * 5 + [_i32] * 3),
+    'iiseg_maxpool2x2_bwd_f64': (C.c_int, [_vp] * 5 + [_i32] * 3),
     'iiseg_sqerr_softmax_bwd_f32': (C.c_int, [_vp] * 4 + [_i32] * 8),
     'iiseg_sqerr_softmax_bwd_f64': (C.c_int, [_vp] * 4 + [_i32] * 8),
     'iiseg_depool_bwd_f32': (C.c_int, [_vp] * 5 + [_i32] * 3),

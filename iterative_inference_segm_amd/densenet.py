@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .datagrads import DataGrads, Layer, Views, flipped
+from .params import Trainable
 
 # mma='bf16c8': TransitionDown and the 1x1 class-score layer as one C8 kernel each (0: the 'bf16' forms on
 # fp32 NCHW copies of the stack, through layout converters)
@@ -71,6 +73,62 @@ def layer_plan(n_layers_per_block=LAYERS_PER_BLOCK, n_pool=N_POOL, growth=GROWTH
             nblock += 1
     plan.append(('softmax', n, n_classes))
     return plan
+
+
+def train_program(n_layers_per_block=LAYERS_PER_BLOCK, n_pool=N_POOL, growth=GROWTH, n_first=N_FILTERS_FIRST):
+    """(steps, caps): what the training walk does per layer of `layer_plan`, in creation order -- dicts with kind, li
+    (the layer's index), sid (the stack it reads), n (it reads channels [0, n); 'tu': [block0, n)), ki (its dropout
+    mask, 'brc' / 'td'), ti ('td': its pre-pool / pooled maps), dst ('td', 'tu': the stack it starts), keep, skip_sid,
+    skip_n ('tu': its filters, the skip stack copied behind them) -- and the channel capacity of every stack (down
+    path, bottleneck, up path).  Host only."""
+    nlpb, g = list(n_layers_per_block), growth
+    steps, caps = [], []
+    li = ki = ti = 0
+    n = n_first
+    caps.append(n + g * nlpb[0])
+    steps.append(dict(kind='first', li=li, sid=0, cout=n))
+    li += 1
+    sid, skips = 0, []
+    for i in range(n_pool):
+        for _ in range(nlpb[i]):
+            steps.append(dict(kind='brc', li=li, sid=sid, n=n, ki=ki))
+            li, ki, n = li + 1, ki + 1, n + g
+        skips.append((sid, n))
+        caps.append(n + g * nlpb[i + 1])
+        steps.append(dict(kind='td', li=li, sid=sid, n=n, ki=ki, ti=ti, dst=sid + 1))
+        li, ki, ti, sid = li + 1, ki + 1, ti + 1, sid + 1
+    skips = skips[::-1]
+    block0 = n
+    for _ in range(nlpb[n_pool]):
+        steps.append(dict(kind='brc', li=li, sid=sid, n=n, ki=ki))
+        li, ki, n = li + 1, ki + 1, n + g
+    for i in range(n_pool):
+        keep = g * nlpb[n_pool + i]
+        skip_sid, skip_n = skips[i]
+        caps.append(keep + skip_n + g * nlpb[n_pool + i + 1])
+        steps.append(dict(kind='tu', li=li, sid=sid, block0=block0, n=n, dst=sid + 1, keep=keep, skip_sid=skip_sid,
+                          skip_n=skip_n))
+        li, sid = li + 1, sid + 1
+        n = block0 = keep + skip_n
+        for _ in range(nlpb[n_pool + i + 1]):
+            steps.append(dict(kind='brc', li=li, sid=sid, n=n, ki=ki))
+            li, ki, n = li + 1, ki + 1, n + g
+    steps.append(dict(kind='softmax', li=li, sid=sid, n=n))
+    return steps, caps
+
+
+def store_names(kinds):
+    """The names of the trainable module's flat parameter buffer, in its order: per layer of the plan 'bn%03d' (the
+    BatchNorm pair (gamma, beta) of a 'brc' / 'td' layer) then 'conv%03d' ((W, b))."""
+    names = []
+    for li, kind in enumerate(kinds):
+        if kind in ('brc', 'td'):
+            names.append('bn%03d' % li)
+        names.append('conv%03d' % li)
+    return names
+
+
+RUNNING_ALPHA = 0.1     # lasagne BatchNormLayer's alpha: the running averages a checkpoint carries
 
 
 class _Stack:
@@ -145,16 +203,35 @@ class _Stack8:
         self.n += k
 
 
-class FCDenseNet:
+class FCDenseNet(Trainable, Views):
+    _BUILT = 'an FCDenseNet'
+
     def __init__(self, params, n_classes=11, layer=('pool4',), n_layers_per_block=LAYERS_PER_BLOCK,
-                 n_pool=N_POOL, growth=GROWTH, device='cuda', dtype=torch.float32, mma=None):
+                 n_pool=N_POOL, growth=GROWTH, device='cuda', dtype=torch.float32, mma=None, trainable=False,
+                 dropout=0.2):
         """mma: 'f32' (default) | 'bf16' (bf16 MFMA operands, fp32 NCHW activations) | 'bf16c8'
         (configs[2] as BASELINE names it: the dense-block stacks as bf16 C8 tensors, every
         BN_ReLU_Conv of a dense block one launch of the 16-row C8 kernel with BatchNorm + ReLU applied
         while the input is staged; the first conv and TransitionUp on the 64-channel C8 kernel;
         TransitionDown (BN + ReLU + 1x1 conv + pool) and the 1x1 score layer one launch each of
-        csrc/conv1x1_c8.hip on the stack -- all 103 convolutions read bf16 C8)."""
+        csrc/conv1x1_c8.hip on the stack -- all 103 convolutions read bf16 C8).
+        trainable=True (float32 with mma='f32', or float64): the parameters live in ONE flat
+        buffer in creation order (`store_names`: a BatchNorm layer as the pair (gamma, beta), so that
+        `weight_ranges()` covers every W and every gamma), every layer holds views of it and runs on the direct /
+        halo / tap kernels only, so that `refresh()` can pack them again in place after an optimizer step.
+        `dropout`: p of the DropoutLayer behind the convolution of every 'brc' / 'td' layer in `forward_train`."""
         mma = mma or ops.DEFAULT_MMA
+        self.trainable = bool(trainable)
+        self.dropout = float(dropout)
+        self._tsaved = None
+        if trainable:
+            # refused here, before any device work
+            if dtype not in (torch.float32, torch.float64) or (dtype == torch.float32 and mma != 'f32'):
+                raise NotImplementedError("training FC-DenseNet: float32 (mma='f32') or float64; the 16-bit legs "
+                                          '(mma=%r) are not trained' % (mma,))
+            if not 0.0 <= self.dropout < 1.0:
+                raise ValueError('dropout must be in [0, 1)')
+            params = self._store_layers(params, dtype, device)
         self.c8 = mma == 'bf16c8' and dtype == torch.float32 and growth == 16
         if mma in ('bf16c8', 'bf16x3'):
             mma_other = 'bf16' if mma == 'bf16c8' else 'f32'
@@ -196,9 +273,230 @@ class FCDenseNet:
                     # TransitionDown / the class-score layer on the C8 stack itself (csrc/conv1x1_c8.hip)
                     e['conv8'] = ops.Conv1x1C8(p['W'], p['b'], device=device)
             self.layers.append(e)
+        if trainable:
+            self._hold_views([e['conv'] for e in self.layers], plain=True)
+            self._steps, caps = train_program(self.nlpb, n_pool, growth, self.layers[0]['conv'].Cout)
+            # lasagne's running averages (alpha = 0.1, from 0 / 1), one vector per stack: every consumer of a channel
+            # sees the same batch statistic.  Written into checkpoints (`state_list`); nothing here reads them.
+            self._run_mean = [torch.zeros(c, dtype=dtype, device=device) for c in caps]
+            self._run_inv_std = [torch.ones(c, dtype=dtype, device=device) for c in caps]
+        self.dgrads = DataGrads(self._dgrad_table() if trainable else [])
 
     def __call__(self, x):
         return self.forward(x)
+
+    # ---- training ------------------------------------------------------------------
+    def _store_layers(self, params, dtype, device):
+        """The parameters into one flat buffer (`store_names`); returns `params` with views of it in place of the
+        arrays."""
+        pairs = {}
+        for li, p in enumerate(params):
+            if p['kind'] in ('brc', 'td'):
+                pairs['bn%03d' % li] = (p['gamma'], p['beta'])
+            pairs['conv%03d' % li] = (p['W'], p['b'])
+        views = self._store_params(pairs, store_names([p['kind'] for p in params]), dtype, device)
+        out = []
+        for li, p in enumerate(params):
+            q = {'kind': p['kind']}
+            if p['kind'] in ('brc', 'td'):
+                q['gamma'], q['beta'] = views['bn%03d' % li]
+            q['W'], q['b'] = views['conv%03d' % li]
+            out.append(q)
+        return out
+
+    def _dgrad_table(self):
+        """[(name, datagrads.Layer)] of every layer with a data gradient on the flipped-filter form: the 3x3 pad-1
+        'brc' layers and the 1x1 'td' / 'softmax' layers ('first' has none; 'tu' is ops.deconv_dgrad)."""
+        table = []
+        for li, e in enumerate(self.layers):
+            if e['kind'] in ('brc', 'td', 'softmax'):
+                conv = e['conv']
+                table.append(('conv%03d' % li, Layer(lambda conv=conv: flipped(conv.W),
+                                                     dict(pad=conv.KH // 2, dtype=self.dtype, mma='f32'), True)))
+        return table
+
+    def _draw(self, shape, keep, generator, device):
+        if keep is None:
+            return (torch.rand(shape, generator=generator, device=device, dtype=torch.float32) >=
+                    self.dropout).to(self.dtype)
+        if tuple(keep.shape) != tuple(shape) or keep.dtype != self.dtype:
+            raise RuntimeError('dropout mask %s %s for a map %s %s' % (tuple(keep.shape), keep.dtype, tuple(shape),
+                                                                      self.dtype))
+        return keep
+
+    def forward_train(self, x, keeps=None, generator=None, deterministic=False):
+        """The training-mode forward: returns the score map (before the softmax) and keeps what `backward` reads --
+        the stacks with their batch statistics, the dropout masks, the pre-pool / pooled maps of every
+        TransitionDown and the crop windows of every TransitionUp.  The normalised copies t = relu(BN(stack)) are
+        NOT kept (their total size grows with the square of a block's depth): `backward` forms them again.
+        keeps: the caller's 0/1 masks, one per 'brc' / 'td' layer in creation order (the convolution's output shape,
+        the module's dtype), else drawn from `generator`.  deterministic=True: no dropout (val_fn's forward), and
+        the running averages stay as they are."""
+        self._need_trainable('forward_train')
+        drop = not deterministic and self.dropout > 0.0
+        n_masks = sum(1 for e in self._steps if e['kind'] in ('brc', 'td'))
+        if keeps is not None and len(keeps) != n_masks:
+            raise RuntimeError('forward_train: %d dropout masks for %d layers' % (len(keeps), n_masks))
+        B, _, H, W = x.shape
+        g, dt, dev, p = self.growth, self.dtype, x.device, self.dropout
+        s = dict(x=x, stacks=[None] * len(self._run_mean), keeps=[None] * n_masks if drop else None, td_pre=[],
+                 td_pooled=[], win={})
+        caps = [v.numel() for v in self._run_mean]
+
+        def conv_drop(e, conv, t):
+            z = conv(t)
+            if drop:
+                k = s['keeps'][e['ki']] = self._draw(z.shape, None if keeps is None else keeps[e['ki']], generator, dev)
+                ops.dropout_apply(z, k, p)
+            return z
+
+        for e in self._steps:
+            L = self.layers[e['li']]
+            conv = L['conv']
+            if e['kind'] == 'first':
+                stack = s['stacks'][0] = _Stack(B, caps[0], H, W, dev, dt)
+                conv(x, out=stack.buf, out_c0=0)
+                stack.added(conv.Cout)
+                continue
+            stack = s['stacks'][e['sid']]
+            if e['kind'] == 'brc':
+                n = e['n']
+                t = ops.bn_relu(stack.buf, n, L['beta'], L['gamma'], stack.mean, stack.inv_std)
+                if drop:
+                    stack.buf[:, n:n + g].copy_(conv_drop(e, conv, t))
+                else:
+                    conv(t, out=stack.buf, out_c0=n)
+                stack.added(g)
+            elif e['kind'] == 'td':
+                n = e['n']
+                t = ops.bn_relu(stack.buf, n, L['beta'], L['gamma'], stack.mean, stack.inv_std)
+                pre = conv_drop(e, conv, t)
+                pooled = ops.maxpool2x2(pre)
+                s['td_pre'].append(pre)
+                s['td_pooled'].append(pooled)
+                new = s['stacks'][e['dst']] = _Stack(B, caps[e['dst']], pooled.shape[2], pooled.shape[3], dev, dt)
+                new.buf[:, :n].copy_(pooled)
+                new.added(n)
+            elif e['kind'] == 'tu':
+                blk = stack.buf[:, e['block0']:e['n']].contiguous()
+                skip = s['stacks'][e['skip_sid']]
+                uh, uw = conv.out_hw(stack.buf.shape[2], stack.buf.shape[3])
+                h, w = min(uh, skip.buf.shape[2]), min(uw, skip.buf.shape[3])
+                if (h, w) != tuple(skip.buf.shape[2:]):
+                    raise NotImplementedError('skip larger than the upsampled map')
+                win = s['win'][e['li']] = ((uh - h) // 2, (uw - w) // 2, h, w)
+                new = s['stacks'][e['dst']] = _Stack(B, caps[e['dst']], h, w, dev, dt)
+                conv(blk, window=win, out=new.buf, out_c0=0)
+                new.buf[:, e['keep']:e['keep'] + e['skip_n']].copy_(skip.buf[:, :e['skip_n']])
+                new.added(e['keep'] + e['skip_n'])
+            else:
+                s['score'] = conv(stack.view())
+        if not deterministic:
+            for st, rm, ri in zip(s['stacks'], self._run_mean, self._run_inv_std):
+                rm.mul_(1.0 - RUNNING_ALPHA).add_(st.mean, alpha=RUNNING_ALPHA)
+                ri.mul_(1.0 - RUNNING_ALPHA).add_(st.inv_std, alpha=RUNNING_ALPHA)
+        self._tsaved = s
+        return s['score']
+
+    def saved_maps(self):
+        """What the last `forward_train` kept, under the names of tests/densenet_train_ref.py; for tests."""
+        s = self._tsaved
+        return dict(x=s['x'], stacks=[st.buf for st in s['stacks']], mean=[st.mean for st in s['stacks']],
+                    inv_std=[st.inv_std for st in s['stacks']], keeps=s['keeps'], td_pre=list(s['td_pre']),
+                    td_pooled=list(s['td_pooled']), win=dict(s['win']), score=s['score'], p=self.dropout)
+
+    def backward(self, g_score):
+        """{name: (dW, db)} (`store_names`; a BatchNorm pair is (dgamma, dbeta)): views of one flat gradient buffer
+        laid out as `self.flat`, for dL/dscore = g_score, after `forward_train`.  A gradient stack, zero at the
+        start, mirrors every feature stack; the layers are walked in reverse creation order.  When a dense-block
+        layer that produced channels [n, n + g) is reached, gstack[:, n:n + g] is complete: times the layer's
+        dropout mask / (1 - p) it is g_z of its convolution; dW, db from g_z and t = bn_relu(stack[:, :n]) formed
+        again; ops.bn_relu_bwd adds the gradient of the 3x3 layer's input into gstack[:, :n] and writes dbeta,
+        dgamma.  TransitionUp hands its data gradient to the channels of the block it upsampled and the gradient of
+        the skip copy to the skip's own gradient stack -- before TransitionDown adds the second share (no ReLU gate
+        behind its pool: ops.maxpool2x2_bwd)."""
+        self._need_trainable('backward')
+        s = self._tsaved
+        if s is None:
+            raise RuntimeError('backward() needs forward_train() first')
+        gv, dgrads, p = self._params.grad_views(), self.dgrads, self.dropout
+        dgrads.prepare()
+        stacks = s['stacks']
+        gst = [None] * len(stacks)
+
+        def gstack(sid):
+            if gst[sid] is None:
+                gst[sid] = torch.zeros_like(stacks[sid].buf)
+            return gst[sid]
+
+        def through_bn(e, L, name, gz, wgrad):
+            stack, n = stacks[e['sid']], e['n']
+            if s['keeps'] is not None:
+                ops.dropout_apply(gz, s['keeps'][e['ki']], p)          # dropout's adjoint: the forward's mask
+            bn = (L['beta'], L['gamma'], stack.mean, stack.inv_std)
+            t = ops.bn_relu(stack.buf, n, *bn)
+            wgrad(t, gz, *gv[name])
+            g_t = dgrads(name, gz)
+            del t
+            dgamma, dbeta = gv['bn%03d' % e['li']]
+            ops.bn_relu_bwd(stack.buf, n, bn, g_t, gstack(e['sid']), dbeta, dgamma)
+
+        for e in reversed(self._steps):
+            L = self.layers[e['li']]
+            name = 'conv%03d' % e['li']
+            stack = stacks[e['sid']]
+            if e['kind'] == 'softmax':
+                ops.conv_wgrad_kxk(stack.view(), g_score, *gv[name])
+                g = dgrads(name, g_score)
+                if g.shape == stack.buf.shape:
+                    gst[e['sid']] = g                                   # the last stack is full: this IS its gstack
+                else:
+                    gstack(e['sid'])[:, :e['n']].copy_(g)
+            elif e['kind'] == 'brc':
+                n = e['n']
+                gz = gstack(e['sid'])[:, n:n + self.growth].contiguous()
+                through_bn(e, L, name, gz, lambda t, gz, dW, db: ops.conv_wgrad(t, gz, dW, db, pad=1))
+            elif e['kind'] == 'td':
+                gpool = gstack(e['dst'])[:, :e['n']].contiguous()
+                gz = ops.maxpool2x2_bwd(gpool, s['td_pre'][e['ti']], s['td_pooled'][e['ti']])
+                through_bn(e, L, name, gz, ops.conv_wgrad_kxk)
+            elif e['kind'] == 'tu':
+                keep, win = e['keep'], s['win'][e['li']]
+                gd = gstack(e['dst'])
+                g = gd[:, :keep].contiguous()
+                blk = stack.buf[:, e['block0']:e['n']].contiguous()
+                ops.deconv_wgrad(blk, g, *gv[name], stride=2, window=win)
+                gx = ops.deconv_dgrad(g, L['conv'].W, 2, tuple(stack.buf.shape[2:]), window=win)
+                # (both targets are still zero: the first share of each)
+                gstack(e['sid'])[:, e['block0']:e['n']].copy_(gx)
+                gstack(e['skip_sid'])[:, :e['skip_n']].copy_(gd[:, keep:keep + e['skip_n']])
+            else:
+                gz = gstack(0)[:, :e['cout']].contiguous()
+                ops.conv_wgrad(s['x'], gz, *gv[name], pad=1)
+        return gv
+
+    def refresh(self):
+        """The parameters (`self.flat`) have been changed in place: every layer packs its weights again into the
+        buffers it already has, and the data-gradient layers take the flipped filters again.  No host wait."""
+        self._need_trainable('refresh')
+        for e in self.layers:
+            e['conv'].refresh()
+        self.dgrads.refresh()
+
+    def state_list(self):
+        """The arrays of a checkpoint in the `arr_%d` order `load_params` reads (float32, host; waits for the
+        device): per 'brc' / 'td' layer beta, gamma, mean, inv_std -- the running averages of the stack channels the
+        layer reads -- then W, b."""
+        self._need_trainable('state_list')
+        host = lambda t: t.detach().cpu().float().numpy()
+        out = []
+        for e in self._steps:
+            L = self.layers[e['li']]
+            if e['kind'] in ('brc', 'td'):
+                out += [host(L['beta']), host(L['gamma']), host(self._run_mean[e['sid']][:e['n']]),
+                        host(self._run_inv_std[e['sid']][:e['n']])]
+            out += [host(L['conv'].W), host(L['conv'].b)]
+        return out
 
     def _brc(self, it, stack, out=None, out_c0=None):
         e = next(it)
@@ -440,21 +738,57 @@ class FCDenseNet:
 
 def build_fcdensenet(input_var=None, layer=('pool4',), nb_in_channels=3, n_classes=11,
                      output_d='4d', from_gt=False, weight_path=None, params=None, device='cuda',
-                     dtype=torch.float32):
+                     dtype=torch.float32, trainable=False, **net_kw):
     """Mirror of models/FCDenseNet.py:196-219 (DenseNet103: 48 first filters, 5 pools, growth 16,
     blocks [4,5,7,10,12,15,12,10,7,5,4]).  Weights: `params` (list in creation order) or an
-    `arr_%d` .npz (BN: beta, gamma, mean, inv_std; conv: W, b -- P10/P14)."""
+    `arr_%d` .npz (BN: beta, gamma, mean, inv_std; conv: W, b -- P10/P14).  trainable=True builds the module
+    `train.DenseNetTrainer` trains (float32 on mma='f32', or float64).  net_kw: further
+    keywords of `FCDenseNet` (a smaller net: n_layers_per_block, n_pool, growth -- and n_first for the plan of
+    a checkpoint; dropout)."""
+    n_first = net_kw.pop('n_first', None)
     if params is None:
         if not weight_path:
             raise ValueError('build_fcdensenet needs `params` or `weight_path`')
-        params = load_params(weight_path, layer_plan(nb_in_channels=nb_in_channels,
-                                                     n_classes=n_classes))
-    return FCDenseNet(params, n_classes, layer=layer, device=device, dtype=dtype)
+        cfg = read_config(weight_path)
+        if cfg is not None and n_first is None and not any(k in net_kw for k in ('n_layers_per_block', 'n_pool',
+                                                                                   'growth')):
+            # a checkpoint of train_fcdensenet.py for another architecture than DenseNet103 says so itself
+            n_first = cfg.pop('n_first')
+            net_kw.update(cfg)
+        params = load_params(weight_path, layer_plan(net_kw.get('n_layers_per_block', LAYERS_PER_BLOCK),
+                                                     net_kw.get('n_pool', N_POOL), net_kw.get('growth', GROWTH),
+                                                     N_FILTERS_FIRST if n_first is None else n_first,
+                                                     nb_in_channels=nb_in_channels, n_classes=n_classes))
+    if trainable:
+        return FCDenseNet(params, n_classes, layer=layer, device=device, dtype=dtype, mma='f32', trainable=True,
+                          **net_kw)
+    return FCDenseNet(params, n_classes, layer=layer, device=device, dtype=dtype, **net_kw)
+
+
+CONFIG_KEY = 'densenet_config'      # [n_pool, growth, n_first, layers per block...]: only in checkpoints of other nets
+
+
+def save_checkpoint(path, net, n_first):
+    """np.savez of `net.state_list()` (the `arr_%d` file `load_params` reads); a net that is not DenseNet103 also
+    records its architecture under CONFIG_KEY, which `build_fcdensenet(weight_path=...)` then follows."""
+    extra = {}
+    if (list(net.nlpb), net.n_pool, net.growth, int(n_first)) != (LAYERS_PER_BLOCK, N_POOL, GROWTH, N_FILTERS_FIRST):
+        extra[CONFIG_KEY] = np.asarray([net.n_pool, net.growth, int(n_first)] + list(net.nlpb), np.int64)
+    np.savez(path, *net.state_list(), **extra)
+
+
+def read_config(path):
+    """{'n_pool', 'growth', 'n_first', 'n_layers_per_block'} of a checkpoint that records them, else None."""
+    with np.load(path) as f:
+        if CONFIG_KEY not in f.files:
+            return None
+        v = [int(a) for a in f[CONFIG_KEY]]
+    return dict(n_pool=v[0], growth=v[1], n_first=v[2], n_layers_per_block=v[3:])
 
 
 def load_params(path, plan):
     with np.load(path) as f:
-        vals = [f['arr_%d' % i] for i in range(len(f.files))]
+        vals = [f['arr_%d' % i] for i in range(sum(1 for k in f.files if k.startswith('arr_')))]
     out, i = [], 0
     for kind, _, _ in plan:
         p = {'kind': kind}

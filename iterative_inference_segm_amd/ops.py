@@ -2007,6 +2007,53 @@ def bn_relu(buf, n, beta, gamma, mean, inv_std, out=None):
     return out
 
 
+def bn_relu_bwd(stack, n, bn, g_t, gstack, dbeta, dgamma):
+    """Backward of t = relu(BatchNorm(stack[:, :n])) with batch statistics for one consumer of the stack (DESIGN.md
+    section 21): bn = (beta, gamma, mean, inv_std), g_t = dL/dt dense (B, n, H, W); writes dbeta, dgamma (n entries)
+    and ADDS g_x into the first n channels of `gstack` (the stack's shape).  y is recomputed from the stack.  Two
+    launches (reduce, apply), deterministic; nothing else is written."""
+    B, cap, H, W = stack.shape
+    dt = stack.dtype
+    n = int(n)
+    beta, gamma, mean, inv_std = bn
+    if not 0 < n <= cap or tuple(g_t.shape) != (B, n, H, W) or gstack.shape != stack.shape or \
+            min(beta.numel(), gamma.numel(), mean.numel(), inv_std.numel(), dbeta.numel(), dgamma.numel()) < n:
+        raise RuntimeError('bn_relu_bwd: stack %s n %d g_t %s gstack %s' % (tuple(stack.shape), n, tuple(g_t.shape),
+                                                                            tuple(gstack.shape)))
+    nws = _count(_lib.load().iiseg_bn_relu_bwd_workspace_elems(n, H * W), 'iiseg_bn_relu_bwd_workspace_elems')
+    ws = _workspace('bn', nws, stack.device)
+    item = float(stack.element_size())
+    planes = item * B * n * H * W
+    _launch_staged(_fn('bn_relu_bwd', dt),
+                   (_ptr(stack, dt), cap * H * W, _ptr(g_t, dt), _ptr(gstack, dt), B, n, H * W, _ptr(beta, dt),
+                    _ptr(gamma, dt), _ptr(mean, dt), _ptr(inv_std, dt), _ptr(dbeta, dt), _ptr(dgamma, dt),
+                    _ptr(ws, torch.float64)), _lib.BN_BWD_REDUCE | _lib.BN_BWD_APPLY,
+                   (('bn_relu_bwd_reduce_kernel', _lib.BN_BWD_REDUCE, 0.0),
+                    ('bn_relu_bwd_apply_kernel', _lib.BN_BWD_APPLY, 0.0)))
+    if CONV_PROFILE is not None:
+        # byte models: x and g_t read; x, g_t and gstack read, gstack written
+        _add_bytes('bn_relu_bwd_reduce_kernel', 2 * planes)
+        _add_bytes('bn_relu_bwd_apply_kernel', 4 * planes)
+
+
+def maxpool2x2_bwd(gpool, pre, pooled):
+    """Adjoint of maxpool2x2 alone (no ReLU gate: `pool_relu_bwd` without the > 0 test), given the pooled map's
+    input `pre` (B,C,H,W) and `pooled`: every position equal to its window's maximum receives gpool, a trailing
+    odd row / column zero."""
+    dt = gpool.dtype
+    B, Cc, H, W = pre.shape
+    if tuple(pooled.shape) != (B, Cc, H // 2, W // 2) or gpool.shape != pooled.shape:
+        raise RuntimeError('maxpool2x2_bwd: gpool %s pre %s pooled %s' % (tuple(gpool.shape), tuple(pre.shape),
+                                                                         tuple(pooled.shape)))
+    out = torch.empty_like(pre)
+    kern = 'maxpool2x2_bwd_kernel'
+    _launch(kern, 0.0, _fn('maxpool2x2_bwd', dt), _ptr(gpool, dt), _ptr(pre, dt), _ptr(pooled, dt), _ptr(out, dt),
+            B * Cc, H, W)
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, float(pre.element_size()) * (2 * pre.numel() + 2 * pooled.numel()))
+    return out
+
+
 def bn_affine(x, bnp, window=None):
     """In place x = (x - mean) * (gamma * inv_std) + beta per channel (stored-average BatchNorm),
     on the window (y0, x0, h, w) of x's planes or everywhere.  bnp = (beta, gamma, mean, inv_std)."""

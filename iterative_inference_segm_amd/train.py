@@ -7,14 +7,15 @@ train_dae.py:334-338,
 for dae kind 'contextmod'  and kind 'standard' with h at a pool point (section 12).
 Forward and data gradient run on the inference layers (ops.Conv), the loss and the optimizer step on
 csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_wgrad.hip (standard DAE); and
-the two of train_fcn8.py:116-137 for FCN-8 itself (FCN8Trainer).
+the two of train_fcn8.py:116-137 for FCN-8 itself (FCN8Trainer) and for FC-DenseNet
+(DenseNetTrainer, section 21).
 Everything is enqueued on the current stream; nothing here waits for the device.
 """
 import functools
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .api import Metrics
 from .params import check_mode
 
@@ -180,6 +181,56 @@ class FCN8Trainer(_Trainer):
     def val_step(self, X, T):
         """val_fn (deterministic: no dropout): (loss, Metrics) -- the loss a device scalar, accuracy and the
         Jaccard counts in the Metrics accumulators (api.Metrics.result() -> acc, jacc(2, C), mse)."""
+        score = self.net.forward_train(X, deterministic=True)
+        res, _, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=False)
+        return res[0], self._metrics(score, T)
+
+
+class DenseNetTrainer(_Trainer):
+    """train_fn / val_fn for an FCDenseNet built with trainable=True (the reference has no
+    FC-DenseNet training script: optimizer and schedule are restated from upstream FC-DenseNet): masked
+    cross-entropy + weight_decay * sum p^2 over every W and every gamma (lasagne marks gamma regularizable; never
+    beta or a bias) under RMSprop (default) or adam; val_fn = loss and Jaccard counts on the deterministic forward.
+    The net is trained in place."""
+
+    def __init__(self, net, n_classes, void_labels=(11,), optimizer='rmsprop', learning_rate=1e-3, weight_decay=0.0,
+                 seed=None):
+        if not getattr(net, 'trainable', False):
+            raise NotImplementedError('training an FCDenseNet needs one built with trainable=True')
+        if optimizer not in ops.OPTIMIZERS:
+            raise ValueError('Unknown optimizer')
+        if not float(weight_decay) >= 0.0:
+            raise ValueError('weight_decay must be >= 0')
+        super().__init__(net, n_classes, void_labels, optimizer, learning_rate, seed)
+        self.net, self.weight_decay = net, float(weight_decay)
+        # ops.l2_term takes a bounded number of ranges per launch; this net has two hundred
+        ranges = net.weight_ranges()
+        step = _lib.L2_MAX_RANGES
+        self.ranges = [ranges[i:i + step] for i in range(0, len(ranges), step)]
+
+    def anneal(self, factor):
+        """lr <- lr * factor on the device."""
+        self.lr.mul_(float(factor))
+
+    def train_step(self, X, T, keeps=None):
+        """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64).  keeps: the
+        caller's dropout masks, one per 'brc' / 'td' layer (tests), else drawn from the trainer's generator.  No
+        host wait."""
+        net = self.net
+        score = net.forward_train(X, keeps, generator=self.generator)
+        res, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=True)
+        net.backward(g)
+        loss = res[0]
+        if self.weight_decay > 0:
+            for chunk in self.ranges:
+                loss = loss + self.weight_decay * ops.l2_term(net.flat, net.gflat, chunk, self.weight_decay)[0]
+        ops.opt_step(self.optimizer, net.flat, net.gflat, self.s1, self.s2, self.lr, self.state, grid=True)
+        net.refresh()
+        return loss
+
+    def val_step(self, X, T):
+        """val_fn (deterministic: no dropout): (loss, Metrics) -- the loss a device scalar, accuracy and the
+        Jaccard counts in the Metrics accumulators."""
         score = self.net.forward_train(X, deterministic=True)
         res, _, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=False)
         return res[0], self._metrics(score, T)

@@ -1,0 +1,278 @@
+#!/usr/bin/env python3
+"""Training FC-DenseNet on MI355X: writes the `FC-DenseNet103_weights.npz`-format checkpoint that
+build_fcdensenet(weight_path=...), train_dae.py and iterative_inference.py load.
+
+The reference has no FC-DenseNet training script; it loads weights trained with upstream FC-DenseNet (SimJeg).  What
+this driver takes from upstream is restated from memory and cannot be verified here: Dropout(0.2) behind the
+convolution of every BN_ReLU_Conv and TransitionDown, RMSprop with learning rate 1e-3 decayed by 0.995 per epoch,
+weight decay 1e-4 on every regularizable parameter (every W and every BatchNorm gamma), batch 3 on 224 x 224 crops.
+The epoch loop, the early stopping on the mean validation Jaccard (patience rule) and the file layout follow
+train_fcn8.py -- except that the best checkpoint is also written after the first epoch, so that a run of any length
+leaves one.  In savepath/<dataset>/fc_densenet/: `FC-DenseNet103_weights_best.npz` / `_last.npz` (np.savez in
+get_all_param_values order: per BatchNorm beta, gamma, mean, inv_std -- the running averages, alpha 0.1 -- then W, b
+per convolution), `errors_best.npz` / `errors_last.npz`, `output.log`, `config.txt`.  Copied to
+<weights_path>/<dataset>/FC-DenseNet103_weights.npz, the best checkpoint is what the other entry points load.
+Initial weights without `--resume`: HeUniform W, zero b, gamma 1, beta 0 (upstream's), seeded and drawn on the host.
+`--layers_per_block / --growth / --n_first` shrink the net (tests); such a checkpoint records its architecture.
+Data augmentation is not built.  What is refused exits with status 2 and the reason on stderr before any GPU work.
+All arithmetic runs in the HIP kernels of libiiseg_hip.so.
+"""
+import argparse
+import json
+import os
+import shutil
+import sys
+import time
+
+import numpy as np
+
+SAVEPATH = os.environ.get('IISEG_SAVEPATH')
+LOADPATH = os.environ.get('IISEG_LOADPATH')
+EXP_NAME = 'fc_densenet'
+MODEL = 'FC-DenseNet103_weights_%s.npz'
+LAYERS_PER_BLOCK = [4, 5, 7, 10, 12, 15, 12, 10, 7, 5, 4]
+OPTIMIZERS = ('rmsprop', 'adam')
+MMA_MODES = ('f32', 'bf16', 'bf16c8', 'bf16x3')
+
+
+def _json(s):
+    return json.loads(s) if isinstance(s, str) else s
+
+
+def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2,
+                    batch_size=(3, 1, 1), num_epochs=1, max_patience=1, learning_rate=1e-3, lr_decay=0.995,
+                    weight_decay=1e-4, layers_per_block=LAYERS_PER_BLOCK, growth=16, n_first=48, image_size=None):
+    """Everything this build does not train and every bad argument, refused with the reason (host only)."""
+    if savepath is None:
+        raise ValueError('A saving directory must be specified')
+    if dataset not in ('camvid', 'polyps912', 'em'):
+        raise ValueError('Unknown dataset')
+    if mma not in MMA_MODES:
+        raise ValueError('mma must be one of %s' % ', '.join(MMA_MODES))
+    if dtype not in ('float32', 'float64') or (dtype == 'float32' and mma != 'f32'):
+        raise NotImplementedError("training FC-DenseNet: float32 (mma 'f32') or float64; the 16-bit legs (dtype %s, "
+                                  'mma %r) are not trained' % (dtype, mma))
+    if optimizer not in OPTIMIZERS:
+        raise ValueError('Unknown optimizer')
+    if not 0.0 <= float(dropout) < 1.0:
+        raise ValueError('dropout must be in [0, 1)')
+    if not (isinstance(batch_size, (list, tuple)) and len(batch_size) == 3 and all(int(b) >= 1 for b in batch_size)):
+        raise ValueError('batch_size must be [train, val, test], each >= 1')
+    if int(num_epochs) < 1 or int(max_patience) < 1:
+        raise ValueError('num_epochs and max_patience must be >= 1')
+    if not float(learning_rate) > 0 or not float(weight_decay) >= 0 or not 0 < float(lr_decay) <= 1:
+        raise ValueError('learning_rate must be > 0, weight_decay >= 0 and lr_decay in (0, 1]')
+    lpb = list(layers_per_block)
+    if len(lpb) < 3 or len(lpb) % 2 != 1 or any(int(v) < 1 for v in lpb) or int(growth) < 1 or int(n_first) < 1:
+        raise ValueError('layers_per_block: an odd number (2 n_pool + 1) of positive counts; growth, n_first >= 1')
+    if image_size is not None:
+        n_pool = len(lpb) // 2
+        if any(int(v) >> n_pool < 1 for v in image_size):
+            raise ValueError('image_size %s is too small for %d pools' % (list(image_size), n_pool))
+
+
+def he_params(plan, seed):
+    """Creation-order parameter dicts for `plan` (densenet.layer_plan): HeUniform W (limit sqrt(6 / fan_in)), zero
+    b, gamma 1, beta 0; seeded."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for kind, cin, cout in plan:
+        p = {'kind': kind}
+        if kind in ('brc', 'td'):
+            p['gamma'], p['beta'] = np.ones(cin, np.float32), np.zeros(cin, np.float32)
+        k = 1 if kind in ('td', 'softmax') else 3
+        shape, fan = ((cin, cout, 3, 3), cout * 9) if kind == 'tu' else ((cout, cin, k, k), cin * k * k)
+        a = np.sqrt(6.0 / fan)
+        p['W'] = rng.uniform(-a, a, size=shape).astype(np.float32)
+        p['b'] = np.zeros(cout, np.float32)
+        out.append(p)
+    return out
+
+
+def one_hot_void_last(L, n_classes):
+    """Integer labels (B,H,W), void = any label >= n_classes, -> one-hot (B,n_classes+1,H,W), void channel last."""
+    L = np.minimum(np.asarray(L).astype(np.int64), n_classes)
+    return np.ascontiguousarray(np.moveaxis(np.eye(n_classes + 1, dtype=np.float32)[L], -1, 1))
+
+
+def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_epochs=750, max_patience=150,
+          savepath=None, loadpath=None, batch_size=None, resume=False, synthetic=False, n_images=20, image_size=None,
+          seed=0, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2, layers_per_block=LAYERS_PER_BLOCK,
+          growth=16, n_first=48, max_batches=None, verbose=True):
+    """Returns the per-epoch lists and the experiment folder."""
+    bs = list(batch_size) if batch_size is not None else [3, 1, 1]
+    lpb = [int(v) for v in layers_per_block]
+    size = tuple(image_size) if image_size is not None else (224, 224)
+    check_supported(dataset, savepath, dtype, mma, optimizer, dropout, bs, num_epochs, max_patience, learning_rate,
+                    lr_decay, weight_decay, lpb, growth, n_first, size)
+    loadpath = loadpath if loadpath is not None else savepath
+    savepath = os.path.join(savepath, dataset, EXP_NAME)
+    loadpath = os.path.join(loadpath, dataset, EXP_NAME)
+    say = print if verbose else (lambda *a, **k: None)
+    os.makedirs(savepath, exist_ok=True)
+    say('Saving directory : ' + savepath)
+    with open(os.path.join(savepath, 'config.txt'), 'w') as f:
+        for key, value in sorted(dict(dataset=dataset, learning_rate=learning_rate, lr_decay=lr_decay,
+                                      weight_decay=weight_decay, num_epochs=num_epochs, max_patience=max_patience,
+                                      batch_size=bs, resume=resume, seed=seed, dtype=dtype, optimizer=optimizer,
+                                      dropout=dropout, layers_per_block=lpb, growth=growth, n_first=n_first,
+                                      image_size=list(size)).items()):
+            f.write('{} = {}\n'.format(key, value))
+
+    # ---- from here on: the GPU ----
+    import torch
+    from iterative_inference_segm_amd.data_loader import load_data
+    from iterative_inference_segm_amd.densenet import FCDenseNet, layer_plan, load_params, save_checkpoint
+    from iterative_inference_segm_amd.train import DenseNetTrainer
+
+    tdt = {'float32': torch.float32, 'float64': torch.float64}[dtype]
+    train_iter, val_iter, test_iter = load_data(dataset, {}, one_hot=False, batch_size=bs,
+                                                synthetic=True if synthetic else None, n_images=n_images,
+                                                image_size=size)
+    n_classes, void_labels = train_iter.non_void_nclasses, train_iter.void_labels
+    nb_in_channels = train_iter.data_shape[0]
+    nb = lambda it: it.nbatches if max_batches is None else min(it.nbatches, int(max_batches))
+    say('Batch. train: %d, val %d, test %d' % (nb(train_iter), nb(val_iter), nb(test_iter) if test_iter else 0))
+    say('Nb of classes: %d' % n_classes)
+
+    n_pool = len(lpb) // 2
+    plan = layer_plan(lpb, n_pool, growth, n_first, nb_in_channels, n_classes)
+    best_path = os.path.join(savepath, MODEL % 'best')
+    if resume:
+        params = load_params(os.path.join(loadpath, MODEL % 'best'), plan)
+    else:
+        params = he_params(plan, 4321 + int(seed))
+    net = FCDenseNet(params, n_classes, layer=[], n_layers_per_block=lpb, n_pool=n_pool, growth=growth, dtype=tdt,
+                     mma='f32', trainable=True, dropout=dropout)
+    trainer = DenseNetTrainer(net, n_classes, void_labels, optimizer=optimizer, learning_rate=learning_rate,
+                              weight_decay=weight_decay, seed=seed)
+
+    def batch(it):
+        X, L = it.next()
+        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda().to(tdt).contiguous()
+        Td = torch.from_numpy(one_hot_void_last(L, n_classes)).cuda().to(tdt).contiguous()
+        return Xd, Td
+
+    def evaluate(it):
+        """(mean loss, mean accuracy, Jaccard counts (2, C)) over the split."""
+        cost = torch.zeros((), dtype=torch.float64, device='cuda')
+        acc_tot, jacc_tot = 0.0, np.zeros((2, n_classes))
+        for _ in range(nb(it)):
+            c, m = trainer.val_step(*batch(it))
+            cost += c
+            acc, jacc, _ = m.result()
+            acc_tot += acc
+            jacc_tot += jacc
+        return float(cost.item()) / nb(it), acc_tot / nb(it), jacc_tot
+
+    def save(tag, errors):
+        save_checkpoint(os.path.join(savepath, MODEL % tag), net, n_first)
+        np.savez(os.path.join(savepath, 'errors_%s.npz' % tag), *[np.asarray(e) for e in errors])
+
+    err_train, err_valid, acc_valid, jacc_valid = [], [], [], []
+    patience, best_jacc_val = 0, None
+    say('Start training')
+    for epoch in range(num_epochs):
+        start_time = time.time()
+        cost = torch.zeros((), dtype=torch.float64, device='cuda')
+        for _ in range(nb(train_iter)):
+            cost += trainer.train_step(*batch(train_iter))     # device scalar: one host read per epoch
+        err_train.append(float(cost.item()) / nb(train_iter))
+        trainer.anneal(lr_decay)
+
+        err, acc, jacc_tot = evaluate(val_iter)
+        err_valid.append(err)
+        acc_valid.append(acc)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            jacc_valid.append(float(np.nanmean(jacc_tot[0, :] / jacc_tot[1, :])))
+
+        out_str = 'EPOCH %i: Avg epoch training cost train %f, cost val %f, acc val %f, jacc val %f took %f s'
+        out_str = out_str % (epoch, err_train[epoch], err_valid[epoch], acc_valid[epoch], jacc_valid[epoch],
+                             time.time() - start_time)
+        print(out_str)
+        with open(os.path.join(savepath, 'output.log'), 'a') as f:
+            f.write(out_str + '\n')
+
+        errors = (err_valid, err_train, acc_valid, jacc_valid)
+        if epoch == 0 or jacc_valid[epoch] > best_jacc_val:
+            best_jacc_val = jacc_valid[epoch]
+            patience = 0
+            save('best', errors)
+        else:
+            patience += 1
+            save('last', errors)
+
+        if patience == max_patience or epoch == num_epochs - 1:
+            if test_iter is not None:
+                # the best weights back into the net's own buffer, in place
+                for p, e in zip(load_params(best_path, plan), net.layers):
+                    if p['kind'] in ('brc', 'td'):
+                        e['beta'].copy_(torch.from_numpy(p['beta']).to(tdt))
+                        e['gamma'].copy_(torch.from_numpy(p['gamma']).to(tdt))
+                    e['conv'].W.copy_(torch.from_numpy(p['W']).to(tdt))
+                    e['conv'].b.copy_(torch.from_numpy(p['b']).to(tdt))
+                net.refresh()
+                err, acc, jacc_tot = evaluate(test_iter)
+                with np.errstate(invalid='ignore', divide='ignore'):
+                    jacc = float(np.nanmean(jacc_tot[0, :] / jacc_tot[1, :]))
+                print('FINAL MODEL: err test % f, acc test %f, jacc test %f' % (err, acc, jacc))
+            if os.path.abspath(savepath) != os.path.abspath(loadpath):
+                say('Copying model and other training files to {}'.format(loadpath))
+                shutil.copytree(savepath, loadpath, dirs_exist_ok=True)
+            break
+    return {'err_train': err_train, 'err_valid': err_valid, 'acc_valid': acc_valid, 'jacc_valid': jacc_valid,
+            'savepath': savepath, 'loadpath': loadpath}
+
+
+def make_parser():
+    parser = argparse.ArgumentParser(description='FC-DenseNet training')
+    parser.add_argument('-dataset', default='camvid', help='Dataset.')
+    parser.add_argument('--synthetic', action='store_true', help='seeded synthetic split (no dataset here)')
+    parser.add_argument('--savepath', type=str, default=SAVEPATH)
+    parser.add_argument('--loadpath', type=str, default=LOADPATH, help='default: --savepath')
+    parser.add_argument('--num_epochs', '-ne', type=int, default=750)
+    parser.add_argument('--learning_rate', type=float, default=1e-3)
+    parser.add_argument('--lr_decay', type=float, default=0.995, help='learning-rate factor per epoch')
+    parser.add_argument('--weight_decay', type=float, default=1e-4, help='on every W and every gamma')
+    parser.add_argument('--batch_size', type=_json, default=[3, 1, 1], help='[train, val, test] (JSON)')
+    parser.add_argument('--max_patience', type=int, default=150)
+    parser.add_argument('--dtype', default='float32', help='float32 | float64')
+    parser.add_argument('--mma', default='f32', help="float32: only 'f32' is trained")
+    parser.add_argument('--optimizer', default='rmsprop', help='rmsprop | adam')
+    parser.add_argument('--dropout', type=float, default=0.2)
+    parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
+    parser.add_argument('--n_images', type=int, default=20, help='images per synthetic split')
+    parser.add_argument('--image_size', type=int, nargs=2, default=None, help='default 224 224')
+    parser.add_argument('--resume', action='store_true', help='start from the best checkpoint under --loadpath')
+    parser.add_argument('--layers_per_block', type=_json, default=list(LAYERS_PER_BLOCK),
+                        help='2 n_pool + 1 layer counts (JSON)')
+    parser.add_argument('--growth', type=int, default=16)
+    parser.add_argument('--n_first', type=int, default=48)
+    parser.add_argument('--max_batches', type=int, default=None, help='cap on the batches of each pass (tests)')
+    return parser
+
+
+def parse_args(argv=None):
+    return make_parser().parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    try:
+        check_supported(args.dataset, args.savepath, args.dtype, args.mma, args.optimizer, args.dropout,
+                        args.batch_size, args.num_epochs, args.max_patience, args.learning_rate, args.lr_decay,
+                        args.weight_decay, args.layers_per_block, args.growth, args.n_first, args.image_size)
+    except (NotImplementedError, ValueError, TypeError) as e:
+        print('train_fcdensenet.py: ' + str(e), file=sys.stderr)
+        return 2
+    train(args.dataset, args.learning_rate, args.lr_decay, args.weight_decay, args.num_epochs, args.max_patience,
+          savepath=args.savepath, loadpath=args.loadpath, batch_size=args.batch_size, resume=args.resume,
+          synthetic=args.synthetic, n_images=args.n_images, image_size=args.image_size, seed=args.seed,
+          dtype=args.dtype, mma=args.mma, optimizer=args.optimizer, dropout=args.dropout,
+          layers_per_block=args.layers_per_block, growth=args.growth, n_first=args.n_first,
+          max_batches=args.max_batches)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
