@@ -250,6 +250,18 @@ int iiseg_conv_wino_f32(void* stream, const iiseg_conv_desc* d, const float* x1,
  *                                    the setting in force (mask_bytes: IISEG_CONV_UNPOOL from mask
  *                                    bytes): 0 per-tile, 1 LDS-staged, 2 streaming; < 0 an IISEG_ERR_* */
 int iiseg_conv_wino_input_wide(int on);
+/* The streaming kernel with TWO consecutive tiles per thread: half the staged loads, offsets and results, 24 KB
+ * of LDS instead of 48 and 8-byte stores, so that its workgroups fit on a compute unit beside the GEMM's.  It runs
+ * wherever the streaming kernel runs and its halved staging buffer holds every workgroup's rows; V is the same,
+ * bit for bit.
+ *   iiseg_conv_wino_input_narrow(on)   on = 0 / 1 for the launches that follow (the default is the environment's
+ *                                      IISEG_WINO_INPUT_NARROW, 1 when unset); on < 0 only asks.  Returns the
+ *                                      setting in force.  For A/B timing and tests.
+ *   iiseg_conv_wino_input_tiles(d, mask_bytes)   tiles per thread of the streaming kernel for such a call under
+ *                                      the settings in force: 4 or 2, 0 where another kernel runs; < 0 an
+ *                                      IISEG_ERR_* */
+int iiseg_conv_wino_input_narrow(int on);
+int iiseg_conv_wino_input_tiles(const iiseg_conv_desc* d, int mask_bytes);
 int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes);
 /* The products M of the separate-GEMM forms (iiseg_conv_wino_f32 without IISEG_WINO_FUSED, the GEMM form of
  * iiseg_conv_wino_bf16, the split-K iiseg_conv_gemm_f32 / iiseg_conv_gemm_bf16) lie in the workspace as
@@ -264,6 +276,15 @@ int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes);
  *                                (IISEG_WINO_GEMM, then IISEG_WINO_OUTPUT): the second would read a layout
  *                                the first did not write. */
 int iiseg_conv_wino_m_quad(int on);
+/* The 256x128 and 128x128 tiles of the fp32 GEMM stage (iiseg_conv_wino_f32 without IISEG_WINO_FUSED and the
+ * split-K iiseg_conv_gemm_f32) hold their load and store addressing in scalar registers and one lane offset per
+ * operand, which leaves room on a compute unit for waves of another stream's kernels beside four GEMM waves per
+ * SIMD.  Loads, the order of the multiply-accumulates, stores and every result are the same, bit for bit.
+ *   iiseg_conv_wino_gemm_slim(on)   on = 0 / 1: the addressing in vector registers / the form above, for the
+ *                                   launches that follow (the default is the environment's IISEG_WINO_GEMM_SLIM,
+ *                                   1 when unset); on < 0 only asks.  Returns the setting in force.  For A/B
+ *                                   timing and tests. */
+int iiseg_conv_wino_gemm_slim(int on);
 /* The Winograd call with the 2x2 max-pool and the DePool2D mask bytes (as iiseg_conv_mask_f32):
  *   pool_out   (may be NULL) the FULL pooled tensor (B, Cout, fullH/2, fullW/2); the pooled
  *              positions of the window are written in place by the output transform (or the fused

@@ -135,6 +135,9 @@ SIGNATURES = {
     'iiseg_conv_wino_input_wide': (C.c_int, [C.c_int]),
     'iiseg_conv_wino_input_path': (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
     'iiseg_conv_wino_m_quad': (C.c_int, [C.c_int]),
+    'iiseg_conv_wino_gemm_slim': (C.c_int, [C.c_int]),
+    'iiseg_conv_wino_input_narrow': (C.c_int, [C.c_int]),
+    'iiseg_conv_wino_input_tiles': (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
     'iiseg_conv_wino_mask_f32': (C.c_int, [_vp, C.POINTER(ConvDesc)] + [_vp] * 12 + [C.c_uint32]),
     'iiseg_conv_wino_bf16_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'iiseg_conv_wino_bf16_weight_bytes': (_i64, [C.POINTER(ConvDesc)]),

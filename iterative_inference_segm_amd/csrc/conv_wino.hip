@@ -384,17 +384,21 @@ __host__ __device__ inline IwChunk iw_chunk(int t0, int t1, int ntx, int nty) {
 constexpr int IW_PBITS = 20;
 static_assert(IW_E <= 32, "one validity bit per staged element");
 
-template <bool MB, int NT>
-__global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p, const int chw) {
-    __shared__ __attribute__((aligned(16))) float Ls[2][IW_E * NT];
+// TPT = 2 (wino_input_narrow below): TWO consecutive tiles per thread, half the staged elements, offsets and
+// results, 8-byte stores -- 24 KB of LDS and a register count that fits beside the GEMM's waves on a compute unit.
+template <bool MB, int NT, int TPT = 4>
+__global__ __launch_bounds__(NT, TPT == 2 ? 4 : 1) void wino_input_wide_kernel(const WinoParams p, const int chw) {
+    static_assert(TPT == 4 || TPT == 2, "a quad or a pair of tiles per thread");
+    constexpr int E = IW_E * TPT / 4;   // staged elements per thread
+    __shared__ __attribute__((aligned(16))) float Ls[2][E * NT];
     const int tid = threadIdx.x;
-    const int tw0 = blockIdx.x * (4 * NT), tw1 = min(tw0 + 4 * NT, p.T);
+    const int tw0 = blockIdx.x * (TPT * NT), tw1 = min(tw0 + TPT * NT, p.T);
     const IwChunk k = iw_chunk(tw0, tw1, p.ntx, p.nty);
     const int NC = 2 * p.ntx + 2, NE = k.NR * NC;
     const int iyb = p.ty0 - p.pad, ixb = p.tx0 - p.pad;
-    uint32_t pk[IW_E], okm = 0;
+    uint32_t pk[E], okm = 0;
 #pragma unroll
-    for (int i = 0; i < IW_E; ++i) {
+    for (int i = 0; i < E; ++i) {
         const int e = i * NT + tid;
         const int r = e / NC, c = e - r * NC;
         int bi = 0, ry = 2 * k.tyf + r;
@@ -415,23 +419,23 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
         okm |= (ok ? 1u : 0u) << i;
     }
     // the thread's four tiles: first staged element of each 4x4 patch
-    const int q4 = tw0 + 4 * tid;
-    int lbase[4];
+    const int q4 = tw0 + TPT * tid;
+    int lbase[TPT];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < TPT; ++j) {
         const int t = min(q4 + j, tw1 - 1);
         const int gr = t / p.ntx, txl = t - gr * p.ntx;
         const int b = gr / p.nty, ty = gr - b * p.nty;
         const int row = b == k.b0 ? 2 * (ty - k.tyf) : k.R0 + (b - k.b0 - 1) * k.RI + 2 * ty;
         lbase[j] = row * NC + 2 * txl;
     }
-    const int nv = min(4, tw1 - q4);   // tiles of the quad below T (<= 0: none)
+    const int nv = min(TPT, tw1 - q4);   // tiles of the quad below T (<= 0: none)
     const int HW = p.H * p.W, hw2 = p.h2 * p.w2;
     const size_t xis = (size_t)p.Kc * p.Tpad;
     const int c0 = blockIdx.y * chw;
     constexpr uint32_t PM = (1u << IW_PBITS) - 1;
-    float v[IW_E];
-    uint32_t mq[MB ? IW_E : 1];
+    float v[E];
+    uint32_t mq[MB ? E : 1];
 
     // all loads of a channel unconditionally, one batch in flight (32-bit byte offsets from the
     // plane of the chunk's first image); they are masked only where they are written to LDS, one
@@ -442,7 +446,9 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
             const uint8_t* mp = p.mask_in + ((size_t)k.b0 * p.C1 + c) * hw2;
             const char* upp = reinterpret_cast<const char*>(p.x1 + ((size_t)k.b0 * p.C1 + c) * hw2);
 #pragma unroll
-            for (int i = 0; i < IW_E; ++i) {
+            for (int i = 0; i < E; ++i) {
+                // (TPT = 2: the offsets are formed again for every channel, not kept in registers across the loop)
+                if constexpr (TPT == 2) asm volatile("" : "+v"(pk[i]));
                 const uint32_t o = (pk[i] >> IW_PBITS) * ist + ((pk[i] & PM) >> 2);
                 mq[i] = mp[o];
                 v[i] = *reinterpret_cast<const float*>(upp + 4u * o);
@@ -454,7 +460,7 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
                 first ? p.x1 + ((size_t)k.b0 * p.C1 + c) * HW
                       : p.x2 + ((size_t)k.b0 * p.C2 + (c - p.C1)) * HW);
 #pragma unroll
-            for (int i = 0; i < IW_E; ++i)
+            for (int i = 0; i < E; ++i)
                 v[i] = *reinterpret_cast<const float*>(src + 4u * ((pk[i] >> IW_PBITS) * ist + (pk[i] & PM)));
         }
     };
@@ -470,7 +476,7 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
         const int c = c0 + cc;
         float* L = Ls[cc & 1];
 #pragma unroll
-        for (int i = 0; i < IW_E; ++i) {   // (every slot of the buffer: those past the staged rows get 0)
+        for (int i = 0; i < E; ++i) {   // (every slot of the buffer: those past the staged rows get 0)
             bool on = (okm >> i) & 1u;
             if constexpr (MB) on = on && ((mq[i] >> (pk[i] & 3u)) & 1u);
             L[i * NT + tid] = on ? v[i] : 0.f;
@@ -485,9 +491,9 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             constexpr int RA[4] = {0, 1, 2, 1}, RB[4] = {2, 2, 1, 3};
-            float o[4][4];
+            float o[4][TPT];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < TPT; ++j) {
                 const float* La = L + lbase[j] + RA[i] * NC;
                 const float* Lb = L + lbase[j] + RB[i] * NC;
                 const float2 alo = *reinterpret_cast<const float2*>(La);
@@ -505,27 +511,34 @@ __global__ __launch_bounds__(NT) void wino_input_wide_kernel(const WinoParams p,
                 o[2][j] = e[2] - e[1];
                 o[3][j] = e[1] - e[3];
             }
-            if (FULL || nv == 4) {
+            if (FULL || nv == TPT) {
 #pragma unroll
                 for (int x = 0; x < 4; ++x)
-                    *reinterpret_cast<float4*>(vo + (size_t)(i * 4 + x) * xis) =
-                        make_float4(o[x][0], o[x][1], o[x][2], o[x][3]);
+                    if constexpr (TPT == 4)
+                        *reinterpret_cast<float4*>(vo + (size_t)(i * 4 + x) * xis) =
+                            make_float4(o[x][0], o[x][1], o[x][2], o[x][3]);
+                    else
+                        *reinterpret_cast<float2*>(vo + (size_t)(i * 4 + x) * xis) = make_float2(o[x][0], o[x][1]);
             } else {   // the quad that holds T: the tiles below T, one by one
 #pragma unroll
                 for (int x = 0; x < 4; ++x)
 #pragma unroll
-                    for (int j = 0; j < 3; ++j)
+                    for (int j = 0; j < TPT - 1; ++j)
                         if (j < nv) vo[(size_t)(i * 4 + x) * xis + j] = o[x][j];
             }
         }
     }
     };
-    if (tw0 + 4 * NT <= p.T) run(std::true_type{});
+    if (tw0 + TPT * NT <= p.T) run(std::true_type{});
     else run(std::false_type{});
 }
 
 // ---- 2. the 16 GEMMs ---------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, int NBUF, int BK = 16>
+// SLIM (wino_gemm_slim below): the same loads, MFMAs and stores with less addressing held in vector registers, so
+// that four waves per SIMD leave room for a fifth of another kernel.  One lane offset per operand serves every
+// LDS-DMA load (the row block of a load, the k-tile, m0 / t0 are wave-uniform and ride on the scalar offset), and one
+// LDS read base per operand serves every read (the k row, the 32-column block and the ring slot are constants).
+template <int BM, int BN, int WM, int WN, int NBUF, int BK = 16, bool SLIM = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoParams p) {
     constexpr int NCH = BK / 2;
     constexpr int WTM = BM / WM, WTN = BN / WN;
@@ -567,6 +580,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoPa
     const bool astager = NW == 4 || wave >= 4;
     const int atid = NW == 8 ? tid - 256 : tid;
     const int awave = NW == 8 ? wave - 4 : wave;
+    // SLIM: a 64-lane load covers 64 / RA rows of A (RA lanes per row); a lane's place inside it never changes
+    constexpr int RA = BM / 4, RB = BN / 4;
+    static_assert(RA <= 64 && RB <= 64 && 64 % RA == 0 && 64 % RB == 0, "whole rows per 64-lane load");
+    const unsigned avo = 4u * (unsigned)((lane / RA) * p.Mpad + (lane % RA) * 4);
+    const unsigned bvo = 4u * (unsigned)((lane / RB) * p.Tpad + (lane % RB) * 4);
+    const int awave_u = __builtin_amdgcn_readfirstlane(awave), bwave_u = __builtin_amdgcn_readfirstlane(wave & 3);
+    const unsigned aso = 4u * (unsigned)(awave_u * (64 / RA) * p.Mpad + m0);
+    const unsigned bso = 4u * (unsigned)(bwave_u * (64 / RB) * p.Tpad + t0);
 
     // global -> LDS directly, 16 bytes per lane: thread-linear == LDS-linear
 #define WINO_STAGE(KT, BUF)                                                                        \
@@ -576,6 +597,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoPa
                 constexpr int j = decltype(J)::value;                                              \
                 const int f = j * NA + atid;                                                       \
                 const int row = f / (BM / 4), c4 = f % (BM / 4);                                   \
+                if constexpr (SLIM)                                                                \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(                                          \
+                    arsrc,                                                                         \
+                    (__attribute__((address_space(3))) void*)(&As[BUF][0][0] + (j * NA + awave_u * 64) * 4), \
+                    16, (int)avo, (int)(aso + 4u * (unsigned)(((KT) * BK + j * NA / RA) * p.Mpad)), 0, 0); \
+                else                                                                               \
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(                                          \
                     arsrc,                                                                         \
                     (__attribute__((address_space(3))) void*)(&As[BUF][0][0] + (j * NA + awave * 64) * 4), \
@@ -586,6 +613,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoPa
                 constexpr int j = decltype(J)::value;                                              \
                 const int f = j * 256 + (tid & 255);                                               \
                 const int row = f / (BN / 4), c4 = f % (BN / 4);                                   \
+                if constexpr (SLIM)                                                                \
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(                                          \
+                    brsrc,                                                                         \
+                    (__attribute__((address_space(3))) void*)(&Bs[BUF][0][0] + (j * 256 + bwave_u * 64) * 4), \
+                    16, (int)bvo, (int)(bso + 4u * (unsigned)(((KT) * BK + j * 256 / RB) * p.Tpad)), 0, 0); \
+                else                                                                               \
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(                                          \
                     brsrc,                                                                         \
                     (__attribute__((address_space(3))) void*)(&Bs[BUF][0][0] + (j * 256 + (wave & 3) * 64) * 4), \
@@ -635,18 +668,23 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoPa
         int sbuf = buf + NBUF - 1;               // ring slot of the tile requested now
         if (sbuf >= NBUF) sbuf -= NBUF;
         float a[2][TM], b[2][TN];
+        // (SLIM: the lane's column in k row lh of this ring slot; As[buf][kk][..] is then ap[a constant])
+        const float* ap = &As[SLIM ? buf : 0][lh][wm * WTM + l31];
+        const float* bp = &Bs[SLIM ? buf : 0][lh][wn * WTN + l31];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) a[0][i] = As[buf][lh][wm * WTM + i * 32 + l31];
+        for (int i = 0; i < TM; ++i) a[0][i] = SLIM ? ap[i * 32] : As[buf][lh][wm * WTM + i * 32 + l31];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) b[0][j] = Bs[buf][lh][wn * WTN + j * 32 + l31];
+        for (int j = 0; j < TN; ++j) b[0][j] = SLIM ? bp[j * 32] : Bs[buf][lh][wn * WTN + j * 32 + l31];
         static_for<0, NCH>([&](auto CH) __attribute__((always_inline)) {
             constexpr int ch = decltype(CH)::value;
             if constexpr (ch + 1 < NCH) {
                 const int kk = (ch + 1) * 2 + lh;
 #pragma unroll
-                for (int i = 0; i < TM; ++i) a[(ch + 1) & 1][i] = As[buf][kk][wm * WTM + i * 32 + l31];
+                for (int i = 0; i < TM; ++i)
+                    a[(ch + 1) & 1][i] = SLIM ? ap[(ch + 1) * 2 * BM + i * 32] : As[buf][kk][wm * WTM + i * 32 + l31];
 #pragma unroll
-                for (int j = 0; j < TN; ++j) b[(ch + 1) & 1][j] = Bs[buf][kk][wn * WTN + j * 32 + l31];
+                for (int j = 0; j < TN; ++j)
+                    b[(ch + 1) & 1][j] = SLIM ? bp[(ch + 1) * 2 * BN + j * 32] : Bs[buf][kk][wn * WTN + j * 32 + l31];
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -693,6 +731,22 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void wino_gemm_kernel(const WinoPa
         return;
     }
     // M[xi][co][t]
+    if constexpr (SLIM) {
+        // a scalar base per (wave, i, r, j) and ONE 32-bit lane offset, 4 * lh rows and the column
+        // (16 * Tpad bytes fit: wino_geometry bounds Tpad * Kc * 4, Kc >= 16), not a 64-bit address per store
+        const int wm_u = __builtin_amdgcn_readfirstlane(wm), wn_u = __builtin_amdgcn_readfirstlane(wn);
+        char* mb = reinterpret_cast<char*>(Mx + (size_t)(m0 + wm_u * WTM) * p.Tpad + t0 + wn_u * WTN);
+        const unsigned lo = 4u * (unsigned)(4 * lh * p.Tpad + l31);
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    *reinterpret_cast<float*>(mb + ((size_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * p.Tpad + j * 32) * 4 + lo) =
+                        acc[i][j][r];
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int t = t0 + wn * WTN + j * 32 + l31;
@@ -1083,6 +1137,20 @@ int input_wide_setting() {
     return v;
 }
 
+// IISEG_WINO_INPUT_NARROW (default 1; iiseg_conv_wino_input_narrow): 1 = the streaming kernel with two tiles per
+// thread (TPT = 2: half the registers and LDS, 8-byte stores; same bits) wherever the streaming kernel runs and the
+// halved staging buffer holds every workgroup's rows; 0 = four tiles per thread everywhere
+std::atomic<int> g_input_narrow{-1};
+
+int input_narrow_setting() {
+    int v = g_input_narrow.load();
+    if (v < 0) {
+        v = getenv("IISEG_WINO_INPUT_NARROW") ? (atoi(getenv("IISEG_WINO_INPUT_NARROW")) != 0) : 1;
+        g_input_narrow.store(v);
+    }
+    return v;
+}
+
 // IISEG_WINO_M_QUAD (default 1; iiseg_conv_wino_m_quad): 0 = the products stay M[slice][Mpad][Tpad] with
 // one-dword stores and loads on both sides (same bits: A/B timing, tests)
 std::atomic<int> g_m_quad{-1};
@@ -1096,6 +1164,20 @@ int m_quad_setting() {
     return v;
 }
 
+// IISEG_WINO_GEMM_SLIM (default 1; iiseg_conv_wino_gemm_slim): 0 = the 256x128 and 128x128 GEMM tiles (Winograd layers
+// and the split-K GEMM) keep their addressing in vector registers (114 of them, 120 allocated: four waves per SIMD fill the file
+// but for 32); 1 = the SLIM form of wino_gemm_kernel (84, 88 allocated: 160 left).  Same loads, MFMAs, stores and bits.
+std::atomic<int> g_gemm_slim{-1};
+
+int gemm_slim_setting() {
+    int v = g_gemm_slim.load();
+    if (v < 0) {
+        v = getenv("IISEG_WINO_GEMM_SLIM") ? (atoi(getenv("IISEG_WINO_GEMM_SLIM")) != 0) : 1;
+        g_gemm_slim.store(v);
+    }
+    return v;
+}
+
 // The layout of a GEMM's products, for its producer and its consumer alike: channel quads,
 // M[slice][Mpad / 4][Tpad][4], when the setting allows and one slice fits the 32-bit byte offsets of
 // the producers' buffer descriptor (Mpad is a multiple of 64 everywhere: quads are whole).
@@ -1104,11 +1186,11 @@ int m_quad(int Mpad, int Tpad) {
 }
 
 // every workgroup's staged rows fit its LDS buffer (exact: the same iw_chunk the kernel runs)
-bool iw_fits(const WinoParams& p, int nt) {
+bool iw_fits(const WinoParams& p, int nt, int tpt) {
     const int NC = 2 * p.ntx + 2;
-    for (int t0 = 0; t0 < p.T; t0 += 4 * nt) {
-        const int t1 = t0 + 4 * nt < p.T ? t0 + 4 * nt : p.T;
-        if ((int64_t)iw_chunk(t0, t1, p.ntx, p.nty).NR * NC > (int64_t)IW_E * nt) return false;
+    for (int t0 = 0; t0 < p.T; t0 += tpt * nt) {
+        const int t1 = t0 + tpt * nt < p.T ? t0 + tpt * nt : p.T;
+        if ((int64_t)iw_chunk(t0, t1, p.ntx, p.nty).NR * NC > (int64_t)(IW_E * tpt / 4) * nt) return false;
     }
     return true;
 }
@@ -1125,7 +1207,8 @@ constexpr int IW_NT = 256;   // threads per workgroup of the streaming kernel
 //    it gains);
 //  - plain maps whose tiles per image fill the LDS-staged kernel's workgroups exactly: that kernel
 //    then already stores at this one's rate (256 channels of 32 x 32 tiles: 0.287 -> 0.299 ms).
-int iw_shape(const WinoParams& p, bool unpool, bool mb) {
+// `tpt`: tiles per thread of the launch, 2 under wino_input_narrow where the halved staging still fits.
+int iw_shape(const WinoParams& p, bool unpool, bool mb, int* tpt) {
     const int setting = input_wide_setting();
     if (!setting || (unpool && !mb)) return 0;
     if (setting != 2) {
@@ -1140,7 +1223,8 @@ int iw_shape(const WinoParams& p, bool unpool, bool mb) {
     int ch = 8;
     if (p.Kc % 32 == 0 && waves1 / 32 >= 2048) ch = 32;
     else if (waves1 / 16 >= 2048) ch = 16;
-    return iw_fits(p, IW_NT) ? ch : 0;
+    *tpt = input_narrow_setting() && iw_fits(p, IW_NT, 2) ? 2 : 4;
+    return *tpt == 2 || iw_fits(p, IW_NT, 4) ? ch : 0;
 }
 
 // tiles per workgroup of the LDS-staged kernel (one image per workgroup), 0 = the per-tile kernel
@@ -1163,9 +1247,12 @@ int ilds_nt(const WinoParams& p) {
 
 void launch_wino_input(hipStream_t s, const WinoParams& p, bool unpool) {
     const bool mb = unpool && p.mask_in;
-    if (const int chw = iw_shape(p, unpool, mb)) {
-        const dim3 g2((p.T + 4 * IW_NT - 1) / (4 * IW_NT), p.Kc / chw);
-        if (mb) IISEG_LAUNCH((wino_input_wide_kernel<true, IW_NT>), g2, dim3(IW_NT), 0, s, p, chw);
+    int tpt = 4;
+    if (const int chw = iw_shape(p, unpool, mb, &tpt)) {
+        const dim3 g2((p.T + tpt * IW_NT - 1) / (tpt * IW_NT), p.Kc / chw);
+        if (mb && tpt == 2) IISEG_LAUNCH((wino_input_wide_kernel<true, IW_NT, 2>), g2, dim3(IW_NT), 0, s, p, chw);
+        else if (mb) IISEG_LAUNCH((wino_input_wide_kernel<true, IW_NT>), g2, dim3(IW_NT), 0, s, p, chw);
+        else if (tpt == 2) IISEG_LAUNCH((wino_input_wide_kernel<false, IW_NT, 2>), g2, dim3(IW_NT), 0, s, p, chw);
         else IISEG_LAUNCH((wino_input_wide_kernel<false, IW_NT>), g2, dim3(IW_NT), 0, s, p, chw);
         return;
     }
@@ -1242,12 +1329,23 @@ extern "C" int iiseg_conv_wino_input_wide(int on) {
     return input_wide_setting();
 }
 
+extern "C" int iiseg_conv_wino_input_narrow(int on) {
+    if (on >= 0) g_input_narrow.store(on ? 1 : 0);
+    return input_narrow_setting();
+}
+
+extern "C" int iiseg_conv_wino_gemm_slim(int on) {
+    if (on >= 0) g_gemm_slim.store(on ? 1 : 0);
+    return gemm_slim_setting();
+}
+
 extern "C" int iiseg_conv_wino_m_quad(int on) {
     if (on >= 0) g_m_quad.store(on ? 1 : 0);
     return m_quad_setting();
 }
 
-extern "C" int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes) {
+// path as iiseg_conv_wino_input_path returns it; *tpt: tiles per thread where it is the streaming kernel
+static int wino_input_path(const iiseg_conv_desc* d, int mask_bytes, int* tpt) {
     WinoGeom g;
     const int st = wino_geom(d, g);
     if (st) return st;
@@ -1256,8 +1354,20 @@ extern "C" int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_byt
     if (mask_bytes && !unpool) return IISEG_ERR_UNSUPPORTED;
     p.B = d->B; p.C1 = d->C1; p.C2 = d->C2; p.H = d->H; p.W = d->W;
     p.nty = g.nty; p.ntx = g.ntx; p.T = g.T; p.Tpad = g.Tpad; p.Kc = g.Kc;
-    if (iw_shape(p, unpool, mask_bytes != 0)) return 2;
+    if (iw_shape(p, unpool, mask_bytes != 0, tpt)) return 2;
+    *tpt = 0;
     return ilds_nt(p) ? 1 : 0;
+}
+
+extern "C" int iiseg_conv_wino_input_path(const iiseg_conv_desc* d, int mask_bytes) {
+    int tpt;
+    return wino_input_path(d, mask_bytes, &tpt);
+}
+
+extern "C" int iiseg_conv_wino_input_tiles(const iiseg_conv_desc* d, int mask_bytes) {
+    int tpt = 0;
+    const int path = wino_input_path(d, mask_bytes, &tpt);
+    return path < 0 ? path : tpt;
 }
 
 extern "C" int64_t iiseg_conv_wino_weight_elems(const iiseg_conv_desc* d) {
@@ -1423,10 +1533,14 @@ static int wino_run(void* stream, const iiseg_conv_desc* d, const float* x1, con
         if (bm == 0) {
         } else if (bm == 256 && nbuf == 3)
             IISEG_LAUNCH((wino_gemm_kernel<256, 128, 4, 2, 3>), dim3(grid), dim3(512), 0, s, p);
+        else if (bm == 256 && gemm_slim_setting())
+            IISEG_LAUNCH((wino_gemm_kernel<256, 128, 4, 2, 2, 16, true>), dim3(grid), dim3(512), 0, s, p);
         else if (bm == 256)
             IISEG_LAUNCH((wino_gemm_kernel<256, 128, 4, 2, 2>), dim3(grid), dim3(512), 0, s, p);
         else if (nbuf == 3)
             IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 3>), dim3(grid2), dim3(256), 0, s, p);
+        else if (gemm_slim_setting())
+            IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 2, 16, true>), dim3(grid2), dim3(256), 0, s, p);
         else
             IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 2>), dim3(grid2), dim3(256), 0, s, p);
     }
@@ -1633,8 +1747,12 @@ extern "C" int iiseg_conv_gemm_f32(void* stream, const iiseg_conv_desc* d, const
     p.mq = m_quad(g.Mpad, g.Tpad);
     const int grid = g.S * p.n_ttiles * p.n_mtiles;
     if (stages & IISEG_WINO_GEMM) {
-        if (g.bm == 256)
+        if (g.bm == 256 && gemm_slim_setting())
+            IISEG_LAUNCH((wino_gemm_kernel<256, 128, 4, 2, 2, 16, true>), dim3(grid), dim3(512), 0, s, p);
+        else if (g.bm == 256)
             IISEG_LAUNCH((wino_gemm_kernel<256, 128, 4, 2, 2>), dim3(grid), dim3(512), 0, s, p);
+        else if (gemm_slim_setting())
+            IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 2, 16, true>), dim3(grid), dim3(256), 0, s, p);
         else
             IISEG_LAUNCH((wino_gemm_kernel<128, 128, 2, 2, 2>), dim3(grid), dim3(256), 0, s, p);
     }

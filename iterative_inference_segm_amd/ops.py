@@ -142,6 +142,14 @@ def wino_input_wide(on=None, force=False):
     return bool(_lib.load().iiseg_conv_wino_input_wide(-1 if on is None else (2 if on and force else int(bool(on)))))
 
 
+# And its form with two tiles per thread: IISEG_WINO_INPUT_NARROW=0, or `wino_input_narrow(False)`, keeps four.
+def wino_input_narrow(on=None):
+    """The streaming input transform for the launches that follow: True = two tiles per thread (24 KB of LDS,
+    8-byte stores) where its staging fits (the default, IISEG_WINO_INPUT_NARROW), False = four; None only asks.
+    Returns the setting in force.  Same bits (A/B timing, tests)."""
+    return bool(_lib.load().iiseg_conv_wino_input_narrow(-1 if on is None else int(bool(on))))
+
+
 # So is the layout of the GEMM products M in the workspace: IISEG_WINO_M_QUAD=0, or `wino_m_quad(False)`.
 def wino_m_quad(on=None):
     """The products M of the separate-GEMM layers (fp32 / bf16 Winograd GEMM, split-K GEMM) for the launches
@@ -149,6 +157,14 @@ def wino_m_quad(on=None):
     M[slice][Mpad][Tpad] in 4-byte pieces; None only asks.  Returns the setting in force.  Same bits (A/B
     timing, tests).  Process-wide: not to be changed between the separately launched stages of one layer."""
     return bool(_lib.load().iiseg_conv_wino_m_quad(-1 if on is None else int(bool(on))))
+
+
+# And the register diet of the fp32 GEMM tiles: IISEG_WINO_GEMM_SLIM=0, or `wino_gemm_slim(False)`.
+def wino_gemm_slim(on=None):
+    """The 256x128 / 128x128 fp32 GEMM tiles (Winograd GEMM stage, split-K GEMM) for the launches that follow:
+    True = addressing in scalar registers, 88 vector registers allocated (the default, IISEG_WINO_GEMM_SLIM),
+    False = 120; None only asks.  Returns the setting in force.  Same bits (A/B timing, tests)."""
+    return bool(_lib.load().iiseg_conv_wino_gemm_slim(-1 if on is None else int(bool(on))))
 
 
 class workspace_tag:
