@@ -1207,6 +1207,20 @@ int iiseg_conv_wgrad_bf16_slabs(const iiseg_conv_wgrad_desc* d);
 int64_t iiseg_conv_wgrad_bf16_workspace_elems(const iiseg_conv_wgrad_desc* d);
 int iiseg_conv_wgrad_bf16(void* stream, const iiseg_conv_wgrad_desc* d, const float* x, const float* gz, float* ws,
                           float* dW, float* db);
+/* The same sums, contract, status codes and NULL rules in the form for few output channels
+ * (csrc/conv_wgrad_bf16_co16.hip; backward-compatible addition): blocks of 16 output x 64
+ * input channels on v_mfma_f32_16x16x32_bf16, any Cout (a ragged last block), slabs and workspace of its own plan.
+ * The order of the fp32 additions differs from iiseg_conv_wgrad_bf16's, so the bits may; each is deterministic. */
+int iiseg_conv_wgrad_bf16_co16_slabs(const iiseg_conv_wgrad_desc* d);
+int64_t iiseg_conv_wgrad_bf16_co16_workspace_elems(const iiseg_conv_wgrad_desc* d);
+int iiseg_conv_wgrad_bf16_co16(void* stream, const iiseg_conv_wgrad_desc* d, const float* x, const float* gz,
+                               float* ws, float* dW, float* db);
+/* db alone, with the bits iiseg_conv_wgrad_f32 gives it for the same descriptor (csrc/conv_wgrad.hip: that kernel's
+ * plan, chains and slab order without x and the products; backward-compatible addition): for a caller that forms dW
+ * on the 16-bit pipe (db = NULL there) and leaves every db as the fp32 mode has it.
+ *   ws : iiseg_conv_wgrad_db_workspace_elems(d) floats of scratch (0 with one slab: may be NULL; else slabs * Cout). */
+int64_t iiseg_conv_wgrad_db_workspace_elems(const iiseg_conv_wgrad_desc* d);
+int iiseg_conv_wgrad_db_f32(void* stream, const iiseg_conv_wgrad_desc* d, const float* gz, float* ws, float* db);
 
 /* ---------------------------------------------------------------------------------------
  * Data gradients on the 16-bit matrix pipe (dgrad='bf16'; backward-compatible addition).

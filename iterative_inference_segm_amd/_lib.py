@@ -320,6 +320,13 @@ SIGNATURES = {
     'iiseg_conv_wgrad_bf16_slabs': (C.c_int, [C.POINTER(ConvWgradDesc)]),
     'iiseg_conv_wgrad_bf16_workspace_elems': (_i64, [C.POINTER(ConvWgradDesc)]),
     'iiseg_conv_wgrad_bf16': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
+    # ... in blocks of 16 output channels (co_block=16)
+    'iiseg_conv_wgrad_bf16_co16_slabs': (C.c_int, [C.POINTER(ConvWgradDesc)]),
+    'iiseg_conv_wgrad_bf16_co16_workspace_elems': (_i64, [C.POINTER(ConvWgradDesc)]),
+    'iiseg_conv_wgrad_bf16_co16': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 5),
+    # db alone, as iiseg_conv_wgrad_f32 forms it
+    'iiseg_conv_wgrad_db_workspace_elems': (_i64, [C.POINTER(ConvWgradDesc)]),
+    'iiseg_conv_wgrad_db_f32': (C.c_int, [_vp, C.POINTER(ConvWgradDesc)] + [_vp] * 3),
     # data gradients on the 16-bit matrix pipe (dgrad='bf16')
     'iiseg_conv_dgrad_bf16_check': (C.c_int, [C.POINTER(ConvDgradDesc)]),
     'iiseg_conv_dgrad_bf16_pack_elems': (_i64, [C.POINTER(ConvDgradDesc)]),

@@ -182,6 +182,108 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(cw_params p, const T
     }
 }
 
+// db alone, with the bits conv_wgrad_kernel<float> gives it for the same descriptor: for the modes that form dW
+// elsewhere (wgrad='bf16' on FC-DenseNet) and must leave every db as it is.  It is that kernel
+// without x and without the products: the same plan (so the slabs depend on Cin as there), the same values (zero
+// outside the active region), the same two chains per output channel (even and odd columns, in tile order), the
+// same border share, the slabs (here [slab][Cout]) added in slab order in double.  Only the staging differs: the
+// g_z tiles of a slab come into LDS several at a time, [tile][pixel][co] with an odd channel stride, with eight
+// loads per thread in flight.
+constexpr int DB_LDS = 12288;                                            // floats: 48 KiB
+constexpr int DB_UNROLL = 8, DB_THREADS = 1024;                          // sixteen waves load; two walk the chains
+
+__global__ __launch_bounds__(DB_THREADS) void conv_wgrad_db_kernel(cw_params p, const float* __restrict__ gz,
+                                                               float* __restrict__ dst) {
+    constexpr int CB = chan_block<float>();
+    __shared__ float gs[DB_LDS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slab = blockIdx.x, co0 = blockIdx.y * CB;
+    const int nco = min(CB, p.Cout - co0);
+    const int LD = nco | 1, tile_ld = PIX * LD, K = DB_LDS / tile_ld;    // K >= 2: PIX * 65 = 4160 floats
+    float asum = 0;
+    const int cw = wave & 1, l31 = lane & 31, half = lane >> 5;
+    const bool chain_on = wave < 2 && cw * 32 < nco;                     // that kernel's waves with ci half 0
+    const int cc = min(cw * 32 + l31, nco - 1);                          // (a lane past nco: its sum is not stored)
+    const long long t0 = (long long)slab * p.tps, t1 = min(p.T, t0 + p.tps);
+    const int per_img = p.tilesY * p.tilesX;
+    for (long long tb = t0; tb < t1; tb += K) {
+        const int kt = (int)min((long long)K, t1 - tb), n = kt * nco * PIX;
+        __syncthreads();                                                 // the previous tiles have been read
+        for (int base = tid; base < n; base += DB_THREADS * DB_UNROLL) {
+            float v[DB_UNROLL];
+            int off[DB_UNROLL];
+#pragma unroll
+            for (int u = 0; u < DB_UNROLL; ++u) {
+                const int idx = base + DB_THREADS * u;
+                v[u] = 0;
+                off[u] = -1;
+                if (idx < n) {
+                    const int tt = idx / (nco * PIX), r = idx - tt * (nco * PIX);
+                    const int col = r & (TW - 1), row = (r >> 4) & (TH - 1), c = r >> 6;
+                    const long long t = tb + tt;
+                    const int b = (int)(t / per_img), rem = (int)(t % per_img);
+                    const int y = p.ay0 + (rem / p.tilesX) * TH + row, xx = p.ax0 + (rem % p.tilesX) * TW + col;
+                    off[u] = tt * tile_ld + (row * TW + col) * LD + c;
+                    if (y < p.ay0 + p.AH && xx < p.ax0 + p.AW)
+                        v[u] = gz[(((size_t)b * p.Cout + co0 + c) * p.OH + y) * p.OW + xx];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < DB_UNROLL; ++u)
+                if (off[u] >= 0) gs[off[u]] = v[u];
+        }
+        __syncthreads();
+        if (chain_on) {
+            for (int tt = 0; tt < kt; ++tt) {
+                const float* ga = gs + tt * tile_ld + cc + half * LD;
+#pragma unroll
+                for (int s = 0; s < PIX / 2; ++s) asum += ga[((s >> 3) * TW + 2 * (s & 7)) * LD];
+            }
+        }
+    }
+    __syncthreads();
+    float* bsum = gs;
+    const long long NB = (long long)p.B * p.nb;
+    const long long q0 = min(NB, (long long)slab * p.bps), q1 = min(NB, q0 + p.bps);
+    for (int c = wave; c < nco; c += DB_THREADS / 64) {        // (a channel is one wave's, whichever)
+        float s = 0;
+        for (long long q = q0 + lane; q < q1; q += 64) {
+            int y, xx;
+            border_pixel(p, q % p.nb, y, xx);
+            s += gz[(((size_t)(q / p.nb) * p.Cout + co0 + c) * p.OH + y) * p.OW + xx];
+        }
+        s = wave_sum(s);
+        if (lane == 0) bsum[c] = s;
+    }
+    __syncthreads();
+    float* dbo = dst + (p.nslab == 1 ? 0 : (long long)slab * p.Cout);
+    if (chain_on) {
+        const float v = asum + __shfl_xor(asum, 32, 64);
+        const int co = cw * 32 + l31;
+        if (half == 0 && co < nco) dbo[co0 + co] = v + bsum[co];
+    }
+}
+
+// db = the slabs added in slab order, in double (conv_wgrad_finalize_kernel's sum): a wave per channel brings the
+// slabs' values into LDS with 64 loads in flight, one lane adds them in order.
+constexpr int DB_FIN = 1024;
+
+__global__ __launch_bounds__(64) void conv_wgrad_db_finalize_kernel(const float* __restrict__ slab, int nslab, int Cout,
+                                                                    float* __restrict__ db) {
+    __shared__ float v[DB_FIN];
+    const int c = blockIdx.x, lane = threadIdx.x;
+    double s = 0.0;
+    for (int k0 = 0; k0 < nslab; k0 += DB_FIN) {
+        const int n = min(DB_FIN, nslab - k0);
+        __syncthreads();
+        for (int k = lane; k < n; k += 64) v[k] = slab[(long long)(k0 + k) * Cout + c];
+        __syncthreads();
+        if (lane == 0)
+            for (int k = 0; k < n; ++k) s += (double)v[k];
+    }
+    if (lane == 0) db[c] = (float)s;
+}
+
 // ---- host side ----
 template <typename T>
 int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p) {
@@ -234,4 +336,24 @@ extern "C" int iiseg_conv_wgrad_f32(void* stream, const iiseg_conv_wgrad_desc* d
 extern "C" int iiseg_conv_wgrad_f64(void* stream, const iiseg_conv_wgrad_desc* d, const double* x, const double* gz,
                                     double* ws, double* dW, double* db) {
     return cw_run<double>(stream, d, x, gz, ws, dW, db);
+}
+extern "C" int64_t iiseg_conv_wgrad_db_workspace_elems(const iiseg_conv_wgrad_desc* d) {
+    const int n = cw_slabs<float>(d);
+    if (n < 0) return n;
+    return n == 1 ? 0 : (int64_t)n * d->Cout;
+}
+extern "C" int iiseg_conv_wgrad_db_f32(void* stream, const iiseg_conv_wgrad_desc* d, const float* gz, float* ws,
+                                       float* db) {
+    cw_params p;
+    if (int st = cw_plan<float>(d, p)) return st;
+    if (!gz || !db || (p.nslab > 1 && !ws)) return IISEG_ERR_NULL;
+    p.want_db = 1;
+    hipStream_t s = (hipStream_t)stream;
+    const int CB = chan_block<float>();
+    const dim3 grid((unsigned)p.nslab, (unsigned)((p.Cout + CB - 1) / CB));
+    IISEG_LAUNCH(conv_wgrad_db_kernel, grid, dim3(DB_THREADS), 0, s, p, gz, p.nslab == 1 ? db : ws);
+    if (p.nslab > 1)
+        IISEG_LAUNCH(conv_wgrad_db_finalize_kernel, dim3((unsigned)p.Cout), dim3(64), 0, s,
+                     (const float*)ws, p.nslab, p.Cout, db);
+    return iiseg_check_launch();
 }

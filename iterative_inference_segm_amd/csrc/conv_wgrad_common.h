@@ -1,5 +1,5 @@
-// What the zero-padded 3x3 weight-gradient kernels share (conv_wgrad.hip: float / double; conv_wgrad_bf16.hip:
-// bf16 operands): the launch parameters, the plan of pixel tiles and slabs, the border pixels of a wide zero
+// What the zero-padded 3x3 weight-gradient kernels share (conv_wgrad.hip: float / double; conv_wgrad_bf16.hip and
+// conv_wgrad_bf16_co16.hip: bf16 operands): the launch parameters, the plan of pixel tiles and slabs, the border pixels of a wide zero
 // padding and the finalize launch that adds the slabs in slab order.
 #pragma once
 #include "mma16_common.h"
@@ -51,9 +51,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_finalize_kernel(const T* __res
 }
 
 // ---- host side ----
-// The plan of a kernel with th x tw pixel tiles and cb x cb channel blocks: slabs of at least min_tps tiles, as
-// many as bring the launch to target_wgs workgroups.
-inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw, int cb, int min_tps, int target_wgs) {
+// The plan of a kernel with th x tw pixel tiles and cbo output x cbi input channel blocks: slabs of at least
+// min_tps tiles, as many as bring the launch to target_wgs workgroups.
+inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw, int cbo, int cbi, int min_tps,
+                   int target_wgs) {
     if (!d) return IISEG_ERR_NULL;
     if (d->K != 3) return IISEG_ERR_SHAPE;
     if (d->B < 1 || d->B > 65535 || d->Cin < 1 || d->Cin > 65535 || d->Cout < 1 || d->Cout > 65535 || d->H < 1 ||
@@ -72,7 +73,7 @@ inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw,
     p.tilesY = (p.AH + th - 1) / th;
     p.tilesX = (p.AW + tw - 1) / tw;
     p.T = (long long)d->B * p.tilesY * p.tilesX;
-    const long long blocks = (long long)((d->Cout + cb - 1) / cb) * ((d->Cin + cb - 1) / cb);
+    const long long blocks = (long long)((d->Cout + cbo - 1) / cbo) * ((d->Cin + cbi - 1) / cbi);
     int64_t tps;
     split_slabs(p.T, blocks, target_wgs, min_tps, &tps, &p.nslab);
     if (tps > ((long long)1 << 30)) return IISEG_ERR_SHAPE;
@@ -85,6 +86,10 @@ inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw,
     p.bps = (NB + p.nslab - 1) / p.nslab;
     p.want_db = 0;
     return IISEG_OK;
+}
+// ... with cb x cb channel blocks
+inline int cw_plan(const iiseg_conv_wgrad_desc* d, cw_params& p, int th, int tw, int cb, int min_tps, int target_wgs) {
+    return cw_plan(d, p, th, tw, cb, cb, min_tps, target_wgs);
 }
 
 }  // namespace

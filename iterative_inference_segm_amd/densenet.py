@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from .datagrads import DataGrads, Layer, Views, flipped
-from .params import Trainable
+from .params import Trainable, check_mode
 
 # mma='bf16c8': TransitionDown and the 1x1 class-score layer as one C8 kernel each (0: the 'bf16' forms on
 # fp32 NCHW copies of the stack, through layout converters)
@@ -128,6 +128,12 @@ def store_names(kinds):
     return names
 
 
+def wgrad_co_block(cout):
+    """The form of ops.conv_wgrad(mma='bf16') a zero-padded 3x3 layer with `cout` filters takes in wgrad='bf16' mode:
+    blocks of 16 output channels up to 16 filters (every 'brc' layer of growth <= 16), else of 64.  Host only."""
+    return 16 if int(cout) <= 16 else 64
+
+
 RUNNING_ALPHA = 0.1     # lasagne BatchNormLayer's alpha: the running averages a checkpoint carries
 
 
@@ -208,7 +214,7 @@ class FCDenseNet(Trainable, Views):
 
     def __init__(self, params, n_classes=11, layer=('pool4',), n_layers_per_block=LAYERS_PER_BLOCK,
                  n_pool=N_POOL, growth=GROWTH, device='cuda', dtype=torch.float32, mma=None, trainable=False,
-                 dropout=0.2):
+                 dropout=0.2, wgrad='f32'):
         """mma: 'f32' (default) | 'bf16' (bf16 MFMA operands, fp32 NCHW activations) | 'bf16c8'
         (configs[2] as BASELINE names it: the dense-block stacks as bf16 C8 tensors, every
         BN_ReLU_Conv of a dense block one launch of the 16-row C8 kernel with BatchNorm + ReLU applied
@@ -219,8 +225,14 @@ class FCDenseNet(Trainable, Views):
         buffer in creation order (`store_names`: a BatchNorm layer as the pair (gamma, beta), so that
         `weight_ranges()` covers every W and every gamma), every layer holds views of it and runs on the direct /
         halo / tap kernels only, so that `refresh()` can pack them again in place after an optimizer step.
-        `dropout`: p of the DropoutLayer behind the convolution of every 'brc' / 'td' layer in `forward_train`."""
+        `dropout`: p of the DropoutLayer behind the convolution of every 'brc' / 'td' layer in `forward_train`.
+        wgrad: operand precision of `backward`'s zero-padded 3x3 weight gradients, the 'brc' layers' and the first
+        convolution's ('f32' default; 'bf16' = operands rounded once to bf16 as they are staged, fp32 accumulation,
+        trainable float32 only: ops.conv_wgrad(mma='bf16') in the form `wgrad_co_block` names, their db by
+        ops.conv_wgrad_db with the bits of the 'f32' mode; everything else of `backward`, the forward and the
+        parameters stay float32 and the same code: DESIGN.md section 22)."""
         mma = mma or ops.DEFAULT_MMA
+        self.wgrad = check_mode('wgrad', wgrad, dtype, trainable)
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
         self._tsaved = None
@@ -429,6 +441,14 @@ class FCDenseNet(Trainable, Views):
                 gst[sid] = torch.zeros_like(stacks[sid].buf)
             return gst[sid]
 
+        def wgrad3x3(t, gz, dW, db):
+            if self.wgrad == 'f32':
+                ops.conv_wgrad(t, gz, dW, db, pad=1, mma='f32')
+            else:
+                # dW on the 16-bit pipe; db stays the fp32 mode's, bit for bit (ops.conv_wgrad_db)
+                ops.conv_wgrad(t, gz, dW, None, pad=1, mma=self.wgrad, co_block=wgrad_co_block(gz.shape[1]))
+                ops.conv_wgrad_db(gz, db, t.shape[1], pad=1)
+
         def through_bn(e, L, name, gz, wgrad):
             stack, n = stacks[e['sid']], e['n']
             if s['keeps'] is not None:
@@ -455,7 +475,7 @@ class FCDenseNet(Trainable, Views):
             elif e['kind'] == 'brc':
                 n = e['n']
                 gz = gstack(e['sid'])[:, n:n + self.growth].contiguous()
-                through_bn(e, L, name, gz, lambda t, gz, dW, db: ops.conv_wgrad(t, gz, dW, db, pad=1))
+                through_bn(e, L, name, gz, wgrad3x3)
             elif e['kind'] == 'td':
                 gpool = gstack(e['dst'])[:, :e['n']].contiguous()
                 gz = ops.maxpool2x2_bwd(gpool, s['td_pre'][e['ti']], s['td_pooled'][e['ti']])
@@ -472,7 +492,7 @@ class FCDenseNet(Trainable, Views):
                 gstack(e['skip_sid'])[:, :e['skip_n']].copy_(gd[:, keep:keep + e['skip_n']])
             else:
                 gz = gstack(0)[:, :e['cout']].contiguous()
-                ops.conv_wgrad(s['x'], gz, *gv[name], pad=1)
+                wgrad3x3(s['x'], gz, *gv[name])
         return gv
 
     def refresh(self):
@@ -744,7 +764,7 @@ def build_fcdensenet(input_var=None, layer=('pool4',), nb_in_channels=3, n_class
     `arr_%d` .npz (BN: beta, gamma, mean, inv_std; conv: W, b -- P10/P14).  trainable=True builds the module
     `train.DenseNetTrainer` trains (float32 on mma='f32', or float64).  net_kw: further
     keywords of `FCDenseNet` (a smaller net: n_layers_per_block, n_pool, growth -- and n_first for the plan of
-    a checkpoint; dropout)."""
+    a checkpoint; dropout; wgrad)."""
     n_first = net_kw.pop('n_first', None)
     if params is None:
         if not weight_path:

@@ -2222,19 +2222,26 @@ def conv_wgrad_desc(x_shape, Cout, pad, Cin_tot=None, ci0=0, layout='oihw'):
 
 
 WGRAD_MODES = DGRAD_MODES = KXK_MODES = FWD_MODES = MODES_16BIT
+WGRAD_CO_BLOCKS = (64, 16)      # output channels per workgroup of the weight-gradient kernels (16: mma='bf16' only)
 
 
-def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
+def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32', co_block=64):
     """dW[:, ci0:ci0 + Cin] (and db, unless None) of the zero-padded 3x3 layer out = conv(xpad, W) + b, written
     in place into the layer's own parameter layout, from its input x (B,Cin,H,W) and gz = dL/dout (ReLU mask
     applied) (B,Cout,H + 2 pad - 2,W + 2 pad - 2).  The other input channels of dW are not touched (the second
     source of a concat layer is a second call).  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU.
     mma='bf16' (float32 tensors only; csrc/conv_wgrad_bf16.hip): x and gz are rounded once to bf16 as they are
     staged and multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulators; db stays the sum of the unrounded
-    gz."""
+    gz.  co_block=16 (with mma='bf16' only; csrc/conv_wgrad_bf16_co16.hip): the same sums
+    in blocks of 16 output x 64 input channels on v_mfma_f32_16x16x32_bf16, the form for layers with few output
+    channels; the caller chooses, nothing here does."""
     dt = x.dtype
     if mma not in WGRAD_MODES:
         raise ValueError("conv_wgrad: mma=%r is not one of %s" % (mma, WGRAD_MODES))
+    if co_block not in WGRAD_CO_BLOCKS:
+        raise ValueError("conv_wgrad: co_block=%r is not one of %s" % (co_block, WGRAD_CO_BLOCKS))
+    if co_block == 16 and mma != 'bf16':
+        raise ValueError("conv_wgrad: co_block=16 is a form of mma='bf16' (got mma=%r)" % (mma,))
     if mma == 'bf16' and not (dt == gz.dtype == dW.dtype == torch.float32 and (db is None or db.dtype == dt)):
         raise ValueError("conv_wgrad: mma='bf16' takes float32 tensors only (x %s, gz %s, dW %s)"
                          % (x.dtype, gz.dtype, dW.dtype))
@@ -2246,7 +2253,11 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
     if tuple(gz.shape) != (B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
         raise RuntimeError('conv_wgrad: shapes x %s gz %s dW %s' % (tuple(x.shape), tuple(gz.shape), tuple(dW.shape)))
     d = conv_wgrad_desc(tuple(x.shape), Cout, pad, Cin_tot, ci0, layout)
-    if mma == 'bf16':                                    # a plan, and a profile name, of its own
+    if mma == 'bf16' and co_block == 16:                 # a plan, and a profile name, of its own
+        n = _count(_lib.load().iiseg_conv_wgrad_bf16_co16_workspace_elems(C.byref(d)),
+                   'iiseg_conv_wgrad_bf16_co16_workspace_elems')
+        kern, fn = 'conv_wgrad_bf16_co16_kernel', _lib.load().iiseg_conv_wgrad_bf16_co16
+    elif mma == 'bf16':
         n = _count(_lib.load().iiseg_conv_wgrad_bf16_workspace_elems(C.byref(d)),
                    'iiseg_conv_wgrad_bf16_workspace_elems')
         kern, fn = 'conv_wgrad_bf16_kernel', _lib.load().iiseg_conv_wgrad_bf16
@@ -2260,6 +2271,23 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32'):
     if CONV_PROFILE is not None:
         # byte model: x and g_z read once, the slabs written and read once
         _add_bytes(kern, float(dW.element_size()) * (x.numel() + gz.numel() + 2 * n))
+
+
+def conv_wgrad_db(gz, db, Cin, pad=1):
+    """db of ops.conv_wgrad(x, gz, dW, db, pad, mma='f32') alone -- the same bits, for any x of Cin channels (the
+    kernel's plan, hence the order of its sums, depends on Cin) -- from gz (B,Cout,OH,OW), float32.  What a caller
+    pairs with conv_wgrad(..., db=None, mma='bf16') to leave the bias gradient as the fp32 mode has it."""
+    _need_f32('conv_wgrad_db', (('gz', gz), ('db', db)), required=('gz', 'db'))
+    B, Cout, OH, OW = gz.shape
+    if db.numel() != Cout or not gz.is_contiguous() or not db.is_contiguous():
+        raise RuntimeError('conv_wgrad_db: gz %s db %s' % (tuple(gz.shape), tuple(db.shape)))
+    d = conv_wgrad_desc((B, int(Cin), OH - 2 * pad + 2, OW - 2 * pad + 2), Cout, pad)
+    n = _count(_lib.load().iiseg_conv_wgrad_db_workspace_elems(C.byref(d)), 'iiseg_conv_wgrad_db_workspace_elems')
+    ws = _workspace('f32', n, gz.device) if n else None
+    _launch('conv_wgrad_db_kernel', 0.0, _lib.load().iiseg_conv_wgrad_db_f32, C.byref(d), _ptr(gz, gz.dtype),
+            _ptr(ws, gz.dtype), _ptr(db, gz.dtype))
+    if CONV_PROFILE is not None:
+        _add_bytes('conv_wgrad_db_kernel', 4.0 * (gz.numel() + 2 * n))
 
 
 # ---- data gradients on the 16-bit matrix pipe (csrc/conv_dgrad_bf16.hip, conv_kxk_bf16.hip; DESIGN.md 16, 17) ----

@@ -5,8 +5,9 @@ trainable net shares (`Trainable`) and the 16-bit training switches of the train
 Plain torch: works on host tensors too, needs no library."""
 import torch
 
-# The 16-bit training switches (keyword and attribute of FCN8 / StandardDAE, option of the drivers): what each is
-# called in messages.  Every one takes MODES_16BIT.
+# The 16-bit training switches (keyword and attribute of the trainable modules -- FCN8 and StandardDAE have
+# several, FCDenseNet has 'wgrad' --, option of the drivers): what each is called in messages.  Every one takes
+# MODES_16BIT.
 SWITCHES_16BIT = {'wgrad': 'weight gradient', 'dgrad': 'data gradient', 'kxk': 'fc6 / fc7 gradients',
                   'fwd': 'training forward'}
 MODES_16BIT = ('f32', 'bf16')

@@ -2,6 +2,7 @@
 """One training step of FC-DenseNet103 (11 classes, default synthetic weights) on 224x224 crops: one JSON line.
 
     python scripts/bench_train_densenet.py [--batches 3 10] [--size 224x224] [--reps 5] [--dtypes float32 float64]
+                                           [--wgrad f32 f32 bf16] [--out profiles/NAME.json]
 
 Per (precision, batch): step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, L2 term,
 RMSprop, refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch
@@ -14,6 +15,15 @@ the launch profile -- bn_stats, bn_relu, the pool, the optimizer's plumbing -- a
     planes against 2 n, about 3 x if both stream;
   * for the Cout = growth weight gradients of the dense-block layers (conv_wgrad_kernel): their summed nominal
     2 Cin Cout 9 OH OW B over their summed ms as a fraction of `--peak_tflops` (157.3: the fp32 matrix-pipe peak).
+--wgrad: the weight-gradient modes to run (FCDenseNet's `wgrad`; bf16: float32 only), one result
+row each per batch in the same process; a mode may be named twice, which gives the spread of the measurement.  Every
+row lists its zero-padded 3x3 weight-gradient launches per layer (`wgrad3x3_layers`, from the profiled step) and per
+resolution (`wgrad3x3_by_resolution`).  A bf16 row also times, for the widest and the narrowest dense-block layer of
+each resolution and on the same operands (the step's own t = bn_relu(stack[:, :n]) and a g_z of the layer's shape),
+the new form (co_block=16 with db=None, plus ops.conv_wgrad_db: the module's two launches), the 64-block conv_wgrad_bf16_kernel twice and the fp32 kernel (`forms`): five back-to-back
+launches between two HIP events each, the fraction of `--peak_tflops_bf16` (2500) on the nominal work.  With both modes
+among the rows, `wgrad_compare` gives per batch the launches' sums and the layers whose bf16 launch took longer than
+both fp32 rows' launch of that layer.  --out: the JSON record also into that file.
 Reads nothing outside the repository.
 """
 import argparse
@@ -42,9 +52,53 @@ def timed(fn, n=5):
     return e0.elapsed_time(e1) / n
 
 
-def one(B, H, W, dt, reps, peak, stream, weight_decay):
+WGRAD_KERNELS = ('conv_wgrad_kernel', 'conv_wgrad_bf16_kernel', 'conv_wgrad_bf16_co16_kernel')
+
+
+def forms(net, B, dt, peak16):
+    """The weight gradient of the widest and the narrowest dense-block layer of each resolution in every form, on
+    the same operands."""
+    sv = net._tsaved
+    by_res = {}
+    for e in net._steps:
+        if e['kind'] == 'brc':
+            hw = tuple(sv['stacks'][e['sid']].buf.shape[2:])
+            lo, hi = by_res.get(hw, (e, e))
+            by_res[hw] = (e if e['n'] < lo['n'] else lo, e if e['n'] > hi['n'] else hi)
+    out = []
+    gen = torch.Generator(device='cuda').manual_seed(7)
+    for hw, pair in sorted(by_res.items(), reverse=True):
+        for which, e in zip(('narrowest', 'widest'), pair):
+            st, L, n, g = sv['stacks'][e['sid']], net.layers[e['li']], e['n'], net.growth
+            t = ops.bn_relu(st.buf, n, L['beta'], L['gamma'], st.mean, st.inv_std)
+            gz = torch.randn((B, g) + hw, generator=gen, device='cuda', dtype=dt)
+            gz = gz * (torch.rand(gz.shape, generator=gen, device='cuda') < 0.5)      # as behind a dropout mask
+            dW, db = torch.empty((g, n, 3, 3), dtype=dt, device='cuda'), torch.empty(g, dtype=dt, device='cuda')
+            run = lambda **kw: timed(lambda: ops.conv_wgrad(t, gz, dW, db, pad=1, **kw))
+            def module_form():                                    # what `backward` launches for the layer
+                ops.conv_wgrad(t, gz, dW, None, pad=1, mma='bf16', co_block=16)
+                ops.conv_wgrad_db(gz, db, n, pad=1)
+            co16 = timed(module_form)
+            b64 = [run(mma='bf16', co_block=64) for _ in range(2)]
+            f32 = run(mma='f32')
+            co16_again = timed(module_form)
+            alone = run(mma='bf16', co_block=16)                  # the kernel with its own db
+            flops = 2.0 * n * g * 9 * B * hw[0] * hw[1]
+            out.append({'resolution': '%dx%d' % hw, 'layer': which, 'li': e['li'], 'cin': n, 'cout': g,
+                        'co16_ms': round(co16, 5), 'co16_again_ms': round(co16_again, 5),
+                        'co16_kernel_own_db_ms': round(alone, 5),
+                        'bf16_64_ms': [round(v, 5) for v in b64], 'f32_ms': round(f32, 5),
+                        'co16_over_bf16_64': round(min(co16, co16_again) / min(b64), 4),
+                        'co16_over_f32': round(min(co16, co16_again) / f32, 4),
+                        'co16_fraction_of_peak': round(flops / (min(co16, co16_again) * 1e-3) / (peak16 * 1e12), 5),
+                        'bf16_64_fraction_of_peak': round(flops / (min(b64) * 1e-3) / (peak16 * 1e12), 5)})
+            del t, gz, dW, db
+    return out
+
+
+def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.0):
     params = S.make_densenet_params(layer_plan(), seed=2024)
-    net = FCDenseNet(params, 11, layer=[], dtype=dt, mma='f32', trainable=True)
+    net = FCDenseNet(params, 11, layer=[], dtype=dt, mma='f32', trainable=True, wgrad=wgrad)
     tr = DenseNetTrainer(net, 11, [11], learning_rate=1e-3, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
@@ -127,19 +181,72 @@ def one(B, H, W, dt, reps, peak, stream, weight_decay):
                    'widest_bn_relu_forward_ms': round(fwd, 4), 'widest_bwd_over_forward': round((tr_ + ta) / fwd, 3)})
     # the dense-block layers' weight gradients (Cout = growth): every conv_wgrad_kernel launch but the first conv's,
     # the last of the walk
-    wg = [(f, t) for k, f, t in back if k == 'conv_wgrad_kernel'][:-1]
+    # (a bf16 layer is two launches: its dW kernel and conv_wgrad_db_kernel, counted together)
+    wg_all, db_ms = [], 0.0
+    for k, f, t in back:
+        if k in WGRAD_KERNELS:
+            wg_all.append((k, f, t))
+        elif k == 'conv_wgrad_db_kernel':
+            wg_all[-1] = (wg_all[-1][0], wg_all[-1][1], wg_all[-1][2] + t)
+            db_ms += t
+    wg = [(f, t) for _, f, t in wg_all][:-1]
     n_brc = sum(1 for e in net._steps if e['kind'] == 'brc')
     if len(wg) != n_brc:
         raise RuntimeError('expected %d dense-block weight gradients, got %d' % (n_brc, len(wg)))
     wg_ms, wg_flops = sum(t for _, t in wg), sum(f for f, _ in wg)
-    return {'dtype': str(dt).replace('torch.', ''), 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+    # every zero-padded 3x3 layer's launch, in backward's order, and their sums per resolution
+    layers3 = [e for e in reversed(net._steps) if e['kind'] in ('brc', 'first')]
+    per_layer, wres = [], {}
+    for e, (k, f, t) in zip(layers3, wg_all):
+        hw = tuple(sv['stacks'][e['sid']].buf.shape[2:])
+        per_layer.append({'li': e['li'], 'kind': e['kind'], 'resolution': '%dx%d' % hw,
+                          'cin': e['n'] if e['kind'] == 'brc' else int(X.shape[1]), 'kernel': k, 'ms': round(t, 5)})
+        r = wres.setdefault(hw, dict(launches=0, ms=0.0, flops=0.0))
+        r['launches'] += 1
+        r['ms'] += t
+        r['flops'] += f
+    wgrad_by_res = [{'resolution': '%dx%d' % hw, 'launches': r['launches'], 'ms': round(r['ms'], 4),
+                     'fraction_of_peak': round(r['flops'] / (r['ms'] * 1e-3) /
+                                               ((peak16 if wgrad == 'bf16' else peak) * 1e12), 5)}
+                    for hw, r in sorted(wres.items(), reverse=True)]
+    extra = {'forms': forms(net, B, dt, peak16)} if wgrad == 'bf16' else {}
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
             'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 2),
             'parameters': int(net.flat.numel()), 'weights': 'default synthetic (synthetic.make_densenet_params)',
             'max_memory_allocated_mb': round(peak_mem / 2.0 ** 20, 1), 'profiled_launches': len(rows),
             'profiled_launch_ms': round(all_ms, 3), 'kernels': kernels, 'bn_backward': bn,
             'bn_backward_ms_total': round(sum(red) + sum(app), 3),
             'wgrad_cout16_ms_total': round(wg_ms, 3),
-            'wgrad_cout16_fraction_of_peak': round(wg_flops / (wg_ms * 1e-3) / (peak * 1e12), 4)}
+            'wgrad_cout16_fraction_of_peak': round(wg_flops / (wg_ms * 1e-3) / (peak * 1e12), 4),
+            'wgrad3x3_ms_total': round(sum(t for _, _, t in wg_all), 3), 'wgrad3x3_db_launches_ms': round(db_ms, 3), 'wgrad3x3_by_resolution': wgrad_by_res,
+            'wgrad3x3_layers': per_layer, **extra}
+
+
+def compare(rows):
+    """Per batch with f32 and bf16 rows (float32): the 3x3 weight-gradient launches together and layer by layer."""
+    out = []
+    for B in sorted({r['batch'] for r in rows}):
+        f32 = [r for r in rows if r['batch'] == B and r['dtype'] == 'float32' and r['wgrad'] == 'f32']
+        b16 = [r for r in rows if r['batch'] == B and r['wgrad'] == 'bf16']
+        if not f32 or not b16:
+            continue
+        tot = [r['wgrad3x3_ms_total'] for r in f32]
+        slower = []
+        for i, lb in enumerate(b16[0]['wgrad3x3_layers']):
+            ref = [r['wgrad3x3_layers'][i]['ms'] for r in f32]
+            if lb['ms'] > max(ref):
+                slower.append({'li': lb['li'], 'resolution': lb['resolution'], 'cin': lb['cin'], 'bf16_ms': lb['ms'],
+                               'f32_ms': ref})
+        by_res = []
+        for j, rb in enumerate(b16[0]['wgrad3x3_by_resolution']):
+            by_res.append({'resolution': rb['resolution'], 'launches': rb['launches'], 'bf16_ms': rb['ms'],
+                           'f32_ms': [r['wgrad3x3_by_resolution'][j]['ms'] for r in f32]})
+        out.append({'batch': B, 'f32_wgrad3x3_ms': tot, 'f32_spread_ms': round(max(tot) - min(tot), 3),
+                    'bf16_wgrad3x3_ms': b16[0]['wgrad3x3_ms_total'],
+                    'gain_ms': round(min(tot) - b16[0]['wgrad3x3_ms_total'], 3),
+                    'f32_step_ms': [r['step_ms'] for r in f32], 'bf16_step_ms': b16[0]['step_ms'],
+                    'by_resolution': by_res, 'layers_slower_than_both_f32_launches': slower})
+    return out
 
 
 def main():
@@ -151,15 +258,26 @@ def main():
     ap.add_argument('--peak_tflops', type=float, default=157.3)
     ap.add_argument('--stream_gbs', type=float, default=6600.0)
     ap.add_argument('--weight_decay', type=float, default=1e-4)
+    ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split('x'))
     rows = []
     for name in a.dtypes:
-        for B in a.batches:
-            rows.append(one(B, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.weight_decay))
-            torch.cuda.empty_cache()
-    print(json.dumps({'bench': 'train_densenet', 'device': torch.cuda.get_device_name(0),
-                      'peak_tflops': a.peak_tflops, 'stream_gbs': a.stream_gbs, 'reps': a.reps, 'results': rows}))
+        for mode in (a.wgrad if name == 'float32' else ['f32']):        # (bf16 operands: float32 only)
+            for B in a.batches:
+                rows.append(one(B, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.weight_decay,
+                                mode, a.peak_tflops_bf16))
+                torch.cuda.empty_cache()
+    record = json.dumps({'bench': 'train_densenet', 'device': torch.cuda.get_device_name(0),
+                         'peak_tflops': a.peak_tflops, 'peak_tflops_bf16': a.peak_tflops_bf16,
+                         'stream_gbs': a.stream_gbs, 'reps': a.reps, 'wgrad': a.wgrad, 'results': rows,
+                         'wgrad_compare': compare(rows)})
+    print(record)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(record + '\n')
 
 
 if __name__ == '__main__':

@@ -14,6 +14,9 @@ per convolution), `errors_best.npz` / `errors_last.npz`, `output.log`, `config.t
 <weights_path>/<dataset>/FC-DenseNet103_weights.npz, the best checkpoint is what the other entry points load.
 Initial weights without `--resume`: HeUniform W, zero b, gamma 1, beta 0 (upstream's), seeded and drawn on the host.
 `--layers_per_block / --growth / --n_first` shrink the net (tests); such a checkpoint records its architecture.
+`--wgrad bf16` (float32 only) forms the weight gradients of the zero-padded 3x3 layers on the
+16-bit matrix pipe, in blocks of 16 output channels for the dense-block layers; everything else stays float32, and
+the experiment folder and the checkpoint names do not change (config.txt records the mode).
 Data augmentation is not built.  What is refused exits with status 2 and the reason on stderr before any GPU work.
 All arithmetic runs in the HIP kernels of libiiseg_hip.so.
 """
@@ -41,8 +44,10 @@ def _json(s):
 
 def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2,
                     batch_size=(3, 1, 1), num_epochs=1, max_patience=1, learning_rate=1e-3, lr_decay=0.995,
-                    weight_decay=1e-4, layers_per_block=LAYERS_PER_BLOCK, growth=16, n_first=48, image_size=None):
+                    weight_decay=1e-4, layers_per_block=LAYERS_PER_BLOCK, growth=16, n_first=48, image_size=None,
+                    wgrad='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
+    from iterative_inference_segm_amd.train import check_wgrad
     if savepath is None:
         raise ValueError('A saving directory must be specified')
     if dataset not in ('camvid', 'polyps912', 'em'):
@@ -52,6 +57,7 @@ def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rm
     if dtype not in ('float32', 'float64') or (dtype == 'float32' and mma != 'f32'):
         raise NotImplementedError("training FC-DenseNet: float32 (mma 'f32') or float64; the 16-bit legs (dtype %s, "
                                   'mma %r) are not trained' % (dtype, mma))
+    check_wgrad(wgrad, dtype)
     if optimizer not in OPTIMIZERS:
         raise ValueError('Unknown optimizer')
     if not 0.0 <= float(dropout) < 1.0:
@@ -98,13 +104,14 @@ def one_hot_void_last(L, n_classes):
 def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_epochs=750, max_patience=150,
           savepath=None, loadpath=None, batch_size=None, resume=False, synthetic=False, n_images=20, image_size=None,
           seed=0, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2, layers_per_block=LAYERS_PER_BLOCK,
-          growth=16, n_first=48, max_batches=None, verbose=True):
-    """Returns the per-epoch lists and the experiment folder."""
+          growth=16, n_first=48, max_batches=None, verbose=True, wgrad='f32'):
+    """Returns the per-epoch lists and the experiment folder.  wgrad ('f32' | 'bf16'): the operand precision of the
+    zero-padded 3x3 weight gradients (FCDenseNet's keyword)."""
     bs = list(batch_size) if batch_size is not None else [3, 1, 1]
     lpb = [int(v) for v in layers_per_block]
     size = tuple(image_size) if image_size is not None else (224, 224)
     check_supported(dataset, savepath, dtype, mma, optimizer, dropout, bs, num_epochs, max_patience, learning_rate,
-                    lr_decay, weight_decay, lpb, growth, n_first, size)
+                    lr_decay, weight_decay, lpb, growth, n_first, size, wgrad)
     loadpath = loadpath if loadpath is not None else savepath
     savepath = os.path.join(savepath, dataset, EXP_NAME)
     loadpath = os.path.join(loadpath, dataset, EXP_NAME)
@@ -116,7 +123,7 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
                                       weight_decay=weight_decay, num_epochs=num_epochs, max_patience=max_patience,
                                       batch_size=bs, resume=resume, seed=seed, dtype=dtype, optimizer=optimizer,
                                       dropout=dropout, layers_per_block=lpb, growth=growth, n_first=n_first,
-                                      image_size=list(size)).items()):
+                                      image_size=list(size), wgrad=wgrad).items()):
             f.write('{} = {}\n'.format(key, value))
 
     # ---- from here on: the GPU ----
@@ -143,7 +150,7 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
     else:
         params = he_params(plan, 4321 + int(seed))
     net = FCDenseNet(params, n_classes, layer=[], n_layers_per_block=lpb, n_pool=n_pool, growth=growth, dtype=tdt,
-                     mma='f32', trainable=True, dropout=dropout)
+                     mma='f32', trainable=True, dropout=dropout, wgrad=wgrad)
     trainer = DenseNetTrainer(net, n_classes, void_labels, optimizer=optimizer, learning_rate=learning_rate,
                               weight_decay=weight_decay, seed=seed)
 
@@ -238,6 +245,8 @@ def make_parser():
     parser.add_argument('--max_patience', type=int, default=150)
     parser.add_argument('--dtype', default='float32', help='float32 | float64')
     parser.add_argument('--mma', default='f32', help="float32: only 'f32' is trained")
+    parser.add_argument('--wgrad', choices=['f32', 'bf16'], default='f32',
+                        help='operand precision of the 3x3 weight gradients (bf16: float32 runs only)')
     parser.add_argument('--optimizer', default='rmsprop', help='rmsprop | adam')
     parser.add_argument('--dropout', type=float, default=0.2)
     parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
@@ -261,7 +270,8 @@ def main(argv=None):
     try:
         check_supported(args.dataset, args.savepath, args.dtype, args.mma, args.optimizer, args.dropout,
                         args.batch_size, args.num_epochs, args.max_patience, args.learning_rate, args.lr_decay,
-                        args.weight_decay, args.layers_per_block, args.growth, args.n_first, args.image_size)
+                        args.weight_decay, args.layers_per_block, args.growth, args.n_first, args.image_size,
+                        args.wgrad)
     except (NotImplementedError, ValueError, TypeError) as e:
         print('train_fcdensenet.py: ' + str(e), file=sys.stderr)
         return 2
@@ -270,7 +280,7 @@ def main(argv=None):
           synthetic=args.synthetic, n_images=args.n_images, image_size=args.image_size, seed=args.seed,
           dtype=args.dtype, mma=args.mma, optimizer=args.optimizer, dropout=args.dropout,
           layers_per_block=args.layers_per_block, growth=args.growth, n_first=args.n_first,
-          max_batches=args.max_batches)
+          max_batches=args.max_batches, wgrad=args.wgrad)
     return 0
 
 
