@@ -1180,6 +1180,28 @@ int iiseg_deconv_wgrad_f32(void* stream, const iiseg_deconv_desc* d, const float
 int iiseg_deconv_wgrad_f64(void* stream, const iiseg_deconv_desc* d, const double* x, const double* g, double* ws,
                            double* dW, double* db);
 
+/* The same gradients of a K = 3, stride-2 layer with the products on the 16-bit matrix pipe (csrc/deconv_grad_bf16.hip;
+ * DESIGN.md section 23), float32 only: x, g and W (the layer's own fp32 parameter) are rounded once to bf16, nearest
+ * even, as they are staged; v_mfma_f32_16x16x32_bf16, fp32 accumulation in an order the descriptor fixes, no atomics.
+ *   wgrad : dW and db (or NULL; the sum of the unrounded g in this kernel's own order -- not the bits of
+ *           iiseg_deconv_wgrad_f32's); ws = iiseg_deconv_wgrad_bf16_workspace_elems(d) floats: 0 with one slab (the
+ *           kernel writes dW and db themselves, ws may be NULL), else slabs * (Cin Cout 9 + Cout), added in slab
+ *           order by a second launch.
+ *   dgrad : gx; the reduction over Cout is not split: its workspace is 0 elements and ws is ignored.
+ * NULL d or a required pointer IISEG_ERR_NULL; sizes as iiseg_deconv_wgrad_f32 (H W <= 2^28) IISEG_ERR_SHAPE; K != 3 or
+ * stride != 2, or an output overlapping an input, IISEG_ERR_UNSUPPORTED.  All before any launch. */
+/* host only: IISEG_OK or the status a launch of `d` would return */
+int iiseg_deconv_grad_bf16_check(const iiseg_deconv_desc* d);
+/* host only: number of slabs (>= 1), or a negative status */
+int iiseg_deconv_wgrad_bf16_slabs(const iiseg_deconv_desc* d);
+/* host only: elements of `ws`, or a negative status */
+int64_t iiseg_deconv_wgrad_bf16_workspace_elems(const iiseg_deconv_desc* d);
+int64_t iiseg_deconv_dgrad_bf16_workspace_elems(const iiseg_deconv_desc* d);
+int iiseg_deconv_wgrad_bf16(void* stream, const iiseg_deconv_desc* d, const float* x, const float* g, float* ws,
+                            float* dW, float* db);
+int iiseg_deconv_dgrad_bf16(void* stream, const iiseg_deconv_desc* d, const float* g, const float* w, float* ws,
+                            float* gx);
+
 int iiseg_relu_gate_f32(void* stream, const float* g, const float* out, float* dst, int64_t n);
 int iiseg_relu_gate_f64(void* stream, const double* g, const double* out, double* dst, int64_t n);
 /* host only: doubles of `partial`, or a negative status */

@@ -311,6 +311,13 @@ SIGNATURES = {
     'iiseg_deconv_wgrad_partials': (C.c_int, [C.POINTER(DeconvDesc)]),
     'iiseg_deconv_wgrad_f32': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 5),
     'iiseg_deconv_wgrad_f64': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 5),
+    # ... of the K = 3 stride-2 layers on the 16-bit matrix pipe (deconv='bf16')
+    'iiseg_deconv_grad_bf16_check': (C.c_int, [C.POINTER(DeconvDesc)]),
+    'iiseg_deconv_wgrad_bf16_slabs': (C.c_int, [C.POINTER(DeconvDesc)]),
+    'iiseg_deconv_wgrad_bf16_workspace_elems': (_i64, [C.POINTER(DeconvDesc)]),
+    'iiseg_deconv_dgrad_bf16_workspace_elems': (_i64, [C.POINTER(DeconvDesc)]),
+    'iiseg_deconv_wgrad_bf16': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 5),
+    'iiseg_deconv_dgrad_bf16': (C.c_int, [_vp, C.POINTER(DeconvDesc)] + [_vp] * 4),
     'iiseg_relu_gate_f32': (C.c_int, [_vp] * 4 + [_i64]),
     'iiseg_relu_gate_f64': (C.c_int, [_vp] * 4 + [_i64]),
     'iiseg_l2_term_partials': (C.c_int, [_i32]),

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB = os.path.join(HERE, 'libiiseg_hip.so')
-SOURCES = ['abi.hip', 'conv_igemm.hip', 'conv_taps.hip', 'conv_wino.hip', 'conv_wino_bf16.hip', 'conv_halo.hip', 'conv_small.hip', 'conv_halo_bf16.hip', 'conv_c8_bf16.hip', 'conv_c8_m16.hip', 'conv_c8_dil.hip', 'conv1x1_c8.hip', 'conv_f64.hip', 'conv_halo_f64.hip', 'conv_wino_f64.hip', 'pool_unpool.hip', 'deconv.hip', 'deconv_phase.hip', 'tail.hip', 'metrics.hip', 'bn.hip', 'crf.hip', 'ctx_train.hip', 'ctx_grad.hip', 'conv_wgrad.hip', 'c8_grad.hip', 'conv_wgrad_kxk.hip', 'deconv_grad.hip', 'fcn8_train.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_bf16_co16.hip', 'conv_dgrad_bf16.hip', 'conv_kxk_bf16.hip', 'bn_grad.hip']
+SOURCES = ['abi.hip', 'conv_igemm.hip', 'conv_taps.hip', 'conv_wino.hip', 'conv_wino_bf16.hip', 'conv_halo.hip', 'conv_small.hip', 'conv_halo_bf16.hip', 'conv_c8_bf16.hip', 'conv_c8_m16.hip', 'conv_c8_dil.hip', 'conv1x1_c8.hip', 'conv_f64.hip', 'conv_halo_f64.hip', 'conv_wino_f64.hip', 'pool_unpool.hip', 'deconv.hip', 'deconv_phase.hip', 'tail.hip', 'metrics.hip', 'bn.hip', 'crf.hip', 'ctx_train.hip', 'ctx_grad.hip', 'conv_wgrad.hip', 'c8_grad.hip', 'conv_wgrad_kxk.hip', 'deconv_grad.hip', 'deconv_grad_bf16.hip', 'fcn8_train.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_bf16_co16.hip', 'conv_dgrad_bf16.hip', 'conv_kxk_bf16.hip', 'bn_grad.hip']
 ARCH = 'gfx950'
 
 
@@ -100,8 +100,8 @@ LAST = {}      # what the latest build() did: {'compiled': [...], 'reused': [...
 def build(force=False, verbose=False):
     """Compile every HIP source for gfx950 and link libiiseg_hip.so.  Returns the path.  An object
     is reused (unless `force`) only when the content key stored next to it -- source + headers +
-    flags + hipcc version -- matches; the library only when its key over the objects' keys does.
-    `LAST` says what happened."""
+    flags + hipcc version -- matches; the library only when its key over the objects' keys does,
+    and then nothing is compiled even where the objects are gone.  `LAST` says what happened."""
     hipcc = _hipcc()
     LAST.clear()
     LAST.update(compiled=[], reused=[], linked=False)
@@ -118,13 +118,23 @@ def build(force=False, verbose=False):
     root = os.path.dirname(HERE)
     key_flags = [f.replace(root, '.') for f in flags]
 
+    # (the keys name the include directories relative to the tree: the same tree under another
+    # root -- the GPU box's scratch copy -- reuses its products)
+    for src in SOURCES:
+        keys[src] = _digest([os.path.join(CSRC, src)] + headers,
+                            extra=key_flags + EXTRA_FLAGS.get(src, []) + [version])
+    lib_key = hashlib.sha256('\n'.join(keys[s] for s in SOURCES).encode()).hexdigest()
+    if not force and not _stale(LIB, lib_key):
+        # the library itself is current (its key is over the sources' keys): a tree that travelled
+        # without its objects compiles nothing
+        LAST['reused'] = list(SOURCES)
+        return LIB
+
     def compile_one(src):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace('.hip', '.o'))
-        # (the key names the include directories relative to the tree: the same tree under another
-        # root -- the GPU box's scratch copy -- reuses its objects)
         extra = EXTRA_FLAGS.get(src, [])
-        key = keys[src] = _digest([s] + headers, extra=key_flags + extra + [version])
+        key = keys[src]
         if force or _stale(o, key):
             cmd = [hipcc] + flags + extra + ['-c', s, '-o', o]
             if verbose:
@@ -140,7 +150,6 @@ def build(force=False, verbose=False):
 
     with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
-    lib_key = hashlib.sha256('\n'.join(keys[s] for s in SOURCES).encode()).hexdigest()
     if force or LAST['compiled'] or _stale(LIB, lib_key):
         cmd = [hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)

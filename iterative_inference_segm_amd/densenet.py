@@ -214,7 +214,7 @@ class FCDenseNet(Trainable, Views):
 
     def __init__(self, params, n_classes=11, layer=('pool4',), n_layers_per_block=LAYERS_PER_BLOCK,
                  n_pool=N_POOL, growth=GROWTH, device='cuda', dtype=torch.float32, mma=None, trainable=False,
-                 dropout=0.2, wgrad='f32'):
+                 dropout=0.2, wgrad='f32', deconv='f32'):
         """mma: 'f32' (default) | 'bf16' (bf16 MFMA operands, fp32 NCHW activations) | 'bf16c8'
         (configs[2] as BASELINE names it: the dense-block stacks as bf16 C8 tensors, every
         BN_ReLU_Conv of a dense block one launch of the 16-row C8 kernel with BatchNorm + ReLU applied
@@ -230,9 +230,14 @@ class FCDenseNet(Trainable, Views):
         convolution's ('f32' default; 'bf16' = operands rounded once to bf16 as they are staged, fp32 accumulation,
         trainable float32 only: ops.conv_wgrad(mma='bf16') in the form `wgrad_co_block` names, their db by
         ops.conv_wgrad_db with the bits of the 'f32' mode; everything else of `backward`, the forward and the
-        parameters stay float32 and the same code: DESIGN.md section 22)."""
+        parameters stay float32 and the same code: DESIGN.md section 22).
+        deconv: operand precision of `backward`'s TransitionUp gradients, the 'tu' layers' dW, db and g_x ('f32'
+        default; 'bf16' = ops.deconv_wgrad / ops.deconv_dgrad with mma='bf16', trainable float32 only: x, g and the
+        layer's own fp32 parameter rounded once to bf16 as they are staged, fp32 accumulation, db the sum of the
+        unrounded g in that kernel's own order; nothing else changes: DESIGN.md section 23)."""
         mma = mma or ops.DEFAULT_MMA
         self.wgrad = check_mode('wgrad', wgrad, dtype, trainable)
+        self.deconv = check_mode('deconv', deconv, dtype, trainable)
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
         self._tsaved = None
@@ -485,8 +490,8 @@ class FCDenseNet(Trainable, Views):
                 gd = gstack(e['dst'])
                 g = gd[:, :keep].contiguous()
                 blk = stack.buf[:, e['block0']:e['n']].contiguous()
-                ops.deconv_wgrad(blk, g, *gv[name], stride=2, window=win)
-                gx = ops.deconv_dgrad(g, L['conv'].W, 2, tuple(stack.buf.shape[2:]), window=win)
+                ops.deconv_wgrad(blk, g, *gv[name], stride=2, window=win, mma=self.deconv)
+                gx = ops.deconv_dgrad(g, L['conv'].W, 2, tuple(stack.buf.shape[2:]), window=win, mma=self.deconv)
                 # (both targets are still zero: the first share of each)
                 gstack(e['sid'])[:, e['block0']:e['n']].copy_(gx)
                 gstack(e['skip_sid'])[:, :e['skip_n']].copy_(gd[:, keep:keep + e['skip_n']])
@@ -764,7 +769,7 @@ def build_fcdensenet(input_var=None, layer=('pool4',), nb_in_channels=3, n_class
     `arr_%d` .npz (BN: beta, gamma, mean, inv_std; conv: W, b -- P10/P14).  trainable=True builds the module
     `train.DenseNetTrainer` trains (float32 on mma='f32', or float64).  net_kw: further
     keywords of `FCDenseNet` (a smaller net: n_layers_per_block, n_pool, growth -- and n_first for the plan of
-    a checkpoint; dropout; wgrad)."""
+    a checkpoint; dropout; wgrad; deconv)."""
     n_first = net_kw.pop('n_first', None)
     if params is None:
         if not weight_path:

@@ -2653,15 +2653,65 @@ def deconv_desc(x_shape, Cout, K, stride, window=None):
     return d
 
 
-def deconv_dgrad(g, W, stride, x_hw, window=None):
+DECONV_MODES = MODES_16BIT
+
+
+def _deconv_bf16_kind(what, K, stride, mma):
+    """The 16-bit transposed-convolution gradients are the K = 3, stride-2 layer's (refused before the library)."""
+    if int(K) != 3 or int(stride) != 2:
+        raise ValueError("%s: mma=%r is the K = 3, stride-2 layer's (got K = %d, stride %d)" % (what, mma, K, stride))
+
+
+def _deconv_bf16_tensors(what, named, mma):
+    """... and take contiguous device tensors (the last check before the library is touched)."""
+    for name, t in named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError("%s: mma=%r takes contiguous tensors (%s)" % (what, mma, name))
+        if t is not None and not t.is_cuda:
+            raise ValueError("%s: mma=%r takes device tensors (%s is on %s)" % (what, mma, name, t.device))
+
+
+def _deconv3_products(d):
+    """The products x . gf of a K = 3 stride-2 layer whose gf element lies in the window, per channel pair."""
+    rows = sum(1 for i in range(d.H) for a in range(3) if d.oy0 <= 2 * i + a < d.oy0 + d.OH)
+    cols = sum(1 for j in range(d.W) for c in range(3) if d.ox0 <= 2 * j + c < d.ox0 + d.OW)
+    return float(d.B) * rows * cols
+
+
+def deconv_dgrad(g, W, stride, x_hw, window=None, mma='f32'):
     """g_x (B,Cin,H,W) of the transposed convolution ops.Deconv(W[in,out,k,k], stride) on an input of x_hw = (H,
-    W), from g = dL/d(`window` of its full output) (B,Cout,OH,OW); outside the window the gradient is zero."""
-    dt = g.dtype
+    W), from g = dL/d(`window` of its full output) (B,Cout,OH,OW); outside the window the gradient is zero.
+    mma='bf16' (float32 device tensors, K = 3 and stride 2 only; csrc/deconv_grad_bf16.hip):
+    g and W -- the layer's own fp32 parameter -- are rounded once to bf16 as they are staged and multiplied by
+    v_mfma_f32_16x16x32_bf16 with fp32 accumulators in a fixed order."""
+    if mma not in DECONV_MODES:
+        raise ValueError("deconv_dgrad: mma=%r is not one of %s" % (mma, DECONV_MODES))
+    dt = g.dtype if torch.is_tensor(g) else None
+    if mma == 'bf16':
+        _need_f32('deconv_dgrad', (('g', g), ('W', W)), required=('g', 'W'))
+        if g.dim() != 4 or W.dim() != 4 or W.shape[2] != W.shape[3] or g.shape[1] != W.shape[1]:
+            raise ValueError('deconv_dgrad: g %s W %s' % (tuple(g.shape), tuple(W.shape)))
+        _deconv_bf16_kind('deconv_dgrad', W.shape[2], stride, mma)
     Cin, Cout, K = int(W.shape[0]), int(W.shape[1]), int(W.shape[2])
     d = deconv_desc((g.shape[0], Cin, x_hw[0], x_hw[1]), Cout, K, stride, window)
     if tuple(g.shape) != (d.B, Cout, d.OH, d.OW) or W.shape[2] != W.shape[3]:
+        if mma == 'bf16':
+            raise ValueError('deconv_dgrad: g %s W %s window %s' % (tuple(g.shape), tuple(W.shape), window))
         raise RuntimeError('deconv_dgrad: g %s W %s window %s' % (tuple(g.shape), tuple(W.shape), window))
+    if mma == 'bf16':
+        _deconv_bf16_tensors('deconv_dgrad', (('g', g), ('W', W)), mma)
     gx = torch.empty((d.B, Cin, d.H, d.W), dtype=dt, device=g.device)
+    if mma == 'bf16':
+        lib = _lib.load()
+        n = _count(lib.iiseg_deconv_dgrad_bf16_workspace_elems(C.byref(d)), 'iiseg_deconv_dgrad_bf16_workspace_elems')
+        ws = _workspace('f32', n, g.device) if n else None
+        kern = 'deconv_dgrad_bf16_kernel'
+        _launch(kern, 2.0 * Cin * Cout * _deconv3_products(d), lib.iiseg_deconv_dgrad_bf16, C.byref(d), _ptr(g),
+                _ptr(W), _ptr(ws), _ptr(gx))
+        if CONV_PROFILE is not None:
+            # byte model: g and the parameter read once, the slabs written and read once, gx written once
+            _add_bytes(kern, 4.0 * (g.numel() + W.numel() + 2 * n + gx.numel()))
+        return gx
     kern = 'deconv_dgrad_kernel'
     _launch(kern, 2.0 * Cin * Cout * (K // int(stride)) ** 2 * g.shape[0] * d.OH * d.OW, _fn('deconv_dgrad', dt),
             C.byref(d), _ptr(g, dt), _ptr(W, dt), _ptr(gx, dt))
@@ -2670,16 +2720,41 @@ def deconv_dgrad(g, W, stride, x_hw, window=None):
     return gx
 
 
-def deconv_wgrad(x, g, dW, db, stride, window=None):
+def deconv_wgrad(x, g, dW, db, stride, window=None, mma='f32'):
     """dW (Cin,Cout,K,K) and db (Cout, or None) of the transposed convolution on x (B,Cin,H,W), written in place,
-    from g = dL/d(`window` of its full output)."""
-    dt = x.dtype
+    from g = dL/d(`window` of its full output).
+    mma='bf16' (float32 device tensors, K = 3 and stride 2 only; csrc/deconv_grad_bf16.hip):
+    x and g are rounded once to bf16 as they are staged, v_mfma_f32_16x16x32_bf16, fp32 accumulation, slabs added in
+    slab order; db is that kernel's own deterministic sum of the unrounded g -- not the bits of the 'f32' mode."""
+    if mma not in DECONV_MODES:
+        raise ValueError("deconv_wgrad: mma=%r is not one of %s" % (mma, DECONV_MODES))
+    dt = x.dtype if torch.is_tensor(x) else None
+    if mma == 'bf16':
+        named = (('x', x), ('g', g), ('dW', dW), ('db', db))
+        _need_f32('deconv_wgrad', named, required=('x', 'g', 'dW'))
+        if x.dim() != 4 or g.dim() != 4 or dW.dim() != 4 or dW.shape[2] != dW.shape[3]:
+            raise ValueError('deconv_wgrad: x %s g %s dW %s' % (tuple(x.shape), tuple(g.shape), tuple(dW.shape)))
+        _deconv_bf16_kind('deconv_wgrad', dW.shape[2], stride, mma)
     Cin, Cout, K = int(dW.shape[0]), int(dW.shape[1]), int(dW.shape[2])
     d = deconv_desc(tuple(x.shape), Cout, K, stride, window)
     if x.shape[1] != Cin or tuple(g.shape) != (d.B, Cout, d.OH, d.OW) or dW.shape[2] != dW.shape[3] or \
             (db is not None and db.numel() != Cout):
-        raise RuntimeError('deconv_wgrad: x %s g %s dW %s window %s' % (tuple(x.shape), tuple(g.shape),
-                                                                       tuple(dW.shape), window))
+        what = 'deconv_wgrad: x %s g %s dW %s window %s' % (tuple(x.shape), tuple(g.shape), tuple(dW.shape), window)
+        if mma == 'bf16':
+            raise ValueError(what)
+        raise RuntimeError(what)
+    if mma == 'bf16':
+        _deconv_bf16_tensors('deconv_wgrad', named, mma)
+        lib = _lib.load()
+        n = _count(lib.iiseg_deconv_wgrad_bf16_workspace_elems(C.byref(d)), 'iiseg_deconv_wgrad_bf16_workspace_elems')
+        ws = _workspace('f32', n, x.device) if n else None
+        kern = 'deconv_wgrad_bf16_kernel'
+        _launch(kern, 2.0 * Cin * Cout * _deconv3_products(d), lib.iiseg_deconv_wgrad_bf16, C.byref(d), _ptr(x),
+                _ptr(g), _ptr(ws), _ptr(dW), _ptr(db))
+        if CONV_PROFILE is not None:
+            # byte model: x and g read once, the slabs written and read once
+            _add_bytes(kern, 4.0 * (x.numel() + g.numel() + 2 * n))
+        return
     nslab = _count(_lib.load().iiseg_deconv_wgrad_partials(C.byref(d)), 'iiseg_deconv_wgrad_partials')
     ws = _workspace(_SUFFIX[dt], nslab * (dW.numel() + Cout), x.device)
     kern = 'deconv_wgrad_kernel'

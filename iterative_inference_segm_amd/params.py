@@ -6,10 +6,10 @@ Plain torch: works on host tensors too, needs no library."""
 import torch
 
 # The 16-bit training switches (keyword and attribute of the trainable modules -- FCN8 and StandardDAE have
-# several, FCDenseNet has 'wgrad' --, option of the drivers): what each is called in messages.  Every one takes
-# MODES_16BIT.
+# several, FCDenseNet has 'wgrad' and 'deconv' --, option of the drivers): what each is called in messages.  Every
+# one takes MODES_16BIT.
 SWITCHES_16BIT = {'wgrad': 'weight gradient', 'dgrad': 'data gradient', 'kxk': 'fc6 / fc7 gradients',
-                  'fwd': 'training forward'}
+                  'fwd': 'training forward', 'deconv': 'transposed-convolution gradients'}
 MODES_16BIT = ('f32', 'bf16')
 
 

@@ -27,6 +27,7 @@ check_wgrad = functools.partial(check_mode, 'wgrad')      # the weight gradients
 check_dgrad = functools.partial(check_mode, 'dgrad')      # the data gradients
 check_kxk = functools.partial(check_mode, 'kxk')          # FCN-8's fc6 / fc7 gradients
 check_fwd = functools.partial(check_mode, 'fwd')          # the training forward, FCN-8's or the standard DAE's
+check_deconv = functools.partial(check_mode, 'deconv')    # FC-DenseNet's TransitionUp gradients
 
 
 def check_supported(kind='contextmod',training_loss=('crossentropy',), ae_h=False, full_im_ft=False,

@@ -2,7 +2,7 @@
 """One training step of FC-DenseNet103 (11 classes, default synthetic weights) on 224x224 crops: one JSON line.
 
     python scripts/bench_train_densenet.py [--batches 3 10] [--size 224x224] [--reps 5] [--dtypes float32 float64]
-                                           [--wgrad f32 f32 bf16] [--out profiles/NAME.json]
+                                           [--wgrad f32 f32 bf16] [--deconv f32 f32 bf16] [--out profiles/NAME.json]
 
 Per (precision, batch): step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, L2 term,
 RMSprop, refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch
@@ -23,10 +23,19 @@ each resolution and on the same operands (the step's own t = bn_relu(stack[:, :n
 the new form (co_block=16 with db=None, plus ops.conv_wgrad_db: the module's two launches), the 64-block conv_wgrad_bf16_kernel twice and the fp32 kernel (`forms`): five back-to-back
 launches between two HIP events each, the fraction of `--peak_tflops_bf16` (2500) on the nominal work.  With both modes
 among the rows, `wgrad_compare` gives per batch the launches' sums and the layers whose bf16 launch took longer than
-both fp32 rows' launch of that layer.  --out: the JSON record also into that file.
+both fp32 rows' launch of that layer.
+--deconv: the modes of the TransitionUp gradients to run (FCDenseNet's `deconv`; bf16: float32 only; DESIGN.md section
+23), one result row per (wgrad mode, deconv mode, batch) in the same process; named more than once it is the study of
+this switch and the `forms` of a bf16 weight-gradient row are left out.  Every row lists, per TransitionUp layer in
+backward's order, its two launches (`deconv_layers`: weight gradient and data gradient from the profiled step, each
+next to its byte model over `--stream_gbs` and its nominal 2 Cin Cout (products inside the window) over
+`--peak_tflops_bf16`).  With both modes among the rows, `deconv_compare` gives per batch the launches' sums, the step
+against the spread of the fp32 rows, and every bf16 launch that took longer than the faster fp32 launch it replaces.
+--out: the JSON record also into that file.
 Reads nothing outside the repository.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -36,7 +45,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from iterative_inference_segm_amd import ops, synthetic as S               # noqa: E402
+from iterative_inference_segm_amd import _lib, ops, synthetic as S         # noqa: E402
 from iterative_inference_segm_amd.densenet import FCDenseNet, layer_plan    # noqa: E402
 from iterative_inference_segm_amd.train import DenseNetTrainer              # noqa: E402
 
@@ -96,9 +105,47 @@ def forms(net, B, dt, peak16):
     return out
 
 
-def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.0):
+DECONV_KERNELS = {'deconv_wgrad_kernel': 'wgrad', 'deconv_wgrad_bf16_kernel': 'wgrad',
+                  'deconv_dgrad_kernel': 'dgrad', 'deconv_dgrad_bf16_kernel': 'dgrad'}
+
+
+def deconv_layers(net, back, B, mode, stream, peak16):
+    """Per TransitionUp layer, in backward's order: its two gradient launches of the profiled step, each against its
+    byte model (ops.deconv_wgrad / ops.deconv_dgrad's: x, g, the parameter and the slabs once, gx once) at `stream`
+    GB/s and its nominal work at `peak16` TFLOP/s."""
+    sv, lib = net._tsaved, _lib.load()
+    launches = [(DECONV_KERNELS[k], k, t) for k, _, t in back if k in DECONV_KERNELS]
+    tus = [e for e in reversed(net._steps) if e['kind'] == 'tu']
+    if [w for w, _, _ in launches] != ['wgrad', 'dgrad'] * len(tus):
+        raise RuntimeError('expected a (wgrad, dgrad) pair of launches per TransitionUp layer, got %s'
+                           % [k for _, k, _ in launches])
+    out = []
+    for i, e in enumerate(tus):
+        cin, cout = e['n'] - e['block0'], e['keep']
+        hw, win = tuple(sv['stacks'][e['sid']].buf.shape[2:]), tuple(sv['win'][e['li']])
+        d = ops.deconv_desc((B, cin) + hw, cout, 3, 2, win)
+        nx, ng, nw = B * cin * hw[0] * hw[1], B * cout * win[2] * win[3], cin * cout * 9
+        if mode == 'bf16':
+            ws = lib.iiseg_deconv_wgrad_bf16_workspace_elems(C.byref(d))
+            slabs = lib.iiseg_deconv_wgrad_bf16_slabs(C.byref(d))
+            wbytes, dbytes = 4.0 * (nx + ng + 2 * ws), 4.0 * (ng + nw + nx)
+        else:
+            slabs = lib.iiseg_deconv_wgrad_partials(C.byref(d))
+            wbytes, dbytes = 4.0 * (nx + ng + 2 * slabs * (nw + cout)), 4.0 * (ng + nx)
+        flops = 2.0 * cin * cout * ops._deconv3_products(d)
+        row = {'li': e['li'], 'resolution': '%dx%d -> %dx%d' % (hw + win[2:]), 'cin': cin, 'cout': cout,
+               'slabs': int(slabs), 'nominal_gflop': round(flops / 1e9, 4)}
+        for (which, kern, t), nbytes in zip(launches[2 * i:2 * i + 2], (wbytes, dbytes)):
+            row[which] = {'kernel': kern, 'ms': round(t, 5), 'model_mb': round(nbytes / 1e6, 3),
+                          'fraction_of_stream': round(nbytes / (t * 1e-3) / 1e9 / stream, 4),
+                          'fraction_of_peak_bf16': round(flops / (t * 1e-3) / (peak16 * 1e12), 5)}
+        out.append(row)
+    return out
+
+
+def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.0, deconv='f32', with_forms=True):
     params = S.make_densenet_params(layer_plan(), seed=2024)
-    net = FCDenseNet(params, 11, layer=[], dtype=dt, mma='f32', trainable=True, wgrad=wgrad)
+    net = FCDenseNet(params, 11, layer=[], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, deconv=deconv)
     tr = DenseNetTrainer(net, 11, [11], learning_rate=1e-3, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
@@ -209,8 +256,10 @@ def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.
                      'fraction_of_peak': round(r['flops'] / (r['ms'] * 1e-3) /
                                                ((peak16 if wgrad == 'bf16' else peak) * 1e12), 5)}
                     for hw, r in sorted(wres.items(), reverse=True)]
-    extra = {'forms': forms(net, B, dt, peak16)} if wgrad == 'bf16' else {}
-    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+    extra = {'forms': forms(net, B, dt, peak16)} if wgrad == 'bf16' and with_forms else {}
+    tu = deconv_layers(net, back, B, deconv, stream, peak16)
+    extra.update(deconv_layers=tu, deconv_ms_total=round(sum(r[w]['ms'] for r in tu for w in ('wgrad', 'dgrad')), 4))
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'deconv': deconv, 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
             'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 2),
             'parameters': int(net.flat.numel()), 'weights': 'default synthetic (synthetic.make_densenet_params)',
             'max_memory_allocated_mb': round(peak_mem / 2.0 ** 20, 1), 'profiled_launches': len(rows),
@@ -249,6 +298,36 @@ def compare(rows):
     return out
 
 
+def compare_deconv(rows):
+    """Per (batch, wgrad mode) with deconv f32 and bf16 rows (float32): the TransitionUp launches together and one
+    by one -- a bf16 launch is slower when it took longer than the FASTER fp32 launch it replaces --, the step
+    against the spread of the fp32 rows."""
+    out = []
+    for B, wg in sorted({(r['batch'], r['wgrad']) for r in rows}):
+        mine = [r for r in rows if r['batch'] == B and r['wgrad'] == wg and r['dtype'] == 'float32']
+        f32, b16 = [r for r in mine if r['deconv'] == 'f32'], [r for r in mine if r['deconv'] == 'bf16']
+        if not f32 or not b16:
+            continue
+        slower, per_layer = [], []
+        for i, lb in enumerate(b16[0]['deconv_layers']):
+            entry = {'li': lb['li'], 'resolution': lb['resolution'], 'channels': lb['cin']}
+            for which in ('wgrad', 'dgrad'):
+                ref = [r['deconv_layers'][i][which]['ms'] for r in f32]
+                entry[which] = {'f32_ms': ref, 'bf16_ms': lb[which]['ms'], 'speedup': round(min(ref) / lb[which]['ms'], 2)}
+                if lb[which]['ms'] > min(ref):
+                    slower.append({'li': lb['li'], 'launch': which, 'bf16_ms': lb[which]['ms'], 'f32_ms': ref})
+            per_layer.append(entry)
+        steps, tot = [r['step_ms'] for r in f32], [r['deconv_ms_total'] for r in f32]
+        out.append({'batch': B, 'wgrad': wg, 'f32_deconv_ms': tot, 'bf16_deconv_ms': b16[0]['deconv_ms_total'],
+                    'f32_step_ms': steps, 'f32_step_spread_ms': round(max(steps) - min(steps), 3),
+                    'bf16_step_ms': b16[0]['step_ms'], 'step_gain_ms': round(min(steps) - b16[0]['step_ms'], 3),
+                    'gain_exceeds_spread': bool(min(steps) - b16[0]['step_ms'] > max(steps) - min(steps)),
+                    'f32_max_memory_mb': [r['max_memory_allocated_mb'] for r in f32],
+                    'bf16_max_memory_mb': b16[0]['max_memory_allocated_mb'],
+                    'layers': per_layer, 'launches_slower_than_the_faster_f32_launch': slower})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batches', type=int, nargs='+', default=[3, 10])
@@ -259,6 +338,7 @@ def main():
     ap.add_argument('--stream_gbs', type=float, default=6600.0)
     ap.add_argument('--weight_decay', type=float, default=1e-4)
     ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--deconv', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -266,14 +346,15 @@ def main():
     rows = []
     for name in a.dtypes:
         for mode in (a.wgrad if name == 'float32' else ['f32']):        # (bf16 operands: float32 only)
-            for B in a.batches:
-                rows.append(one(B, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs, a.weight_decay,
-                                mode, a.peak_tflops_bf16))
-                torch.cuda.empty_cache()
+            for dmode in (a.deconv if name == 'float32' else ['f32']):
+                for B in a.batches:
+                    rows.append(one(B, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs,
+                                    a.weight_decay, mode, a.peak_tflops_bf16, dmode, with_forms=len(a.deconv) == 1))
+                    torch.cuda.empty_cache()
     record = json.dumps({'bench': 'train_densenet', 'device': torch.cuda.get_device_name(0),
                          'peak_tflops': a.peak_tflops, 'peak_tflops_bf16': a.peak_tflops_bf16,
-                         'stream_gbs': a.stream_gbs, 'reps': a.reps, 'wgrad': a.wgrad, 'results': rows,
-                         'wgrad_compare': compare(rows)})
+                         'stream_gbs': a.stream_gbs, 'reps': a.reps, 'wgrad': a.wgrad, 'deconv': a.deconv,
+                         'results': rows, 'wgrad_compare': compare(rows), 'deconv_compare': compare_deconv(rows)})
     print(record)
     if a.out:
         with open(a.out, 'w') as f:

@@ -17,6 +17,8 @@ Initial weights without `--resume`: HeUniform W, zero b, gamma 1, beta 0 (upstre
 `--wgrad bf16` (float32 only) forms the weight gradients of the zero-padded 3x3 layers on the
 16-bit matrix pipe, in blocks of 16 output channels for the dense-block layers; everything else stays float32, and
 the experiment folder and the checkpoint names do not change (config.txt records the mode).
+`--deconv bf16` (float32 only) does the same for the data and weight gradients of the five
+TransitionUp layers (K = 3, stride-2 transposed convolutions); config.txt records it, no name changes.
 Data augmentation is not built.  What is refused exits with status 2 and the reason on stderr before any GPU work.
 All arithmetic runs in the HIP kernels of libiiseg_hip.so.
 """
@@ -45,9 +47,9 @@ def _json(s):
 def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2,
                     batch_size=(3, 1, 1), num_epochs=1, max_patience=1, learning_rate=1e-3, lr_decay=0.995,
                     weight_decay=1e-4, layers_per_block=LAYERS_PER_BLOCK, growth=16, n_first=48, image_size=None,
-                    wgrad='f32'):
+                    wgrad='f32', deconv='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
-    from iterative_inference_segm_amd.train import check_wgrad
+    from iterative_inference_segm_amd.train import check_deconv, check_wgrad
     if savepath is None:
         raise ValueError('A saving directory must be specified')
     if dataset not in ('camvid', 'polyps912', 'em'):
@@ -58,6 +60,7 @@ def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rm
         raise NotImplementedError("training FC-DenseNet: float32 (mma 'f32') or float64; the 16-bit legs (dtype %s, "
                                   'mma %r) are not trained' % (dtype, mma))
     check_wgrad(wgrad, dtype)
+    check_deconv(deconv, dtype)
     if optimizer not in OPTIMIZERS:
         raise ValueError('Unknown optimizer')
     if not 0.0 <= float(dropout) < 1.0:
@@ -104,14 +107,14 @@ def one_hot_void_last(L, n_classes):
 def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_epochs=750, max_patience=150,
           savepath=None, loadpath=None, batch_size=None, resume=False, synthetic=False, n_images=20, image_size=None,
           seed=0, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2, layers_per_block=LAYERS_PER_BLOCK,
-          growth=16, n_first=48, max_batches=None, verbose=True, wgrad='f32'):
-    """Returns the per-epoch lists and the experiment folder.  wgrad ('f32' | 'bf16'): the operand precision of the
-    zero-padded 3x3 weight gradients (FCDenseNet's keyword)."""
+          growth=16, n_first=48, max_batches=None, verbose=True, wgrad='f32', deconv='f32'):
+    """Returns the per-epoch lists and the experiment folder.  wgrad, deconv ('f32' | 'bf16'): the operand precision
+    of the zero-padded 3x3 weight gradients and of the TransitionUp gradients (FCDenseNet's keywords)."""
     bs = list(batch_size) if batch_size is not None else [3, 1, 1]
     lpb = [int(v) for v in layers_per_block]
     size = tuple(image_size) if image_size is not None else (224, 224)
     check_supported(dataset, savepath, dtype, mma, optimizer, dropout, bs, num_epochs, max_patience, learning_rate,
-                    lr_decay, weight_decay, lpb, growth, n_first, size, wgrad)
+                    lr_decay, weight_decay, lpb, growth, n_first, size, wgrad, deconv)
     loadpath = loadpath if loadpath is not None else savepath
     savepath = os.path.join(savepath, dataset, EXP_NAME)
     loadpath = os.path.join(loadpath, dataset, EXP_NAME)
@@ -123,7 +126,7 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
                                       weight_decay=weight_decay, num_epochs=num_epochs, max_patience=max_patience,
                                       batch_size=bs, resume=resume, seed=seed, dtype=dtype, optimizer=optimizer,
                                       dropout=dropout, layers_per_block=lpb, growth=growth, n_first=n_first,
-                                      image_size=list(size), wgrad=wgrad).items()):
+                                      image_size=list(size), wgrad=wgrad, deconv=deconv).items()):
             f.write('{} = {}\n'.format(key, value))
 
     # ---- from here on: the GPU ----
@@ -150,7 +153,7 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
     else:
         params = he_params(plan, 4321 + int(seed))
     net = FCDenseNet(params, n_classes, layer=[], n_layers_per_block=lpb, n_pool=n_pool, growth=growth, dtype=tdt,
-                     mma='f32', trainable=True, dropout=dropout, wgrad=wgrad)
+                     mma='f32', trainable=True, dropout=dropout, wgrad=wgrad, deconv=deconv)
     trainer = DenseNetTrainer(net, n_classes, void_labels, optimizer=optimizer, learning_rate=learning_rate,
                               weight_decay=weight_decay, seed=seed)
 
@@ -247,6 +250,8 @@ def make_parser():
     parser.add_argument('--mma', default='f32', help="float32: only 'f32' is trained")
     parser.add_argument('--wgrad', choices=['f32', 'bf16'], default='f32',
                         help='operand precision of the 3x3 weight gradients (bf16: float32 runs only)')
+    parser.add_argument('--deconv', choices=['f32', 'bf16'], default='f32',
+                        help='operand precision of the TransitionUp gradients (bf16: float32 runs only)')
     parser.add_argument('--optimizer', default='rmsprop', help='rmsprop | adam')
     parser.add_argument('--dropout', type=float, default=0.2)
     parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
@@ -271,7 +276,7 @@ def main(argv=None):
         check_supported(args.dataset, args.savepath, args.dtype, args.mma, args.optimizer, args.dropout,
                         args.batch_size, args.num_epochs, args.max_patience, args.learning_rate, args.lr_decay,
                         args.weight_decay, args.layers_per_block, args.growth, args.n_first, args.image_size,
-                        args.wgrad)
+                        args.wgrad, args.deconv)
     except (NotImplementedError, ValueError, TypeError) as e:
         print('train_fcdensenet.py: ' + str(e), file=sys.stderr)
         return 2
@@ -280,7 +285,7 @@ def main(argv=None):
           synthetic=args.synthetic, n_images=args.n_images, image_size=args.image_size, seed=args.seed,
           dtype=args.dtype, mma=args.mma, optimizer=args.optimizer, dropout=args.dropout,
           layers_per_block=args.layers_per_block, growth=args.growth, n_first=args.n_first,
-          max_batches=args.max_batches, wgrad=args.wgrad)
+          max_batches=args.max_batches, wgrad=args.wgrad, deconv=args.deconv)
     return 0
 
 
