@@ -2,8 +2,8 @@
 checkpoint's layouts) with views per layer, and its gradient twin: what the optimizer step (ops.opt_step) walks
 and what every layer object of the DAE holds views of (DESIGN.md sections 9 and 12); the parameter side every
 trainable net shares (`Trainable`) and the 16-bit training switches of the trainable modules.
-Plain torch: works on host tensors too, needs no library."""
-import torch
+Plain torch: works on host tensors too, needs no library.  torch is imported where a tensor is made or compared, not
+with the module: the training drivers read the switches' names before they parse their arguments."""
 
 # The 16-bit training switches (keyword and attribute of the trainable modules -- FCN8 and StandardDAE have
 # several, FCDenseNet has 'wgrad' and 'deconv' --, option of the drivers): what each is called in messages.  Every
@@ -23,6 +23,7 @@ def check_mode(switch, mode, dtype, trainable=None):
             raise NotImplementedError("%s='bf16' rounds float32 operands for the 16-bit matrix pipe: dtype must "
                                       'be float32 (got %s)' % (switch, dtype))
     else:
+        import torch
         if mode not in MODES_16BIT:
             raise ValueError("%s=%r is not one of %s" % (switch, mode, MODES_16BIT))
         if mode == 'bf16' and not (trainable and dtype == torch.float32):
@@ -34,6 +35,7 @@ def check_mode(switch, mode, dtype, trainable=None):
 class ParamStore:
     def __init__(self, params, order, dtype, device):
         """params: {name: (W, b)} (arrays or tensors); order: the names, in the order of the flat buffer."""
+        import torch
         host = [(n, torch.as_tensor(params[n][0]), torch.as_tensor(params[n][1])) for n in order]
         self._layout = [(n, tuple(W.shape), W.numel(), b.numel()) for n, W, b in host]
         self.flat = torch.empty(sum(nW + nb for _, _, nW, nb in self._layout), dtype=dtype, device=device)
@@ -54,6 +56,7 @@ class ParamStore:
     def gflat(self):
         """The gradient buffer, laid out as `flat`: zeros, allocated at first use."""
         if self._gflat is None:
+            import torch
             self._gflat = torch.zeros_like(self.flat)
             self._gviews = self._carve(self._gflat)
         return self._gflat

@@ -6,9 +6,9 @@ train_dae.py:334-338,
 
 for dae kind 'contextmod'  and kind 'standard' with h at a pool point (section 12).
 Forward and data gradient run on the inference layers (ops.Conv), the loss and the optimizer step on
-csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_wgrad.hip (standard DAE); and
-the two of train_fcn8.py:116-137 for FCN-8 itself (FCN8Trainer) and for FC-DenseNet
-(DenseNetTrainer, section 21).
+csrc/ctx_train.hip, the weight gradients there (context module) or on csrc/conv_wgrad.hip (standard DAE) --
+DAETrainer; and the two of train_fcn8.py:116-137 for the segmentation nets themselves -- _NetTrainer (DESIGN.md
+section 24), which FCN8Trainer (section 14) and DenseNetTrainer (section 21) only name and give their defaults.
 Everything is enqueued on the current stream; nothing here waits for the device.
 """
 import functools
@@ -152,73 +152,40 @@ class DAETrainer(_Trainer):
         return res[0], self._metrics(score, T), res[2]
 
 
-class FCN8Trainer(_Trainer):
-    """The two compiled functions of the reference's train_fcn8.py:116-137 for an FCN8 built with trainable=True
-    (DESIGN.md section 14): train_fn = masked cross-entropy + weight_decay * sum W^2 under adam, val_fn = loss and
-    Jaccard counts on the deterministic forward.  The net is trained in place."""
+class _NetTrainer(_Trainer):
+    """train_fn / val_fn of a segmentation net built with trainable=True, trained in place: train_fn = masked
+    cross-entropy + weight_decay * sum p^2 over the net's weight_ranges(), val_fn = loss and Jaccard counts on the
+    deterministic forward.  A subclass names the net (_NET) and says in its constructor which optimizer and
+    learning rate it defaults to and whether the optimizer can be chosen."""
 
-    def __init__(self, net, n_classes, void_labels=(11,), learning_rate=1e-4, weight_decay=0.0, seed=None):
+    _NET = None
+
+    def __init__(self, net, n_classes, void_labels, optimizer, learning_rate, weight_decay, seed):
         if not getattr(net, 'trainable', False):
-            raise NotImplementedError('training an FCN8 needs one built with trainable=True')
-        if not float(weight_decay) >= 0.0:
-            raise ValueError('weight_decay must be >= 0')
-        super().__init__(net, n_classes, void_labels, 'adam', learning_rate, seed)
-        self.net, self.weight_decay, self.ranges = net, float(weight_decay), net.weight_ranges()
-
-    def train_step(self, X, T, keep6=None, keep7=None):
-        """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64).  keep6 / keep7:
-        the caller's dropout masks (tests), else drawn from the trainer's generator."""
-        net = self.net
-        score = net.forward_train(X, keep6, keep7, generator=self.generator)
-        res, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=True)
-        net.backward(g)
-        loss = res[0]
-        if self.weight_decay > 0:
-            loss = loss + self.weight_decay * ops.l2_term(net.flat, net.gflat, self.ranges, self.weight_decay)[0]
-        ops.opt_step('adam', net.flat, net.gflat, self.s1, self.s2, self.lr, self.state, grid=True)
-        net.refresh()
-        return loss
-
-    def val_step(self, X, T):
-        """val_fn (deterministic: no dropout): (loss, Metrics) -- the loss a device scalar, accuracy and the
-        Jaccard counts in the Metrics accumulators (api.Metrics.result() -> acc, jacc(2, C), mse)."""
-        score = self.net.forward_train(X, deterministic=True)
-        res, _, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=False)
-        return res[0], self._metrics(score, T)
-
-
-class DenseNetTrainer(_Trainer):
-    """train_fn / val_fn for an FCDenseNet built with trainable=True (the reference has no
-    FC-DenseNet training script: optimizer and schedule are restated from upstream FC-DenseNet): masked
-    cross-entropy + weight_decay * sum p^2 over every W and every gamma (lasagne marks gamma regularizable; never
-    beta or a bias) under RMSprop (default) or adam; val_fn = loss and Jaccard counts on the deterministic forward.
-    The net is trained in place."""
-
-    def __init__(self, net, n_classes, void_labels=(11,), optimizer='rmsprop', learning_rate=1e-3, weight_decay=0.0,
-                 seed=None):
-        if not getattr(net, 'trainable', False):
-            raise NotImplementedError('training an FCDenseNet needs one built with trainable=True')
+            raise NotImplementedError('training %s needs one built with trainable=True' % self._NET)
         if optimizer not in ops.OPTIMIZERS:
             raise ValueError('Unknown optimizer')
         if not float(weight_decay) >= 0.0:
             raise ValueError('weight_decay must be >= 0')
         super().__init__(net, n_classes, void_labels, optimizer, learning_rate, seed)
         self.net, self.weight_decay = net, float(weight_decay)
-        # ops.l2_term takes a bounded number of ranges per launch; this net has two hundred
-        ranges = net.weight_ranges()
-        step = _lib.L2_MAX_RANGES
-        self.ranges = [ranges[i:i + step] for i in range(0, len(ranges), step)]
+        self.ranges = self.chunks(net.weight_ranges())     # a list of CHUNKS of ranges: one ops.l2_term call each
+
+    @staticmethod
+    def chunks(ranges, step=_lib.L2_MAX_RANGES):
+        """ops.l2_term takes a bounded number of ranges per launch (FC-DenseNet has two hundred, FCN-8 twenty-one)."""
+        return [ranges[i:i + step] for i in range(0, len(ranges), step)]
 
     def anneal(self, factor):
         """lr <- lr * factor on the device."""
         self.lr.mul_(float(factor))
 
-    def train_step(self, X, T, keeps=None):
-        """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64).  keeps: the
-        caller's dropout masks, one per 'brc' / 'td' layer (tests), else drawn from the trainer's generator.  No
-        host wait."""
+    def train_step(self, X, T, *masks, **mask_kw):
+        """One step of train_fn: returns the loss BEFORE the update as a device scalar (float64).  masks: the
+        caller's dropout masks as net.forward_train takes them (tests), else drawn from the trainer's generator.
+        No host wait."""
         net = self.net
-        score = net.forward_train(X, keeps, generator=self.generator)
+        score = net.forward_train(X, *masks, generator=self.generator, **mask_kw)
         res, g, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=True)
         net.backward(g)
         loss = res[0]
@@ -231,7 +198,30 @@ class DenseNetTrainer(_Trainer):
 
     def val_step(self, X, T):
         """val_fn (deterministic: no dropout): (loss, Metrics) -- the loss a device scalar, accuracy and the
-        Jaccard counts in the Metrics accumulators."""
+        Jaccard counts in the Metrics accumulators (api.Metrics.result() -> acc, jacc(2, C), mse)."""
         score = self.net.forward_train(X, deterministic=True)
         res, _, _ = ops.ctx_loss(score, T, ('crossentropy',), 1.0, grad=False)
         return res[0], self._metrics(score, T)
+
+
+class FCN8Trainer(_NetTrainer):
+    """The two compiled functions of the reference's train_fcn8.py:116-137 for an FCN8, under
+    adam; train_step(X, T, keep6, keep7)."""
+
+    _NET = 'an FCN8'
+
+    def __init__(self, net, n_classes, void_labels=(11,), learning_rate=1e-4, weight_decay=0.0, seed=None):
+        super().__init__(net, n_classes, void_labels, 'adam', learning_rate, weight_decay, seed)
+
+
+class DenseNetTrainer(_NetTrainer):
+    """For an FCDenseNet (the reference has no FC-DenseNet training script: optimizer and
+    schedule are restated from upstream FC-DenseNet), under RMSprop (default) or adam; the weight decay is over every
+    W and every gamma (lasagne marks gamma regularizable; never beta or a bias); train_step(X, T, keeps), one mask
+    per 'brc' / 'td' layer."""
+
+    _NET = 'an FCDenseNet'
+
+    def __init__(self, net, n_classes, void_labels=(11,), optimizer='rmsprop', learning_rate=1e-3, weight_decay=0.0,
+                 seed=None):
+        super().__init__(net, n_classes, void_labels, optimizer, learning_rate, weight_decay, seed)

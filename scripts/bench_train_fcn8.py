@@ -114,7 +114,8 @@ def one(B, H, W, dt, reps, peak, stream, width_div, fc_channels, weight_decay, w
         with marked(net.dgrads.layers, prof) as log:
             net.backward(g)
         if weight_decay > 0:
-            ops.l2_term(net.flat, net.gflat, tr.ranges, weight_decay)
+            for chunk in tr.ranges:
+                ops.l2_term(net.flat, net.gflat, chunk, weight_decay)
         torch.cuda.synchronize()
     finally:
         ops.CONV_PROFILE = None

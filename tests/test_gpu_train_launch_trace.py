@@ -11,7 +11,8 @@ covers refresh(), stale filter images and buffer reuse), val_step, backward_y (w
 flipped-filter form) -- and its C8 adjoint (mma='bf16c8', keep_pre: scores, backward_y); FCN-8 (SMALL of
 tests/fcn8_train_ref.py at 26x30, batch 3) in five modes -- two train steps under given dropout masks, val_step; the
 context-module DAE (the case of tests/test_gpu_ctx_train.py) in both precisions -- two train steps, val_step,
-backward_y, sqerr_backward."""
+backward_y, sqerr_backward; FC-DenseNet (THIN of tests/densenet_train_ref.py at 13x18, batch 2) in three modes -- two
+train steps under given dropout masks, val_step."""
 import contextlib
 import ctypes as C
 import json
@@ -26,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if __name__ == '__main__':
     sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 
+import densenet_train_ref as RD
 import fcn8_train_ref as RF
 import std_train_ref as R
 
@@ -89,6 +91,7 @@ STD_MODES = {'f32': ('f32', {}), 'bf16': ('f32', dict(wgrad='bf16', dgrad='bf16'
              'dgrad16': ('f32', dict(dgrad='bf16')), 'f64': ('f64', {})}
 FCN_MODES = {'f32': ('f32', {}), 'bf16': ('f32', dict(wgrad='bf16', dgrad='bf16', kxk='bf16', fwd='bf16')),
              'kxk16': ('f32', dict(kxk='bf16')), 'dgrad16': ('f32', dict(dgrad='bf16')), 'f64': ('f64', {})}
+DENSE_MODES = {'f32': ('f32', {}), 'bf16': ('f32', dict(wgrad='bf16', deconv='bf16')), 'f64': ('f64', {})}
 _DATA = {}
 
 
@@ -140,6 +143,23 @@ def _fcn(mode):
     return dict(flat=net.flat, gflat=net.gflat)
 
 
+def _densenet(mode):
+    from iterative_inference_segm_amd.densenet import FCDenseNet
+    from iterative_inference_segm_amd.train import DenseNetTrainer
+    cfg = RD.THIN
+    params, x, T, keeps = _data('densenet', lambda: RD.make_case(cfg, seed=3))
+    dt = DT[DENSE_MODES[mode][0]]
+    C_ = cfg['n_classes']
+    net = FCDenseNet(params, C_, layer=[], n_layers_per_block=cfg['nlpb'], n_pool=cfg['n_pool'], growth=cfg['growth'],
+                     dtype=dt, mma='f32', trainable=True, **DENSE_MODES[mode][1])
+    tr = DenseNetTrainer(net, C_, [C_], learning_rate=1e-3, weight_decay=1e-4)
+    xd, Td, kd = _dev(x, dt), _dev(T, dt), [_dev(k, dt) for k in keeps]
+    for _ in range(2):
+        tr.train_step(xd, Td, kd)
+    tr.val_step(xd, Td)
+    return dict(flat=net.flat, gflat=net.gflat)
+
+
 def _ctx_case(B=2, H=40, W=36, seed=11):
     from iterative_inference_segm_amd import synthetic as S
     rng = np.random.default_rng(seed)
@@ -172,6 +192,7 @@ CASES = {'std/%s/%s' % (w, m): (lambda w=w, m=m: _std(w, m)) for w in STD_MODELS
 CASES['std/second/c8_adjoint'] = _std_c8
 CASES.update({'fcn8/%s' % m: (lambda m=m: _fcn(m)) for m in FCN_MODES})
 CASES.update({'ctx/%s' % m: (lambda m=m: _ctx(m)) for m in ('f32', 'f64')})
+CASES.update({'densenet/%s' % m: (lambda m=m: _densenet(m)) for m in DENSE_MODES})
 
 
 def run_case(name):

@@ -22,26 +22,20 @@ TransitionUp layers (K = 3, stride-2 transposed convolutions); config.txt record
 Data augmentation is not built.  What is refused exits with status 2 and the reason on stderr before any GPU work.
 All arithmetic runs in the HIP kernels of libiiseg_hip.so.
 """
-import argparse
-import json
 import os
-import shutil
 import sys
-import time
 
 import numpy as np
 
-SAVEPATH = os.environ.get('IISEG_SAVEPATH')
-LOADPATH = os.environ.get('IISEG_LOADPATH')
+from iterative_inference_segm_amd import train_loop
+from iterative_inference_segm_amd.train_loop import one_hot_void_last      # noqa: F401  (the drivers' own name for it)
+
 EXP_NAME = 'fc_densenet'
 MODEL = 'FC-DenseNet103_weights_%s.npz'
 LAYERS_PER_BLOCK = [4, 5, 7, 10, 12, 15, 12, 10, 7, 5, 4]
 OPTIMIZERS = ('rmsprop', 'adam')
 MMA_MODES = ('f32', 'bf16', 'bf16c8', 'bf16x3')
-
-
-def _json(s):
-    return json.loads(s) if isinstance(s, str) else s
+SWITCHES = {'wgrad': 'the zero-padded 3x3 layers', 'deconv': 'the five TransitionUp layers, weights and data'}
 
 
 def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2,
@@ -49,26 +43,19 @@ def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rm
                     weight_decay=1e-4, layers_per_block=LAYERS_PER_BLOCK, growth=16, n_first=48, image_size=None,
                     wgrad='f32', deconv='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
-    from iterative_inference_segm_amd.train import check_deconv, check_wgrad
-    if savepath is None:
-        raise ValueError('A saving directory must be specified')
-    if dataset not in ('camvid', 'polyps912', 'em'):
-        raise ValueError('Unknown dataset')
+    train_loop.check_savepath(savepath)
+    train_loop.check_dataset(dataset)
     if mma not in MMA_MODES:
         raise ValueError('mma must be one of %s' % ', '.join(MMA_MODES))
     if dtype not in ('float32', 'float64') or (dtype == 'float32' and mma != 'f32'):
         raise NotImplementedError("training FC-DenseNet: float32 (mma 'f32') or float64; the 16-bit legs (dtype %s, "
                                   'mma %r) are not trained' % (dtype, mma))
-    check_wgrad(wgrad, dtype)
-    check_deconv(deconv, dtype)
+    train_loop.check_switches(dtype, wgrad=wgrad, deconv=deconv)
     if optimizer not in OPTIMIZERS:
         raise ValueError('Unknown optimizer')
     if not 0.0 <= float(dropout) < 1.0:
         raise ValueError('dropout must be in [0, 1)')
-    if not (isinstance(batch_size, (list, tuple)) and len(batch_size) == 3 and all(int(b) >= 1 for b in batch_size)):
-        raise ValueError('batch_size must be [train, val, test], each >= 1')
-    if int(num_epochs) < 1 or int(max_patience) < 1:
-        raise ValueError('num_epochs and max_patience must be >= 1')
+    train_loop.check_schedule(batch_size, num_epochs, max_patience)
     if not float(learning_rate) > 0 or not float(weight_decay) >= 0 or not 0 < float(lr_decay) <= 1:
         raise ValueError('learning_rate must be > 0, weight_decay >= 0 and lr_decay in (0, 1]')
     lpb = list(layers_per_block)
@@ -98,12 +85,6 @@ def he_params(plan, seed):
     return out
 
 
-def one_hot_void_last(L, n_classes):
-    """Integer labels (B,H,W), void = any label >= n_classes, -> one-hot (B,n_classes+1,H,W), void channel last."""
-    L = np.minimum(np.asarray(L).astype(np.int64), n_classes)
-    return np.ascontiguousarray(np.moveaxis(np.eye(n_classes + 1, dtype=np.float32)[L], -1, 1))
-
-
 def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_epochs=750, max_patience=150,
           savepath=None, loadpath=None, batch_size=None, resume=False, synthetic=False, n_images=20, image_size=None,
           seed=0, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2, layers_per_block=LAYERS_PER_BLOCK,
@@ -115,19 +96,13 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
     size = tuple(image_size) if image_size is not None else (224, 224)
     check_supported(dataset, savepath, dtype, mma, optimizer, dropout, bs, num_epochs, max_patience, learning_rate,
                     lr_decay, weight_decay, lpb, growth, n_first, size, wgrad, deconv)
-    loadpath = loadpath if loadpath is not None else savepath
-    savepath = os.path.join(savepath, dataset, EXP_NAME)
-    loadpath = os.path.join(loadpath, dataset, EXP_NAME)
     say = print if verbose else (lambda *a, **k: None)
-    os.makedirs(savepath, exist_ok=True)
-    say('Saving directory : ' + savepath)
-    with open(os.path.join(savepath, 'config.txt'), 'w') as f:
-        for key, value in sorted(dict(dataset=dataset, learning_rate=learning_rate, lr_decay=lr_decay,
-                                      weight_decay=weight_decay, num_epochs=num_epochs, max_patience=max_patience,
-                                      batch_size=bs, resume=resume, seed=seed, dtype=dtype, optimizer=optimizer,
-                                      dropout=dropout, layers_per_block=lpb, growth=growth, n_first=n_first,
-                                      image_size=list(size), wgrad=wgrad, deconv=deconv).items()):
-            f.write('{} = {}\n'.format(key, value))
+    savepath, loadpath = train_loop.experiment_folders(
+        savepath, loadpath, dataset, EXP_NAME,
+        dict(dataset=dataset, learning_rate=learning_rate, lr_decay=lr_decay, weight_decay=weight_decay,
+             num_epochs=num_epochs, max_patience=max_patience, batch_size=bs, resume=resume, seed=seed, dtype=dtype,
+             optimizer=optimizer, dropout=dropout, layers_per_block=lpb, growth=growth, n_first=n_first,
+             image_size=list(size), wgrad=wgrad, deconv=deconv), say)
 
     # ---- from here on: the GPU ----
     import torch
@@ -157,112 +132,50 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
     trainer = DenseNetTrainer(net, n_classes, void_labels, optimizer=optimizer, learning_rate=learning_rate,
                               weight_decay=weight_decay, seed=seed)
 
-    def batch(it):
-        X, L = it.next()
-        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda().to(tdt).contiguous()
-        Td = torch.from_numpy(one_hot_void_last(L, n_classes)).cuda().to(tdt).contiguous()
-        return Xd, Td
-
-    def evaluate(it):
-        """(mean loss, mean accuracy, Jaccard counts (2, C)) over the split."""
-        cost = torch.zeros((), dtype=torch.float64, device='cuda')
-        acc_tot, jacc_tot = 0.0, np.zeros((2, n_classes))
-        for _ in range(nb(it)):
-            c, m = trainer.val_step(*batch(it))
-            cost += c
-            acc, jacc, _ = m.result()
-            acc_tot += acc
-            jacc_tot += jacc
-        return float(cost.item()) / nb(it), acc_tot / nb(it), jacc_tot
-
     def save(tag, errors):
         save_checkpoint(os.path.join(savepath, MODEL % tag), net, n_first)
         np.savez(os.path.join(savepath, 'errors_%s.npz' % tag), *[np.asarray(e) for e in errors])
 
-    err_train, err_valid, acc_valid, jacc_valid = [], [], [], []
-    patience, best_jacc_val = 0, None
+    def reload_best():
+        """The best weights back into the net's own buffer, in place (every run has written them)."""
+        for p, e in zip(load_params(best_path, plan), net.layers):
+            if p['kind'] in ('brc', 'td'):
+                e['beta'].copy_(torch.from_numpy(p['beta']).to(tdt))
+                e['gamma'].copy_(torch.from_numpy(p['gamma']).to(tdt))
+            e['conv'].W.copy_(torch.from_numpy(p['W']).to(tdt))
+            e['conv'].b.copy_(torch.from_numpy(p['b']).to(tdt))
+        net.refresh()
+        return True
+
+    nanmean_jaccard = lambda jacc_tot: float(np.nanmean(train_loop.per_class_jaccard(jacc_tot)))
     say('Start training')
-    for epoch in range(num_epochs):
-        start_time = time.time()
-        cost = torch.zeros((), dtype=torch.float64, device='cuda')
-        for _ in range(nb(train_iter)):
-            cost += trainer.train_step(*batch(train_iter))     # device scalar: one host read per epoch
-        err_train.append(float(cost.item()) / nb(train_iter))
-        trainer.anneal(lr_decay)
-
-        err, acc, jacc_tot = evaluate(val_iter)
-        err_valid.append(err)
-        acc_valid.append(acc)
-        with np.errstate(invalid='ignore', divide='ignore'):
-            jacc_valid.append(float(np.nanmean(jacc_tot[0, :] / jacc_tot[1, :])))
-
-        out_str = 'EPOCH %i: Avg epoch training cost train %f, cost val %f, acc val %f, jacc val %f took %f s'
-        out_str = out_str % (epoch, err_train[epoch], err_valid[epoch], acc_valid[epoch], jacc_valid[epoch],
-                             time.time() - start_time)
-        print(out_str)
-        with open(os.path.join(savepath, 'output.log'), 'a') as f:
-            f.write(out_str + '\n')
-
-        errors = (err_valid, err_train, acc_valid, jacc_valid)
-        if epoch == 0 or jacc_valid[epoch] > best_jacc_val:
-            best_jacc_val = jacc_valid[epoch]
-            patience = 0
-            save('best', errors)
-        else:
-            patience += 1
-            save('last', errors)
-
-        if patience == max_patience or epoch == num_epochs - 1:
-            if test_iter is not None:
-                # the best weights back into the net's own buffer, in place
-                for p, e in zip(load_params(best_path, plan), net.layers):
-                    if p['kind'] in ('brc', 'td'):
-                        e['beta'].copy_(torch.from_numpy(p['beta']).to(tdt))
-                        e['gamma'].copy_(torch.from_numpy(p['gamma']).to(tdt))
-                    e['conv'].W.copy_(torch.from_numpy(p['W']).to(tdt))
-                    e['conv'].b.copy_(torch.from_numpy(p['b']).to(tdt))
-                net.refresh()
-                err, acc, jacc_tot = evaluate(test_iter)
-                with np.errstate(invalid='ignore', divide='ignore'):
-                    jacc = float(np.nanmean(jacc_tot[0, :] / jacc_tot[1, :]))
-                print('FINAL MODEL: err test % f, acc test %f, jacc test %f' % (err, acc, jacc))
-            if os.path.abspath(savepath) != os.path.abspath(loadpath):
-                say('Copying model and other training files to {}'.format(loadpath))
-                shutil.copytree(savepath, loadpath, dirs_exist_ok=True)
-            break
-    return {'err_train': err_train, 'err_valid': err_valid, 'acc_valid': acc_valid, 'jacc_valid': jacc_valid,
-            'savepath': savepath, 'loadpath': loadpath}
+    lists = train_loop.run_epochs(
+        num_epochs, max_patience, rule=train_loop.first_epoch_best_rule,
+        train_pass=lambda: train_loop.train_steps(trainer, train_iter, nb(train_iter), n_classes),
+        n_train=nb(train_iter), val_pass=lambda: train_loop.evaluate(trainer, val_iter, nb(val_iter), n_classes),
+        metric=nanmean_jaccard, save=save, log_path=os.path.join(savepath, 'output.log'),
+        after_train=lambda: trainer.anneal(lr_decay),
+        test_pass=None if test_iter is None else
+        lambda: train_loop.evaluate(trainer, test_iter, nb(test_iter), n_classes),
+        reload_best=reload_best, best_name=MODEL % 'best', savepath=savepath, loadpath=loadpath, say=say)
+    return dict(zip(('err_train', 'err_valid', 'acc_valid', 'jacc_valid'), lists), savepath=savepath,
+                loadpath=loadpath)
 
 
 def make_parser():
-    parser = argparse.ArgumentParser(description='FC-DenseNet training')
-    parser.add_argument('-dataset', default='camvid', help='Dataset.')
-    parser.add_argument('--synthetic', action='store_true', help='seeded synthetic split (no dataset here)')
-    parser.add_argument('--savepath', type=str, default=SAVEPATH)
-    parser.add_argument('--loadpath', type=str, default=LOADPATH, help='default: --savepath')
-    parser.add_argument('--num_epochs', '-ne', type=int, default=750)
+    parser = train_loop.make_parser('FC-DenseNet training', SWITCHES)
     parser.add_argument('--learning_rate', type=float, default=1e-3)
     parser.add_argument('--lr_decay', type=float, default=0.995, help='learning-rate factor per epoch')
     parser.add_argument('--weight_decay', type=float, default=1e-4, help='on every W and every gamma')
-    parser.add_argument('--batch_size', type=_json, default=[3, 1, 1], help='[train, val, test] (JSON)')
+    parser.add_argument('--batch_size', type=train_loop.json_arg, default=[3, 1, 1], help='[train, val, test] (JSON)')
     parser.add_argument('--max_patience', type=int, default=150)
-    parser.add_argument('--dtype', default='float32', help='float32 | float64')
     parser.add_argument('--mma', default='f32', help="float32: only 'f32' is trained")
-    parser.add_argument('--wgrad', choices=['f32', 'bf16'], default='f32',
-                        help='operand precision of the 3x3 weight gradients (bf16: float32 runs only)')
-    parser.add_argument('--deconv', choices=['f32', 'bf16'], default='f32',
-                        help='operand precision of the TransitionUp gradients (bf16: float32 runs only)')
     parser.add_argument('--optimizer', default='rmsprop', help='rmsprop | adam')
     parser.add_argument('--dropout', type=float, default=0.2)
-    parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
-    parser.add_argument('--n_images', type=int, default=20, help='images per synthetic split')
-    parser.add_argument('--image_size', type=int, nargs=2, default=None, help='default 224 224')
-    parser.add_argument('--resume', action='store_true', help='start from the best checkpoint under --loadpath')
-    parser.add_argument('--layers_per_block', type=_json, default=list(LAYERS_PER_BLOCK),
+    parser.add_argument('--layers_per_block', type=train_loop.json_arg, default=list(LAYERS_PER_BLOCK),
                         help='2 n_pool + 1 layer counts (JSON)')
     parser.add_argument('--growth', type=int, default=16)
     parser.add_argument('--n_first', type=int, default=48)
-    parser.add_argument('--max_batches', type=int, default=None, help='cap on the batches of each pass (tests)')
     return parser
 
 
@@ -271,22 +184,17 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    args = parse_args(argv)
-    try:
-        check_supported(args.dataset, args.savepath, args.dtype, args.mma, args.optimizer, args.dropout,
-                        args.batch_size, args.num_epochs, args.max_patience, args.learning_rate, args.lr_decay,
-                        args.weight_decay, args.layers_per_block, args.growth, args.n_first, args.image_size,
-                        args.wgrad, args.deconv)
-    except (NotImplementedError, ValueError, TypeError) as e:
-        print('train_fcdensenet.py: ' + str(e), file=sys.stderr)
-        return 2
-    train(args.dataset, args.learning_rate, args.lr_decay, args.weight_decay, args.num_epochs, args.max_patience,
-          savepath=args.savepath, loadpath=args.loadpath, batch_size=args.batch_size, resume=args.resume,
-          synthetic=args.synthetic, n_images=args.n_images, image_size=args.image_size, seed=args.seed,
-          dtype=args.dtype, mma=args.mma, optimizer=args.optimizer, dropout=args.dropout,
-          layers_per_block=args.layers_per_block, growth=args.growth, n_first=args.n_first,
-          max_batches=args.max_batches, wgrad=args.wgrad, deconv=args.deconv)
-    return 0
+    a = parse_args(argv)
+    return train_loop.main(
+        'train_fcdensenet.py',
+        lambda: check_supported(a.dataset, a.savepath, a.dtype, a.mma, a.optimizer, a.dropout, a.batch_size,
+                                a.num_epochs, a.max_patience, a.learning_rate, a.lr_decay, a.weight_decay,
+                                a.layers_per_block, a.growth, a.n_first, a.image_size, a.wgrad, a.deconv),
+        lambda: train(a.dataset, a.learning_rate, a.lr_decay, a.weight_decay, a.num_epochs, a.max_patience,
+                      savepath=a.savepath, loadpath=a.loadpath, batch_size=a.batch_size, resume=a.resume,
+                      synthetic=a.synthetic, n_images=a.n_images, image_size=a.image_size, seed=a.seed, dtype=a.dtype,
+                      mma=a.mma, optimizer=a.optimizer, dropout=a.dropout, layers_per_block=a.layers_per_block,
+                      growth=a.growth, n_first=a.n_first, max_batches=a.max_batches, wgrad=a.wgrad, deconv=a.deconv))
 
 
 if __name__ == '__main__':

@@ -34,23 +34,17 @@ the 16-bit matrix pipe from the parameters and g_z rounded once to bf16; config.
 validation forward on the 16-bit matrix pipe, operands rounded once to bf16, fp32 accumulation and fp32 maps;
 config.txt records it as well.
 """
-import argparse
-import json
 import os
-import shutil
 import sys
-import time
 
 import numpy as np
 
-SAVEPATH = os.environ.get('IISEG_SAVEPATH')
-LOADPATH = os.environ.get('IISEG_LOADPATH')
+from iterative_inference_segm_amd import train_loop
+from iterative_inference_segm_amd.train_loop import one_hot_void_last      # noqa: F401  (the drivers' own name for it)
 
 DATA_AUGMENTATION = {'crop_size': [224, 224], 'horizontal_flip': True, 'fill_mode': 'constant'}   # :301
-
-
-def _json(s):
-    return json.loads(s) if isinstance(s, str) else s
+SWITCHES = {'wgrad': 'the thirteen 3x3 layers', 'dgrad': 'the twelve 3x3 layers of the backward pass',
+            'kxk': 'weights and data', 'fwd': 'the 3x3 layers, fc6 and fc7, in training and validation'}
 
 
 def _bool(s):
@@ -73,33 +67,18 @@ def glorot_params(shapes, seed):
     return out
 
 
-def one_hot_void_last(L, n_classes):
-    """Integer labels (B,H,W), void = any label >= n_classes, -> one-hot (B,n_classes+1,H,W), void channel last."""
-    L = np.minimum(np.asarray(L).astype(np.int64), n_classes)
-    return np.ascontiguousarray(np.moveaxis(np.eye(n_classes + 1, dtype=np.float32)[L], -1, 1))
-
-
 def check_supported(dataset, savepath, pascal=False, dtype='float32', batch_size=(10, 1, 1), num_epochs=1,
                     max_patience=1, learning_rate=1e-4, weight_decay=0.0, early_stop_class=None, wgrad='f32',
                     dgrad='f32', kxk='f32', fwd='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
-    from iterative_inference_segm_amd.train import check_dgrad, check_fwd, check_kxk, check_wgrad
-    if savepath is None:
-        raise ValueError('A saving directory must be specified')                        # train_fcn8.py:55-56
+    train_loop.check_savepath(savepath)
     if pascal:
         raise NotImplementedError('pascal .mat weights are not supported')              # as buildFCN8
-    if dataset not in ('camvid', 'polyps912', 'em'):
-        raise ValueError('Unknown dataset')
+    train_loop.check_dataset(dataset)
     if dtype not in ('float32', 'float64'):
         raise NotImplementedError('training FCN-8: float32 or float64; the 16-bit legs are not trained')
-    check_wgrad(wgrad, dtype)
-    check_dgrad(dgrad, dtype)
-    check_kxk(kxk, dtype)
-    check_fwd(fwd, dtype)
-    if not (isinstance(batch_size, (list, tuple)) and len(batch_size) == 3 and all(int(b) >= 1 for b in batch_size)):
-        raise ValueError('batch_size must be [train, val, test], each >= 1')
-    if int(num_epochs) < 1 or int(max_patience) < 1:
-        raise ValueError('num_epochs and max_patience must be >= 1')
+    train_loop.check_switches(dtype, wgrad=wgrad, dgrad=dgrad, kxk=kxk, fwd=fwd)
+    train_loop.check_schedule(batch_size, num_epochs, max_patience)
     if not float(learning_rate) > 0 or not float(weight_decay) >= 0:
         raise ValueError('learning_rate must be > 0 and penal_cst >= 0')
     if early_stop_class is not None and int(early_stop_class) < 0:
@@ -118,21 +97,13 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
     bs = list(batch_size) if batch_size is not None else [10, 1, 1]                     # :84-87
     check_supported(dataset, savepath, False, dtype, bs, num_epochs, max_patience, learn_step, weight_decay,
                     early_stop_class, wgrad, dgrad, kxk, fwd)
-    exp_name = experiment_name(data_augmentation)
-    loadpath = loadpath if loadpath is not None else savepath
-    savepath = os.path.join(savepath, dataset, exp_name)
-    loadpath = os.path.join(loadpath, dataset, exp_name)
     say = print if verbose else (lambda *a, **k: None)
-    os.makedirs(savepath, exist_ok=True)
-    say('Saving directory : ' + savepath)
-    with open(os.path.join(savepath, 'config.txt'), 'w') as f:
-        for key, value in sorted(dict(dataset=dataset, learn_step=learn_step, weight_decay=weight_decay,
-                                      num_epochs=num_epochs, max_patience=max_patience,
-                                      data_augmentation=data_augmentation, early_stop_class=early_stop_class,
-                                      batch_size=bs, resume=resume, train_from_0_255=train_from_0_255, seed=seed,
-                                      dtype=dtype, width_div=width_div, fc_channels=fc_channels,
-                                      wgrad=wgrad, dgrad=dgrad, kxk=kxk, fwd=fwd).items()):
-            f.write('{} = {}\n'.format(key, value))
+    savepath, loadpath = train_loop.experiment_folders(
+        savepath, loadpath, dataset, experiment_name(data_augmentation),
+        dict(dataset=dataset, learn_step=learn_step, weight_decay=weight_decay, num_epochs=num_epochs,
+             max_patience=max_patience, data_augmentation=data_augmentation, early_stop_class=early_stop_class,
+             batch_size=bs, resume=resume, train_from_0_255=train_from_0_255, seed=seed, dtype=dtype,
+             width_div=width_div, fc_channels=fc_channels, wgrad=wgrad, dgrad=dgrad, kxk=kxk, fwd=fwd), say)
 
     # ---- from here on: the GPU ----
     import torch
@@ -158,6 +129,7 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
     say('Nb of classes: %d' % n_classes)
     say('Nb. of input channels: %d' % nb_in_channels)
 
+    best_path = os.path.join(savepath, 'new_fcn8_model_best.npz')
     if resume:
         params = load_param_list(os.path.join(loadpath, 'new_fcn8_model_best.npz'), PARAM_ORDER)
     else:
@@ -167,131 +139,54 @@ def train(dataset, learn_step=0.005, weight_decay=1e-4, num_epochs=500, max_pati
                wgrad=wgrad, dgrad=dgrad, kxk=kxk, fwd=fwd)
     trainer = FCN8Trainer(net, n_classes, void_labels, learning_rate=learn_step, weight_decay=weight_decay, seed=seed)
 
-    def batch(it):
-        X, L = it.next()
-        Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda().to(tdt).contiguous()
-        Td = torch.from_numpy(one_hot_void_last(L, n_classes)).cuda().to(tdt).contiguous()
-        return Xd, Td
-
-    def evaluate(it):
-        """(mean loss, mean accuracy, Jaccard counts (2, C)) over the split: val_fn, train_fcn8.py:170-187."""
-        cost = torch.zeros((), dtype=torch.float64, device='cuda')
-        acc_tot, jacc_tot = 0.0, np.zeros((2, n_classes))
-        for _ in range(nb(it)):
-            c, m = trainer.val_step(*batch(it))
-            cost += c
-            acc, jacc, _ = m.result()
-            acc_tot += acc
-            jacc_tot += jacc
-        return float(cost.item()) / nb(it), acc_tot / nb(it), jacc_tot
-
     def save(tag, errors):
         save_param_list(os.path.join(savepath, 'new_fcn8_model_%s.npz' % tag), net.state_arrays(), PARAM_ORDER)
         np.savez(os.path.join(savepath, 'fcn8_errors_%s.npz' % tag), *[np.asarray(e) for e in errors])
 
-    err_train, err_valid, acc_valid, jacc_valid = [], [], [], []
-    patience, best_jacc_val = 0, None
+    def reload_best():
+        """The best weights back into the net's own buffer, in place; False: this run wrote none."""
+        if not os.path.exists(best_path):
+            return False
+        for name, (W, b) in load_param_list(best_path, PARAM_ORDER).items():
+            Wd, bd = net.parameters()[name]
+            Wd.copy_(torch.from_numpy(W).to(tdt))
+            bd.copy_(torch.from_numpy(b).to(tdt))
+        net.refresh()
+        return True
+
+    mean_jaccard = lambda jacc_tot: float(np.mean(train_loop.per_class_jaccard(jacc_tot)))
+    class_jaccard = lambda jacc_tot: float(train_loop.per_class_jaccard(jacc_tot)[int(early_stop_class)])
     say('Start training')
-    for epoch in range(num_epochs):
-        start_time = time.time()
-        cost = torch.zeros((), dtype=torch.float64, device='cuda')
-        for _ in range(nb(train_iter)):
-            cost += trainer.train_step(*batch(train_iter))     # device scalar: one host read per epoch
-        err_train.append(float(cost.item()) / nb(train_iter))
-
-        err, acc, jacc_tot = evaluate(val_iter)
-        err_valid.append(err)
-        acc_valid.append(acc)
-        with np.errstate(invalid='ignore', divide='ignore'):
-            per_class = jacc_tot[0, :] / jacc_tot[1, :]
-        jacc_valid.append(float(np.mean(per_class)) if early_stop_class is None
-                          else float(per_class[int(early_stop_class)]))                 # :189-192
-
-        out_str = 'EPOCH %i: Avg epoch training cost train %f, cost val %f, acc val %f, jacc val %f took %f s'
-        out_str = out_str % (epoch, err_train[epoch], err_valid[epoch], acc_valid[epoch], jacc_valid[epoch],
-                             time.time() - start_time)
-        print(out_str)
-        with open(os.path.join(savepath, 'fcn8_output.log'), 'a') as f:
-            f.write(out_str + '\n')
-
-        errors = (err_valid, err_train, acc_valid, jacc_valid)                          # :215-217
-        if epoch == 0:                                                                  # :208-224
-            best_jacc_val = jacc_valid[epoch]
-        elif epoch > 1 and jacc_valid[epoch] > best_jacc_val:
-            best_jacc_val = jacc_valid[epoch]
-            patience = 0
-            save('best', errors)
-        else:
-            patience += 1
-            save('last', errors)
-
-        if patience == max_patience or epoch == num_epochs - 1:                         # :227-271
-            best = os.path.join(savepath, 'new_fcn8_model_best.npz')
-            if test_iter is not None and os.path.exists(best):
-                # the best weights back into the net's own buffer, in place
-                for name, (W, b) in load_param_list(best, PARAM_ORDER).items():
-                    Wd, bd = net.parameters()[name]
-                    Wd.copy_(torch.from_numpy(W).to(tdt))
-                    bd.copy_(torch.from_numpy(b).to(tdt))
-                net.refresh()
-                err, acc, jacc_tot = evaluate(test_iter)
-                with np.errstate(invalid='ignore', divide='ignore'):
-                    jacc = float(np.mean(jacc_tot[0, :] / jacc_tot[1, :]))
-                print('FINAL MODEL: err test % f, acc test %f, jacc test %f' % (err, acc, jacc))
-            elif test_iter is not None:
-                # (the reference would fail here: it never wrote a best model in a run this short)
-                say('no new_fcn8_model_best.npz was written: the test pass is skipped')
-            if os.path.abspath(savepath) != os.path.abspath(loadpath):
-                say('Copying model and other training files to {}'.format(loadpath))
-                shutil.copytree(savepath, loadpath, dirs_exist_ok=True)
-            break
-    return {'err_train': err_train, 'err_valid': err_valid, 'acc_valid': acc_valid, 'jacc_valid': jacc_valid,
-            'savepath': savepath, 'loadpath': loadpath}
+    lists = train_loop.run_epochs(
+        num_epochs, max_patience, rule=train_loop.fcn8_rule,                            # :208-224, `epoch > 1` kept
+        train_pass=lambda: train_loop.train_steps(trainer, train_iter, nb(train_iter), n_classes),
+        n_train=nb(train_iter), val_pass=lambda: train_loop.evaluate(trainer, val_iter, nb(val_iter), n_classes),
+        metric=mean_jaccard if early_stop_class is None else class_jaccard, save=save,  # :189-192
+        log_path=os.path.join(savepath, 'fcn8_output.log'),
+        test_pass=None if test_iter is None else
+        lambda: train_loop.evaluate(trainer, test_iter, nb(test_iter), n_classes),
+        test_metric=mean_jaccard, reload_best=reload_best, best_name='new_fcn8_model_best.npz',
+        savepath=savepath, loadpath=loadpath, say=say)
+    return dict(zip(('err_train', 'err_valid', 'acc_valid', 'jacc_valid'), lists), savepath=savepath,
+                loadpath=loadpath)
 
 
 def make_parser():
-    parser = argparse.ArgumentParser(description='FCN-8 training')
-    parser.add_argument('-dataset', default='camvid', help='Dataset.')
+    parser = train_loop.make_parser('FCN-8 training', SWITCHES)
     parser.add_argument('-learning_rate', default=0.0001, help='Learning Rate')
     parser.add_argument('-penal_cst', default=0.0, help='regularization constant')
-    parser.add_argument('--num_epochs', '-ne', type=int, default=750,
-                        help='Optional. Int to indicate the max number of epochs.')
     parser.add_argument('-max_patience', type=int, default=100, help='Max patience')
-    parser.add_argument('-batch_size', type=_json, default=[10, 1, 1], help='Batch size [train, val, test] (JSON)')
-    parser.add_argument('-data_augmentation', type=_json, default=dict(DATA_AUGMENTATION),
+    parser.add_argument('-batch_size', type=train_loop.json_arg, default=[10, 1, 1],
+                        help='Batch size [train, val, test] (JSON)')
+    parser.add_argument('-data_augmentation', type=train_loop.json_arg, default=dict(DATA_AUGMENTATION),
                         help='use data augmentation (JSON): recorded, names the experiment folder; crop_size sets '
                              'the synthetic image size')
     parser.add_argument('-early_stop_class', type=int, default=None, help='class to early stop on')
     parser.add_argument('-train_from_0_255', type=_bool, default=False,
                         help='Whether to train from images within 0-255 range')
     parser.add_argument('-pascal', type=_bool, default=False, help='start from PASCAL .mat weights (refused)')
-    parser.add_argument('--synthetic', action='store_true', help='seeded synthetic split (no dataset here)')
-    parser.add_argument('--savepath', type=str, default=SAVEPATH)
-    parser.add_argument('--loadpath', type=str, default=LOADPATH, help='default: --savepath')
-    parser.add_argument('--resume', action='store_true', help='start from new_fcn8_model_best.npz under --loadpath')
-    parser.add_argument('--dtype', default='float32', help='float32 | float64')
-    parser.add_argument('--wgrad', choices=['f32', 'bf16'], default='f32',
-                        help='float32: operand precision of the 3x3 weight gradients (bf16: v_mfma_f32_32x32x16_bf16 '
-                             'on operands rounded once, fp32 accumulation; everything else stays float32).  Recorded '
-                             'in config.txt, not in the experiment name')
-    parser.add_argument('--dgrad', choices=['f32', 'bf16'], default='f32',
-                        help="float32: operand precision of the backward pass's twelve 3x3 data gradients (bf16: "
-                             'v_mfma_f32_32x32x16_bf16 on the parameters and g_z rounded once, fp32 accumulation).  '
-                             'Recorded in config.txt, not in the experiment name')
-    parser.add_argument('--kxk', choices=['f32', 'bf16'], default='f32',
-                        help="float32: operand precision of fc6's and fc7's weight and data gradients (bf16: "
-                             'v_mfma_f32_32x32x16_bf16 on operands rounded once, fp32 accumulation).  '
-                             'Recorded in config.txt, not in the experiment name')
-    parser.add_argument('--fwd', choices=['f32', 'bf16'], default='f32',
-                        help="float32: operand precision of the training and validation forward's 3x3 layers, fc6 "
-                             'and fc7 (bf16: v_mfma_f32_32x32x16_bf16 on operands rounded once, fp32 accumulation, '
-                             'fp32 maps).  Recorded in config.txt, not in the experiment name')
-    parser.add_argument('--seed', type=int, default=0, help='initial weights and the dropout generator')
     parser.add_argument('--width_div', type=int, default=1, help='divide the channel counts (small nets for tests)')
     parser.add_argument('--fc_channels', type=int, default=4096)
-    parser.add_argument('--n_images', type=int, default=20, help='images per synthetic split')
-    parser.add_argument('--image_size', type=int, nargs=2, default=None)
-    parser.add_argument('--max_batches', type=int, default=None, help='cap on the batches of each pass (tests)')
     return parser
 
 
@@ -300,22 +195,18 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    args = parse_args(argv)
-    try:
-        check_supported(args.dataset, args.savepath, args.pascal, args.dtype, args.batch_size, args.num_epochs,
-                        args.max_patience, args.learning_rate, args.penal_cst, args.early_stop_class, args.wgrad,
-                        args.dgrad, args.kxk, args.fwd)
-    except (NotImplementedError, ValueError, TypeError) as e:
-        print('train_fcn8.py: ' + str(e), file=sys.stderr)
-        return 2
-    train(args.dataset, float(args.learning_rate), float(args.penal_cst), int(args.num_epochs),
-          int(args.max_patience), data_augmentation=args.data_augmentation, batch_size=args.batch_size,
-          early_stop_class=args.early_stop_class, savepath=args.savepath, loadpath=args.loadpath,
-          resume=args.resume, train_from_0_255=args.train_from_0_255, synthetic=args.synthetic,
-          n_images=args.n_images, image_size=args.image_size, seed=args.seed, dtype=args.dtype,
-          width_div=args.width_div, fc_channels=args.fc_channels, max_batches=args.max_batches, wgrad=args.wgrad,
-          dgrad=args.dgrad, kxk=args.kxk, fwd=args.fwd)
-    return 0
+    a = parse_args(argv)
+    return train_loop.main(
+        'train_fcn8.py',
+        lambda: check_supported(a.dataset, a.savepath, a.pascal, a.dtype, a.batch_size, a.num_epochs, a.max_patience,
+                                a.learning_rate, a.penal_cst, a.early_stop_class, a.wgrad, a.dgrad, a.kxk, a.fwd),
+        lambda: train(a.dataset, float(a.learning_rate), float(a.penal_cst), int(a.num_epochs), int(a.max_patience),
+                      data_augmentation=a.data_augmentation, batch_size=a.batch_size,
+                      early_stop_class=a.early_stop_class, savepath=a.savepath, loadpath=a.loadpath, resume=a.resume,
+                      train_from_0_255=a.train_from_0_255, synthetic=a.synthetic, n_images=a.n_images,
+                      image_size=a.image_size, seed=a.seed, dtype=a.dtype, width_div=a.width_div,
+                      fc_channels=a.fc_channels, max_batches=a.max_batches, wgrad=a.wgrad, dgrad=a.dgrad, kxk=a.kxk,
+                      fwd=a.fwd))
 
 
 if __name__ == '__main__':
