@@ -1341,6 +1341,42 @@ int64_t iiseg_conv_fwd_kxk_bf16_workspace_elems(const iiseg_conv_fwd_kxk_desc* d
 int iiseg_conv_fwd_kxk_bf16(void* stream, const iiseg_conv_fwd_kxk_desc* d, const float* x, const float* W,
                             const float* bias, float* ws, float* z);
 
+/* ---------------------------------------------------------------------------------------
+ * Training forward of FC-DenseNet's dense-block layer -- BatchNorm with batch statistics, ReLU, zero-padded 3 x 3
+ * convolution, bias, dropout mask -- as one launch on the 16-bit matrix pipe (fwd='bf16' on FC-DenseNet;
+ * csrc/bnrelu_conv_bf16.hip; backward-compatible addition).  fp32 tensors:
+ *   y = (x[b][c][i][j] - mean[c]) * (gamma[c] * inv_std[c]) + beta[c]       (iiseg_bn_relu_f32's expression)
+ *   t = max(y, 0) inside the map, exactly 0 on the padding ring
+ *   z[b][co][i][j] = (sum_{c<n,ky,kx} bf16(W[co][c][ky][kx]) bf16(tpad[b][c][i + ky][j + kx]) + bias[co])
+ *                    * keep[b][co][i][j] * (1 / (1 - p))                    (iiseg_dropout_apply_f32's expression;
+ *                                                                            keep NULL: no factor)
+ * every operand rounded once (to nearest, ties to even) as it is staged, v_mfma_f32_16x16x32_bf16 accumulating in
+ * fp32 in a fixed order, the slabs of a split reduction over input channels added in slab order before bias, mask
+ * and scale: no atomics, the same inputs give the same bits, and an element's bits do not depend on B (the slab rule
+ * reads n, Cout, H and W only).  No packed copy of W: the parameter is read as it is.
+ *   x    : (B, cap, H, W) contiguous, channels [0, n) read.     beta, gamma, mean, inv_std : n floats at least.
+ *   W    : (Cout, n, 3, 3) contiguous ('oihw').    bias : Cout floats.    keep : (B, Cout, H, W) contiguous or NULL.
+ *   z    : (B, out_cap, H, W) contiguous; channels [out_c0, out_c0 + Cout) are written, nothing else.  z may be x
+ *          itself (cap == out_cap) with out_c0 >= n.
+ *   ws   : iiseg_bnrelu_conv_fwd_bf16_workspace_elems(d) floats (0 with one slab).
+ * NULL d, x, a BatchNorm vector, W, bias, z (ws with several slabs) IISEG_ERR_NULL; non-positive sizes, cap < n,
+ * out_c0 < 0 or out_c0 + Cout > out_cap, more than 65535 channels or images, H W > 2^28, Cout n 9 >= 2^31, p outside
+ * [0, 1) IISEG_ERR_SHAPE; z overlapping what is read of x (other than as above), W, keep or ws
+ * IISEG_ERR_UNSUPPORTED.  All before any launch.
+ * ------------------------------------------------------------------------------------- */
+typedef struct iiseg_bnrelu_conv_desc {
+    int32_t B, n, cap, Cout, H, W;
+    int32_t out_cap, out_c0;
+} iiseg_bnrelu_conv_desc;
+
+/* host only: IISEG_OK or the status a launch of `d` would return */
+int iiseg_bnrelu_conv_fwd_bf16_check(const iiseg_bnrelu_conv_desc* d);
+int iiseg_bnrelu_conv_fwd_bf16_slabs(const iiseg_bnrelu_conv_desc* d);
+int64_t iiseg_bnrelu_conv_fwd_bf16_workspace_elems(const iiseg_bnrelu_conv_desc* d);
+int iiseg_bnrelu_conv_fwd_bf16(void* stream, const iiseg_bnrelu_conv_desc* d, const float* x, const float* beta,
+                               const float* gamma, const float* mean, const float* inv_std, const float* W,
+                               const float* bias, const float* keep, float p, float* ws, float* z);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,11 @@ class ConvFwdKxKDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('B', 'Cin', 'Cout', 'H', 'W', 'K', 'relu', 'reserved')]
 
 
+class BnReluConvDesc(C.Structure):
+    """struct iiseg_bnrelu_conv_desc"""
+    _fields_ = [(n, C.c_int32) for n in ('B', 'n', 'cap', 'Cout', 'H', 'W', 'out_cap', 'out_c0')]
+
+
 L2_MAX_RANGES = 64
 BN_BWD_REDUCE, BN_BWD_APPLY = 1, 2       # iiseg_bn_relu_bwd_*'s stages
 
@@ -353,6 +358,11 @@ SIGNATURES = {
     'iiseg_conv_fwd_kxk_bf16_slabs': (C.c_int, [C.POINTER(ConvFwdKxKDesc)]),
     'iiseg_conv_fwd_kxk_bf16_workspace_elems': (_i64, [C.POINTER(ConvFwdKxKDesc)]),
     'iiseg_conv_fwd_kxk_bf16': (C.c_int, [_vp, C.POINTER(ConvFwdKxKDesc)] + [_vp] * 5),
+    # FC-DenseNet's dense-block layer, BatchNorm + ReLU + 3x3 + bias + dropout mask in one launch (fwd='bf16')
+    'iiseg_bnrelu_conv_fwd_bf16_check': (C.c_int, [C.POINTER(BnReluConvDesc)]),
+    'iiseg_bnrelu_conv_fwd_bf16_slabs': (C.c_int, [C.POINTER(BnReluConvDesc)]),
+    'iiseg_bnrelu_conv_fwd_bf16_workspace_elems': (_i64, [C.POINTER(BnReluConvDesc)]),
+    'iiseg_bnrelu_conv_fwd_bf16': (C.c_int, [_vp, C.POINTER(BnReluConvDesc)] + [_vp] * 8 + [C.c_float] + [_vp] * 2),
 }
 
 _lib = None

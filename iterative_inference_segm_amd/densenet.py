@@ -214,7 +214,7 @@ class FCDenseNet(Trainable, Views):
 
     def __init__(self, params, n_classes=11, layer=('pool4',), n_layers_per_block=LAYERS_PER_BLOCK,
                  n_pool=N_POOL, growth=GROWTH, device='cuda', dtype=torch.float32, mma=None, trainable=False,
-                 dropout=0.2, wgrad='f32', deconv='f32'):
+                 dropout=0.2, wgrad='f32', deconv='f32', fwd='f32'):
         """mma: 'f32' (default) | 'bf16' (bf16 MFMA operands, fp32 NCHW activations) | 'bf16c8'
         (configs[2] as BASELINE names it: the dense-block stacks as bf16 C8 tensors, every
         BN_ReLU_Conv of a dense block one launch of the 16-row C8 kernel with BatchNorm + ReLU applied
@@ -234,10 +234,18 @@ class FCDenseNet(Trainable, Views):
         deconv: operand precision of `backward`'s TransitionUp gradients, the 'tu' layers' dW, db and g_x ('f32'
         default; 'bf16' = ops.deconv_wgrad / ops.deconv_dgrad with mma='bf16', trainable float32 only: x, g and the
         layer's own fp32 parameter rounded once to bf16 as they are staged, fp32 accumulation, db the sum of the
-        unrounded g in that kernel's own order; nothing else changes: DESIGN.md section 23)."""
+        unrounded g in that kernel's own order; nothing else changes: DESIGN.md section 23).
+        fwd: operand precision of `forward_train`'s dense-block layers, the 'brc' layers' BatchNorm + ReLU + 3x3
+        convolution + dropout, in training and in val_fn's deterministic forward ('f32' default; 'bf16' = ONE
+        ops.bnrelu_conv_fwd launch per layer straight into the stack's next slice, trainable float32 only: t and the
+        layer's own fp32 parameter rounded once to bf16 as they are staged, fp32 accumulation, bn_relu's and
+        dropout_apply's expressions in fp32 around it; the first convolution, TransitionDown, TransitionUp, the score
+        layer, `backward` -- which still forms t again in fp32 --, the parameters, checkpoints and running averages
+        stay as they are, and so does the non-trainable module: DESIGN.md section 25)."""
         mma = mma or ops.DEFAULT_MMA
         self.wgrad = check_mode('wgrad', wgrad, dtype, trainable)
         self.deconv = check_mode('deconv', deconv, dtype, trainable)
+        self.fwd = check_mode('fwd', fwd, dtype, trainable)
         self.trainable = bool(trainable)
         self.dropout = float(dropout)
         self._tsaved = None
@@ -376,7 +384,16 @@ class FCDenseNet(Trainable, Views):
                 stack.added(conv.Cout)
                 continue
             stack = s['stacks'][e['sid']]
-            if e['kind'] == 'brc':
+            if e['kind'] == 'brc' and self.fwd == 'bf16':
+                # BatchNorm, ReLU, convolution, bias and mask in one launch, straight into the stack's next slice
+                n, k = e['n'], None
+                if drop:
+                    k = s['keeps'][e['ki']] = self._draw((B, g) + tuple(stack.buf.shape[2:]),
+                                                         None if keeps is None else keeps[e['ki']], generator, dev)
+                ops.bnrelu_conv_fwd(stack.buf, n, (L['beta'], L['gamma'], stack.mean, stack.inv_std), conv.W, conv.b,
+                                    out=stack.buf, out_c0=n, keep=k, p=p)
+                stack.added(g)
+            elif e['kind'] == 'brc':
                 n = e['n']
                 t = ops.bn_relu(stack.buf, n, L['beta'], L['gamma'], stack.mean, stack.inv_std)
                 if drop:
@@ -769,7 +786,7 @@ def build_fcdensenet(input_var=None, layer=('pool4',), nb_in_channels=3, n_class
     `arr_%d` .npz (BN: beta, gamma, mean, inv_std; conv: W, b -- P10/P14).  trainable=True builds the module
     `train.DenseNetTrainer` trains (float32 on mma='f32', or float64).  net_kw: further
     keywords of `FCDenseNet` (a smaller net: n_layers_per_block, n_pool, growth -- and n_first for the plan of
-    a checkpoint; dropout; wgrad; deconv)."""
+    a checkpoint; dropout; wgrad; deconv; fwd)."""
     n_first = net_kw.pop('n_first', None)
     if params is None:
         if not weight_path:

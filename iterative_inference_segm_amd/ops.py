@@ -2642,6 +2642,89 @@ def conv_fwd_kxk(x, W, b=None, relu=True, out=None):
     return out
 
 
+def bnrelu_conv_desc(stack_shape, n, Cout, out_cap=None, out_c0=0):
+    """The iiseg_bnrelu_conv_desc of a dense-block layer with `Cout` filters on the first `n` channels of a stack of
+    `stack_shape` = (B,cap,H,W), written at channel `out_c0` of a tensor with `out_cap` channels (default: a dense
+    (B,Cout,H,W) one)."""
+    d = _lib.BnReluConvDesc()
+    d.B, d.cap, d.H, d.W = (int(v) for v in stack_shape)
+    d.n, d.Cout, d.out_c0 = int(n), int(Cout), int(out_c0)
+    d.out_cap = int(Cout) if out_cap is None else int(out_cap)
+    return d
+
+
+def bnrelu_conv_fwd(stack, n, bn, W, b, out=None, out_c0=0, keep=None, p=0.0):
+    """The training forward of a dense-block layer of FC-DenseNet as ONE launch on the 16-bit matrix pipe
+    (csrc/bnrelu_conv_bf16.hip): t = relu(BatchNorm(stack[:, :n])) with bn = (beta, gamma,
+    mean, inv_std) -- `bn_relu`'s expression, the padding ring zeros of t --, the zero-padded 3x3 layer with the fp32
+    'oihw' parameter W (Cout,n,3,3), read as it is, and bias b, then `dropout_apply`'s expression with the 0/1 mask
+    `keep` (B,Cout,H,W) and p (keep=None: no factor): z = (sum bf16(W) bf16(t) + b) * keep / (1 - p).  W and t are
+    rounded once (nearest, ties to even) as they are staged, v_mfma_f32_16x16x32_bf16 accumulates in fp32 in a fixed
+    order, the slabs of a split reduction are added in slab order before bias, mask and scale.  Into channels
+    [out_c0, out_c0 + Cout) of `out` (B,out_cap,H,W) -- which may be `stack` itself with out_c0 >= n -- and nothing
+    else of it; out=None: a new dense (B,Cout,H,W) tensor.  float32 contiguous device tensors only."""
+    what = 'bnrelu_conv_fwd'
+    if not isinstance(bn, (tuple, list)) or len(bn) != 4:
+        raise ValueError('%s: bn must be (beta, gamma, mean, inv_std)' % what)
+    beta, gamma, mean, inv_std = bn
+    named = (('stack', stack), ('beta', beta), ('gamma', gamma), ('mean', mean), ('inv_std', inv_std), ('W', W),
+             ('b', b), ('out', out), ('keep', keep))
+    _need_f32(what, named, required=('stack', 'beta', 'gamma', 'mean', 'inv_std', 'W', 'b'))
+    n, out_c0 = int(n), int(out_c0)
+    if stack.dim() != 4 or min(stack.shape) < 1 or not 1 <= n <= stack.shape[1]:
+        raise ValueError('%s: the first %d channels of a stack %s' % (what, n, tuple(stack.shape)))
+    B, cap, H, Wd = (int(v) for v in stack.shape)
+    if W.dim() != 4 or tuple(W.shape[1:]) != (n, 3, 3) or W.shape[0] < 1:
+        raise ValueError("%s: W %s is not a 3x3 'oihw' parameter on %d channels" % (what, tuple(W.shape), n))
+    Cout = int(W.shape[0])
+    if tuple(b.shape) != (Cout,):
+        raise ValueError('%s: b %s for %d output channels' % (what, tuple(b.shape), Cout))
+    for name, v in (('beta', beta), ('gamma', gamma), ('mean', mean), ('inv_std', inv_std)):
+        if v.dim() != 1 or v.numel() < n:
+            raise ValueError('%s: %s %s for %d channels' % (what, name, tuple(v.shape), n))
+    if out is None:
+        if out_c0 != 0:
+            raise ValueError('%s: out_c0 = %d without `out`' % (what, out_c0))
+    else:
+        if out.dim() != 4 or (out.shape[0], out.shape[2], out.shape[3]) != (B, H, Wd) or out_c0 < 0 or \
+                out_c0 + Cout > out.shape[1]:
+            raise ValueError('%s: channels [%d, %d) of out %s, the map is %s' % (what, out_c0, out_c0 + Cout,
+                                                                               tuple(out.shape), (B, Cout, H, Wd)))
+        if out.data_ptr() == stack.data_ptr() and (out.shape[1] != cap or out_c0 < n):
+            raise ValueError('%s: out is the stack and out_c0 = %d < n = %d: the channels read and written would '
+                             'overlap' % (what, out_c0, n))
+    if keep is not None and tuple(keep.shape) != (B, Cout, H, Wd):
+        raise ValueError('%s: keep %s, the map is %s' % (what, tuple(keep.shape), (B, Cout, H, Wd)))
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError('%s: p = %r is not in [0, 1)' % (what, p))
+    for name, t in named:
+        if t is not None and not t.is_contiguous():
+            raise ValueError('%s: %s must be contiguous' % (what, name))
+    for name, t in named:
+        if t is not None and not t.is_cuda:
+            raise ValueError('%s: %s must be a device tensor (got %s)' % (what, name, t.device))
+    d = bnrelu_conv_desc((B, cap, H, Wd), n, Cout, None if out is None else out.shape[1], out_c0)
+    lib = _lib.load()
+    nws = _count(lib.iiseg_bnrelu_conv_fwd_bf16_workspace_elems(C.byref(d)),
+                 'iiseg_bnrelu_conv_fwd_bf16_workspace_elems')
+    if out is None:
+        out = torch.empty((B, Cout, H, Wd), dtype=torch.float32, device=stack.device)
+    ws = _workspace('f32', nws, stack.device) if nws else None
+    kern = 'bnrelu_conv_bf16_kernel'
+    _launch(kern, 2.0 * n * Cout * 9 * B * H * Wd, lib.iiseg_bnrelu_conv_fwd_bf16, C.byref(d), _ptr(stack),
+            _ptr(beta), _ptr(gamma), _ptr(mean), _ptr(inv_std), _ptr(W), _ptr(b), _ptr(keep), p, _ptr(ws), _ptr(out))
+    if CONV_PROFILE is not None:
+        _add_bytes(kern, bnrelu_conv_bytes(B, n, Cout, H, Wd, keep is not None) + 8.0 * nws)
+    return out
+
+
+def bnrelu_conv_bytes(B, n, Cout, H, W, keep):
+    """The byte model of one `bnrelu_conv_fwd` launch without a split: the n stack planes read once, the Cout planes
+    written once (the mask's read once), the parameter read once."""
+    return 4.0 * (B * H * W * (n + Cout * (2 if keep else 1)) + Cout * n * 9)
+
+
 def deconv_desc(x_shape, Cout, K, stride, window=None):
     """The iiseg_deconv_desc of a transposed convolution on x (B,Cin,H,W); window = (oy0, ox0, OH, OW) of its
     full output, default all of it."""

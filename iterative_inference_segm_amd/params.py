@@ -6,8 +6,8 @@ Plain torch: works on host tensors too, needs no library.  torch is imported whe
 with the module: the training drivers read the switches' names before they parse their arguments."""
 
 # The 16-bit training switches (keyword and attribute of the trainable modules -- FCN8 and StandardDAE have
-# several, FCDenseNet has 'wgrad' and 'deconv' --, option of the drivers): what each is called in messages.  Every
-# one takes MODES_16BIT.
+# several, FCDenseNet has 'wgrad', 'deconv' and 'fwd' (there: the dense-block layers' fused BatchNorm + ReLU +
+# convolution) --, option of the drivers): what each is called in messages.  Every one takes MODES_16BIT.
 SWITCHES_16BIT = {'wgrad': 'weight gradient', 'dgrad': 'data gradient', 'kxk': 'fc6 / fc7 gradients',
                   'fwd': 'training forward', 'deconv': 'transposed-convolution gradients'}
 MODES_16BIT = ('f32', 'bf16')

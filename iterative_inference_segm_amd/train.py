@@ -218,7 +218,8 @@ class DenseNetTrainer(_NetTrainer):
     """For an FCDenseNet (the reference has no FC-DenseNet training script: optimizer and
     schedule are restated from upstream FC-DenseNet), under RMSprop (default) or adam; the weight decay is over every
     W and every gamma (lasagne marks gamma regularizable; never beta or a bias); train_step(X, T, keeps), one mask
-    per 'brc' / 'td' layer."""
+    per 'brc' / 'td' layer.  The 16-bit modes (wgrad, deconv, fwd) are the net's own: train_fn and val_fn run whatever
+    its forward_train and backward run."""
 
     _NET = 'an FCDenseNet'
 

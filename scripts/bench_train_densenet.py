@@ -2,7 +2,8 @@
 """One training step of FC-DenseNet103 (11 classes, default synthetic weights) on 224x224 crops: one JSON line.
 
     python scripts/bench_train_densenet.py [--batches 3 10] [--size 224x224] [--reps 5] [--dtypes float32 float64]
-                                           [--wgrad f32 f32 bf16] [--deconv f32 f32 bf16] [--out profiles/NAME.json]
+                                           [--wgrad f32 f32 bf16] [--deconv f32 f32 bf16] [--fwd f32 f32 bf16]
+                                           [--out profiles/NAME.json]
 
 Per (precision, batch): step ms (median of `reps` warm steps between two HIP events: forward, loss, backward, L2 term,
 RMSprop, refresh) and images/s; then, from the dispatch times of ONE more step run under the library's launch
@@ -31,6 +32,17 @@ backward's order, its two launches (`deconv_layers`: weight gradient and data gr
 next to its byte model over `--stream_gbs` and its nominal 2 Cin Cout (products inside the window) over
 `--peak_tflops_bf16`).  With both modes among the rows, `deconv_compare` gives per batch the launches' sums, the step
 against the spread of the fp32 rows, and every bf16 launch that took longer than the faster fp32 launch it replaces.
+--fwd: the modes of the dense-block layers' training forward to run (FCDenseNet's `fwd`; bf16: float32 only; DESIGN.md
+section 25), one result row per (wgrad mode, deconv mode, fwd mode, batch) in the same process; named more than once it
+is the study of this switch.  Every row lists the forward launch of every dense-block layer from the profiled step
+(`fwd_brc_layers`: the fp32 convolution launch alone, or the fused launch) and their sums per resolution
+(`fwd_brc_by_resolution`).  A bf16 row also times, for the widest and the narrowest dense-block layer of each
+resolution on the step's own stack (`fwd_forms`, five back-to-back launches between two HIP events each): the fused
+launch with and without a mask, the fp32 chain it replaces (bn_relu + convolution + dropout_apply + slice copy) and
+the fp32 convolution launch alone, the fused launch's byte model (ops.bnrelu_conv_bytes) over `--stream_gbs` and its
+nominal work over `--peak_tflops_bf16`.  With both modes among the rows, `fwd_compare` gives per batch the step against
+the spread of the fp32 rows, the peak memory, the launches' sums and every fused launch that took longer than the
+fp32 convolution launch of the same layer in either fp32 row.
 --out: the JSON record also into that file.
 Reads nothing outside the repository.
 """
@@ -105,6 +117,73 @@ def forms(net, B, dt, peak16):
     return out
 
 
+def brc_forward(net, fwd_rows, B):
+    """The forward launch of every dense-block layer in the profiled step's forward rows, in creation order: the row
+    whose nominal work is the layer's (2 n g 9 B H W: the fp32 convolution's and the fused launch's alike)."""
+    sv, g = net._tsaved, net.growth
+    out, i = [], 0
+    for e in net._steps:
+        if e['kind'] != 'brc':
+            continue
+        hw = tuple(sv['stacks'][e['sid']].buf.shape[2:])
+        want = 2.0 * e['n'] * g * 9 * B * hw[0] * hw[1]
+        while i < len(fwd_rows) and fwd_rows[i][1] != want:
+            i += 1
+        if i == len(fwd_rows):
+            raise RuntimeError('no forward launch found for dense-block layer %d' % e['li'])
+        out.append({'li': e['li'], 'resolution': '%dx%d' % hw, 'cin': e['n'], 'kernel': fwd_rows[i][0],
+                    'ms': round(fwd_rows[i][2], 5)})
+        i += 1
+    return out
+
+
+def fwd_forms(net, B, dt, stream, peak16):
+    """The widest and the narrowest dense-block layer of each resolution, on the step's own stack: the fused launch
+    (with and without a mask) into the stack's slice, the fp32 chain it replaces and the fp32 convolution alone."""
+    sv, g, p = net._tsaved, net.growth, net.dropout
+    by_res = {}
+    for e in net._steps:
+        if e['kind'] == 'brc':
+            hw = tuple(sv['stacks'][e['sid']].buf.shape[2:])
+            lo, hi = by_res.get(hw, (e, e))
+            by_res[hw] = (e if e['n'] < lo['n'] else lo, e if e['n'] > hi['n'] else hi)
+    out = []
+    gen = torch.Generator(device='cuda').manual_seed(11)
+    for hw, pair in sorted(by_res.items(), reverse=True):
+        for which, e in zip(('narrowest', 'widest'), pair):
+            st, L, n = sv['stacks'][e['sid']], net.layers[e['li']], e['n']
+            conv = L['conv']
+            bn = (L['beta'], L['gamma'], st.mean, st.inv_std)
+            keep = (torch.rand((B, g) + hw, generator=gen, device='cuda') >= p).to(dt)
+            fused = lambda k: ops.bnrelu_conv_fwd(st.buf, n, bn, conv.W, conv.b, out=st.buf, out_c0=n, keep=k, p=p)
+
+            def chain():
+                t = ops.bn_relu(st.buf, n, *bn)
+                z = conv(t)
+                ops.dropout_apply(z, keep, p)
+                st.buf[:, n:n + g].copy_(z)
+            t = ops.bn_relu(st.buf, n, *bn)
+            z = torch.empty((B, g) + hw, dtype=dt, device='cuda')
+            ms = {'fused_keep': timed(lambda: fused(keep)), 'fused_no_keep': timed(lambda: fused(None)),
+                  'f32_chain': timed(chain), 'f32_conv_alone': timed(lambda: conv(t, out=z)),
+                  'fused_keep_again': timed(lambda: fused(keep))}
+            d = ops.bnrelu_conv_desc(tuple(st.buf.shape), n, g, st.buf.shape[1], n)
+            best = min(ms['fused_keep'], ms['fused_keep_again'])
+            nbytes = ops.bnrelu_conv_bytes(B, n, g, hw[0], hw[1], True)
+            flops = 2.0 * n * g * 9 * B * hw[0] * hw[1]
+            out.append({'resolution': '%dx%d' % hw, 'layer': which, 'li': e['li'], 'cin': n, 'cout': g,
+                        'slabs': int(_lib.load().iiseg_bnrelu_conv_fwd_bf16_slabs(C.byref(d))),
+                        **{k + '_ms': round(v, 5) for k, v in ms.items()},
+                        'model_mb': round(nbytes / 1e6, 3),
+                        'model_us_at_stream': round(nbytes / (stream * 1e9) * 1e6, 2),
+                        'fused_fraction_of_stream': round(nbytes / (best * 1e-3) / 1e9 / stream, 4),
+                        'fused_fraction_of_peak_bf16': round(flops / (best * 1e-3) / (peak16 * 1e12), 5),
+                        'fused_over_f32_chain': round(best / ms['f32_chain'], 4),
+                        'fused_over_f32_conv_alone': round(best / ms['f32_conv_alone'], 4)})
+            del t, z, keep
+    return out
+
+
 DECONV_KERNELS = {'deconv_wgrad_kernel': 'wgrad', 'deconv_wgrad_bf16_kernel': 'wgrad',
                   'deconv_dgrad_kernel': 'dgrad', 'deconv_dgrad_bf16_kernel': 'dgrad'}
 
@@ -143,9 +222,10 @@ def deconv_layers(net, back, B, mode, stream, peak16):
     return out
 
 
-def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.0, deconv='f32', with_forms=True):
+def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.0, deconv='f32', with_forms=True,
+        fwd_mode='f32'):
     params = S.make_densenet_params(layer_plan(), seed=2024)
-    net = FCDenseNet(params, 11, layer=[], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, deconv=deconv)
+    net = FCDenseNet(params, 11, layer=[], dtype=dt, mma='f32', trainable=True, wgrad=wgrad, deconv=deconv, fwd=fwd_mode)
     tr = DenseNetTrainer(net, 11, [11], learning_rate=1e-3, weight_decay=weight_decay, seed=1)
     X = torch.from_numpy(S.make_images(B, H, W, seed=2)).to(dt).cuda().contiguous()
     T = torch.from_numpy(S.make_labels(B, H, W, n_classes=11, seed=3)).to(dt).cuda().contiguous()
@@ -259,7 +339,18 @@ def one(B, H, W, dt, reps, peak, stream, weight_decay, wgrad='f32', peak16=2500.
     extra = {'forms': forms(net, B, dt, peak16)} if wgrad == 'bf16' and with_forms else {}
     tu = deconv_layers(net, back, B, deconv, stream, peak16)
     extra.update(deconv_layers=tu, deconv_ms_total=round(sum(r[w]['ms'] for r in tu for w in ('wgrad', 'dgrad')), 4))
-    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'deconv': deconv, 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
+    brc = brc_forward(net, rows[:n_fwd], B)
+    fres = {}
+    for r in brc:
+        q = fres.setdefault(r['resolution'], dict(launches=0, ms=0.0))
+        q['launches'] += 1
+        q['ms'] += r['ms']
+    extra.update(fwd_brc_layers=brc, fwd_brc_ms_total=round(sum(r['ms'] for r in brc), 4),
+                 fwd_brc_by_resolution=[{'resolution': k, 'launches': q['launches'], 'ms': round(q['ms'], 4)}
+                                        for k, q in fres.items()])
+    if fwd_mode == 'bf16':
+        extra['fwd_forms'] = fwd_forms(net, B, dt, stream, peak16)         # (last: it writes into the saved stacks)
+    return {'dtype': str(dt).replace('torch.', ''), 'wgrad': wgrad, 'deconv': deconv, 'fwd': fwd_mode, 'batch': B, 'size': '%dx%d' % (H, W), 'step_ms': round(step, 3),
             'step_ms_min': round(float(np.min(ms)), 3), 'images_per_s': round(B / (step * 1e-3), 2),
             'parameters': int(net.flat.numel()), 'weights': 'default synthetic (synthetic.make_densenet_params)',
             'max_memory_allocated_mb': round(peak_mem / 2.0 ** 20, 1), 'profiled_launches': len(rows),
@@ -328,6 +419,38 @@ def compare_deconv(rows):
     return out
 
 
+def compare_fwd(rows):
+    """Per (batch, wgrad mode, deconv mode) with fwd f32 and bf16 rows (float32): the step against the spread of the
+    fp32 rows, the peak memory, the dense-block layers' forward launches together, per resolution and one by one -- a
+    fused launch is slower when it took longer than the fp32 CONVOLUTION launch alone of that layer in either row."""
+    out = []
+    for B, wg, dc in sorted({(r['batch'], r['wgrad'], r['deconv']) for r in rows}):
+        mine = [r for r in rows if (r['batch'], r['wgrad'], r['deconv']) == (B, wg, dc) and r['dtype'] == 'float32']
+        f32, b16 = [r for r in mine if r['fwd'] == 'f32'], [r for r in mine if r['fwd'] == 'bf16']
+        if not f32 or not b16:
+            continue
+        slower = []
+        for i, lb in enumerate(b16[0]['fwd_brc_layers']):
+            ref = [r['fwd_brc_layers'][i]['ms'] for r in f32]
+            if lb['ms'] > min(ref):
+                slower.append({'li': lb['li'], 'resolution': lb['resolution'], 'cin': lb['cin'], 'bf16_ms': lb['ms'],
+                               'f32_conv_ms': ref})
+        by_res = [{'resolution': rb['resolution'], 'launches': rb['launches'], 'bf16_ms': rb['ms'],
+                   'f32_conv_ms': [r['fwd_brc_by_resolution'][j]['ms'] for r in f32]}
+                  for j, rb in enumerate(b16[0]['fwd_brc_by_resolution'])]
+        steps = [r['step_ms'] for r in f32]
+        out.append({'batch': B, 'wgrad': wg, 'deconv': dc, 'f32_step_ms': steps,
+                    'f32_step_spread_ms': round(max(steps) - min(steps), 3), 'bf16_step_ms': b16[0]['step_ms'],
+                    'step_gain_ms': round(min(steps) - b16[0]['step_ms'], 3),
+                    'gain_exceeds_spread': bool(min(steps) - b16[0]['step_ms'] > max(steps) - min(steps)),
+                    'f32_max_memory_mb': [r['max_memory_allocated_mb'] for r in f32],
+                    'bf16_max_memory_mb': b16[0]['max_memory_allocated_mb'],
+                    'f32_conv_launches_ms': [r['fwd_brc_ms_total'] for r in f32],
+                    'bf16_fused_launches_ms': b16[0]['fwd_brc_ms_total'], 'by_resolution': by_res,
+                    'fused_launches_slower_than_an_f32_conv_launch': slower})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batches', type=int, nargs='+', default=[3, 10])
@@ -339,6 +462,7 @@ def main():
     ap.add_argument('--weight_decay', type=float, default=1e-4)
     ap.add_argument('--wgrad', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--deconv', nargs='+', choices=['f32', 'bf16'], default=['f32'])
+    ap.add_argument('--fwd', nargs='+', choices=['f32', 'bf16'], default=['f32'])
     ap.add_argument('--peak_tflops_bf16', type=float, default=2500.0)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -347,14 +471,17 @@ def main():
     for name in a.dtypes:
         for mode in (a.wgrad if name == 'float32' else ['f32']):        # (bf16 operands: float32 only)
             for dmode in (a.deconv if name == 'float32' else ['f32']):
-                for B in a.batches:
-                    rows.append(one(B, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs,
-                                    a.weight_decay, mode, a.peak_tflops_bf16, dmode, with_forms=len(a.deconv) == 1))
-                    torch.cuda.empty_cache()
+                for fmode in (a.fwd if name == 'float32' else ['f32']):
+                    for B in a.batches:
+                        rows.append(one(B, H, W, getattr(torch, name), a.reps, a.peak_tflops, a.stream_gbs,
+                                        a.weight_decay, mode, a.peak_tflops_bf16, dmode,
+                                        with_forms=len(a.deconv) == 1 and len(a.fwd) == 1, fwd_mode=fmode))
+                        torch.cuda.empty_cache()
     record = json.dumps({'bench': 'train_densenet', 'device': torch.cuda.get_device_name(0),
                          'peak_tflops': a.peak_tflops, 'peak_tflops_bf16': a.peak_tflops_bf16,
-                         'stream_gbs': a.stream_gbs, 'reps': a.reps, 'wgrad': a.wgrad, 'deconv': a.deconv,
-                         'results': rows, 'wgrad_compare': compare(rows), 'deconv_compare': compare_deconv(rows)})
+                         'stream_gbs': a.stream_gbs, 'reps': a.reps, 'wgrad': a.wgrad, 'deconv': a.deconv, 'fwd': a.fwd,
+                         'results': rows, 'wgrad_compare': compare(rows), 'deconv_compare': compare_deconv(rows),
+                         'fwd_compare': compare_fwd(rows)})
     print(record)
     if a.out:
         with open(a.out, 'w') as f:

@@ -19,6 +19,8 @@ Initial weights without `--resume`: HeUniform W, zero b, gamma 1, beta 0 (upstre
 the experiment folder and the checkpoint names do not change (config.txt records the mode).
 `--deconv bf16` (float32 only) does the same for the data and weight gradients of the five
 TransitionUp layers (K = 3, stride-2 transposed convolutions); config.txt records it, no name changes.
+`--fwd bf16` (float32 only) runs every dense-block layer's BatchNorm + ReLU + 3x3 convolution +
+dropout as one launch on the 16-bit matrix pipe, in training and in validation; config.txt records it, no name changes.
 Data augmentation is not built.  What is refused exits with status 2 and the reason on stderr before any GPU work.
 All arithmetic runs in the HIP kernels of libiiseg_hip.so.
 """
@@ -35,13 +37,14 @@ MODEL = 'FC-DenseNet103_weights_%s.npz'
 LAYERS_PER_BLOCK = [4, 5, 7, 10, 12, 15, 12, 10, 7, 5, 4]
 OPTIMIZERS = ('rmsprop', 'adam')
 MMA_MODES = ('f32', 'bf16', 'bf16c8', 'bf16x3')
-SWITCHES = {'wgrad': 'the zero-padded 3x3 layers', 'deconv': 'the five TransitionUp layers, weights and data'}
+SWITCHES = {'wgrad': 'the zero-padded 3x3 layers', 'deconv': 'the five TransitionUp layers, weights and data',
+            'fwd': 'the dense-block 3x3 layers, in training and validation'}
 
 
 def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2,
                     batch_size=(3, 1, 1), num_epochs=1, max_patience=1, learning_rate=1e-3, lr_decay=0.995,
                     weight_decay=1e-4, layers_per_block=LAYERS_PER_BLOCK, growth=16, n_first=48, image_size=None,
-                    wgrad='f32', deconv='f32'):
+                    wgrad='f32', deconv='f32', fwd='f32'):
     """Everything this build does not train and every bad argument, refused with the reason (host only)."""
     train_loop.check_savepath(savepath)
     train_loop.check_dataset(dataset)
@@ -50,7 +53,7 @@ def check_supported(dataset, savepath, dtype='float32', mma='f32', optimizer='rm
     if dtype not in ('float32', 'float64') or (dtype == 'float32' and mma != 'f32'):
         raise NotImplementedError("training FC-DenseNet: float32 (mma 'f32') or float64; the 16-bit legs (dtype %s, "
                                   'mma %r) are not trained' % (dtype, mma))
-    train_loop.check_switches(dtype, wgrad=wgrad, deconv=deconv)
+    train_loop.check_switches(dtype, wgrad=wgrad, deconv=deconv, fwd=fwd)
     if optimizer not in OPTIMIZERS:
         raise ValueError('Unknown optimizer')
     if not 0.0 <= float(dropout) < 1.0:
@@ -88,21 +91,22 @@ def he_params(plan, seed):
 def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_epochs=750, max_patience=150,
           savepath=None, loadpath=None, batch_size=None, resume=False, synthetic=False, n_images=20, image_size=None,
           seed=0, dtype='float32', mma='f32', optimizer='rmsprop', dropout=0.2, layers_per_block=LAYERS_PER_BLOCK,
-          growth=16, n_first=48, max_batches=None, verbose=True, wgrad='f32', deconv='f32'):
-    """Returns the per-epoch lists and the experiment folder.  wgrad, deconv ('f32' | 'bf16'): the operand precision
-    of the zero-padded 3x3 weight gradients and of the TransitionUp gradients (FCDenseNet's keywords)."""
+          growth=16, n_first=48, max_batches=None, verbose=True, wgrad='f32', deconv='f32', fwd='f32'):
+    """Returns the per-epoch lists and the experiment folder.  wgrad, deconv, fwd ('f32' | 'bf16'): the operand
+    precision of the zero-padded 3x3 weight gradients, of the TransitionUp gradients and of the dense-block layers'
+    forward (FCDenseNet's keywords)."""
     bs = list(batch_size) if batch_size is not None else [3, 1, 1]
     lpb = [int(v) for v in layers_per_block]
     size = tuple(image_size) if image_size is not None else (224, 224)
     check_supported(dataset, savepath, dtype, mma, optimizer, dropout, bs, num_epochs, max_patience, learning_rate,
-                    lr_decay, weight_decay, lpb, growth, n_first, size, wgrad, deconv)
+                    lr_decay, weight_decay, lpb, growth, n_first, size, wgrad, deconv, fwd)
     say = print if verbose else (lambda *a, **k: None)
     savepath, loadpath = train_loop.experiment_folders(
         savepath, loadpath, dataset, EXP_NAME,
         dict(dataset=dataset, learning_rate=learning_rate, lr_decay=lr_decay, weight_decay=weight_decay,
              num_epochs=num_epochs, max_patience=max_patience, batch_size=bs, resume=resume, seed=seed, dtype=dtype,
              optimizer=optimizer, dropout=dropout, layers_per_block=lpb, growth=growth, n_first=n_first,
-             image_size=list(size), wgrad=wgrad, deconv=deconv), say)
+             image_size=list(size), wgrad=wgrad, deconv=deconv, fwd=fwd), say)
 
     # ---- from here on: the GPU ----
     import torch
@@ -128,7 +132,7 @@ def train(dataset, learning_rate=1e-3, lr_decay=0.995, weight_decay=1e-4, num_ep
     else:
         params = he_params(plan, 4321 + int(seed))
     net = FCDenseNet(params, n_classes, layer=[], n_layers_per_block=lpb, n_pool=n_pool, growth=growth, dtype=tdt,
-                     mma='f32', trainable=True, dropout=dropout, wgrad=wgrad, deconv=deconv)
+                     mma='f32', trainable=True, dropout=dropout, wgrad=wgrad, deconv=deconv, fwd=fwd)
     trainer = DenseNetTrainer(net, n_classes, void_labels, optimizer=optimizer, learning_rate=learning_rate,
                               weight_decay=weight_decay, seed=seed)
 
@@ -189,12 +193,13 @@ def main(argv=None):
         'train_fcdensenet.py',
         lambda: check_supported(a.dataset, a.savepath, a.dtype, a.mma, a.optimizer, a.dropout, a.batch_size,
                                 a.num_epochs, a.max_patience, a.learning_rate, a.lr_decay, a.weight_decay,
-                                a.layers_per_block, a.growth, a.n_first, a.image_size, a.wgrad, a.deconv),
+                                a.layers_per_block, a.growth, a.n_first, a.image_size, a.wgrad, a.deconv, a.fwd),
         lambda: train(a.dataset, a.learning_rate, a.lr_decay, a.weight_decay, a.num_epochs, a.max_patience,
                       savepath=a.savepath, loadpath=a.loadpath, batch_size=a.batch_size, resume=a.resume,
                       synthetic=a.synthetic, n_images=a.n_images, image_size=a.image_size, seed=a.seed, dtype=a.dtype,
                       mma=a.mma, optimizer=a.optimizer, dropout=a.dropout, layers_per_block=a.layers_per_block,
-                      growth=a.growth, n_first=a.n_first, max_batches=a.max_batches, wgrad=a.wgrad, deconv=a.deconv))
+                      growth=a.growth, n_first=a.n_first, max_batches=a.max_batches, wgrad=a.wgrad, deconv=a.deconv,
+                      fwd=a.fwd))
 
 
 if __name__ == '__main__':
