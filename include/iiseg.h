@@ -1230,7 +1230,7 @@ int64_t iiseg_conv_wgrad_bf16_workspace_elems(const iiseg_conv_wgrad_desc* d);
 int iiseg_conv_wgrad_bf16(void* stream, const iiseg_conv_wgrad_desc* d, const float* x, const float* gz, float* ws,
                           float* dW, float* db);
 /* The same sums, contract, status codes and NULL rules in the form for few output channels
- * (csrc/conv_wgrad_bf16_co16.hip; backward-compatible addition): blocks of 16 output x 64
+ * (csrc/conv_wgrad_bf16.hip's co16 form; backward-compatible addition): blocks of 16 output x 64
  * input channels on v_mfma_f32_16x16x32_bf16, any Cout (a ragged last block), slabs and workspace of its own plan.
  * The order of the fp32 additions differs from iiseg_conv_wgrad_bf16's, so the bits may; each is deterministic. */
 int iiseg_conv_wgrad_bf16_co16_slabs(const iiseg_conv_wgrad_desc* d);

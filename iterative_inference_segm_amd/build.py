@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB = os.path.join(HERE, 'libiiseg_hip.so')
-SOURCES = ['abi.hip', 'conv_igemm.hip', 'conv_taps.hip', 'conv_wino.hip', 'conv_wino_bf16.hip', 'conv_halo.hip', 'conv_small.hip', 'conv_halo_bf16.hip', 'conv_c8_bf16.hip', 'conv_c8_m16.hip', 'conv_c8_dil.hip', 'conv1x1_c8.hip', 'conv_f64.hip', 'conv_halo_f64.hip', 'conv_wino_f64.hip', 'pool_unpool.hip', 'deconv.hip', 'deconv_phase.hip', 'tail.hip', 'metrics.hip', 'bn.hip', 'crf.hip', 'ctx_train.hip', 'ctx_grad.hip', 'conv_wgrad.hip', 'c8_grad.hip', 'conv_wgrad_kxk.hip', 'deconv_grad.hip', 'deconv_grad_bf16.hip', 'fcn8_train.hip', 'conv_wgrad_bf16.hip', 'conv_wgrad_bf16_co16.hip', 'conv_dgrad_bf16.hip', 'conv_kxk_bf16.hip', 'bn_grad.hip', 'bnrelu_conv_bf16.hip']
+SOURCES = ['abi.hip', 'conv_igemm.hip', 'conv_taps.hip', 'conv_wino.hip', 'conv_wino_bf16.hip', 'conv_halo.hip', 'conv_small.hip', 'conv_halo_bf16.hip', 'conv_c8_bf16.hip', 'conv_c8_m16.hip', 'conv_c8_dil.hip', 'conv1x1_c8.hip', 'conv_f64.hip', 'conv_halo_f64.hip', 'conv_wino_f64.hip', 'pool_unpool.hip', 'deconv.hip', 'deconv_phase.hip', 'tail.hip', 'metrics.hip', 'bn.hip', 'crf.hip', 'ctx_train.hip', 'ctx_grad.hip', 'conv_wgrad.hip', 'c8_grad.hip', 'conv_wgrad_kxk.hip', 'deconv_grad.hip', 'deconv_grad_bf16.hip', 'fcn8_train.hip', 'conv_wgrad_bf16.hip', 'conv_dgrad_bf16.hip', 'conv_kxk_bf16.hip', 'bn_grad.hip', 'bnrelu_conv_bf16.hip']
 ARCH = 'gfx950'
 
 

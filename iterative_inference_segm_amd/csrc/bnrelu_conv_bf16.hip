@@ -34,8 +34,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TH = 8, TW = 32;                     // output pixel tile
 constexpr int PH = TH + 2, PW = TW + 2;            // its patch of t
 constexpr int PPIX = PH * PW;                      // 340 patch pixels

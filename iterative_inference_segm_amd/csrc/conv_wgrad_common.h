@@ -1,5 +1,5 @@
-// What the zero-padded 3x3 weight-gradient kernels share (conv_wgrad.hip: float / double; conv_wgrad_bf16.hip and
-// conv_wgrad_bf16_co16.hip: bf16 operands): the launch parameters, the plan of pixel tiles and slabs, the border pixels of a wide zero
+// What the zero-padded 3x3 weight-gradient kernels share (conv_wgrad.hip: float / double; conv_wgrad_bf16.hip's two
+// forms: bf16 operands): the launch parameters, the plan of pixel tiles and slabs, the border pixels of a wide zero
 // padding and the finalize launch that adds the slabs in slab order.
 #pragma once
 #include "mma16_common.h"

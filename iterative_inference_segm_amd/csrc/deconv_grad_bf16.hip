@@ -18,7 +18,7 @@
 // columns): tap (a, c) at tile pixel (i, j) reads P[a & 1][c & 1][i + (a >> 1)][j + (c >> 1)], so every tap is a
 // unit-stride run and the stride-2 gather happens once, in the LDS address of the staging store.
 //
-// wgrad (deconv_wgrad_bf16_kernel): conv_wgrad_bf16_co16.hip's scheme.  k = pixels, A = g (rows co), B = x (columns
+// wgrad (deconv_wgrad_bf16_kernel): conv_wgrad_bf16.hip's co16 scheme.  k = pixels, A = g (rows co), B = x (columns
 //   ci), nine accumulators per 16 x 16 channel pair on v_mfma_f32_16x16x32_bf16; the k-group of a lane is 8
 //   consecutive j of one tile row, two rows per group pair: two k-steps per tile.  A workgroup owns 32 output x 64
 //   input channels and a slab of tiles; wave w of eight multiplies output group w & 1 with input group w >> 1.  LDS,
@@ -41,19 +41,11 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TI = 4, TJ = 16;                           // input pixel tile
 constexpr int GH = 2 * TI + 1, GW = 2 * TJ + 1;          // the piece of gf it reaches
 constexpr int GPIX = GH * GW;                            // 297
 constexpr int GN = (GPIX + 63) / 64;                     // positions lane + 64 n of it
 constexpr int NWAVE = 8;
-
-__device__ __forceinline__ bf16x8 frag(unsigned a, unsigned b, unsigned c, unsigned d) {
-    u32x4 v;
-    v.x = a; v.y = b; v.z = c; v.w = d;
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 struct db_params {
     int B, Cin, Cout, H, W;
@@ -189,8 +181,7 @@ __global__ __launch_bounds__(512) void deconv_wgrad_bf16_kernel(db_params p, con
                 const unsigned e4 = *reinterpret_cast<const unsigned*>(r + 8);
                 const u32x4 o = *reinterpret_cast<const u32x4*>(r + PX1);
                 const bf16x8 a0 = __builtin_bit_cast(bf16x8, e), a1 = __builtin_bit_cast(bf16x8, o);
-                const bf16x8 a2 = frag(__builtin_amdgcn_alignbyte(e.y, e.x, 2), __builtin_amdgcn_alignbyte(e.z, e.y, 2),
-                                       __builtin_amdgcn_alignbyte(e.w, e.z, 2), __builtin_amdgcn_alignbyte(e4, e.w, 2));
+                const bf16x8 a2 = frag_shift1(e.x, e.y, e.z, e.w, e4);
                 acc[a * 3 + 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b, acc[a * 3 + 0], 0, 0, 0);
                 acc[a * 3 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b, acc[a * 3 + 1], 0, 0, 0);
                 acc[a * 3 + 2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b, acc[a * 3 + 2], 0, 0, 0);

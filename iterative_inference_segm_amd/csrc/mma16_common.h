@@ -1,7 +1,8 @@
-// What the gradient kernels of the 16-bit matrix pipe share (conv_wgrad_bf16.hip, conv_dgrad_bf16.hip,
-// conv_kxk_bf16.hip) and, on the host side, the plans of every split reduction (those three, conv_wgrad.hip and
-// conv_wgrad_kxk.hip): the MFMA operand types and the fp32 -> bf16 packing, the parameter-layout check, the slab
-// split, the overlap test and the K = 1 .. 7 launch ladder.
+// What the kernels of the 16-bit matrix pipe share (conv_wgrad_bf16.hip, conv_dgrad_bf16.hip, conv_kxk_bf16.hip,
+// deconv_grad_bf16.hip, bnrelu_conv_bf16.hip) and, on the host side, the plans of every split reduction (those five,
+// and conv_wgrad.hip -- through conv_wgrad_common.h, as conv_wgrad_bf16.hip -- and conv_wgrad_kxk.hip): the MFMA
+// operand types, the fp32 -> bf16 packing, the operand of "the same pixels, one further", the parameter-layout check,
+// the slab split, the overlap test and the K = 1 .. 7 launch ladder.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -9,6 +10,7 @@
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -22,6 +24,18 @@ __device__ __forceinline__ u32x4 pack8(const float* v) {
     u32x4 w;
     w.x = pack2(v[0], v[1]); w.y = pack2(v[2], v[3]); w.z = pack2(v[4], v[5]); w.w = pack2(v[6], v[7]);
     return w;
+}
+
+// An MFMA operand of 8 bf16 from four dwords ...
+__device__ __forceinline__ bf16x8 frag(unsigned a, unsigned b, unsigned c, unsigned d) {
+    u32x4 v;
+    v.x = a; v.y = b; v.z = c; v.w = d;
+    return __builtin_bit_cast(bf16x8, v);
+}
+// ... and the one of pixels 1 .. 8 of the ten in five dwords: the run shifted by one element (v_alignbyte)
+__device__ __forceinline__ bf16x8 frag_shift1(unsigned d0, unsigned d1, unsigned d2, unsigned d3, unsigned d4) {
+    return frag(__builtin_amdgcn_alignbyte(d1, d0, 2), __builtin_amdgcn_alignbyte(d2, d1, 2),
+                __builtin_amdgcn_alignbyte(d3, d2, 2), __builtin_amdgcn_alignbyte(d4, d3, 2));
 }
 
 // ---- host side ----

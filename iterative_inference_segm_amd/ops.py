@@ -2223,6 +2223,14 @@ def conv_wgrad_desc(x_shape, Cout, pad, Cin_tot=None, ci0=0, layout='oihw'):
 
 WGRAD_MODES = DGRAD_MODES = KXK_MODES = FWD_MODES = MODES_16BIT
 WGRAD_CO_BLOCKS = (64, 16)      # output channels per workgroup of the weight-gradient kernels (16: mma='bf16' only)
+# (mma, co_block) -> (workspace entry point, profile name, launch function or None: the dtype's iiseg_conv_wgrad_*);
+# each form has a plan, and a profile name, of its own
+_WGRAD_FORMS = {
+    ('f32', 64): ('iiseg_conv_wgrad_workspace_elems', 'conv_wgrad_kernel', None),
+    ('bf16', 64): ('iiseg_conv_wgrad_bf16_workspace_elems', 'conv_wgrad_bf16_kernel', 'iiseg_conv_wgrad_bf16'),
+    ('bf16', 16): ('iiseg_conv_wgrad_bf16_co16_workspace_elems', 'conv_wgrad_bf16_co16_kernel',
+                   'iiseg_conv_wgrad_bf16_co16'),
+}
 
 
 def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32', co_block=64):
@@ -2232,7 +2240,7 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32', co_bl
     source of a concat layer is a second call).  float32: v_mfma_f32_32x32x2_f32; float64: vector ALU.
     mma='bf16' (float32 tensors only; csrc/conv_wgrad_bf16.hip): x and gz are rounded once to bf16 as they are
     staged and multiplied by v_mfma_f32_32x32x16_bf16 with fp32 accumulators; db stays the sum of the unrounded
-    gz.  co_block=16 (with mma='bf16' only; csrc/conv_wgrad_bf16_co16.hip): the same sums
+    gz.  co_block=16 (with mma='bf16' only; the same source's co16 form): the same sums
     in blocks of 16 output x 64 input channels on v_mfma_f32_16x16x32_bf16, the form for layers with few output
     channels; the caller chooses, nothing here does."""
     dt = x.dtype
@@ -2253,18 +2261,10 @@ def conv_wgrad(x, gz, dW, db=None, pad=1, ci0=0, layout='oihw', mma='f32', co_bl
     if tuple(gz.shape) != (B, Cout, OH, OW) or (db is not None and db.numel() != Cout):
         raise RuntimeError('conv_wgrad: shapes x %s gz %s dW %s' % (tuple(x.shape), tuple(gz.shape), tuple(dW.shape)))
     d = conv_wgrad_desc(tuple(x.shape), Cout, pad, Cin_tot, ci0, layout)
-    if mma == 'bf16' and co_block == 16:                 # a plan, and a profile name, of its own
-        n = _count(_lib.load().iiseg_conv_wgrad_bf16_co16_workspace_elems(C.byref(d)),
-                   'iiseg_conv_wgrad_bf16_co16_workspace_elems')
-        kern, fn = 'conv_wgrad_bf16_co16_kernel', _lib.load().iiseg_conv_wgrad_bf16_co16
-    elif mma == 'bf16':
-        n = _count(_lib.load().iiseg_conv_wgrad_bf16_workspace_elems(C.byref(d)),
-                   'iiseg_conv_wgrad_bf16_workspace_elems')
-        kern, fn = 'conv_wgrad_bf16_kernel', _lib.load().iiseg_conv_wgrad_bf16
-    else:
-        n = _count(_lib.load().iiseg_conv_wgrad_workspace_elems(C.byref(d), dW.element_size()),
-                   'iiseg_conv_wgrad_workspace_elems')
-        kern, fn = 'conv_wgrad_kernel', _fn('conv_wgrad', dt)
+    ws_elems, kern, launch = _WGRAD_FORMS[mma, co_block]
+    # (the fp32 / f64 entry points take the element size, and there is one launch function per dtype)
+    n = _count(getattr(_lib.load(), ws_elems)(C.byref(d), *(() if launch else (dW.element_size(),))), ws_elems)
+    fn = getattr(_lib.load(), launch) if launch else _fn('conv_wgrad', dt)
     ws = _workspace(_SUFFIX[dt], n, x.device) if n else None
     _launch(kern, 2.0 * Cin * Cout * 9 * B * OH * OW, fn, C.byref(d), _ptr(x, dt), _ptr(gz, dt),
             _ptr(ws, dt), _ptr(dW, dt), _ptr(db, dt))

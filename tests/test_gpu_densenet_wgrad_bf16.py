@@ -1,5 +1,5 @@
 """GPU: wgrad='bf16' on FC-DenseNet -- the 16-output-channel form of the bf16 weight gradient
-(csrc/conv_wgrad_bf16_co16.hip; ops.conv_wgrad(mma='bf16', co_block=16)) and the switch through the module, the
+(csrc/conv_wgrad_bf16.hip's co16 form; ops.conv_wgrad(mma='bf16', co_block=16)) and the switch through the module, the
 trainer and train_fcdensenet.py.  The kernel: exact on data bf16 holds exactly, over every descriptor feature; on
 real data within the any-order fp32 accumulation bound of the float64 sum over operands rounded on the CPU with
 .to(torch.bfloat16), ties and direction included, db from the unrounded g_z, the same bits twice.  The module: nothing
@@ -17,50 +17,28 @@ import pytest
 import torch
 
 import densenet_train_ref as R
+import wgrad_bf16_ref as WR
+from wgrad_bf16_ref import F32, U, bound_check as _bound_check, dev as _dev, pad as _pad, taps as _taps
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = torch.float32
-U = 2.0 ** -24
 KW = dict(mma='bf16', co_block=16)
-
-
-def _dev(a, dt=F32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dt).cuda().contiguous()
-
-
-def _taps(g, xp, OH, OW):
-    """[co, ci, ky, kx] = sum_{b,y,x} g[b, co, y, x] xp[b, ci, y + ky, x + kx]"""
-    return np.stack([np.stack([np.tensordot(g, xp[:, :, ky:ky + OH, kx:kx + OW], axes=([0, 2, 3], [0, 2, 3]))
-                               for kx in range(3)], axis=-1) for ky in range(3)], axis=-2)
-
-
-def _pad(x, pad):
-    return np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
 
 
 # ---- 1. exact on small integers ----
 GEOMETRY = [(7, 7, 1), (14, 13, 1), (37, 150, 1), (3, 4, 5), (14, 13, 5), (1, 1, 1), (2, 9, 1)]
 CHANNELS = [(1, 16), (5, 16), (48, 16), (67, 16), (24, 4), (24, 11), (20, 33)]
 DEEP = [(130, 16), (300, 16), (1072, 16)]                        # several input-channel blocks; on the small maps only
+# the edges of the blocks that the staging decides: at most 16 / 32 / 64 input channels and one more (the kernel
+# stages 2, 4 or 8 x channels per wave), and a second block of output channels; on three small maps
+EDGES = [(16, 16), (17, 16), (32, 16), (33, 16), (64, 16), (65, 16), (24, 17)]
 INT_CASES = [(ci, co, h, w, p) for ci, co in CHANNELS for h, w, p in GEOMETRY] + \
-            [(ci, co, h, w, p) for ci, co in DEEP for h, w, p in GEOMETRY[:2]]
-_REF = {}
+            [(ci, co, h, w, p) for ci, co in DEEP for h, w, p in GEOMETRY[:2]] + \
+            [(ci, co, h, w, p) for ci, co in EDGES for h, w, p in (GEOMETRY[0], GEOMETRY[1], GEOMETRY[3])]
 
 
 def _int_case(Cin, Cout, B, H, W, pad):
-    key = (Cin, Cout, B, H, W, pad)
-    if key not in _REF:
-        rng = np.random.default_rng(Cin * 1000 + Cout + 7 * B + H + 3 * pad)
-        OH, OW = H + 2 * pad - 2, W + 2 * pad - 2
-        x = rng.integers(-2, 3, size=(B, Cin, H, W))
-        gz = rng.integers(-2, 3, size=(B, Cout, OH, OW))
-        gz[rng.integers(0, 2, size=gz.shape) == 0] = 0           # as behind a ReLU mask
-        dW = _taps(gz.astype(np.float64), _pad(x.astype(np.float64), pad), OH, OW)
-        db = gz.astype(np.float64).sum(axis=(0, 2, 3))
-        assert dW.dtype == np.float64 and np.abs(dW).max() < 2 ** 24 and np.abs(db).max() < 2 ** 24
-        _REF[key] = (x, gz, dW, db)
-    return _REF[key]
+    return WR.int_case(Cin, Cout, B, H, W, pad, np.float64)
 
 
 @pytest.mark.parametrize('B', [1, 3])
@@ -94,26 +72,6 @@ def test_co16_weight_gradient_is_exact_on_integers(built_lib, Cin, Cout, B, H, W
 
 
 # ---- 2. the rounding point ----
-def _rounded(t):
-    """float64 numpy of a float32 tensor rounded to bf16 on the CPU"""
-    return t.detach().cpu().to(torch.bfloat16).double().numpy()
-
-
-def _bound_check(dW, x, gz, pad, what=''):
-    """dW (Cout, Cin, 3, 3) against the float64 sum over x, gz (float32 tensors) rounded to bf16 on the CPU: every
-    entry within (n + 1) 2^-24 sum|a b|, the bound of n fp32 additions of exact products in ANY order, sum|a b|
-    per entry from the rounded data.  Returns (worst error / bound, ref, mag)."""
-    OH, OW = gz.shape[2:]
-    n = gz.shape[0] * OH * OW
-    g, xp = _rounded(gz), _pad(_rounded(x), pad)
-    ref, mag = _taps(g, xp, OH, OW), _taps(np.abs(g), np.abs(xp), OH, OW)
-    err = np.abs(dW.detach().cpu().double().numpy() - ref)
-    bound = (n + 1) * U * mag
-    frac = float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0
-    assert (err <= bound).all(), '%s: worst error / bound %.3g over %d terms' % (what, frac, n)
-    return frac, ref, mag
-
-
 def test_operands_are_rounded_to_nearest_once_and_db_is_not(built_lib):
     from iterative_inference_segm_amd import ops
     rng = np.random.default_rng(5)

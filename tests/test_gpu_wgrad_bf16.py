@@ -19,50 +19,29 @@ import torch
 
 import fcn8_train_ref as RF
 import std_train_ref as R
+import wgrad_bf16_ref as WR
+from wgrad_bf16_ref import F32, U, bound_check as _bound_check, dev as _dev, pad as _pad, taps as _taps
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = torch.float32
-U = 2.0 ** -24
-
-
-def _dev(a, dt=F32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dt).cuda().contiguous()
-
-
-def _taps(g, xp, OH, OW):
-    """[co, ci, ky, kx] = sum_{b,y,x} g[b, co, y, x] xp[b, ci, y + ky, x + kx]"""
-    return np.stack([np.stack([np.tensordot(g, xp[:, :, ky:ky + OH, kx:kx + OW], axes=([0, 2, 3], [0, 2, 3]))
-                               for kx in range(3)], axis=-1) for ky in range(3)], axis=-2)
-
-
-def _pad(x, pad):
-    return np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
 
 
 # ---- 1. exact on small integers ----
 CHANNELS = [(11, 64), (24, 16), (64, 130), (130, 33)]            # none a multiple of the 64-channel block
 GEOMETRY = [(7, 7, 1), (14, 13, 1), (37, 150, 1), (3, 4, 5), (14, 13, 5), (1, 1, 1), (2, 9, 1)]
-_REF = {}
+# the edges of `wave_on`: a wave multiplies a 32 x 32 sub-block of the 64 x 64 block only if it holds a real channel;
+# on three small maps
+EDGES = [(32, 32), (33, 33), (65, 65)]
+INT_CASES = [(ci, co, b, h, w, p) for h, w, p in GEOMETRY for b in (1, 3) for ci, co in CHANNELS] + \
+            [(ci, co, b, h, w, p) for h, w, p in (GEOMETRY[0], GEOMETRY[1], GEOMETRY[3]) for b in (1, 3)
+             for ci, co in EDGES]
 
 
 def _int_case(Cin, Cout, B, H, W, pad):
-    key = (Cin, Cout, B, H, W, pad)
-    if key not in _REF:
-        rng = np.random.default_rng(Cin * 1000 + Cout + 7 * B + H + 3 * pad)
-        OH, OW = H + 2 * pad - 2, W + 2 * pad - 2
-        x = rng.integers(-2, 3, size=(B, Cin, H, W))
-        gz = rng.integers(-2, 3, size=(B, Cout, OH, OW))
-        gz[rng.integers(0, 2, size=gz.shape) == 0] = 0           # as behind a ReLU mask
-        dW, db = _taps(gz.astype(np.int64), _pad(x.astype(np.int64), pad), OH, OW), gz.sum(axis=(0, 2, 3))
-        assert dW.dtype == np.int64 and np.abs(dW).max() < 2 ** 24 and np.abs(db).max() < 2 ** 24
-        _REF[key] = (x, gz, dW, db)
-    return _REF[key]
+    return WR.int_case(Cin, Cout, B, H, W, pad, np.int64)
 
 
-@pytest.mark.parametrize('H,W,pad', GEOMETRY)
-@pytest.mark.parametrize('B', [1, 3])
-@pytest.mark.parametrize('Cin,Cout', CHANNELS)
+@pytest.mark.parametrize('Cin,Cout,B,H,W,pad', INT_CASES)
 def test_bf16_weight_gradient_is_exact_on_integers(built_lib, Cin, Cout, B, H, W, pad):
     from iterative_inference_segm_amd import _lib, ops
     x, gz, dW_ref, db_ref = _int_case(Cin, Cout, B, H, W, pad)
@@ -92,26 +71,6 @@ def test_bf16_weight_gradient_is_exact_on_integers(built_lib, Cin, Cout, B, H, W
 
 
 # ---- 2. the rounding point ----
-def _rounded(t):
-    """float64 numpy of a float32 tensor rounded to bf16 on the CPU"""
-    return t.detach().cpu().to(torch.bfloat16).double().numpy()
-
-
-def _bound_check(dW, x, gz, pad, what=''):
-    """dW (Cout, Cin, 3, 3) against the float64 sum over x, gz (float32 tensors) rounded to bf16 on the CPU: every
-    entry within (n + 1) 2^-24 sum|a b|, the bound of n fp32 additions of exact products in ANY order, sum|a b|
-    per entry from the rounded data.  Returns (worst error / bound, ref, mag)."""
-    OH, OW = gz.shape[2:]
-    n = gz.shape[0] * OH * OW
-    g, xp = _rounded(gz), _pad(_rounded(x), pad)
-    ref, mag = _taps(g, xp, OH, OW), _taps(np.abs(g), np.abs(xp), OH, OW)
-    err = np.abs(dW.detach().cpu().double().numpy() - ref)
-    bound = (n + 1) * U * mag
-    frac = float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0
-    assert (err <= bound).all(), '%s: worst error / bound %.3g over %d terms' % (what, frac, n)
-    return frac, ref, mag
-
-
 def test_operands_are_rounded_to_nearest_once_and_db_is_not(built_lib):
     from iterative_inference_segm_amd import ops
     rng = np.random.default_rng(5)

@@ -1,6 +1,7 @@
 """CPU: the plans behind the bf16 gradient / forward entry points (csrc/mma16_common.h: the parameter-layout check,
-the slab split; csrc/conv_wgrad_common.h, conv_wgrad_kxk.hip, conv_dgrad_bf16.hip, conv_kxk_bf16.hip) return what
-they returned before the shared helpers existed.  tests/golden/mma16_plans.json holds, for the table of descriptors
+the slab split; csrc/conv_wgrad_common.h, conv_wgrad_bf16.hip's two forms, conv_wgrad_kxk.hip, conv_dgrad_bf16.hip,
+conv_kxk_bf16.hip, deconv_grad_bf16.hip, bnrelu_conv_bf16.hip) return what they returned before the shared helpers
+existed.  tests/golden/mma16_plans.json holds, for the table of descriptors
 below, the value of every *_check / *_slabs / *_workspace_elems / *_pack_elems entry point as the library answered
 before the helpers moved (`python tests/test_mma16_plans_host.py --record` rewrites it from the library in the
 tree: only for a change that is meant to alter a plan)."""
@@ -18,6 +19,7 @@ GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'mma16_plans.json')
 FAMILIES = {
     'wgrad': ('ConvWgradDesc', dict(B=2, Cin=24, Cout=16, H=20, W=20, K=3, pad=1),
               [('iiseg_conv_wgrad_bf16_slabs', ()), ('iiseg_conv_wgrad_bf16_workspace_elems', ()),
+               ('iiseg_conv_wgrad_bf16_co16_slabs', ()), ('iiseg_conv_wgrad_bf16_co16_workspace_elems', ()),
                ('iiseg_conv_wgrad_check', ()), ('iiseg_conv_wgrad_slabs', (4,)), ('iiseg_conv_wgrad_slabs', (8,)),
                ('iiseg_conv_wgrad_workspace_elems', (4,)), ('iiseg_conv_wgrad_workspace_elems', (8,))]),
     'dgrad': ('ConvDgradDesc', dict(B=2, Cin=24, Cout=16, H=20, W=20, K=3, pad=1),
@@ -33,9 +35,16 @@ FAMILIES = {
     'kxk_fwd': ('ConvFwdKxKDesc', dict(B=2, Cin=24, Cout=16, H=13, W=13, K=7, relu=1),
                 [('iiseg_conv_fwd_kxk_bf16_check', ()), ('iiseg_conv_fwd_kxk_bf16_slabs', ()),
                  ('iiseg_conv_fwd_kxk_bf16_workspace_elems', ())]),
+    'deconv': ('DeconvDesc', dict(B=2, Cin=24, Cout=16, H=10, W=10, K=3, stride=2, OH=21, OW=21),
+               [('iiseg_deconv_grad_bf16_check', ()), ('iiseg_deconv_wgrad_bf16_slabs', ()),
+                ('iiseg_deconv_wgrad_bf16_workspace_elems', ()), ('iiseg_deconv_dgrad_bf16_workspace_elems', ())]),
+    'bnrelu_fwd': ('BnReluConvDesc', dict(B=2, n=24, cap=40, Cout=16, H=20, W=20, out_cap=40, out_c0=24),
+                   [('iiseg_bnrelu_conv_fwd_bf16_check', ()), ('iiseg_bnrelu_conv_fwd_bf16_slabs', ()),
+                    ('iiseg_bnrelu_conv_fwd_bf16_workspace_elems', ())]),
 }
 
 EDGES = (1, 63, 64, 65, 100)                       # around the 64-channel block, and a non-multiple of 16
+EDGES16 = (1, 15, 16, 17, 63, 64, 65)              # ... and around the 16-channel block of the later kernels
 # what every family gets: the layouts, a channel slice, the channel edges, the refusal branches (one fault each, then
 # two at once: the first check that fires answers)
 COMMON = [dict(), dict(layout='iohw'), dict(ci0=5, Cin_tot=40), dict(ci0=5, Cin_tot=40, layout='iohw')] + \
@@ -46,7 +55,9 @@ KS = [dict(K=k, H=9, W=11) for k in range(1, 8)] + [dict(K=k, H=k - 1, W=k + 3) 
 TABLE = {
     # min-per-slab clamp (the default map), the target decides, the unsplit grid exceeds the target, a wide padding
     'wgrad': COMMON + [dict(B=4, H=200, W=200), dict(Cin=1024, Cout=1024), dict(Cin=1024, Cout=1024, B=4, H=200, W=200),
-                       dict(pad=100, H=4, W=4), dict(pad=0, H=2, W=9)],
+                       dict(pad=100, H=4, W=4), dict(pad=0, H=2, W=9)] +
+             [dict(Cin=c) for c in (15, 16, 17)] + [dict(Cout=c) for c in (15, 16, 17)] +      # the co16 form's blocks
+             [dict(Cin=1024, Cout=16), dict(Cin=300, Cout=16, H=14, W=13), dict(Cin=67, Cout=16, B=3, H=37, W=150)],
     'dgrad': COMMON + [dict(pad=0), dict(accumulate=1), dict(accumulate=2), dict(Cin=512, Cout=512, H=422, W=422)],
     'kxk_wgrad': COMMON + KS + [dict(K=3, Cin=512, Cout=512, B=4, H=66, W=66), dict(K=3, Cin=1024, Cout=1024),
                                 dict(K=1, H=37, W=150, B=3), dict(B=10, Cin=512, Cout=4096),
@@ -56,6 +67,26 @@ TABLE = {
     'kxk_fwd': [r for r in COMMON if not set(r) & {'layout', 'ci0', 'Cin_tot', 'so', 'sc'}] + KS +
                [dict(Cin=4096, Cout=4096), dict(B=16, H=70, W=70, Cout=256), dict(relu=2),
                 dict(K=1, H=37, W=150, B=3, Cin=512, Cout=21)],
+    # the whole (2H + 1) x (2W + 1) map (split: the min-per-slab clamp), the channel edges, a cropped window, one tile,
+    # the target decides, the unsplit grid reaches the target; then the refusals in db_plan's order
+    'deconv': [dict()] + [dict(Cin=c) for c in EDGES16] + [dict(Cout=c) for c in EDGES16] +
+              [dict(oy0=1, ox0=1, OH=20, OW=20), dict(oy0=0, ox0=1, OH=19, OW=17), dict(B=1, H=4, W=16, OH=9, OW=33),
+               dict(B=3, H=56, W=56, OH=112, OW=112, oy0=1, ox0=1, Cin=48, Cout=48), dict(Cin=1024, Cout=1024),
+               dict(B=0), dict(oy0=-1), dict(B=65536), dict(K=1025), dict(OH=22), dict(ox0=1),
+               dict(H=16384, W=16384, OH=32769, OW=32769), dict(K=2, OH=20, OW=20), dict(stride=1, OH=12, OW=12),
+               dict(K=4, stride=3, OH=31, OW=31), dict(Cin=65535, Cout=65535),
+               dict(B=65535, H=16384, W=16384, OH=9, OW=9), dict(B=0, K=2), dict(K=2, OH=22)],
+    # one slab (the min-per-slab clamp), the channel edges (n: the k-tile of 32 as well), the reduction splits, the
+    # map alone fills the target, the output behind the channels read and elsewhere; then bc_plan's refusals
+    'bnrelu_fwd': [dict()] + [dict(n=c, cap=c + 16, out_cap=c + 16, out_c0=c) for c in EDGES16 + (31, 32, 33)] +
+                  [dict(Cout=c, out_cap=24 + c) for c in EDGES16] +
+                  [dict(n=256, cap=272, out_cap=272, out_c0=256), dict(n=256, cap=272, out_cap=272, out_c0=256, B=7),
+                   dict(n=1000, cap=1000, out_cap=16, out_c0=0, H=7, W=7), dict(H=224, W=224), dict(H=37, W=150, B=3),
+                   dict(out_cap=16, out_c0=0),
+                   dict(B=0), dict(n=0), dict(Cout=0), dict(W=0), dict(cap=23), dict(out_c0=-1), dict(out_c0=25),
+                   dict(B=65536), dict(cap=65536), dict(out_cap=65536), dict(H=16385, W=16384),
+                   dict(n=60000, cap=60000, Cout=60000, out_cap=60000, out_c0=0), dict(B=65535, H=16384, W=16384),
+                   dict(n=0, out_c0=25), dict(cap=65536, H=16385, W=16384)],
 }
 
 
